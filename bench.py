@@ -16,7 +16,15 @@ a mode that meets the north star's parity clause (see "parity": every arg-max di
 the exact-fp32 mode over the whole timed cloud; "pair_cascade_mode" is last round's headline f16x3c on the same box, "x8_guard" the
 conditioning guard's counters, "x8_e4m3_mode" the same with the cross terms in FP8 e4m3 instead of the default block-scaled FP6).  The plain 16-bit mode ("fast_mode", f16) is faster still and does NOT meet it.
 
+A plain run sets up, warms up, times --steps steps of the headline mode and prints the line (metric, value, ms_per_step, the
+gate's and the guard's counters of the timed steps).  Everything else the line can carry -- the roofline and its single-stream
+pass, the parity object against the exact-fp32 mode and its oracle adjudication, the other modes, the MuPS leg, the strong
+projection, the RMS angle error, the CPU baseline and, at N > 1, the strong-scaling leg -- comes with --full.
+--dump-outputs DIR writes what the last timed step returned (normals, expert, probs of every cloud) as float32 .npy files.
+
     python bench.py --gpus 1 --steps 2 --warmup 1
+    python bench.py --gpus 1 --steps 2 --warmup 1 --dump-outputs bench_outputs
+    python bench.py --gpus 1 --steps 2 --warmup 1 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 2 --warmup 1
 """
@@ -52,6 +60,7 @@ X8_DEFAULT_FORMAT = 6                 # the library's default form of the cross 
 X6_PRODUCTS = 1.5                     # FP6 form: per tap pair 2 f16 MFMAs + 1 FP6 MFMA of K = 64 that runs 8 passes like ONE of them
 X8_K5_PRODUCTS = 2.0                  # (flat pairing: half an FP8 instruction per tap) each counted as TWO f16 instructions -- its pipe time at the nominal
                                       # 2x rate: 2.0 f16-equivalents per multiply instead of 3
+DUMP_MAX_BYTES = 64 << 20             # --dump-outputs: above this a fixed, seeded sample of the rows is written
 
 
 def make_clouds(n_clouds, n_points, stream=False):
@@ -187,8 +196,9 @@ def timed_run(args, cfg, W, clouds_np, dtype, steps, warmup, dev, world, rank, u
               streams=1, graph=None, x8_layers=None, x8_format=None):
     """W warm-up steps, then exactly ``steps`` timed steps between barrier + synchronize pairs; max over ranks.
     ``strong``: a step is ONE cloud (clouds_np[0]) whose rows are sharded over the ranks (dist.estimate_sharded).
-    Returns the elapsed seconds, the kernel-time table (rank 0), the last cloud's gathered results, this rank's
-    results for its shard of cloud 0 (for the parity leg), the model's MAC counts and the two-stage gate's counters."""
+    Returns the elapsed seconds, the kernel-time table (rank 0), every cloud's gathered results of the last step ("outs";
+    "out": the last cloud's), this rank's results for its shard of cloud 0 (for the parity leg), the model's MAC counts and
+    the two-stage gate's counters."""
     lib = _lib.load()
     if strong:
         clouds_np = clouds_np[:1]
@@ -232,9 +242,9 @@ def timed_run(args, cfg, W, clouds_np, dtype, steps, warmup, dev, world, rank, u
         for c in clouds:
             c.build_grid()                                    # search structure: part of the path
         if strong:
-            return ndist.estimate_sharded(est, clouds[0])
+            return [ndist.estimate_sharded(est, clouds[0])]
         # this rank's row blocks of all clouds as one stream of batches + one all-gather (dist.estimate_sharded_many)
-        return ndist.estimate_sharded_many(est, clouds)[-1]
+        return ndist.estimate_sharded_many(est, clouds)
 
     def sync():
         torch.cuda.synchronize(dev)
@@ -270,11 +280,12 @@ def timed_run(args, cfg, W, clouds_np, dtype, steps, warmup, dev, world, rank, u
         res["x8_guard"] = {**est.net.x8_guard_stats(), "thr_calibrated": res.get("x8_guard_thr"), "x8_layers": x8_layers if x8_layers is not None else 0xF,
                            "x8_format": x8_format if x8_format is not None else X8_DEFAULT_FORMAT}
     res.update({"elapsed": elapsed, "batch": est.batch, "streams": est.n_streams, "steps": steps,
-                "out": [t.cpu().numpy() for t in out]})
-    if rank == 0:
-        if want_shard0:
-            lo, hi = ndist.shard_range(clouds[0].patch_count, 0, world)
-            res["shard0"] = [t.cpu().numpy() for t in est.run(clouds[0], lo, hi - lo)]     # outside the timed region
+                "outs": [[t.cpu().numpy() for t in o] for o in out]})       # the last step's results, one triple per cloud
+    res["out"] = res["outs"][-1]
+    if rank == 0 and want_shard0:
+        lo, hi = ndist.shard_range(clouds[0].patch_count, 0, world)
+        res["shard0"] = [t.cpu().numpy() for t in est.run(clouds[0], lo, hi - lo)]     # outside the timed region
+    if timing:                                                    # the MAC counts behind roofline()
         h = est.net._handle
         nom, use, iss = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
         macs = {}
@@ -459,6 +470,23 @@ def adjudicate_flips(cfg, W, cloud_np, rows, test, ref, limit=32):
     return parity.adjudicate(rows, np.asarray(test[1])[rows], np.asarray(ref[1])[rows], np.asarray(ref[2])[rows], probs.numpy())
 
 
+def dump_outputs(path, outs):
+    """--dump-outputs: the (normals, expert, probs) triples of the last timed step, rows of all clouds concatenated in cloud
+    order, as normals.npy [R, 3], expert.npy [R] and probs.npy [R, E] in float32.  Above DUMP_MAX_BYTES a fixed sample of the
+    rows (seed 0, same for every run with the same arguments) is written, their indices in rows.npy (float64)."""
+    arrs = {name: np.concatenate([np.asarray(o[i]) for o in outs]).astype(np.float32)
+            for i, name in enumerate(("normals", "expert", "probs"))}
+    n = len(arrs["normals"])
+    row_bytes = sum(a[0].nbytes for a in arrs.values())
+    if n * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BYTES // (row_bytes + 8), replace=False))
+        arrs = {name: a[rows] for name, a in arrs.items()}
+        arrs["rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -482,6 +510,12 @@ def main():
                          "0xA = the 5^3 layers only)")
     ap.add_argument("--x8-guard-thr", type=float, default=None,
                     help="dtypes f16x8 / f16x8c, experiments: override the conditioning guard's |n| threshold after its calibration (negative: guard off)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: roofline (+ its single-stream pass), parity against the exact-fp32 "
+                         "mode, the other modes, the MuPS leg, the strong projection, the RMS angle error, the CPU baseline and, at "
+                         "N > 1, the strong-scaling leg (the --no-* options below trim a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's normals / expert / probs (every cloud) to DIR/<name>.npy in float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the parity leg (fp32-mode rerun of rank 0's shard of cloud 0)")
@@ -548,25 +582,31 @@ def main():
         sp, sn = cp.build(0, min(512, args.points))
         W = calibrate_gate(cfg, W, sp, sn, device=dev)
         del cp, sp, sn
-    timing = (rank == 0) and not args.no_kernel_timing
+    # a plain run does what its headline figure needs and nothing else; every other leg and object of the line is --full's
+    kernel_timing = args.full and not args.no_kernel_timing
+    parity_on = args.full and not args.no_parity
+    secondary = args.full and not args.no_secondary
+    timing = (rank == 0) and kernel_timing
     headline = not args.stream_clouds
     eff_streams = 1 if args.graph else args.streams          # a captured graph replays on one stream (--graph)
     main_run = timed_run(args, cfg, W, clouds_np, args.dtype, args.steps, args.warmup, dev, world, rank, use_pg,
-                         timing and eff_streams == 1 and not args.graph, want_shard0=not args.no_parity and args.dtype != "f32", streams=eff_streams,
+                         timing and eff_streams == 1 and not args.graph, want_shard0=parity_on and args.dtype != "f32", streams=eff_streams,
                          x8_layers=args.x8_layers)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, main_run["outs"])
     # per-kernel times need launches that do not overlap: a short single-stream pass of the same workload carries the roofline
     # (every rank takes part -- the pass contains the same collectives as the headline run -- but only rank 0 records events)
     # (a replayed hipGraph records no events either: with --graph the pass runs the same batches eagerly)
     roof_run = main_run
-    if not args.no_kernel_timing and (main_run["streams"] > 1 or args.graph):
+    if kernel_timing and (main_run["streams"] > 1 or args.graph):
         roof_run = timed_run(args, cfg, W, clouds_np, args.dtype, 2, 1, dev, world, rank, use_pg, timing, want_shard0=False, graph=False,
                              x8_layers=args.x8_layers)
     strong = None
-    if headline and (world > 1 or args.strong):
+    if headline and ((args.full and world > 1) or args.strong):
         strong = timed_run(args, cfg, W, clouds_np, args.dtype, max(2, min(args.steps, 5)), 1, dev, world, rank, use_pg, False,
                            want_shard0=False, strong=True, streams=args.streams, x8_layers=args.x8_layers)
     legs = {}
-    if headline and not args.no_secondary and world == 1:
+    if headline and secondary and world == 1:
         # the other modes on the same workload, a few steps each, each with its own parity object against the fp32 mode
         for key, dt, st in (("fast_mode", "f16", 3), ("full_pair_mode", "f16x3", 1), ("pair_cascade_mode", "f16x3c", 2)) + ((("bf16_mode", "bf16", 3),) if args.bf16 else ()):
             if dt != args.dtype:
@@ -622,11 +662,12 @@ def main():
         # checkpoint ships with the reference), so this is the error of an UNTRAINED network -- close to the 52 degrees of random
         # directions -- and says nothing about Nesti-Net's accuracy; it is printed so that the line carries the metric's name and
         # the evaluation code runs on the bench's own output
-        from nesti_net_amd.evaluate import shape_metrics
-        sm = shape_metrics(normals, clouds_np[-1][1])
-        res["rms_angle_error_deg"] = {"value": float(sm["rms"]), "pgp10": float(sm["pgp10"]), "oriented": float(sm["rms_o"]),
-                                      "against": "analytic normals of the synthetic surface, last cloud of the step",
-                                      "note": "synthetic (untrained) weights: not an accuracy figure of Nesti-Net"}
+        if args.full:
+            from nesti_net_amd.evaluate import shape_metrics
+            sm = shape_metrics(normals, clouds_np[-1][1])
+            res["rms_angle_error_deg"] = {"value": float(sm["rms"]), "pgp10": float(sm["pgp10"]), "oriented": float(sm["rms_o"]),
+                                          "against": "analytic normals of the synthetic surface, last cloud of the step",
+                                          "note": "synthetic (untrained) weights: not an accuracy figure of Nesti-Net"}
         if timing:
             res["roofline"] = roofline(roof_run, args.dtype, cfg, clouds_np, world, frac, cal)
             if roof_run is not main_run:
@@ -642,11 +683,11 @@ def main():
                              "ms_per_step": 1e3 * strong["elapsed"] / strong["steps"], "batch": strong["batch"],
                              "workload": "ONE %d-point cloud per step, its query rows block-sharded over %d rank(s), one all-gather "
                                          "(dist.estimate_sharded)" % (len(clouds_np[0][0]), world)}
-        if headline and world == 1 and not args.no_secondary:
+        if headline and world == 1 and secondary:
             res["strong_projection"] = strong_projection(args, cfg, W, clouds_np[0][0], args.dtype, dev,
                                                          1e3 * elapsed / max(1, args.steps))
         ref = None
-        if not args.no_parity and args.dtype != "f32":
+        if parity_on and args.dtype != "f32":
             from nesti_net_amd import parity
             ref, ref_rate = reference_run(args, cfg, W, clouds_np[0][0], dev, world)
             res["parity"] = parity.compare(main_run["shard0"], ref)
@@ -678,7 +719,7 @@ def main():
             if ref is not None:
                 from nesti_net_amd import parity
                 res[key]["parity"] = parity.compare(run["shard0"], ref)
-        if headline and not args.no_secondary and world == 1:
+        if headline and secondary and world == 1:
             m = mups_leg(args.points, 3, 1, cfg, dev)          # BASELINE config 1, driver-timed: the MuPS kernel against its VALU / HBM roofs
             res["mups"] = {"value": m["value"], "unit": m["unit"], "ms_per_step": m["ms_per_step"], "steps": 3, "roofline": m["roofline"],
                            "workload": m["config"]["workload"]}
@@ -698,7 +739,7 @@ def main():
                     "hbm_frac_of_8TBps": nq * alg_b / pk_s / 8e12 if pk_s else None,
                     "note": "MuPS-sweep lane-ops only (the fused ball query and subsample are extra, non-algorithmic work of the "
                             "same kernel); measured HBM bytes: profiles/r05_pmc_traffic.json -> patches_mups_kernel"}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(cfg, W, clouds_np[0][0], frac)
         print(json.dumps(res))
     if use_pg:

@@ -69,22 +69,6 @@ __device__ __forceinline__ uint4 lds128q(unsigned addr) {
   return make_uint4(v.x, v.y, v.z, v.w);
 }
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-template <int DT> __device__ __forceinline__ void mma16(f32x4& acc, const uint4& a, const uint4& b);
-template <> __device__ __forceinline__ void mma16<NESTI_BF16>(f32x4& acc, const uint4& a, const uint4& b) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
-}
-template <> __device__ __forceinline__ void mma16<NESTI_F16>(f32x4& acc, const uint4& a, const uint4& b) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
-}
-template <> __device__ __forceinline__ void mma16<NESTI_F32>(f32x4& acc, const uint4& a, const uint4& b) {
-  // exact fp32: lane (row, kb) holds channels 4 kb .. 4 kb + 3 of the 16-channel chunk; A and B use the same order
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.x), __uint_as_float(b.x), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.y), __uint_as_float(b.y), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
-}
-
 // 16-B slot swizzle key of row r of a 16-row tile (see the header): with it the four row quads a ds_read_b128 lane group
 // touches land in four different 16-B columns of the 64-B row
 __device__ __forceinline__ int swz4(int r) { return (0x78 >> (2 * ((r >> 2) & 3))) & 3; }

@@ -16,10 +16,18 @@
 //     all k^3 taps and a tap's weight tile serves 4 points instead of one: a quarter of the weight stream per output;
 //   * the only per-lane padding test left is x + dx: an out-of-range lane reads an LDS address beyond the allocation, which
 //     returns zeros on gfx950 (scripts/lds_oob_probe.hip; checked at model creation, conv8_selftest), so no zero rows are kept;
-//   * a wave owns FOUR x-line tiles x TWO 32-column tiles, so that every A fragment read from LDS feeds two MFMAs (plain
-//     modes) or three + three (pair modes): 0.75 / 0.5 KB of LDS reads per MFMA (round 3: 1.125 / 0.75 with eight tiles x one
-//     column tile per wave, 2-5 % slower same-box; these kernels sit within ~10 % of the matrix pipe's own rate on such data,
-//     DESIGN.md 4.3).
+//   * a wave owns FOUR x-line tiles x TWO 32-column tiles, so that every A fragment read from LDS feeds two 32x32x16 MFMAs or
+//     three + three (pair modes): 0.75 / 0.5 KB of LDS reads per 32x32x16-sized product (round 3: 1.125 / 0.75 with eight tiles x
+//     one column tile per wave, 2-5 % slower same-box; these kernels sit within ~10 % of the matrix pipe's own rate on such data,
+//     DESIGN.md 4.3);
+//   * the plain f16 loop (MODE 0, M16) issues the same products as 16x16x32 MFMAs -- per (tile, tap) 2 row halves
+//     x 4 column quarters = 8 instructions instead of 4, from the SAME two A and four B ds_read_b128 per tap (a 16x16x32 lane holds
+//     16 B of one 64-B row: a tile's row half is one read, a column quarter one read), the same tiles, skips, barriers and
+//     128 accumulator registers.  Equal cycles per FLOP, but the chip holds a higher clock on this shape under load
+//     (profiles/r07_shape_probe.txt: the loop's skeleton 1.11x the FLOP/s on random data, in-kernel clock 2.04 against
+//     1.78 GHz); the gate's 5^3 / 3^3 launches run ~10 % faster.  The bf16 form would gain ~8 %, but the changed summation order
+//     moves the bf16 switching model's noise estimate across its threshold on a test query, so bf16 keeps
+//     32x32x16, like the exact-fp32 form (32x32x2f32) and the pair, X8 and X6 loops.
 //
 // Workgroup = 4 points x ONE z half of the output volume (z in [4h, 4h + 4)) x 64 output channels.  It stages the
 // NZ = 4 + k/2 source planes that half can reach (6 of 8 for k = 5: 96 KiB instead of 128) and 4 KiB of weights per tap.
@@ -36,8 +44,8 @@
 //
 // LDS: [0, 64 KiB) weight slots (3 x 20 KiB rows for k = 5, 2 x 24 KiB row pairs for k = 3), [64 KiB, 64 + 16 NZ KiB) the
 // input chunk; rows are 64 B with the 16-B slot XOR-swizzled by the point index (input) / (row >> 2) & 3 (weights), applied on
-// the DMA source address, which makes every ds_read_b128 lane group conflict-free.  The epilogue reuses the LDS as an fp32
-// staging tile.
+// the DMA source address, which makes every ds_read_b128 lane group conflict-free (M16: with the K-slot order of its per-lane
+// coordinates below).  The epilogue reuses the LDS as an fp32 staging tile.
 //
 // X3 (pair modes, model.hip: PackedLayer::x3n): the K chunk is 16 channels -- an LDS row holds [hi k0..15 | lo k0..15] of the
 // activation pair (staged from the two planes of the [hi 64 | lo 64] row groups) and a weight row [W_hi k0..15 | W_lo k0..15]
@@ -110,6 +118,7 @@ typedef int i32x8n_t __attribute__((ext_vector_type(8)));
 template <int DT, int K, int MODE>     // MODE 0: plain, 1: the pair K loop (X3), 2: f16 hi * W_hi + FP8 cross terms (X8), 3: the same with FP6 blocks (X6)
 __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned bid, const int tid_in) {
   constexpr bool X3 = MODE == 1, X8 = MODE >= 2, X6 = MODE == 3;
+  constexpr bool M16 = MODE == 0 && DT == NESTI_F16;   // the plain f16 loop runs on v_mfma_f32_16x16x32 (see the header)
   static_assert(!X8 || DT == NESTI_F16, "the FP8 cross-term loop is an f16 pair-mode variant");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int kEsz = (DT == NESTI_F32) ? 4 : 2;
@@ -194,12 +203,22 @@ __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned 
   };
 
   // ---- per-lane fragment coordinates ---------------------------------------------------------------------------
+  // 32x32x16 (f32x16 accumulators): lane = row l & 31 of the tile x 16-B slot khalf of the row; the second K-step (slot khalf + 2)
+  // sits 32 B above or below.  M16 (16x16x32, f32x4 accumulators): lane = row l & 15 of the tile's first 16-row half x the
+  // 16-B slot ks of lane group l >> 4, one K-step per 64-B row; the second half (rows 16 .. 31, points 2, 3: key ^ 2) sits
+  // 1024 +- 32 B away, a weight row's second 16 columns 1024 B.  The groups take the row's slots in the order {0, 3, 1, 2}
+  // (A and B alike, so the K sum is the same): with it every ds_read_b128 lane group ({0-3, 12-15, 20-27}, ...) meets each
+  // 16-B bank column once under BOTH row keys the staging and the weight packing apply (point index, (row >> 2) & 3) -- in
+  // the order {0, 1, 2, 3} the A and B reads are 2-way.
   const int l31 = lane & 31, khalf = lane >> 5;
-  const int pt = l31 >> 3, rx = l31 & 7;
-  const int a_sw = (khalf ^ pt) & 3, b_sw = (khalf ^ (l31 >> 2)) & 3;
+  const int lr = M16 ? (lane & 15) : l31;               // fragment row: A 8 pt + x, B the output column in its tile
+  const int ks = M16 ? (0x9C >> (2 * (lane >> 4))) & 3 : khalf;
+  const int pt = lr >> 3, rx = lr & 7;
+  const int a_sw = (ks ^ pt) & 3, b_sw = (ks ^ (lr >> 2)) & 3;
   const unsigned a_lane = lds0 + kAOffN + (unsigned)((pt * 8 + rx) * 64 + (a_sw << 4));
-  const unsigned b_lane = lds0 + (unsigned)(l31 * 64 + (b_sw << 4));
-  const unsigned a_d1 = (a_sw & 2) ? (unsigned)-32 : 32u, b_d1 = (b_sw & 2) ? (unsigned)-32 : 32u;
+  const unsigned b_lane = lds0 + (unsigned)(lr * 64 + (b_sw << 4));
+  const unsigned a_d1 = (M16 ? 1024u : 0u) + ((a_sw & 2) ? (unsigned)-32 : 32u);
+  const unsigned b_d1 = M16 ? 1024u : (b_sw & 2) ? (unsigned)-32 : 32u;
 
   // liveness of this wave's tiles: tile j is (y = (wave - z0 - j) & 7, z = z0 + j); 4 bits per dy / per dz
   unsigned ymask_pack = 0u, zmask_pack = 0u;
@@ -242,16 +261,21 @@ __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned 
     return (((wave + dyi + dzi - 2 * LO) & 7) * NZ + (z0 - zlo + dzi - LO)) * kTileN;
   };
 
-  f32x16 acc[4][2];
+  f32x16 acc[4][2];                                      // [x-line tile][32-column tile]
+  f32x4 acc4[4][2][4];                                   // M16: [x-line tile][16-row half][16-column quarter]; the other set is dead
 #pragma unroll
   for (int j = 0; j < 4; ++j)
 #pragma unroll
-    for (int n = 0; n < 2; ++n)
+    for (int n = 0; n < 2; ++n) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[j][n][r] = 0.f;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc4[j][n][q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
 
-  // b[u & 1] holds tap u's weight fragments [column tile][K-step, or hi / lo]; K is odd, so the last tap of a row leaves the
-  // next row's first set in b[1]: it is moved to b[0] once per row
+  // b[u & 1] holds tap u's weight fragments [column tile][K-step, or hi / lo; M16: its first / second 16 columns]; K is odd, so
+  // the last tap of a row leaves the next row's first set in b[1]: it is moved to b[0] once per row.  a[j] = [K-step, or hi / lo;
+  // M16: row half]
   uint4 a[4][2], b[2][2][2];
   auto load_b = [&](uint4 (&dst)[2][2], unsigned src) __attribute__((always_inline)) {
 #pragma unroll
@@ -261,13 +285,18 @@ __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned 
     }
   };
   auto tile_mma = [&](int j, const uint4 (&bc)[2][2]) __attribute__((always_inline)) {
-    if (X3) {   // hi * W_hi, lo * W_hi, hi * W_lo for both column tiles (a[j][0] = hi, a[j][1] = lo; bc[n][0] = W_hi, bc[n][1] = W_lo)
+    if constexpr (X3) {   // hi * W_hi, lo * W_hi, hi * W_lo for both column tiles (a[j][0] = hi, a[j][1] = lo; bc[n][0] = W_hi, bc[n][1] = W_lo)
       mma<DT>(acc[j][0], a[j][0], bc[0][0]);
       mma<DT>(acc[j][1], a[j][0], bc[1][0]);
       mma<DT>(acc[j][0], a[j][1], bc[0][0]);
       mma<DT>(acc[j][1], a[j][1], bc[1][0]);
       mma<DT>(acc[j][0], a[j][0], bc[0][1]);
       mma<DT>(acc[j][1], a[j][0], bc[1][1]);
+    } else if constexpr (M16) {   // row half h x column quarter q = 2 n + k: eight 16x16x32, K = the whole 64-B row
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) mma16<DT>(acc4[j][h][q], a[j][h], bc[q >> 1][q & 1]);
     } else {
       mma<DT>(acc[j][0], a[j][0], bc[0][0]);
       mma<DT>(acc[j][1], a[j][0], bc[1][0]);
@@ -521,16 +550,37 @@ __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned 
   auto epi_pass = [&](auto NN) __attribute__((always_inline)) {
     constexpr int n = decltype(NN)::value;
     const int n_tile = 2 * n_pair + n;
-    const float bv = p.bias[n_tile * 32 + l31];
     const int out_col0 = p.out_coff + n_tile * 32;
+    if constexpr (M16) {                                 // lane: columns 16 k + (l & 15), rows 16 h + 4 (l >> 4) + r
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {                        // z = z0 + j, y = (wave - z0 - j) & 7
-      const int y = (wave - z0 - j) & 7;
+      for (int k = 0; k < 2; ++k) {
+        const int col = 16 * k + (lane & 15);
+        const float bv = p.bias[n_tile * 32 + col];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = (r & 3) + 8 * (r >> 2) + 4 * khalf;      // MFMA row = 8 pt + x
-        const int row = ((((m >> 3) * 4 + j) * 8 + y) << 3) + (m & 7);
-        *reinterpret_cast<float*>(smem + row * kEpiStrideN + l31 * 4) = fmaxf(fmaf(acc[j][n][r], p.acc_scale, bv), act_floor);
+        for (int j = 0; j < 4; ++j) {                    // z = z0 + j, y = (wave - z0 - j) & 7
+          const int y = (wave - z0 - j) & 7;
+#pragma unroll
+          for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int m = 16 * h + 4 * (lane >> 4) + r;          // MFMA row = 8 pt + x
+              const int row = ((((m >> 3) * 4 + j) * 8 + y) << 3) + (m & 7);
+              *reinterpret_cast<float*>(smem + row * kEpiStrideN + col * 4) =
+                  fmaxf(fmaf(acc4[j][h][2 * n + k][r], p.acc_scale, bv), act_floor);
+            }
+        }
+      }
+    } else {
+      const float bv = p.bias[n_tile * 32 + l31];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {                      // z = z0 + j, y = (wave - z0 - j) & 7
+        const int y = (wave - z0 - j) & 7;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int m = (r & 3) + 8 * (r >> 2) + 4 * khalf;    // MFMA row = 8 pt + x
+          const int row = ((((m >> 3) * 4 + j) * 8 + y) << 3) + (m & 7);
+          *reinterpret_cast<float*>(smem + row * kEpiStrideN + l31 * 4) = fmaxf(fmaf(acc[j][n][r], p.acc_scale, bv), act_floor);
+        }
       }
     }
     __syncthreads();

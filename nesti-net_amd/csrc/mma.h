@@ -1,4 +1,4 @@
-// MFMA / LDS-DMA primitives shared by the conv kernels (conv.hip, conv8n.hip).  gfx950 only.
+// MFMA / LDS-DMA primitives shared by the conv kernels (conv.hip, conv8n.hip, conv4n.hip).  gfx950 only.
 #pragma once
 #include "kernels.h"
 
@@ -8,6 +8,7 @@ namespace {
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 template <int DT> __device__ __forceinline__ void mma(f32x16& acc, const uint4& a, const uint4& b);
 template <> __device__ __forceinline__ void mma<NESTI_BF16>(f32x16& acc, const uint4& a, const uint4& b) {
@@ -21,6 +22,21 @@ template <> __device__ __forceinline__ void mma<NESTI_F32>(f32x16& acc, const ui
   acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.y), __uint_as_float(b.y), acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
+}
+
+template <int DT> __device__ __forceinline__ void mma16(f32x4& acc, const uint4& a, const uint4& b);
+template <> __device__ __forceinline__ void mma16<NESTI_BF16>(f32x4& acc, const uint4& a, const uint4& b) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
+}
+template <> __device__ __forceinline__ void mma16<NESTI_F16>(f32x4& acc, const uint4& a, const uint4& b) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
+}
+template <> __device__ __forceinline__ void mma16<NESTI_F32>(f32x4& acc, const uint4& a, const uint4& b) {
+  // exact fp32 (conv4n.hip): lane (row, kb) holds channels 4 kb .. 4 kb + 3 of the 16-channel chunk; A and B use the same order
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.x), __uint_as_float(b.x), acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.y), __uint_as_float(b.y), acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
 }
 
 typedef __attribute__((address_space(3))) unsigned char* lptr_t;

@@ -405,6 +405,64 @@ uint32_t nesti_crc32c(const void* data, size_t n, uint32_t crc);
  * checked against the instruction's own decoding without a device (tests/test_abi.py; scripts/fp6_probe.hip holds the device side). */
 int nesti_f32_to_e2m3(float value, float inv_scale);
 
+/* ---- test hooks: one tower, launch by launch (no reference counterpart) -------------------------------------------
+ * The per-layer conformance tests (tests/test_gpu_layers.py) check every conv and pool launch against an fp64 evaluation of
+ * the same layer on the launch's own input.  nesti_debug_tower_ops describes a tower's buffers and launches from the
+ * configuration alone (no device): where run_tower places every buffer in the tower workspace for `batch` queries, and what
+ * every launch reads, computes and writes.  nesti_debug_tower_step runs launch `op` of that tower ALONE, on a caller
+ * workspace laid out as described; steps 0 .. n_ops - 1 in order are exactly the product's tower pass. */
+enum { NESTI_DEBUG_OP_CONV = 0, NESTI_DEBUG_OP_MAX = 1 /* max_pool3d 2^3 stride 2 */, NESTI_DEBUG_OP_MAX3 = 2 /* 3^3 stride 2 SAME, 3^3 grid */ };
+enum { NESTI_DEBUG_FORM_PLAIN = 0, /* one product of f32 / f16 / bf16 elements                                          */
+       NESTI_DEBUG_FORM_PAIR = 1,  /* hi W_hi + lo W_hi + hi W_lo (NESTI_F16X3 / NESTI_BF16X3; lo W_lo is dropped)         */
+       NESTI_DEBUG_FORM_X2 = 2,    /* plain 16-bit activations times the pair-packed weights: hi (W_hi + W_lo) (filter pass) */
+       NESTI_DEBUG_FORM_X8 = 3,    /* hi W_hi in f16 + the cross terms as e4m3 products (NESTI_F16X8 experts, format 8)     */
+       NESTI_DEBUG_FORM_X6 = 4 };  /* ... as block-scaled e2m3 products (format 6)                                          */
+typedef struct {
+  int fast;     /* 1: the two-stage gate's plain-f16 filter pass (gating net of NESTI_F16X3C / NESTI_F16X8C models)          */
+  int x8_mask;  /* expert towers of NESTI_F16X8 / NESTI_F16X8C models: the tap layers that take the narrow cross terms
+                 * (nesti_model_set_x8_layers; 0 = f16x3 proper)                                                           */
+  int x8_fmt;   /* 8 or 6 (nesti_model_set_x8_format); 0 = 6.  nesti_debug_tower_step refuses a format the model does not run */
+} nesti_debug_pass_t;
+typedef struct {
+  int64_t offset;  /* byte offset in the tower workspace; -1 for buffer 0, the caller's MuPS tensor                     */
+  int64_t bytes;   /* bytes reserved for it (0: buffer 0, or a buffer this tower never uses)                            */
+  int log2S;       /* rows per query: 2^(3 log2S), row = query * 2^(3 log2S) + voxel, channels last                     */
+  int C;           /* logical channels of a row (zero-padded to 64)                                                     */
+  int f32, aux8;   /* f32: a tower output in f32; aux8: a side buffer of cross-term codes, 2 bytes per channel          */
+  int planes;      /* 2: pair layout (per 64-channel group [hi 64 | lo 64]); else 1                                     */
+  int elem;        /* NESTI_F32 / NESTI_F16 / NESTI_BF16; -1 for aux8                                                    */
+  int first, last; /* lifetime: the first op that writes it, the last op that reads it (n_ops: the tower's output)       */
+} nesti_debug_buf_t;
+typedef struct {
+  int kind;             /* NESTI_DEBUG_OP_*                                                                          */
+  int family;           /* conv: 0 conv_igemm_kernel, 2 conv8n_kernel, 3 conv4n_kernel; pools: -1                     */
+  int form;             /* NESTI_DEBUG_FORM_* (pools: PLAIN or PAIR, the layout of their values)                      */
+  int elem, planes;     /* element type and planes of the op's 16-bit / f32 activations                              */
+  int layer;            /* conv: index of the layer in the model                                                     */
+  const char* scope;    /* conv: TF scope; valid until the next call on this thread                                  */
+  const char* scope2;   /* conv: "" or the fused 1x1x1 layer whose columns start at out_coff2 (conv4 of an inception) */
+  int k, log2S, s_real, is_fc, bn, relu, pool_k, n_taps;
+  int cin, cout, Cin_p, Cout_p;
+  int in_pos_off;       /* conv: in_pos[in_pos_off + c] = padded input channel (relative to in_coff) of real channel c */
+  int in_buf, in_coff, in_cstride, in_planes;   /* in_cstride: logical channels of an input row (a flattened view for fc1) */
+  int out_buf, out_coff, out_coff2, out_f32;
+  int mp_buf, mp_mode, mp_mode2;   /* fused 2^3 max-pool epilogue (kernels.h: ConvParams::mp_mode / mp_mode2)          */
+  int aux_in_buf, aux_layer;       /* X8 / X6: the side buffer read and the layer that wrote it (else -1)              */
+  int aux_out_buf;                 /* a producer in this pass: the side buffer it writes (else -1)                     */
+  int C;                /* pools: channels                                                                           */
+} nesti_debug_op_t;
+/* tower -1 = gating net, 0..E-1 an expert; dtype as nesti_model_create; pass NULL = the model's main pass.  Array arguments
+ * may be NULL (counts only); *ws_bytes = the tower workspace run_tower needs.  Host only. */
+int nesti_debug_tower_ops(const nesti_config_t* cfg, int dtype, int tower, int batch, const nesti_debug_pass_t* pass,
+                          nesti_debug_buf_t* bufs, int max_bufs, int* n_bufs, nesti_debug_op_t* ops, int max_ops, int* n_ops,
+                          int32_t* in_pos, int max_in_pos, int* n_in_pos, size_t* ws_bytes);
+/* Launch `op` of the tower on ws_dev (laid out for capacity `batch`), reading the MuPS tensor mups_dev.  The routed form
+ * (experts): point_index_dev gathers the MuPS rows, npoints_dev holds the live count (both NULL: rows 0 .. batch - 1).
+ * walk: 0, 1 (the default walking grid) or a multiple of 8 workgroups (kernels.h: ConvParams::walk). */
+int nesti_debug_tower_step(const nesti_model_t* m, int tower, const nesti_debug_pass_t* pass, int op, const void* mups_dev, int batch,
+                           const int32_t* point_index_dev, const int32_t* npoints_dev, int walk, void* ws_dev, size_t ws_bytes,
+                           void* stream);
+
 /* ---- measurement support (bench.py's roofline leg; no reference counterpart) ------------
  * nesti_profile_enable(1) makes every kernel launch of the forward path record a pair of
  * hipEvents on its stream; nesti_profile_read() synchronises on them and returns, per

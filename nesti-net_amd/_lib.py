@@ -40,6 +40,28 @@ class CX8GuardStats(ctypes.Structure):
                 ("max_dn", ctypes.c_float), ("thr", ctypes.c_float), ("thr_eff", ctypes.c_float)]
 
 
+class CDebugPass(ctypes.Structure):
+    """Mirror of ``nesti_debug_pass_t``."""
+    _fields_ = [("fast", ctypes.c_int), ("x8_mask", ctypes.c_int), ("x8_fmt", ctypes.c_int)]
+
+
+class CDebugBuf(ctypes.Structure):
+    """Mirror of ``nesti_debug_buf_t``."""
+    _fields_ = [("offset", ctypes.c_int64), ("bytes", ctypes.c_int64)] + \
+               [(n, ctypes.c_int) for n in ("log2S", "C", "f32", "aux8", "planes", "elem", "first", "last")]
+
+
+class CDebugOp(ctypes.Structure):
+    """Mirror of ``nesti_debug_op_t``."""
+    _fields_ = [(n, ctypes.c_int) for n in ("kind", "family", "form", "elem", "planes", "layer")] + \
+               [("scope", ctypes.c_char_p), ("scope2", ctypes.c_char_p)] + \
+               [(n, ctypes.c_int) for n in ("k", "log2S", "s_real", "is_fc", "bn", "relu", "pool_k", "n_taps",
+                                            "cin", "cout", "Cin_p", "Cout_p", "in_pos_off",
+                                            "in_buf", "in_coff", "in_cstride", "in_planes", "out_buf", "out_coff", "out_coff2",
+                                            "out_f32", "mp_buf", "mp_mode", "mp_mode2", "aux_in_buf", "aux_layer", "aux_out_buf",
+                                            "C")]
+
+
 X8_GUARD_BAR, X8_GUARD_WIDEN, X8_GUARD_DEFAULT = 2.5e-6, 1.5, 0.25   # NESTI_X8_GUARD_* (include/nesti_hip.h)
 GATE_WIDEN = 1.5      # NESTI_GATE_WIDEN (include/nesti_hip.h)
 GATE_WIDEN_PASSES = 3  # NESTI_GATE_WIDEN_PASSES
@@ -97,6 +119,10 @@ SIGNATURES = {
                                     _vp, _sz, _vp, _vp, _vp, _vp]),
     "nesti_crc32c": (ctypes.c_uint32, [_vp, _sz, ctypes.c_uint32]),
     "nesti_f32_to_e2m3": (_i, [ctypes.c_float, ctypes.c_float]),
+    "nesti_debug_tower_ops": (_i, [_cfgp, _i, _i, _i, ctypes.POINTER(CDebugPass), ctypes.POINTER(CDebugBuf), _i, ctypes.POINTER(_i),
+                                   ctypes.POINTER(CDebugOp), _i, ctypes.POINTER(_i), _vp, _i, ctypes.POINTER(_i),
+                                   ctypes.POINTER(_sz)]),
+    "nesti_debug_tower_step": (_i, [_vp, _i, ctypes.POINTER(CDebugPass), _i, _vp, _i, _vp, _vp, _i, _vp, _sz, _vp]),
     "nesti_write_text_f32": (_i, [ctypes.c_char_p, _vp, ctypes.c_int64, _i]),
     "nesti_write_text_i32": (_i, [ctypes.c_char_p, _vp, ctypes.c_int64]),
     "nesti_estimate_normals_multi": (_i, [_vp, ctypes.POINTER(CShapeQueries), _i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),

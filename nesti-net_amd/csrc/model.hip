@@ -617,6 +617,18 @@ bool use_conv4(const LayerDesc& d, int dtype) {
   return act_planes(dtype) == 1 || !(d.k & 1);   // pair modes: the even kernels only (conv4n.hip: launch_conv4n_dt)
 }
 
+// PackedLayer::kind of a layer packed for `dtype` (pack_layer)
+int layer_kind(const LayerDesc& d, int dtype) { return use_conv8(d) ? 2 : use_conv4(d, dtype) ? 3 : 0; }
+// PackedLayer::n_taps: the k^3 taps that can land inside the volume (pack_layer keeps only those)
+int layer_taps(const LayerDesc& d) {
+  const int S = d.s_real ? d.s_real : (1 << d.log2S), lo = (d.k - 1) / 2;
+  int n = 0;
+  for (int a = 0; a < d.k; ++a)
+    for (int bb = 0; bb < d.k; ++bb)
+      for (int c = 0; c < d.k; ++c) n += abs(a - lo) < S && abs(bb - lo) < S && abs(c - lo) < S;
+  return n;
+}
+
 // Error attribution in the pair modes (scripts/exp_attribution.py), ONLY in builds made with -DNESTI_ATTRIBUTION (the product
 // library has no such switch): NESTI_X3_PLAIN = "regex,regex,..." -- a layer whose scope matches drops the hi * W_lo product
 // (its W_lo weights are packed as zeros: the layer then sees its weights rounded to 16 bits).  Round 3's full sweep
@@ -839,7 +851,7 @@ int pack_layer(const LayerDesc& d, const TensorTable& tt, int dtype, PackedLayer
   // plain chunk holds (the kernels' pair K loop multiplies hi*W_hi + lo*W_hi + hi*W_lo from it: conv.hip / conv8n.hip, X3)
   const int planes = act_planes(dtype);
   const int drop = planes > 1 ? x3_drop_mask(d) : 0;
-  pl->kind = use_conv8(d) ? 2 : use_conv4(d, dtype) ? 3 : 0;
+  pl->kind = layer_kind(d, dtype);
   if (pl->kind >= 2 && d.Cout_p % 64) NESTI_FAIL("internal: conv8n_kernel / conv4n_kernel need 64-column tiles");
   pl->x3n = planes > 1;
   const int K_phys = d.Cin_p * planes;
@@ -947,6 +959,7 @@ size_t buf_bytes(const BufSpec& b, int NB, int dtype) {
 // brings the gating tower from 2.5 to 1.6 MB per query in 16-bit and lets one library batch cover a 100k-point cloud.
 struct Placement {
   std::vector<size_t> off;   // per buffer (index 0 = the external MuPS tensor: unused)
+  std::vector<int> first, last;   // per buffer: the first op that writes it, the last op that reads it (n_ops: the tower's output)
   size_t total = 0;
 };
 Placement place_tower(const Tower& T, int NB, int dtype) {
@@ -967,6 +980,7 @@ Placement place_tower(const Tower& T, int NB, int dtype) {
   std::vector<Block> live, freeb;
   Placement P;
   P.off.assign(n, 0);
+  P.first = first; P.last = last;
   for (int i : order) {
     // release what is no longer read, coalescing neighbours
     for (size_t j = 0; j < live.size();) {
@@ -1038,93 +1052,106 @@ struct RunCtx {
                                  // FP8 cross-term loop; their block's conv1 then also writes the e4m3 planes)
 };
 
-int run_tower(const RunCtx& rc, const Tower& T, const void* X0, unsigned char* ws, size_t ws_bytes, float** out) {
+// The buffers of a tower in a workspace laid out by place_tower (ptr[0] = the MuPS tensor X0 the tower reads)
+int tower_ptrs(const RunCtx& rc, const Tower& T, const void* X0, unsigned char* ws, size_t ws_bytes, std::vector<unsigned char*>* ptr) {
+  const int dtype = rc.fast ? NESTI_F16 : rc.m->dtype;
+  ptr->assign(T.bufs.size(), nullptr);
+  (*ptr)[0] = (unsigned char*)X0;
+  const Placement P = place_tower(T, rc.NB, dtype);
+  for (size_t i = 1; i < T.bufs.size(); ++i) (*ptr)[i] = ws + P.off[i];
+  if (P.total > ws_bytes) NESTI_FAIL("workspace too small for this batch");
+  return 0;
+}
+
+// One launch of a tower: the body of run_tower's loop, also reached alone through nesti_debug_tower_step
+int run_op(const RunCtx& rc, const Tower& T, const Op& op, const std::vector<unsigned char*>& ptr) {
   const int dtype = rc.fast ? NESTI_F16 : rc.m->dtype;
   const int x0_planes = act_planes(rc.m->dtype);
-  std::vector<unsigned char*> ptr(T.bufs.size(), nullptr);
-  ptr[0] = (unsigned char*)X0;
-  const Placement P = place_tower(T, rc.NB, dtype);
-  for (size_t i = 1; i < T.bufs.size(); ++i) ptr[i] = ws + P.off[i];
-  if (P.total > ws_bytes) NESTI_FAIL("workspace too small for this batch");
-  for (const Op& op : T.ops) {
-    const bool ext_in = op.in_buf < 1;
-    if (op.kind == Op::CONV) {
-      const LayerDesc& d = rc.m->graph.layers[op.layer];
-      const bool mixl = !rc.fast && rc.mix && op.layer < (int)rc.m->packed_mix.size() && rc.m->packed_mix[op.layer].wpk &&
-                        ((rc.mix >> rc.m->packed_mix[op.layer].mix_bit) & 1);
-      // NESTI_F16X3C filter pass: its one-tap layers (1x1x1 conv1|conv4, FC) multiply the plain-f16 activations by the model's own
-      // PAIR-packed weights (conv_igemm_kernel's X2 loop: hi * W_hi + hi * W_lo).  Those layers are fill-bound, so the second product
-      // costs ~20 % more weight-tile fill and no matrix-pipe time that shows, and it removes the weight-rounding part of their error:
-      // the filter's sigma on a logit difference drops from 0.021 to 0.012 (profiles/r05_gate_medium.txt), the threshold with it
-      const bool x2l = rc.fast && rc.m->packed_fast[op.layer].wpk == nullptr;
-      const bool x8l = !rc.fast && !mixl && op.aux_in_buf >= 0 && op.x8_bit >= 0 && ((rc.x8 >> op.x8_bit) & 1) &&
-                       op.layer < (int)rc.m->packed_x8.size() && rc.m->packed_x8[op.layer].wpk;
-      const bool x6 = rc.m->x8_fmt == 6;
-      const PackedLayer& pl = x2l ? rc.m->packed[op.layer] : rc.fast ? rc.m->packed_fast[op.layer]
-                              : mixl ? rc.m->packed_mix[op.layer] : x8l ? (x6 ? rc.m->packed_x6 : rc.m->packed_x8)[op.layer] : rc.m->packed[op.layer];
-      ConvParams p;
-      memset(&p, 0, sizeof(p));
-      p.in_pair = mixl ? 1 : 0;
-      p.x2 = x2l ? 1 : 0;
-      p.in = ptr[op.in_buf]; p.out = ptr[op.out_buf]; p.wpk = pl.wpk; p.bias = pl.bias;
-      p.npoints_ptr = rc.npoints_ptr; p.point_index = ext_in ? rc.point_index : nullptr;
-      p.npoints = rc.NB;
-      // pair modes: strides and the input offset are physical (a 64-aligned logical offset x 3), output column
-      // offsets stay logical (kernels.h: ConvParams::split); an fp32 output buffer is an ordinary one
-      const int planes = act_planes(dtype);
-      p.split = planes > 1 ? (rc.zero_lo ? 2 : 1) : 0;
-      const int in_planes = ext_in ? x0_planes : planes;
-      p.in_cstride = (op.in_cstride ? op.in_cstride : T.bufs[op.in_buf].C) * in_planes; p.in_coff = op.in_coff * in_planes;
-      // distance between consecutive K chunks of a PLAIN kernel's input row: 128 B, except in the NESTI_F16X3C filter pass,
-      // whose plain-f16 first layer reads the hi plane of each 64-channel group [hi | lo] of the pair-layout MuPS tensor
-      p.in_chunk_bytes = kRowBytes * (planes == 1 ? in_planes : 1);
-      p.out_cstride = T.bufs[op.out_buf].C * (op.out_f32 ? 1 : planes); p.out_coff = op.out_coff;
-      p.n_chunks = pl.n_chunks; p.n_taps = pl.n_taps; p.tap_k = d.k; p.log2S = d.log2S; p.s_real = d.s_real;
-      p.relu = d.relu ? 1 : 0; p.out_f32 = op.out_f32 ? 1 : 0; p.acc_scale = pl.acc_scale; p.x3native = (pl.x3n && !x2l) ? 1 : 0;
-      const long long rows = (long long)rc.NB << (3 * d.log2S);
-      p.m_tiles = pl.kind == 3 ? (rc.NB + 15) / 16 : pl.kind == 2 ? (rc.NB + 3) / 4 : (int)((rows + kTileM - 1) / kTileM);
-      p.n_tiles = pl.n_tiles; p.split_tile = pl.split_tile; p.out_coff2 = op.out_coff2; p.pool_k = d.pool_k;
-      if (op.mp_buf >= 0) { p.mp_out = ptr[op.mp_buf]; p.mp_cstride = T.bufs[op.mp_buf].C * planes; p.mp_mode = op.mp_mode; p.mp_mode2 = op.mp_mode2; }
-      if (x8l) {                                   // consumer: the FP8 cross-term loop on the planes the block's conv1 wrote
-        const int sc = rc.m->packed[op.aux_layer].x8_sc;
-        p.x8 = 1; p.aux8_in = ptr[op.aux_in_buf]; p.aux8_stride = T.bufs[op.aux_in_buf].C * 2;
-        p.x8_scale_a = 127 - (sc + 11); p.x8_scale_b = 127 - pl.x8_sb;
-        p.x8_fmt = x6 ? 6 : 8;
-      }
-      if (!rc.fast && op.aux_out_buf >= 0 && (rc.x8 & op.x8_bits) && !rc.m->packed_x8.empty()) {   // producer
-        p.aux8_out = ptr[op.aux_out_buf]; p.aux8_stride = T.bufs[op.aux_out_buf].C * 2;
-        p.x8_sc = rc.m->packed[op.layer].x8_sc; p.x8_sa = p.x8_sc + 11;
-        p.x8_fmt = x6 ? 6 : 8;
-      }
-      memcpy(p.tap, pl.tap, sizeof(p.tap));
-      p.remap = conv_remap(d.k, d.log2S, pl.n_taps);
-      p.walk = rc.walk;
-      const int cat = conv_category(d, pl);
-      const int tok = prof_begin(cat, rc.stream);
-      // (a mixed layer is a plain f16 / bf16 kernel inside a pair-mode tower: kernel_dtype is the same element type either way)
-      const int rcv = pl.kind == 2   ? launch_conv8n(p, kernel_dtype(dtype), d.k, rc.stream)
-                      : pl.kind == 3 ? launch_conv4n(p, kernel_dtype(dtype), d.k, rc.stream)
-                                     : launch_conv(p, kernel_dtype(dtype), pl.TN, rc.stream);
-      prof_end(cat, tok, rc.stream);
-      if (rcv) return 1;
-    } else {
-      PoolParams p;
-      memset(&p, 0, sizeof(p));
-      p.in = ptr[op.in_buf]; p.out = ptr[op.out_buf];
-      p.npoints_ptr = rc.npoints_ptr;
-      p.npoints = rc.NB;
-      const int planes = act_planes(dtype);
-      p.split = planes > 1 ? 1 : 0;
-      p.in_cstride = T.bufs[op.in_buf].C * planes; p.in_coff = op.in_coff;
-      p.out_cstride = T.bufs[op.out_buf].C * planes; p.out_coff = op.out_coff;
-      p.C = op.C; p.log2S = op.log2S;
-      const int tok = prof_begin(NESTI_PROF_POOL, rc.stream);
-      const int rcp = op.kind == Op::MAX3 ? launch_maxpool3s2(p, kernel_dtype(dtype), rc.stream)
-                                          : launch_maxpool2(p, kernel_dtype(dtype), rc.stream);
-      prof_end(NESTI_PROF_POOL, tok, rc.stream);
-      if (rcp) return 1;
+  const bool ext_in = op.in_buf < 1;
+  if (op.kind == Op::CONV) {
+    const LayerDesc& d = rc.m->graph.layers[op.layer];
+    const bool mixl = !rc.fast && rc.mix && op.layer < (int)rc.m->packed_mix.size() && rc.m->packed_mix[op.layer].wpk &&
+                      ((rc.mix >> rc.m->packed_mix[op.layer].mix_bit) & 1);
+    // NESTI_F16X3C filter pass: its one-tap layers (1x1x1 conv1|conv4, FC) multiply the plain-f16 activations by the model's own
+    // PAIR-packed weights (conv_igemm_kernel's X2 loop: hi * W_hi + hi * W_lo).  Those layers are fill-bound, so the second product
+    // costs ~20 % more weight-tile fill and no matrix-pipe time that shows, and it removes the weight-rounding part of their error:
+    // the filter's sigma on a logit difference drops from 0.021 to 0.012 (profiles/r05_gate_medium.txt), the threshold with it
+    const bool x2l = rc.fast && rc.m->packed_fast[op.layer].wpk == nullptr;
+    const bool x8l = !rc.fast && !mixl && op.aux_in_buf >= 0 && op.x8_bit >= 0 && ((rc.x8 >> op.x8_bit) & 1) &&
+                     op.layer < (int)rc.m->packed_x8.size() && rc.m->packed_x8[op.layer].wpk;
+    const bool x6 = rc.m->x8_fmt == 6;
+    const PackedLayer& pl = x2l ? rc.m->packed[op.layer] : rc.fast ? rc.m->packed_fast[op.layer]
+                            : mixl ? rc.m->packed_mix[op.layer] : x8l ? (x6 ? rc.m->packed_x6 : rc.m->packed_x8)[op.layer] : rc.m->packed[op.layer];
+    ConvParams p;
+    memset(&p, 0, sizeof(p));
+    p.in_pair = mixl ? 1 : 0;
+    p.x2 = x2l ? 1 : 0;
+    p.in = ptr[op.in_buf]; p.out = ptr[op.out_buf]; p.wpk = pl.wpk; p.bias = pl.bias;
+    p.npoints_ptr = rc.npoints_ptr; p.point_index = ext_in ? rc.point_index : nullptr;
+    p.npoints = rc.NB;
+    // pair modes: strides and the input offset are physical (a 64-aligned logical offset x 3), output column
+    // offsets stay logical (kernels.h: ConvParams::split); an fp32 output buffer is an ordinary one
+    const int planes = act_planes(dtype);
+    p.split = planes > 1 ? (rc.zero_lo ? 2 : 1) : 0;
+    const int in_planes = ext_in ? x0_planes : planes;
+    p.in_cstride = (op.in_cstride ? op.in_cstride : T.bufs[op.in_buf].C) * in_planes; p.in_coff = op.in_coff * in_planes;
+    // distance between consecutive K chunks of a PLAIN kernel's input row: 128 B, except in the NESTI_F16X3C filter pass,
+    // whose plain-f16 first layer reads the hi plane of each 64-channel group [hi | lo] of the pair-layout MuPS tensor
+    p.in_chunk_bytes = kRowBytes * (planes == 1 ? in_planes : 1);
+    p.out_cstride = T.bufs[op.out_buf].C * (op.out_f32 ? 1 : planes); p.out_coff = op.out_coff;
+    p.n_chunks = pl.n_chunks; p.n_taps = pl.n_taps; p.tap_k = d.k; p.log2S = d.log2S; p.s_real = d.s_real;
+    p.relu = d.relu ? 1 : 0; p.out_f32 = op.out_f32 ? 1 : 0; p.acc_scale = pl.acc_scale; p.x3native = (pl.x3n && !x2l) ? 1 : 0;
+    const long long rows = (long long)rc.NB << (3 * d.log2S);
+    p.m_tiles = pl.kind == 3 ? (rc.NB + 15) / 16 : pl.kind == 2 ? (rc.NB + 3) / 4 : (int)((rows + kTileM - 1) / kTileM);
+    p.n_tiles = pl.n_tiles; p.split_tile = pl.split_tile; p.out_coff2 = op.out_coff2; p.pool_k = d.pool_k;
+    if (op.mp_buf >= 0) { p.mp_out = ptr[op.mp_buf]; p.mp_cstride = T.bufs[op.mp_buf].C * planes; p.mp_mode = op.mp_mode; p.mp_mode2 = op.mp_mode2; }
+    if (x8l) {                                   // consumer: the FP8 cross-term loop on the planes the block's conv1 wrote
+      const int sc = rc.m->packed[op.aux_layer].x8_sc;
+      p.x8 = 1; p.aux8_in = ptr[op.aux_in_buf]; p.aux8_stride = T.bufs[op.aux_in_buf].C * 2;
+      p.x8_scale_a = 127 - (sc + 11); p.x8_scale_b = 127 - pl.x8_sb;
+      p.x8_fmt = x6 ? 6 : 8;
     }
+    if (!rc.fast && op.aux_out_buf >= 0 && (rc.x8 & op.x8_bits) && !rc.m->packed_x8.empty()) {   // producer
+      p.aux8_out = ptr[op.aux_out_buf]; p.aux8_stride = T.bufs[op.aux_out_buf].C * 2;
+      p.x8_sc = rc.m->packed[op.layer].x8_sc; p.x8_sa = p.x8_sc + 11;
+      p.x8_fmt = x6 ? 6 : 8;
+    }
+    memcpy(p.tap, pl.tap, sizeof(p.tap));
+    p.remap = conv_remap(d.k, d.log2S, pl.n_taps);
+    p.walk = rc.walk;
+    const int cat = conv_category(d, pl);
+    const int tok = prof_begin(cat, rc.stream);
+    // (a mixed layer is a plain f16 / bf16 kernel inside a pair-mode tower: kernel_dtype is the same element type either way)
+    const int rcv = pl.kind == 2   ? launch_conv8n(p, kernel_dtype(dtype), d.k, rc.stream)
+                    : pl.kind == 3 ? launch_conv4n(p, kernel_dtype(dtype), d.k, rc.stream)
+                                   : launch_conv(p, kernel_dtype(dtype), pl.TN, rc.stream);
+    prof_end(cat, tok, rc.stream);
+    if (rcv) return 1;
+  } else {
+    PoolParams p;
+    memset(&p, 0, sizeof(p));
+    p.in = ptr[op.in_buf]; p.out = ptr[op.out_buf];
+    p.npoints_ptr = rc.npoints_ptr;
+    p.npoints = rc.NB;
+    const int planes = act_planes(dtype);
+    p.split = planes > 1 ? 1 : 0;
+    p.in_cstride = T.bufs[op.in_buf].C * planes; p.in_coff = op.in_coff;
+    p.out_cstride = T.bufs[op.out_buf].C * planes; p.out_coff = op.out_coff;
+    p.C = op.C; p.log2S = op.log2S;
+    const int tok = prof_begin(NESTI_PROF_POOL, rc.stream);
+    const int rcp = op.kind == Op::MAX3 ? launch_maxpool3s2(p, kernel_dtype(dtype), rc.stream)
+                                        : launch_maxpool2(p, kernel_dtype(dtype), rc.stream);
+    prof_end(NESTI_PROF_POOL, tok, rc.stream);
+    if (rcp) return 1;
   }
+  return 0;
+}
+
+int run_tower(const RunCtx& rc, const Tower& T, const void* X0, unsigned char* ws, size_t ws_bytes, float** out) {
+  std::vector<unsigned char*> ptr;
+  if (tower_ptrs(rc, T, X0, ws, ws_bytes, &ptr)) return 1;
+  for (const Op& op : T.ops)
+    if (run_op(rc, T, op, ptr)) return 1;
   *out = reinterpret_cast<float*>(ptr[T.out_buf]);
   return 0;
 }
@@ -1897,4 +1924,122 @@ int nesti_model_macs(const nesti_model_t* m, int tower, int kind, double* nomina
   return 0;
 }
 
+// ---- test hooks: one tower, launch by launch (include/nesti_hip.h) ----------------------------------------------------------
+static const nesti_debug_pass_t kMainPass = {0, 0, 0};
+
+int nesti_debug_tower_ops(const nesti_config_t* cfg, int dtype, int tower, int batch, const nesti_debug_pass_t* pass,
+                          nesti_debug_buf_t* bufs, int max_bufs, int* n_bufs, nesti_debug_op_t* ops, int max_ops, int* n_ops,
+                          int32_t* in_pos, int max_in_pos, int* n_in_pos, size_t* ws_bytes) {
+  if (!cfg || !n_bufs || !n_ops) NESTI_FAIL("nesti_debug_tower_ops: null argument");
+  if (batch <= 0) NESTI_FAIL("nesti_debug_tower_ops: batch must be positive");
+  const nesti_debug_pass_t& ps = pass ? *pass : kMainPass;
+  Graph g;
+  if (build_graph(cfg, &g, dtype_x8(dtype))) return 1;
+  if (tower < -1 || tower >= (int)g.experts.size()) NESTI_FAIL("nesti_debug_tower_ops: tower must be -1 (gate) or an expert index");
+  if (tower < 0 && g.cfg.arch != NESTI_ARCH_EXPERTS && g.cfg.arch != NESTI_ARCH_SWITCH) NESTI_FAIL("nesti_debug_tower_ops: this model has no gating net");
+  if (ps.fast && !(dtype_cascade(dtype) && tower < 0))
+    NESTI_FAIL("nesti_debug_tower_ops: the filter pass is the gating net's of NESTI_F16X3C / NESTI_F16X8C models");
+  if (ps.x8_mask < 0 || ps.x8_mask > 0xF || (ps.x8_mask && !(g.x8 && tower >= 0)))
+    NESTI_FAIL("nesti_debug_tower_ops: x8_mask has four bits and applies to the expert towers of NESTI_F16X8 / NESTI_F16X8C models");
+  if (ps.x8_fmt != 0 && ps.x8_fmt != 6 && ps.x8_fmt != 8) NESTI_FAIL("nesti_debug_tower_ops: x8_fmt is 0 (= 6), 6 or 8");
+  const Tower& T = tower < 0 ? g.gate : g.experts[tower];
+  const int mdt = main_dtype(dtype), dt = ps.fast ? NESTI_F16 : mdt;   // as run_op
+  const int planes = act_planes(dt);
+  const Placement P = place_tower(T, batch, dt);
+  int npos = 0;
+  for (const Op& op : T.ops) if (op.kind == Op::CONV) npos += g.layers[op.layer].cin;
+  *n_bufs = (int)T.bufs.size();
+  *n_ops = (int)T.ops.size();
+  if (n_in_pos) *n_in_pos = npos;
+  if (ws_bytes) *ws_bytes = P.total;
+  if ((bufs && max_bufs < *n_bufs) || (ops && max_ops < *n_ops) || (in_pos && max_in_pos < npos))
+    NESTI_FAIL("nesti_debug_tower_ops: output arrays too small");
+  for (int i = 0; bufs && i < *n_bufs; ++i) {
+    const BufSpec& b = T.bufs[i];
+    nesti_debug_buf_t& o = bufs[i];
+    memset(&o, 0, sizeof(o));
+    o.offset = i == 0 ? -1 : (int64_t)P.off[i];
+    o.bytes = i == 0 || P.last[i] < 0 ? 0 : (int64_t)buf_bytes(b, batch, dt);
+    o.log2S = b.log2S; o.C = b.C; o.f32 = b.f32; o.aux8 = b.aux8;
+    o.planes = b.aux8 || b.f32 ? 1 : act_planes(i == 0 ? mdt : dt);
+    o.elem = b.aux8 ? -1 : b.f32 ? NESTI_F32 : kernel_dtype(i == 0 ? mdt : dt);
+    o.first = i == 0 ? -1 : P.first[i] == (1 << 30) ? -1 : P.first[i];
+    o.last = P.last[i];
+  }
+  static thread_local std::vector<std::string> names;
+  names.clear();
+  names.reserve(2 * T.ops.size());
+  int pos = 0;
+  for (int k = 0; ops && k < *n_ops; ++k) {
+    const Op& op = T.ops[k];
+    nesti_debug_op_t& o = ops[k];
+    memset(&o, 0, sizeof(o));
+    o.kind = op.kind == Op::CONV ? NESTI_DEBUG_OP_CONV : op.kind == Op::MAX ? NESTI_DEBUG_OP_MAX : NESTI_DEBUG_OP_MAX3;
+    o.family = -1; o.layer = -1; o.in_pos_off = -1;
+    o.elem = kernel_dtype(dt); o.planes = planes;
+    o.in_buf = op.in_buf; o.in_coff = op.in_coff; o.in_cstride = op.in_cstride ? op.in_cstride : T.bufs[op.in_buf].C;
+    o.in_planes = op.in_buf < 1 ? act_planes(mdt) : planes;
+    o.out_buf = op.out_buf; o.out_coff = op.out_coff; o.out_coff2 = op.out_coff2; o.out_f32 = op.out_f32;
+    o.mp_buf = op.mp_buf; o.mp_mode = op.mp_mode; o.mp_mode2 = op.mp_mode2;
+    o.aux_in_buf = o.aux_out_buf = o.aux_layer = -1;
+    o.form = planes > 1 ? NESTI_DEBUG_FORM_PAIR : NESTI_DEBUG_FORM_PLAIN;
+    o.log2S = op.log2S; o.C = op.C;
+    if (op.kind != Op::CONV) continue;
+    const LayerDesc& d = g.layers[op.layer];
+    names.push_back(d.scope);
+    o.scope = names.back().c_str();
+    names.push_back(d.scope2);
+    o.scope2 = names.back().c_str();
+    o.layer = op.layer; o.k = d.k; o.log2S = d.log2S; o.s_real = d.s_real; o.is_fc = d.is_fc; o.bn = d.bn; o.relu = d.relu;
+    o.pool_k = d.pool_k; o.n_taps = layer_taps(d);
+    o.cin = d.cin; o.cout = d.cout; o.Cin_p = d.Cin_p; o.Cout_p = d.Cout_p;
+    // the packing run_op picks for this pass (nesti_model_create: the filter pass keeps no plain copy of a one-tap conv_igemm layer
+    // and runs it on the pair packing; the x8 copies exist for the consumer layers only)
+    const bool x2l = ps.fast && layer_kind(d, mdt) == 0 && o.n_taps == 1;
+    const bool x8l = !ps.fast && op.aux_in_buf >= 0 && op.x8_bit >= 0 && ((ps.x8_mask >> op.x8_bit) & 1);
+    o.family = x2l ? layer_kind(d, mdt) : layer_kind(d, dt);
+    if (x2l) o.form = NESTI_DEBUG_FORM_X2;
+    if (x8l) {
+      o.form = ps.x8_fmt == 8 ? NESTI_DEBUG_FORM_X8 : NESTI_DEBUG_FORM_X6;
+      o.aux_in_buf = op.aux_in_buf; o.aux_layer = op.aux_layer;
+    }
+    if (!ps.fast && op.aux_out_buf >= 0 && (ps.x8_mask & op.x8_bits)) o.aux_out_buf = op.aux_out_buf;
+    o.in_pos_off = pos;
+    for (int c = 0; c < d.cin; ++c, ++pos) if (in_pos) in_pos[pos] = d.in_pos[c];
+  }
+  return 0;
+}
+
+int nesti_debug_tower_step(const nesti_model_t* m, int tower, const nesti_debug_pass_t* pass, int op, const void* mups_dev, int batch,
+                           const int32_t* point_index_dev, const int32_t* npoints_dev, int walk, void* ws_dev, size_t ws_bytes,
+                           void* stream) {
+  if (!m || !mups_dev || !ws_dev) NESTI_FAIL("nesti_debug_tower_step: null argument");
+  if (batch <= 0) NESTI_FAIL("nesti_debug_tower_step: batch must be positive");
+  const nesti_debug_pass_t& ps = pass ? *pass : kMainPass;
+  const Graph& g = m->graph;
+  if (tower < -1 || tower >= (int)g.experts.size()) NESTI_FAIL("nesti_debug_tower_step: tower must be -1 (gate) or an expert index");
+  if (tower < 0 && g.cfg.arch != NESTI_ARCH_EXPERTS && g.cfg.arch != NESTI_ARCH_SWITCH) NESTI_FAIL("nesti_debug_tower_step: this model has no gating net");
+  if (ps.fast && !(m->cascade && tower < 0)) NESTI_FAIL("nesti_debug_tower_step: the filter pass is the gating net's of NESTI_F16X3C / NESTI_F16X8C models");
+  if (ps.x8_mask < 0 || ps.x8_mask > 0xF || (ps.x8_mask && !(g.x8 && tower >= 0)))
+    NESTI_FAIL("nesti_debug_tower_step: x8_mask has four bits and applies to the expert towers of NESTI_F16X8 / NESTI_F16X8C models");
+  if (ps.x8_fmt != 0 && ps.x8_fmt != m->x8_fmt) NESTI_FAIL("nesti_debug_tower_step: x8_fmt differs from the model's (nesti_model_set_x8_format)");
+  if (walk < 0 || (walk > 1 && walk % 8)) NESTI_FAIL("nesti_debug_tower_step: walk is 0, 1 or a multiple of 8");
+  const Tower& T = tower < 0 ? g.gate : g.experts[tower];
+  if (op < 0 || op >= (int)T.ops.size()) NESTI_FAIL("nesti_debug_tower_step: op index outside the tower");
+  // the RunCtx of the product's passes: experts_impl (expert towers), gate_impl (gating net), gate_cascade (filter pass)
+  RunCtx rc{m, batch, npoints_dev, point_index_dev, (hipStream_t)stream, ps.fast != 0};
+  if (tower >= 0) {
+    rc.mix = m->expert_mix;
+    rc.x8 = ps.x8_mask;
+  } else if (!ps.fast) {
+    rc.mix = m->gate_mix ? (1 << kGateMixBit) : 0;
+    rc.zero_lo = m->gate_mix == 2;
+  }
+  rc.walk = walk;
+  std::vector<unsigned char*> ptr;
+  if (tower_ptrs(rc, T, mups_dev, (unsigned char*)ws_dev, ws_bytes, &ptr)) return 1;
+  return run_op(rc, T, T.ops[op], ptr);
+}
+
 }  // extern "C"
+

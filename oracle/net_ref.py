@@ -45,19 +45,26 @@ def conv3d_same_direct(x, w, b):
     return y.permute(0, 2, 3, 4, 1)
 
 
-def conv3d_same_taps(x, w, b):
-    """The same convolution as a sum over the k^3 taps of [positions, Cin] @ [Cin, Cout] on the zero-padded volume --
-    the definition itself, and 6-12x faster than torch's fp64 conv3d (which unfolds the input 125-fold for a 5^3 kernel);
-    equal to :func:`conv3d_same_direct` to rounding (``tests/test_oracle_net.py``)."""
-    k = w.shape[0]
+def same_taps(x, k):
+    """The k^3 taps of a SAME convolution at stride 1 on x [B,D,H,W,C]: yields ((a, b, c), the input each output position sees
+    through that tap, [B*D*H*W, C]) on the zero-padded volume (any device)."""
     lo, hi = _same_pad(k)
     B, D, H, Wd, C = x.shape
     xp = F.pad(x, (0, 0, lo, hi, lo, hi, lo, hi))
-    out = torch.zeros((B * D * H * Wd, w.shape[4]), dtype=x.dtype)
     for a in range(k):
         for bb in range(k):
             for c in range(k):
-                out.addmm_(xp[:, a:a + D, bb:bb + H, c:c + Wd, :].reshape(-1, C), w[a, bb, c])
+                yield (a, bb, c), xp[:, a:a + D, bb:bb + H, c:c + Wd, :].reshape(-1, C)
+
+
+def conv3d_same_taps(x, w, b):
+    """The same convolution as a sum over the k^3 taps of [positions, Cin] @ [Cin, Cout] on the zero-padded volume --
+    the definition itself, and 6-12x faster than torch's fp64 conv3d (which unfolds the input 125-fold for a 5^3 kernel);
+    equal to :func:`conv3d_same_direct` to rounding (``tests/test_oracle_net.py``).  Runs on x's device."""
+    B, D, H, Wd, _ = x.shape
+    out = torch.zeros((B * D * H * Wd, w.shape[4]), dtype=x.dtype, device=x.device)
+    for t, xs in same_taps(x, w.shape[0]):
+        out.addmm_(xs, w[t])
     return (out + b).reshape(B, D, H, Wd, -1)
 
 
@@ -77,7 +84,7 @@ def avg_pool3d_same(x, k):
     lo, hi = _same_pad(k)
     xc = F.pad(x.permute(0, 4, 1, 2, 3), (lo, hi, lo, hi, lo, hi))
     s = F.avg_pool3d(xc, k, stride=1) * float(k ** 3)
-    ones = F.pad(torch.ones((1, 1) + tuple(x.shape[1:4]), dtype=x.dtype), (lo, hi, lo, hi, lo, hi))
+    ones = F.pad(torch.ones((1, 1) + tuple(x.shape[1:4]), dtype=x.dtype, device=x.device), (lo, hi, lo, hi, lo, hi))
     cnt = F.avg_pool3d(ones, k, stride=1) * float(k ** 3)
     return (s / cnt).permute(0, 2, 3, 4, 1)
 

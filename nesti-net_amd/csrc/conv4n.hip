@@ -357,48 +357,16 @@ __global__ __launch_bounds__(kThreads4) void conv4n_kernel(const ConvParams p) {
   if constexpr (!WALK) {
     conv4n_tile<DT, K, X3>(p, blockIdx.x, threadIdx.x);
   } else {
-    // walking launch (kernels.h: ConvParams::walk), a kernel of its own so that the one-tile-per-workgroup kernel keeps its register
-    // allocation: only the tiles below the live row count; the thread index is laundered per trip, otherwise hipcc hoists every
-    // per-lane address out of the tile loop and spills
-    unsigned n_blocks;
-    {
-      int npts = p.npoints;
-      if (p.npoints_ptr) npts = min(npts, *p.npoints_ptr);
-      const unsigned m_live = (unsigned)((npts + kPts4 - 1) / kPts4);
-        n_blocks = (m_live + 7) / 8 * 8 * (unsigned)p.n_tiles;
-    }
-    for (unsigned bid = blockIdx.x; bid < n_blocks; bid += gridDim.x) {
-      if (bid != blockIdx.x) __syncthreads();    // the previous tile's epilogue is done with the LDS
-      int tid = threadIdx.x;
-      asm volatile("" : "+v"(tid));
-      conv4n_tile<DT, K, X3>(p, bid, tid);
-    }
+    const unsigned m_live = (unsigned)((live_points(p) + kPts4 - 1) / kPts4);
+    const unsigned n_blocks = tile_rows8(m_live) * (unsigned)p.n_tiles;
+    for (unsigned bid = blockIdx.x; bid < n_blocks; bid += gridDim.x) conv4n_tile<DT, K, X3>(p, bid, walk_trip(bid));
   }
 }
 
-template <int DT, int K, bool X3, bool WALK>
-int launch_conv4n_one_w(const ConvParams& p, hipStream_t stream) {
-  constexpr int kMaxDevices = 64;
-  static bool attr_set[kMaxDevices] = {};
-  int dev = 0;
-  NESTI_CHECK_HIP(hipGetDevice(&dev));
-  if (dev < 0 || dev >= kMaxDevices || !attr_set[dev]) {
-    NESTI_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv4n_kernel<DT, K, X3, WALK>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds4<K>()));
-    if (dev >= 0 && dev < kMaxDevices) attr_set[dev] = true;
-  }
-  const int groups = (p.m_tiles + 7) / 8;
-  const unsigned n_blocks = (unsigned)(groups * 8 * p.n_tiles);
-  dim3 grid(WALK ? std::min(n_blocks, p.walk > 1 ? (unsigned)p.walk : kWalkGrid) : n_blocks), block(kThreads4);
-  hipLaunchKernelGGL((conv4n_kernel<DT, K, X3, WALK>), grid, block, lds4<K>(), stream, p);
-  NESTI_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-// p.walk picks the walking instantiation (a separate kernel: kernels.h, ConvParams::walk)
 template <int DT, int K, bool X3>
 int launch_conv4n_one(const ConvParams& p, hipStream_t stream) {
-  return p.walk ? launch_conv4n_one_w<DT, K, X3, true>(p, stream) : launch_conv4n_one_w<DT, K, X3, false>(p, stream);
+  return launch_tiles<conv4n_kernel<DT, K, X3, false>, conv4n_kernel<DT, K, X3, true>>(p, lds4<K>(), kThreads4,
+                                                                                      tile_rows8(p.m_tiles) * p.n_tiles, stream);
 }
 
 template <int DT>
@@ -437,10 +405,7 @@ int launch_conv4n(const ConvParams& p, int dtype, int k, hipStream_t stream) {
   if (p.pool_k > 1 || p.split_tile != p.n_tiles) NESTI_FAIL("launch_conv4n: no fused avg-pool / merged layers");
   if (p.mp_mode == 2) NESTI_FAIL("launch_conv4n: max-pool mode 2 is conv1's (a 1x1x1 layer)");
   if (p.mp_mode != 0 && !p.mp_out) NESTI_FAIL("launch_conv4n: fused max-pool needs an output");
-  if (dtype == NESTI_BF16) return launch_conv4n_dt<NESTI_BF16>(p, k, stream);
-  if (dtype == NESTI_F16) return launch_conv4n_dt<NESTI_F16>(p, k, stream);
-  if (dtype == NESTI_F32) return launch_conv4n_dt<NESTI_F32>(p, k, stream);
-  NESTI_FAIL("launch_conv4n: unsupported dtype");
+  return with_elem_type(dtype, "launch_conv4n", [&](auto dt) { return launch_conv4n_dt<decltype(dt)::value>(p, k, stream); });
 }
 
 }  // namespace nesti

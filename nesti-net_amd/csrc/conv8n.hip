@@ -302,12 +302,6 @@ __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned 
       mma<DT>(acc[j][1], a[j][0], bc[1][0]);
       mma<DT>(acc[j][0], a[j][1], bc[0][1]);
       mma<DT>(acc[j][1], a[j][1], bc[1][1]);
-#ifdef CONV8N_DOUBLE_MMA   // timing-only experiment (wrong results): twice the MFMAs per (chunk, tap) step on the same fragment reads
-      mma<DT>(acc[j][0], a[j][0], bc[0][1]);
-      mma<DT>(acc[j][1], a[j][0], bc[1][1]);
-      mma<DT>(acc[j][0], a[j][1], bc[0][0]);
-      mma<DT>(acc[j][1], a[j][1], bc[1][0]);
-#endif
     }
   };
   // one (dz, dy) row of K taps
@@ -625,50 +619,18 @@ __global__ __launch_bounds__(kThreadsN) void conv8n_kernel(const ConvParams p) {
   if constexpr (!WALK) {
     conv8n_tile<DT, K, MODE>(p, blockIdx.x, threadIdx.x);
   } else {
-    // walking launch (kernels.h: ConvParams::walk), a kernel of its own so that the one-tile-per-workgroup kernel keeps its register
-    // allocation: only the tiles below the live row count; the thread index is laundered per trip, otherwise hipcc hoists every
-    // per-lane address out of the tile loop and spills
-    unsigned n_blocks;
-    {
-      int npts = p.npoints;
-      if (p.npoints_ptr) npts = min(npts, *p.npoints_ptr);
-      const unsigned m_live = (unsigned)((npts + kPtsN - 1) / kPtsN);
-        n_blocks = (m_live + 7) / 8 * 8 * 2u * (unsigned)p.n_tiles;
-    }
-    for (unsigned bid = blockIdx.x; bid < n_blocks; bid += gridDim.x) {
-      if (bid != blockIdx.x) __syncthreads();    // the previous tile's epilogue is done with the LDS
-      int tid = threadIdx.x;
-      asm volatile("" : "+v"(tid));
-      conv8n_tile<DT, K, MODE>(p, bid, tid);
-    }
+    const unsigned m_live = (unsigned)((live_points(p) + kPtsN - 1) / kPtsN);
+    const unsigned n_blocks = tile_rows8(m_live) * 2u * (unsigned)p.n_tiles;
+    for (unsigned bid = blockIdx.x; bid < n_blocks; bid += gridDim.x) conv8n_tile<DT, K, MODE>(p, bid, walk_trip(bid));
   }
 }
 
-template <int DT, int K, int MODE, bool WALK>
-int launch_conv8n_one_w(const ConvParams& p, hipStream_t stream) {
-  constexpr int kMaxDevices = 64;
-  static bool attr_set[kMaxDevices] = {};
-  int dev = 0;
-  NESTI_CHECK_HIP(hipGetDevice(&dev));
-  constexpr int lds = lds_bytes_n<K>();
-  static_assert(lds <= 163840 && 1024 * kEpiStrideN <= lds, "LDS budget");
-  if (dev < 0 || dev >= kMaxDevices || !attr_set[dev]) {
-    NESTI_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv8n_kernel<DT, K, MODE, WALK>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    if (dev >= 0 && dev < kMaxDevices) attr_set[dev] = true;
-  }
-  const int groups = (p.m_tiles + 7) / 8;
-  const unsigned n_blocks = (unsigned)(groups * 8 * 2 * p.n_tiles);
-  dim3 grid(WALK ? std::min(n_blocks, p.walk > 1 ? (unsigned)p.walk : kWalkGrid) : n_blocks), block(kThreadsN);
-  hipLaunchKernelGGL((conv8n_kernel<DT, K, MODE, WALK>), grid, block, lds, stream, p);
-  NESTI_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-// p.walk picks the walking instantiation (a separate kernel: kernels.h, ConvParams::walk)
 template <int DT, int K, int MODE>
 int launch_conv8n_one(const ConvParams& p, hipStream_t stream) {
-  return p.walk ? launch_conv8n_one_w<DT, K, MODE, true>(p, stream) : launch_conv8n_one_w<DT, K, MODE, false>(p, stream);
+  constexpr int lds = lds_bytes_n<K>();
+  static_assert(lds <= 163840 && 1024 * kEpiStrideN <= lds, "LDS budget");
+  return launch_tiles<conv8n_kernel<DT, K, MODE, false>, conv8n_kernel<DT, K, MODE, true>>(p, lds, kThreadsN,
+                                                                                          tile_rows8(p.m_tiles) * 2 * p.n_tiles, stream);
 }
 
 template <int DT>
@@ -753,10 +715,7 @@ int launch_conv8n(const ConvParams& p, int dtype, int k, hipStream_t stream) {
   if (p.pool_k > 1 || p.split_tile != p.n_tiles) NESTI_FAIL("launch_conv8n: no fused avg-pool / merged layers");
   if (p.mp_mode == 2) NESTI_FAIL("launch_conv8n: max-pool mode 2 is conv1's (a 1x1x1 layer)");
   if (p.mp_mode != 0 && !p.mp_out) NESTI_FAIL("launch_conv8n: fused max-pool needs an output");
-  if (dtype == NESTI_BF16) return launch_conv8n_dt<NESTI_BF16>(p, k, stream);
-  if (dtype == NESTI_F16) return launch_conv8n_dt<NESTI_F16>(p, k, stream);
-  if (dtype == NESTI_F32) return launch_conv8n_dt<NESTI_F32>(p, k, stream);
-  NESTI_FAIL("launch_conv8n: unsupported dtype");
+  return with_elem_type(dtype, "launch_conv8n", [&](auto dt) { return launch_conv8n_dt<decltype(dt)::value>(p, k, stream); });
 }
 
 }  // namespace nesti

@@ -463,13 +463,19 @@ struct PackedLayer {
   int kind = 0;              // 0: conv_igemm_kernel (conv.hip), 2: conv8n_kernel (conv8n.hip: 4 points x a z half x 64 columns
                              // per workgroup), 3: conv4n_kernel (conv4n.hip: 16 points x 64 voxels x 64 columns)
   bool x3n = false;          // pair modes: K chunks [hi | lo] / [W_hi | W_lo], three MFMAs per fragment set
-  int mix_bit = -1;          // packed_mix entries: which bit of nesti_model::expert_mix switches this layer to the single-product loop
   float acc_scale = 1.0f;    // 2^-s when the packed weights carry a 2^s scale (NESTI_F16X3)
-  bool x8 = false;           // packed_x8 entries: rows [W_hi f16 16 ch | W_hi8 16 ch | W_lo8 16 ch] (conv8n.hip X8)
-  int x8_sb = 0;             // ... W_hi8 = e4m3(W_hi 2^sb), W_lo8 = e4m3(W_lo 2^(sb + 11))
+  int x8_sb = 0;             // X8 / X6 entries (rows [W_hi f16 16 ch | W_hi8 16 ch | W_lo8 16 ch], conv8n.hip X8): W_hi8 = e4m3(W_hi 2^sb),
+                             // W_lo8 = e4m3(W_lo 2^(sb + 11))
   int x8_sc = 0;             // producer layers (an 8^3 block's conv1): hi8 = e4m3(v 2^sc), lo8 = e4m3(lo 2^(sc + 11))
   int8_t tap[kMaxTaps][4];
 };
+
+// The form of a launch (launch_form): the NESTI_DEBUG_FORM_* values of include/nesti_hip.h and, EXPERIMENT
+// (nesti_model_set_expert_mix / _gate_mix), a tap layer of a pair-mode tower in plain f16 / bf16 -- it reads the hi
+// planes of its pair-layout input, multiplies ONE product and writes its outputs as pairs again
+constexpr int kFormMix = NESTI_DEBUG_FORM_X6 + 1;
+// ... and the packed weights it runs on: its own, except that X2 multiplies by the pair packing
+inline int form_packing(int form) { return form == NESTI_DEBUG_FORM_X2 ? NESTI_DEBUG_FORM_PAIR : form; }
 
 }  // namespace
 }  // namespace nesti
@@ -477,23 +483,26 @@ struct PackedLayer {
 struct nesti_model {
   nesti::Graph graph;
   int dtype = NESTI_BF16;                      // compute dtype of everything that reaches the outputs (NESTI_F16X3C -> NESTI_F16X3)
-  std::vector<nesti::PackedLayer> packed;
-  // NESTI_F16X3C: the gating net's layers once more in plain f16 (indexed like `packed`, other entries empty), the gate
-  // margin and the device counters of the two-stage gate (include/nesti_hip.h: nesti_cascade_stats_t)
+  // every (packing, layer) launch_form names over the passes a model of this dtype runs (nesti_model_create), device-resident
+  std::map<std::pair<int, int>, nesti::PackedLayer> packed;
+  const nesti::PackedLayer* packing(int form, int layer) const {
+    auto it = packed.find({nesti::form_packing(form), layer});
+    return it == packed.end() ? nullptr : &it->second;
+  }
+  // the layers in the model's own dtype: every layer has this one
+  const nesti::PackedLayer& main_packing(int layer) const {
+    return *packing(nesti::act_planes(dtype) > 1 ? NESTI_DEBUG_FORM_PAIR : NESTI_DEBUG_FORM_PLAIN, layer);
+  }
+  // NESTI_F16X3C: the two-stage gate (its filter pass runs the gating net's tap layers on plain-f16 packings), the gate margin and
+  // the device counters (include/nesti_hip.h: nesti_cascade_stats_t)
   bool cascade = false;
-  std::vector<nesti::PackedLayer> packed_fast;
-  // pair modes, EXPERIMENT (nesti_model_set_expert_mix): the experts' k^3 tap layers at 8^3 / 4^3 once more
-  // in plain f16 -- a layer whose bit is set in expert_mix reads the hi planes of its pair-layout input, multiplies ONE product
-  // and writes its outputs as pairs again
-  std::vector<nesti::PackedLayer> packed_mix;
+  // EXPERIMENT: models created after nesti_experiment_mix_enable(1) also hold kFormMix packings of their tap layers; expert_mix /
+  // gate_mix switch them on
+  bool has_mix = false;
   int expert_mix = 0;
-  // NESTI_F16X8 / NESTI_F16X8C: the experts' tap layers at 8^3 once more in the FP8 cross-term packing; x8_mask picks which of them run
-  // it (include/nesti_hip.h: nesti_model_set_x8_layers)
-  std::vector<nesti::PackedLayer> packed_x8;
+  // NESTI_F16X8 / NESTI_F16X8C: x8_mask picks which of the experts' tap layers at 8^3 run their cross terms in FP8 / FP6
+  // (include/nesti_hip.h: nesti_model_set_x8_layers), x8_fmt which of the two forms forward calls use (8 or 6; nesti_model_set_x8_format)
   int x8_mask = 0;
-  // the same layers once more in the block-scaled FP6 form of the cross terms, and which of the two forms forward calls use (8 or 6;
-  // include/nesti_hip.h: nesti_model_set_x8_format)
-  std::vector<nesti::PackedLayer> packed_x6;
   int x8_fmt = 6;
   // ... and their conditioning guard (pool.hip: x8_guard_*): outputs with |n| below max(x8_guard_thr, NESTI_X8_GUARD_WIDEN x largest
   // measured |dn| / theta) are re-evaluated in f16x3 proper; gstat = the device counters (include/nesti_hip.h: nesti_x8_guard_stats_t)
@@ -526,11 +535,10 @@ struct nesti_model {
   float tau = 0.25f;
   unsigned long long* cstat = nullptr;
   ~nesti_model() {
-    for (auto* v : {&packed, &packed_fast, &packed_mix, &packed_x8, &packed_x6})
-      for (auto& p : *v) {
-        if (p.wpk) (void)hipFree(p.wpk);
-        if (p.bias) (void)hipFree(p.bias);
-      }
+    for (auto& p : packed) {
+      if (p.second.wpk) (void)hipFree(p.second.wpk);
+      if (p.second.bias) (void)hipFree(p.second.bias);
+    }
     if (cstat) (void)hipFree(cstat);
     if (gstat) (void)hipFree(gstat);
     for (auto& gl : glane) {
@@ -629,6 +637,65 @@ int layer_taps(const LayerDesc& d) {
   return n;
 }
 
+// ------------------------------------------------------------------------------------------
+// the form of a launch
+// ------------------------------------------------------------------------------------------
+// One pass of a tower: what, beside the graph and the model's dtype, decides how its launches compute
+struct Pass {
+  int tower = -1;          // -1: the gating net, else an expert
+  bool fast = false;       // NESTI_F16X3C filter pass: the tower runs in plain f16 while the MuPS tensor it reads keeps the model's pair
+                           // layout (only the hi plane is read)
+  int x8_mask = 0;         // expert towers of NESTI_F16X8 / NESTI_F16X8C models: the tap layers at 8^3 whose bit (Op::x8_bit) is set run
+  int x8_fmt = 6;          // their cross terms in FP8 (8) or FP6 (6), on the planes their block's conv1 then also writes
+  int mix = 0;             // EXPERIMENT: the tap layers whose mix_bit is set here run single-product (kFormMix)
+  bool zero_lo = false;    // EXPERIMENT (gate_mix == 2): every layer writes its outputs rounded to 16 bits (lo plane = 0)
+};
+
+// EXPERIMENT: the bit of Pass::mix that switches a layer of a pair-mode model to kFormMix (-1: none) -- the tap layers on
+// conv8n_kernel / conv4n_kernel; the gating net's share one bit, the experts' are "inception<B>Expert_<i>_conv<2|3>" of blocks
+// 1, 2 (8^3) and 4 (4^3), two bits per block (conv2, the smaller kernel, first)
+constexpr int kGateMixBit = 8;
+int mix_bit(const LayerDesc& d, int tower, int mdt) {
+  if (act_planes(mdt) == 1 || layer_kind(d, mdt) < 2) return -1;
+  if (tower < 0) return kGateMixBit;
+  const int blk = d.scope.size() > 9 ? d.scope[9] - '0' : 0;
+  const int idx = blk == 1 ? 0 : blk == 2 ? 1 : blk == 4 ? 2 : -1;
+  return idx < 0 ? -1 : 2 * idx + (d.scope.back() == '3' ? 1 : 0);
+}
+
+struct LaunchForm {
+  int form;        // NESTI_DEBUG_FORM_* or kFormMix
+  int family;      // PackedLayer::kind of the packing the launch runs on
+  bool producer;   // an 8^3 block's conv1 that also writes the FP8 / FP6 planes of its outputs for the block's tap layers
+};
+// How the conv launch `op` of a pass computes, for a model whose main dtype is mdt.  THE place that decides it: nesti_model_create
+// packs what it names, run_op launches it and nesti_debug_tower_ops reports it.  A function of the configuration alone.
+LaunchForm launch_form(const Graph& g, const Op& op, const Pass& ps, int mdt) {
+  const LayerDesc& d = g.layers[op.layer];
+  LaunchForm f;
+  f.producer = !ps.fast && op.aux_out_buf >= 0 && (ps.x8_mask & op.x8_bits);
+  const int mb = !ps.fast && ps.mix ? mix_bit(d, ps.tower, mdt) : -1;
+  if (ps.fast) {
+    // the filter pass's one-tap layers (1x1x1 conv1|conv4, FC) multiply the plain-f16 activations by the model's own PAIR-packed
+    // weights (conv_igemm_kernel's X2 loop: hi * W_hi + hi * W_lo).  Those layers are fill-bound, so the second product costs ~20 %
+    // more weight-tile fill and no matrix-pipe time that shows, and it removes the weight-rounding part of their error: the filter's
+    // sigma on a logit difference drops from 0.021 to 0.012 (profiles/r05_gate_medium.txt), the threshold with it
+    const bool x2 = layer_kind(d, mdt) == 0 && layer_taps(d) == 1;
+    f.form = x2 ? NESTI_DEBUG_FORM_X2 : NESTI_DEBUG_FORM_PLAIN;
+    f.family = x2 ? 0 : layer_kind(d, NESTI_F16);
+  } else if (mb >= 0 && ((ps.mix >> mb) & 1)) {
+    f.form = kFormMix;
+    f.family = layer_kind(d, kernel_dtype(mdt));
+  } else if (op.aux_in_buf >= 0 && op.x8_bit >= 0 && ((ps.x8_mask >> op.x8_bit) & 1)) {
+    f.form = ps.x8_fmt == 8 ? NESTI_DEBUG_FORM_X8 : NESTI_DEBUG_FORM_X6;
+    f.family = 2;
+  } else {
+    f.form = act_planes(mdt) > 1 ? NESTI_DEBUG_FORM_PAIR : NESTI_DEBUG_FORM_PLAIN;
+    f.family = layer_kind(d, mdt);
+  }
+  return f;
+}
+
 // Error attribution in the pair modes (scripts/exp_attribution.py), ONLY in builds made with -DNESTI_ATTRIBUTION (the product
 // library has no such switch): NESTI_X3_PLAIN = "regex,regex,..." -- a layer whose scope matches drops the hi * W_lo product
 // (its W_lo weights are packed as zeros: the layer then sees its weights rounded to 16 bits).  Round 3's full sweep
@@ -707,7 +774,7 @@ inline uint8_t host_f32_to_e2m3(float f, float inv_scale) {
 // (the order the producer's conversion instruction writes [lo | hi] activations in, so that slot products are lo W_hi and hi W_lo) -- and
 // in byte 24 the E8M0 code of s 2^-11 (s = 2^(E - 2), E = exponent of the chunk's largest |W_hi|; the 2^-11 undoes BOTH 2^11 pre-scales,
 // the activations' and the weights', since every product carries exactly one of them).
-int pack_layer_x8(const LayerDesc& d, const TensorTable& tt, PackedLayer* pl, int fmt = 8) {
+int pack_layer_x8(const LayerDesc& d, const TensorTable& tt, PackedLayer* pl, int fmt) {
   if (!use_conv8(d) || !d.scope2.empty()) NESTI_FAIL("internal: pack_layer_x8 is for the k^3 tap layers at 8^3");
   Folded f;
   if (fold_layer(d, d.scope, tt, &f)) return 1;
@@ -722,7 +789,7 @@ int pack_layer_x8(const LayerDesc& d, const TensorTable& tt, PackedLayer* pl, in
         tap_widx.push_back((a * d.k + bb) * d.k + c);
         ++pl->n_taps;
       }
-  pl->kind = 2; pl->x3n = false; pl->x8 = true; pl->TN = 64;
+  pl->kind = 2; pl->x3n = false; pl->TN = 64;
   if (d.Cout_p % 64 || d.Cin_p % kSplitGroup) NESTI_FAIL("internal: pack_layer_x8 needs 64-aligned channel counts");
   pl->n_tiles = d.Cout_p / 64; pl->split_tile = pl->n_tiles;
   constexpr int chunk_ch = 16;
@@ -947,6 +1014,17 @@ int pack_layer(const LayerDesc& d, const TensorTable& tt, int dtype, PackedLayer
   return 0;
 }
 
+// The packing of a layer for the launches of one form (form_packing), in a model whose main dtype is mdt
+int pack_form(const LayerDesc& d, const TensorTable& tt, int form, int mdt, PackedLayer* pl) {
+  switch (form) {
+    case NESTI_DEBUG_FORM_X8: return pack_layer_x8(d, tt, pl, 8);
+    case NESTI_DEBUG_FORM_X6: return pack_layer_x8(d, tt, pl, 6);
+    case kFormMix: return pack_layer(d, tt, kernel_dtype(mdt), pl);
+    case NESTI_DEBUG_FORM_PLAIN: return pack_layer(d, tt, act_planes(mdt) > 1 ? NESTI_F16 : mdt, pl);   // pair models: the filter pass
+    default: return pack_layer(d, tt, mdt, pl);
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // workspace planning and tower execution
 // ------------------------------------------------------------------------------------------
@@ -1034,27 +1112,32 @@ int conv_category(const LayerDesc& d, const PackedLayer& pl) {
   return pl.n_taps > 1 ? NESTI_PROF_TAPS : NESTI_PROF_ONE_BY_ONE;
 }
 
-constexpr int kGateMixBit = 8;   // packed_mix entries of the gating net: RunCtx::mix bit 8 switches all of them
-
 struct RunCtx {
   const nesti_model* m;
+  Pass pass;
   int NB;                        // capacity (points)
   const int32_t* npoints_ptr;    // device-side live count or NULL
   const int32_t* point_index;    // gather for reads of bufs 0/1, or NULL
   hipStream_t stream;
-  bool fast = false;             // NESTI_F16X3C filter pass: this tower runs in plain f16 on rc.m->packed_fast while the
-                                 // MuPS tensor it reads keeps the model's pair layout (only the hi plane is read)
-  int mix = 0;                   // expert towers in a pair mode: the layers whose packed_mix bit is set here run single-product
-  bool zero_lo = false;          // experiment (gate_mix == 2): every layer writes its outputs rounded to 16 bits (lo plane = 0)
-  int walk = 0;                  // this pass over a device-side list is probably empty (a later round, a widening pass): its conv
+  int walk;                      // this pass over a device-side list is probably empty (a later round, a widening pass): its conv
                                  // launches use small walking grids (kernels.h: ConvParams::walk)
-  int x8 = 0;                    // expert towers of an NESTI_F16X8 / NESTI_F16X8C model: nesti_model::x8_mask (which tap layers run the
-                                 // FP8 cross-term loop; their block's conv1 then also writes the e4m3 planes)
 };
+// The RunCtx of a pass of the product: the gating net (tower -1) of gate_impl and of gate_cascade, filter pass (fast) and recheck;
+// the expert towers of experts_impl with the model's x8_mask, and with x8_mask 0 -- the three-product loop everywhere -- for the
+// conditioning guard's re-evaluation.  The experiment switches ride along: expert_mix on the experts, gate_mix on the gating net
+// of a model without the two-stage gate
+RunCtx pass_ctx(const nesti_model* m, int tower, bool fast, int x8_mask, int NB, const int32_t* npoints_ptr, const int32_t* point_index,
+                hipStream_t stream, int walk) {
+  Pass ps;
+  ps.tower = tower; ps.fast = fast; ps.x8_mask = x8_mask; ps.x8_fmt = m->x8_fmt;
+  if (tower >= 0) ps.mix = m->expert_mix;
+  else if (!m->cascade && m->gate_mix) { ps.mix = 1 << kGateMixBit; ps.zero_lo = m->gate_mix == 2; }
+  return RunCtx{m, ps, NB, npoints_ptr, point_index, stream, walk};
+}
 
 // The buffers of a tower in a workspace laid out by place_tower (ptr[0] = the MuPS tensor X0 the tower reads)
 int tower_ptrs(const RunCtx& rc, const Tower& T, const void* X0, unsigned char* ws, size_t ws_bytes, std::vector<unsigned char*>* ptr) {
-  const int dtype = rc.fast ? NESTI_F16 : rc.m->dtype;
+  const int dtype = rc.pass.fast ? NESTI_F16 : rc.m->dtype;
   ptr->assign(T.bufs.size(), nullptr);
   (*ptr)[0] = (unsigned char*)X0;
   const Placement P = place_tower(T, rc.NB, dtype);
@@ -1065,23 +1148,19 @@ int tower_ptrs(const RunCtx& rc, const Tower& T, const void* X0, unsigned char* 
 
 // One launch of a tower: the body of run_tower's loop, also reached alone through nesti_debug_tower_step
 int run_op(const RunCtx& rc, const Tower& T, const Op& op, const std::vector<unsigned char*>& ptr) {
-  const int dtype = rc.fast ? NESTI_F16 : rc.m->dtype;
+  const Pass& ps = rc.pass;
+  const int dtype = ps.fast ? NESTI_F16 : rc.m->dtype;
   const int x0_planes = act_planes(rc.m->dtype);
   const bool ext_in = op.in_buf < 1;
   if (op.kind == Op::CONV) {
     const LayerDesc& d = rc.m->graph.layers[op.layer];
-    const bool mixl = !rc.fast && rc.mix && op.layer < (int)rc.m->packed_mix.size() && rc.m->packed_mix[op.layer].wpk &&
-                      ((rc.mix >> rc.m->packed_mix[op.layer].mix_bit) & 1);
-    // NESTI_F16X3C filter pass: its one-tap layers (1x1x1 conv1|conv4, FC) multiply the plain-f16 activations by the model's own
-    // PAIR-packed weights (conv_igemm_kernel's X2 loop: hi * W_hi + hi * W_lo).  Those layers are fill-bound, so the second product
-    // costs ~20 % more weight-tile fill and no matrix-pipe time that shows, and it removes the weight-rounding part of their error:
-    // the filter's sigma on a logit difference drops from 0.021 to 0.012 (profiles/r05_gate_medium.txt), the threshold with it
-    const bool x2l = rc.fast && rc.m->packed_fast[op.layer].wpk == nullptr;
-    const bool x8l = !rc.fast && !mixl && op.aux_in_buf >= 0 && op.x8_bit >= 0 && ((rc.x8 >> op.x8_bit) & 1) &&
-                     op.layer < (int)rc.m->packed_x8.size() && rc.m->packed_x8[op.layer].wpk;
-    const bool x6 = rc.m->x8_fmt == 6;
-    const PackedLayer& pl = x2l ? rc.m->packed[op.layer] : rc.fast ? rc.m->packed_fast[op.layer]
-                            : mixl ? rc.m->packed_mix[op.layer] : x8l ? (x6 ? rc.m->packed_x6 : rc.m->packed_x8)[op.layer] : rc.m->packed[op.layer];
+    const LaunchForm f = launch_form(rc.m->graph, op, ps, rc.m->dtype);
+    const PackedLayer* plp = rc.m->packing(f.form, op.layer);
+    if (!plp || plp->kind != f.family)
+      NESTI_FAIL("internal: layer " + d.scope + " is not packed for form " + std::to_string(f.form) + " of this pass");
+    const PackedLayer& pl = *plp;
+    const bool mixl = f.form == kFormMix, x2l = f.form == NESTI_DEBUG_FORM_X2;
+    const bool x8l = f.form == NESTI_DEBUG_FORM_X8 || f.form == NESTI_DEBUG_FORM_X6, x6 = ps.x8_fmt == 6;
     ConvParams p;
     memset(&p, 0, sizeof(p));
     p.in_pair = mixl ? 1 : 0;
@@ -1092,7 +1171,7 @@ int run_op(const RunCtx& rc, const Tower& T, const Op& op, const std::vector<uns
     // pair modes: strides and the input offset are physical (a 64-aligned logical offset x 3), output column
     // offsets stay logical (kernels.h: ConvParams::split); an fp32 output buffer is an ordinary one
     const int planes = act_planes(dtype);
-    p.split = planes > 1 ? (rc.zero_lo ? 2 : 1) : 0;
+    p.split = planes > 1 ? (ps.zero_lo ? 2 : 1) : 0;
     const int in_planes = ext_in ? x0_planes : planes;
     p.in_cstride = (op.in_cstride ? op.in_cstride : T.bufs[op.in_buf].C) * in_planes; p.in_coff = op.in_coff * in_planes;
     // distance between consecutive K chunks of a PLAIN kernel's input row: 128 B, except in the NESTI_F16X3C filter pass,
@@ -1106,14 +1185,14 @@ int run_op(const RunCtx& rc, const Tower& T, const Op& op, const std::vector<uns
     p.n_tiles = pl.n_tiles; p.split_tile = pl.split_tile; p.out_coff2 = op.out_coff2; p.pool_k = d.pool_k;
     if (op.mp_buf >= 0) { p.mp_out = ptr[op.mp_buf]; p.mp_cstride = T.bufs[op.mp_buf].C * planes; p.mp_mode = op.mp_mode; p.mp_mode2 = op.mp_mode2; }
     if (x8l) {                                   // consumer: the FP8 cross-term loop on the planes the block's conv1 wrote
-      const int sc = rc.m->packed[op.aux_layer].x8_sc;
+      const int sc = rc.m->main_packing(op.aux_layer).x8_sc;
       p.x8 = 1; p.aux8_in = ptr[op.aux_in_buf]; p.aux8_stride = T.bufs[op.aux_in_buf].C * 2;
       p.x8_scale_a = 127 - (sc + 11); p.x8_scale_b = 127 - pl.x8_sb;
       p.x8_fmt = x6 ? 6 : 8;
     }
-    if (!rc.fast && op.aux_out_buf >= 0 && (rc.x8 & op.x8_bits) && !rc.m->packed_x8.empty()) {   // producer
+    if (f.producer) {
       p.aux8_out = ptr[op.aux_out_buf]; p.aux8_stride = T.bufs[op.aux_out_buf].C * 2;
-      p.x8_sc = rc.m->packed[op.layer].x8_sc; p.x8_sa = p.x8_sc + 11;
+      p.x8_sc = rc.m->main_packing(op.layer).x8_sc; p.x8_sa = p.x8_sc + 11;
       p.x8_fmt = x6 ? 6 : 8;
     }
     memcpy(p.tap, pl.tap, sizeof(p.tap));
@@ -1217,7 +1296,7 @@ int gate_cascade(const nesti_model* m, const void* X0, int B, unsigned char* ws,
   int32_t* fcounts = (int32_t*)(ws + L.fcounts);           // kernels.h: kRoundCountsOff, kTauEffOff, kWidenCountOff, kWidenRoundsOff
   const int lstride = m->graph.gate.bufs[m->graph.gate.out_buf].C;
   float* logits = nullptr;
-  RunCtx fast{m, B, nullptr, nullptr, stream, /*fast=*/true};
+  const RunCtx fast = pass_ctx(m, -1, /*fast=*/true, 0, B, nullptr, nullptr, stream, 0);
   prof_phase(NESTI_PHASE_GATE);
   if (run_tower(fast, m->graph.gate, X0, tower_ws, tower_bytes_, &logits)) return 1;
   prof_phase(NESTI_PHASE_RECHECK);
@@ -1233,8 +1312,9 @@ int gate_cascade(const nesti_model* m, const void* X0, int B, unsigned char* ws,
     if (pass >= 1 && launch_gate_widen(keep, B, E, NESTI_GATE_WIDEN, fcounts, flag_list, cap, rounds, m->cstat, stream)) return 1;
     const int32_t* round_counts = fcounts + (pass == 0 ? kRoundCountsOff : kWidenRoundsOff);
     for (int r = 0; r < rounds; ++r) {
-      RunCtx exact{m, cap, round_counts + r, flag_list + (size_t)r * cap, stream};
-      exact.walk = pass >= 1 ? NESTI_GATE_WIDEN_WALK_GRID : r >= 1 ? 1 : 0;   // round 0 of pass 0 holds the flagged rows; everything after it is normally empty
+      // round 0 of pass 0 holds the flagged rows; everything after it is normally empty
+      const RunCtx exact = pass_ctx(m, -1, false, 0, cap, round_counts + r, flag_list + (size_t)r * cap, stream,
+                                    pass >= 1 ? NESTI_GATE_WIDEN_WALK_GRID : r >= 1 ? 1 : 0);
       if (run_tower(exact, m->graph.gate, X0, tower_ws, tower_bytes_, &logits)) return 1;
       if (launch_gate_recheck(logits, lstride, flag_list + (size_t)r * cap, round_counts + r, cap, E, keep, probs, expert,
                               m->cstat, stream))
@@ -1247,8 +1327,7 @@ int gate_cascade(const nesti_model* m, const void* X0, int B, unsigned char* ws,
 
 int gate_impl(const nesti_model* m, const void* X0, int B, unsigned char* tower_ws, size_t tower_bytes_,
               float* probs, int32_t* expert, int32_t* counts, int32_t* lists, hipStream_t stream) {
-  RunCtx rc{m, B, nullptr, nullptr, stream, false, m->gate_mix ? (1 << kGateMixBit) : 0};
-  rc.zero_lo = m->gate_mix == 2;
+  const RunCtx rc = pass_ctx(m, -1, false, 0, B, nullptr, nullptr, stream, 0);
   float* logits = nullptr;
   prof_phase(NESTI_PHASE_GATE);
   if (run_tower(rc, m->graph.gate, X0, tower_ws, tower_bytes_, &logits)) return 1;
@@ -1294,8 +1373,7 @@ int experts_impl(const nesti_model* m, const void* X0, int B, int NB, unsigned c
     int32_t* gl = glist + (size_t)e * gcap;
     if (launch_x8_guard_flag(lists + (size_t)e * B, counts + e, B, normals, gslot, gl, gcount + e, gcap, m->gstat, st)) return 1;
     float* out = nullptr;
-    RunCtx rc{m, gcap, gcount + e, gl, st, false, m->expert_mix};
-    rc.walk = walk_grid;                       // x8 = 0: the three-product loop everywhere; a small walking grid (a few dozen rows)
+    const RunCtx rc = pass_ctx(m, e, false, /*x8_mask=*/0, gcap, gcount + e, gl, st, walk_grid);   // a small walking grid (a few dozen rows)
     if (run_tower(rc, T, X0, arena, arena_bytes, &out)) return 1;
     return launch_x8_guard_fix(out, T.bufs[T.out_buf].C, gl, gcount + e, gcap, normals, m->gstat, st);
   };
@@ -1308,15 +1386,13 @@ int experts_impl(const nesti_model* m, const void* X0, int B, int NB, unsigned c
       if (counts) {   // top-1 routing: only the points whose arg-max is e (test_n_est_w_experts.py:150-152), `cap` of them per round
         const int32_t* list = lists + (size_t)e * B + (size_t)r * cap;
         const int32_t* cnt = ecounts + e * rounds + r;
-        RunCtx rc{m, cap, cnt, list, stream, false, m->expert_mix};
-        rc.x8 = m->x8_mask;
-        rc.walk = r >= 1;                      // an expert sees ~1 / E of a batch: rounds after the first are normally empty
+        // an expert sees ~1 / E of a batch: rounds after the first are normally empty
+        const RunCtx rc = pass_ctx(m, e, false, m->x8_mask, cap, cnt, list, stream, /*walk=*/r >= 1);
         if (run_tower(rc, T, X0, tower_ws, tower_bytes_, &out)) return 1;
         if (launch_scatter3(out, ostride, list, cnt, cap, normals, stream)) return 1;
       } else {        // reference behaviour: every expert on every point -> [E,B,3], rows [r * cap, ...) of the batch per round
         const int take = std::min(cap, B - r * cap);
-        RunCtx rc{m, take, nullptr, nullptr, stream, false, m->expert_mix};
-        rc.x8 = m->x8_mask;
+        const RunCtx rc = pass_ctx(m, e, false, m->x8_mask, take, nullptr, nullptr, stream, 0);
         if (run_tower(rc, T, (const unsigned char*)X0 + (size_t)r * cap * x0_row, tower_ws, tower_bytes_, &out)) return 1;
         if (launch_scatter3(out, ostride, nullptr, nullptr, take, normals + ((size_t)e * B + (size_t)r * cap) * 3, stream)) return 1;
       }
@@ -1361,11 +1437,7 @@ extern "C" {
 
 const char* nesti_last_error(void) { return g_error.c_str(); }
 const char* nesti_version(void) {
-  // _lib.py refuses a library whose version string contains "TIMING-EXPERIMENTS" (common.h); measurement builds are named too
-  return "nesti-hip 0.6 (gfx950)"
-#ifdef NESTI_TIMING_EXPERIMENTS
-         " TIMING-EXPERIMENTS build: WRONG RESULTS by construction"
-#endif
+  return "nesti-hip 0.6 (gfx950)"   // measurement builds are named
 #ifdef NESTI_ATTRIBUTION
          " [measurement build: NESTI_ATTRIBUTION]"
 #endif
@@ -1458,50 +1530,36 @@ int nesti_model_create(const nesti_config_t* cfg, const nesti_tensor_t* tensors,
   if (build_graph(cfg, &m->graph, x8)) return 1;
   TensorTable tt;
   for (int i = 0; i < n_tensors; ++i) if (tensors[i].name) tt.by_name[tensors[i].name] = &tensors[i];
-  m->packed.resize(m->graph.layers.size());
-  for (size_t i = 0; i < m->graph.layers.size(); ++i)
-    if (pack_layer(m->graph.layers[i], tt, dtype, &m->packed[i])) return 1;
   // the 8^3 tap kernel's x padding relies on out-of-range LDS reads returning zero: checked once per device, and only for
   // models that have such layers
   bool any_conv8 = false;
-  for (const PackedLayer& pl : m->packed) any_conv8 = any_conv8 || pl.kind == 2;
+  for (const LayerDesc& d : m->graph.layers) any_conv8 = any_conv8 || layer_kind(d, dtype) == 2;
   if (any_conv8 && conv8_selftest()) return 1;
-  if (g_experiment_mix && act_planes(dtype) > 1 && cfg->arch == NESTI_ARCH_EXPERTS && cfg->grid_n == 8) {
-    m->packed_mix.resize(m->graph.layers.size());
-    const int plain = kernel_dtype(dtype);
-    // the gating net's tap layers (conv8n_kernel / conv4n_kernel): one switch for all of them, bit kGateMixBit
-    for (const Op& op : m->graph.gate.ops) {
-      if (op.kind != Op::CONV) continue;
-      const LayerDesc& d = m->graph.layers[op.layer];
-      if (!use_conv8(d) && !(use_conv4(d, plain) && m->packed[op.layer].kind == 3)) continue;
-      if (pack_layer(d, tt, plain, &m->packed_mix[op.layer])) return 1;
-      m->packed_mix[op.layer].mix_bit = kGateMixBit;
-    }
-    for (const Tower& T : m->graph.experts)
-      for (const Op& op : T.ops) {
+  // the passes a model of this dtype runs, per tower (-1: the gating net): the main pass; the filter pass of the two-stage gate; the
+  // experts' cross-term passes in both formats (x8_mask 0, the guard's re-evaluation, is the main pass); the experiment's
+  // single-product passes.  Every (packing, layer) launch_form names over them is packed once
+  m->has_mix = g_experiment_mix && act_planes(dtype) > 1 && cfg->arch == NESTI_ARCH_EXPERTS && cfg->grid_n == 8;
+  for (int t = -1; t < (int)m->graph.experts.size(); ++t) {
+    std::vector<Pass> passes(1);
+    if (m->cascade && t < 0) { passes.push_back(Pass()); passes.back().fast = true; }
+    for (int fmt : {8, 6})
+      if (x8 && t >= 0) { passes.push_back(Pass()); passes.back().x8_mask = 0xF; passes.back().x8_fmt = fmt; }
+    if (m->has_mix) { passes.push_back(Pass()); passes.back().mix = t < 0 ? 1 << kGateMixBit : 0x3F; }
+    for (Pass& ps : passes) {
+      ps.tower = t;
+      for (const Op& op : (t < 0 ? m->graph.gate : m->graph.experts[t]).ops) {
         if (op.kind != Op::CONV) continue;
         const LayerDesc& d = m->graph.layers[op.layer];
-        if (!use_conv8(d) && !(use_conv4(d, plain) && m->packed[op.layer].kind == 3)) continue;
-        // "inception<B>Expert_<i>_conv<2|3>": blocks 1, 2 (8^3) and 4 (4^3); conv2 is the smaller kernel of the block
-        const int blk = d.scope.size() > 9 ? d.scope[9] - '0' : 0;
-        const int idx = blk == 1 ? 0 : blk == 2 ? 1 : blk == 4 ? 2 : -1;
-        if (idx < 0) continue;
-        if (pack_layer(d, tt, plain, &m->packed_mix[op.layer])) return 1;
-        m->packed_mix[op.layer].mix_bit = 2 * idx + (d.scope.back() == '3' ? 1 : 0);
+        const LaunchForm f = launch_form(m->graph, op, ps, dtype);
+        const int packing = form_packing(f.form);
+        PackedLayer& pl = m->packed[{packing, op.layer}];
+        if (!pl.wpk && pack_form(d, tt, packing, dtype, &pl)) return 1;
+        if (f.producer) pl.x8_sc = x8_activation_exponent(d, tt);   // the pre-scale of the planes it writes
       }
+    }
   }
   if (x8) {
-    // the experts' tap layers at 8^3 once more in the FP8 cross-term packing, and the pre-scale of the planes their block's conv1 writes
-    m->packed_x8.resize(m->graph.layers.size());
-    m->packed_x6.resize(m->graph.layers.size());
-    for (const Tower& T : m->graph.experts)
-      for (const Op& op : T.ops) {
-        if (op.kind != Op::CONV) continue;
-        if (op.aux_out_buf >= 0) m->packed[op.layer].x8_sc = x8_activation_exponent(m->graph.layers[op.layer], tt);
-        if (op.aux_in_buf >= 0 && pack_layer_x8(m->graph.layers[op.layer], tt, &m->packed_x8[op.layer])) return 1;
-        if (op.aux_in_buf >= 0 && pack_layer_x8(m->graph.layers[op.layer], tt, &m->packed_x6[op.layer], 6)) return 1;
-      }
-    m->x8_mask = 0xF;          // all four tap layers at 8^3 (include/nesti_hip.h: nesti_model_set_x8_layers)
+    m->x8_mask = 0xF;         // all four tap layers at 8^3 (include/nesti_hip.h: nesti_model_set_x8_layers)
     NESTI_CHECK_HIP(hipMalloc((void**)&m->gstat, 64));
     NESTI_CHECK_HIP(hipMemset(m->gstat, 0, 64));
     for (auto& gl : m->glane) {
@@ -1511,14 +1569,6 @@ int nesti_model_create(const nesti_config_t* cfg, const nesti_tensor_t* tensors,
     }
   }
   if (m->cascade) {
-    m->packed_fast.resize(m->graph.layers.size());
-    for (const Op& op : m->graph.gate.ops) {
-      if (op.kind != Op::CONV) continue;
-      // the tap layers in plain f16; the one-tap layers (conv_igemm_kernel, kind 0, a single tap) keep an EMPTY entry: the filter pass
-      // runs them on the model's pair-packed weights (run_tower: x2l)
-      if (m->packed[op.layer].kind == 0 && m->packed[op.layer].n_taps == 1) continue;
-      if (pack_layer(m->graph.layers[op.layer], tt, NESTI_F16, &m->packed_fast[op.layer])) return 1;
-    }
     NESTI_CHECK_HIP(hipMalloc((void**)&m->cstat, 64));
     NESTI_CHECK_HIP(hipMemset(m->cstat, 0, 64));
   }
@@ -1543,7 +1593,7 @@ int nesti_experiment_mix_enable(int on) {
 
 int nesti_model_set_expert_mix(nesti_model_t* m, int mask) {
   if (!m) NESTI_FAIL("nesti_model_set_expert_mix: null model");
-  if (mask && m->packed_mix.empty()) NESTI_FAIL("nesti_model_set_expert_mix: pair-mode experts_n_est models (8^3 grid) created after nesti_experiment_mix_enable(1) only");
+  if (mask && !m->has_mix) NESTI_FAIL("nesti_model_set_expert_mix: pair-mode experts_n_est models (8^3 grid) created after nesti_experiment_mix_enable(1) only");
   if (mask < 0 || mask >= (1 << 6)) NESTI_FAIL("nesti_model_set_expert_mix: mask has six bits");
   m->expert_mix = mask;
   return 0;
@@ -1551,7 +1601,7 @@ int nesti_model_set_expert_mix(nesti_model_t* m, int mask) {
 
 int nesti_model_set_x8_layers(nesti_model_t* m, int mask) {
   if (!m) NESTI_FAIL("nesti_model_set_x8_layers: null model");
-  if (m->packed_x8.empty()) NESTI_FAIL("nesti_model_set_x8_layers: not an NESTI_F16X8 / NESTI_F16X8C model");
+  if (!m->graph.x8) NESTI_FAIL("nesti_model_set_x8_layers: not an NESTI_F16X8 / NESTI_F16X8C model");
   if (mask < 0 || mask > 0xF) NESTI_FAIL("nesti_model_set_x8_layers: mask has four bits (inception1 conv2 / conv3, inception2 conv2 / conv3)");
   m->x8_mask = mask;
   return 0;
@@ -1561,7 +1611,7 @@ int nesti_f32_to_e2m3(float value, float inv_scale) { return (int)host_f32_to_e2
 
 int nesti_model_set_x8_format(nesti_model_t* m, int bits) {
   if (!m) NESTI_FAIL("nesti_model_set_x8_format: null model");
-  if (m->packed_x8.empty()) NESTI_FAIL("nesti_model_set_x8_format: not an NESTI_F16X8 / NESTI_F16X8C model");
+  if (!m->graph.x8) NESTI_FAIL("nesti_model_set_x8_format: not an NESTI_F16X8 / NESTI_F16X8C model");
   if (bits != 8 && bits != 6) NESTI_FAIL("nesti_model_set_x8_format: 8 (e4m3, one scale per layer) or 6 (e2m3, one scale per 16-channel block)");
   m->x8_fmt = bits;
   return 0;
@@ -1591,7 +1641,7 @@ int nesti_model_x8_guard_stats(const nesti_model_t* m, nesti_x8_guard_stats_t* o
 
 int nesti_model_set_gate_mix(nesti_model_t* m, int on) {
   if (!m) NESTI_FAIL("nesti_model_set_gate_mix: null model");
-  if (on && m->packed_mix.empty()) NESTI_FAIL("nesti_model_set_gate_mix: pair-mode experts_n_est models (8^3 grid) created after nesti_experiment_mix_enable(1) only");
+  if (on && !m->has_mix) NESTI_FAIL("nesti_model_set_gate_mix: pair-mode experts_n_est models (8^3 grid) created after nesti_experiment_mix_enable(1) only");
 #ifndef NESTI_EXPERIMENT_XW
   if (on == 2) NESTI_FAIL("nesti_model_set_gate_mix: mode 2 (the exact-weight filter emulation of profiles/r05_gate_medium.txt) needs a "
                           "library built with EXTRA_CXXFLAGS=-DNESTI_EXPERIMENT_XW");
@@ -1892,7 +1942,7 @@ int nesti_model_macs(const nesti_model_t* m, int tower, int kind, double* nomina
   for (const Op& op : T.ops) {
     if (op.kind != Op::CONV) continue;
     const LayerDesc& d = m->graph.layers[op.layer];
-    const PackedLayer& pl = m->packed[op.layer];
+    const PackedLayer& pl = m->main_packing(op.layer);
     if (kind >= 0 && conv_category(d, pl) != kind) continue;
     const int S = d.s_real ? d.s_real : (1 << d.log2S), V = S * S * S, lo = (d.k - 1) / 2;
     long long valid = 0;   // sum over output voxels of the taps that land inside the volume
@@ -1927,6 +1977,17 @@ int nesti_model_macs(const nesti_model_t* m, int tower, int kind, double* nomina
 // ---- test hooks: one tower, launch by launch (include/nesti_hip.h) ----------------------------------------------------------
 static const nesti_debug_pass_t kMainPass = {0, 0, 0};
 
+// the pass arguments of the two hooks against the graph (cascade: a model with the two-stage gate); `who` prefixes the message
+static int check_pass(const std::string& who, const Graph& g, bool cascade, int tower, const nesti_debug_pass_t& ps) {
+  if (tower < -1 || tower >= (int)g.experts.size()) NESTI_FAIL(who + ": tower must be -1 (gate) or an expert index");
+  if (tower < 0 && g.cfg.arch != NESTI_ARCH_EXPERTS && g.cfg.arch != NESTI_ARCH_SWITCH) NESTI_FAIL(who + ": this model has no gating net");
+  if (ps.fast && !(cascade && tower < 0)) NESTI_FAIL(who + ": the filter pass is the gating net's of NESTI_F16X3C / NESTI_F16X8C models");
+  if (ps.x8_mask < 0 || ps.x8_mask > 0xF || (ps.x8_mask && !(g.x8 && tower >= 0)))
+    NESTI_FAIL(who + ": x8_mask has four bits and applies to the expert towers of NESTI_F16X8 / NESTI_F16X8C models");
+  if (ps.x8_fmt != 0 && ps.x8_fmt != 6 && ps.x8_fmt != 8) NESTI_FAIL(who + ": x8_fmt is 0 (= 6), 6 or 8");
+  return 0;
+}
+
 int nesti_debug_tower_ops(const nesti_config_t* cfg, int dtype, int tower, int batch, const nesti_debug_pass_t* pass,
                           nesti_debug_buf_t* bufs, int max_bufs, int* n_bufs, nesti_debug_op_t* ops, int max_ops, int* n_ops,
                           int32_t* in_pos, int max_in_pos, int* n_in_pos, size_t* ws_bytes) {
@@ -1935,14 +1996,10 @@ int nesti_debug_tower_ops(const nesti_config_t* cfg, int dtype, int tower, int b
   const nesti_debug_pass_t& ps = pass ? *pass : kMainPass;
   Graph g;
   if (build_graph(cfg, &g, dtype_x8(dtype))) return 1;
-  if (tower < -1 || tower >= (int)g.experts.size()) NESTI_FAIL("nesti_debug_tower_ops: tower must be -1 (gate) or an expert index");
-  if (tower < 0 && g.cfg.arch != NESTI_ARCH_EXPERTS && g.cfg.arch != NESTI_ARCH_SWITCH) NESTI_FAIL("nesti_debug_tower_ops: this model has no gating net");
-  if (ps.fast && !(dtype_cascade(dtype) && tower < 0))
-    NESTI_FAIL("nesti_debug_tower_ops: the filter pass is the gating net's of NESTI_F16X3C / NESTI_F16X8C models");
-  if (ps.x8_mask < 0 || ps.x8_mask > 0xF || (ps.x8_mask && !(g.x8 && tower >= 0)))
-    NESTI_FAIL("nesti_debug_tower_ops: x8_mask has four bits and applies to the expert towers of NESTI_F16X8 / NESTI_F16X8C models");
-  if (ps.x8_fmt != 0 && ps.x8_fmt != 6 && ps.x8_fmt != 8) NESTI_FAIL("nesti_debug_tower_ops: x8_fmt is 0 (= 6), 6 or 8");
+  if (check_pass("nesti_debug_tower_ops", g, dtype_cascade(dtype), tower, ps)) return 1;
   const Tower& T = tower < 0 ? g.gate : g.experts[tower];
+  Pass run;
+  run.tower = tower; run.fast = ps.fast != 0; run.x8_mask = ps.x8_mask; run.x8_fmt = ps.x8_fmt == 8 ? 8 : 6;
   const int mdt = main_dtype(dtype), dt = ps.fast ? NESTI_F16 : mdt;   // as run_op
   const int planes = act_planes(dt);
   const Placement P = place_tower(T, batch, dt);
@@ -1993,17 +2050,10 @@ int nesti_debug_tower_ops(const nesti_config_t* cfg, int dtype, int tower, int b
     o.layer = op.layer; o.k = d.k; o.log2S = d.log2S; o.s_real = d.s_real; o.is_fc = d.is_fc; o.bn = d.bn; o.relu = d.relu;
     o.pool_k = d.pool_k; o.n_taps = layer_taps(d);
     o.cin = d.cin; o.cout = d.cout; o.Cin_p = d.Cin_p; o.Cout_p = d.Cout_p;
-    // the packing run_op picks for this pass (nesti_model_create: the filter pass keeps no plain copy of a one-tap conv_igemm layer
-    // and runs it on the pair packing; the x8 copies exist for the consumer layers only)
-    const bool x2l = ps.fast && layer_kind(d, mdt) == 0 && o.n_taps == 1;
-    const bool x8l = !ps.fast && op.aux_in_buf >= 0 && op.x8_bit >= 0 && ((ps.x8_mask >> op.x8_bit) & 1);
-    o.family = x2l ? layer_kind(d, mdt) : layer_kind(d, dt);
-    if (x2l) o.form = NESTI_DEBUG_FORM_X2;
-    if (x8l) {
-      o.form = ps.x8_fmt == 8 ? NESTI_DEBUG_FORM_X8 : NESTI_DEBUG_FORM_X6;
-      o.aux_in_buf = op.aux_in_buf; o.aux_layer = op.aux_layer;
-    }
-    if (!ps.fast && op.aux_out_buf >= 0 && (ps.x8_mask & op.x8_bits)) o.aux_out_buf = op.aux_out_buf;
+    const LaunchForm f = launch_form(g, op, run, mdt);
+    o.family = f.family; o.form = f.form;
+    if (f.form == NESTI_DEBUG_FORM_X8 || f.form == NESTI_DEBUG_FORM_X6) { o.aux_in_buf = op.aux_in_buf; o.aux_layer = op.aux_layer; }
+    if (f.producer) o.aux_out_buf = op.aux_out_buf;
     o.in_pos_off = pos;
     for (int c = 0; c < d.cin; ++c, ++pos) if (in_pos) in_pos[pos] = d.in_pos[c];
   }
@@ -2017,25 +2067,12 @@ int nesti_debug_tower_step(const nesti_model_t* m, int tower, const nesti_debug_
   if (batch <= 0) NESTI_FAIL("nesti_debug_tower_step: batch must be positive");
   const nesti_debug_pass_t& ps = pass ? *pass : kMainPass;
   const Graph& g = m->graph;
-  if (tower < -1 || tower >= (int)g.experts.size()) NESTI_FAIL("nesti_debug_tower_step: tower must be -1 (gate) or an expert index");
-  if (tower < 0 && g.cfg.arch != NESTI_ARCH_EXPERTS && g.cfg.arch != NESTI_ARCH_SWITCH) NESTI_FAIL("nesti_debug_tower_step: this model has no gating net");
-  if (ps.fast && !(m->cascade && tower < 0)) NESTI_FAIL("nesti_debug_tower_step: the filter pass is the gating net's of NESTI_F16X3C / NESTI_F16X8C models");
-  if (ps.x8_mask < 0 || ps.x8_mask > 0xF || (ps.x8_mask && !(g.x8 && tower >= 0)))
-    NESTI_FAIL("nesti_debug_tower_step: x8_mask has four bits and applies to the expert towers of NESTI_F16X8 / NESTI_F16X8C models");
+  if (check_pass("nesti_debug_tower_step", g, m->cascade, tower, ps)) return 1;
   if (ps.x8_fmt != 0 && ps.x8_fmt != m->x8_fmt) NESTI_FAIL("nesti_debug_tower_step: x8_fmt differs from the model's (nesti_model_set_x8_format)");
   if (walk < 0 || (walk > 1 && walk % 8)) NESTI_FAIL("nesti_debug_tower_step: walk is 0, 1 or a multiple of 8");
   const Tower& T = tower < 0 ? g.gate : g.experts[tower];
   if (op < 0 || op >= (int)T.ops.size()) NESTI_FAIL("nesti_debug_tower_step: op index outside the tower");
-  // the RunCtx of the product's passes: experts_impl (expert towers), gate_impl (gating net), gate_cascade (filter pass)
-  RunCtx rc{m, batch, npoints_dev, point_index_dev, (hipStream_t)stream, ps.fast != 0};
-  if (tower >= 0) {
-    rc.mix = m->expert_mix;
-    rc.x8 = ps.x8_mask;
-  } else if (!ps.fast) {
-    rc.mix = m->gate_mix ? (1 << kGateMixBit) : 0;
-    rc.zero_lo = m->gate_mix == 2;
-  }
-  rc.walk = walk;
+  const RunCtx rc = pass_ctx(m, tower, ps.fast != 0, ps.x8_mask, batch, npoints_dev, point_index_dev, (hipStream_t)stream, walk);
   std::vector<unsigned char*> ptr;
   if (tower_ptrs(rc, T, mups_dev, (unsigned char*)ws_dev, ws_bytes, &ptr)) return 1;
   return run_op(rc, T, T.ops[op], ptr);

@@ -40,6 +40,21 @@ constexpr int kPairPlanes = 2;    // hi, lo
 static inline int act_planes(int dt) { return (dt == NESTI_BF16X3 || dt == NESTI_F16X3) ? kPairPlanes : 1; }
 constexpr int kSplitGroup = 64;
 __host__ __device__ __forceinline__ int split_col(int col) { return (col >> 6) * (kPairPlanes * kSplitGroup) + (col & (kSplitGroup - 1)); }
+// Where the tap kernels (conv8n.hip, conv4n.hip) find a 64-byte K chunk in an activation row, in bytes.  Plain rows: chunk c
+// of 32 channels at 64 c.  Pair-layout rows [hi 64 | lo 64] per 64-channel group: the pair loop's chunk c is 16 channels of
+// BOTH planes (PAIR; 32 bytes into each plane per chunk), and a plain loop that reads only the hi planes of such a tensor
+// (in_pair, ConvParams::in_pair) finds its 32-channel chunk c in the hi plane of group c >> 1.
+template <bool PAIR>
+__device__ __forceinline__ size_t tap_chunk_offset(int c, int in_pair) {
+  return PAIR ? (size_t)(c >> 2) * (2 * kPairPlanes * kSplitGroup) + (size_t)(c & 3) * 32
+              : in_pair ? (size_t)(c >> 1) * (2 * kPairPlanes * kSplitGroup) + (size_t)(c & 1) * 64 : (size_t)c * 64;
+}
+// ... and the 16-byte slot `slot` (0 .. 3) of the chunk's LDS row inside it: PAIR rows are [hi k0..15 | lo k0..15], slots 0, 1
+// from the hi plane and 2, 3 from the lo plane one plane (2 * kSplitGroup bytes) further
+template <bool PAIR>
+__device__ __forceinline__ int tap_slot_offset(int slot) {
+  return PAIR ? (slot & 1) * 16 + (slot >> 1) * (2 * kSplitGroup) : slot * 16;
+}
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // ---- element conversion (device) ------------------------------------------
@@ -128,6 +143,30 @@ __device__ __forceinline__ void store_act8(unsigned char* base, long long row_el
   unsigned char* d0 = base + (row_elems + split_col(col)) * 2;
   *reinterpret_cast<uint4*>(d0) = h;
   *reinterpret_cast<uint4*>(d0 + 2 * kSplitGroup) = l;
+}
+// Four / eight consecutive output channels of a conv epilogue; out_esz = bytes per output element: 4 = fp32 (ConvParams::out_f32,
+// and the exact-fp32 kernels always), else the kernel's 16-bit type (DT; pairs with `split`).  The kernel computes out_esz once:
+// derived in here from (out_f32, DT), hipcc schedules every tile kernel's epilogue differently
+template <int DT>
+__device__ __forceinline__ void store_out4(unsigned char* base, long long row_elems, int col, const float4& v, int out_esz, int split) {
+  if (out_esz == 4) {
+    *reinterpret_cast<float4*>(base + (row_elems + col) * 4) = v;
+  } else {
+    using E = Elem<DT == NESTI_F32 ? NESTI_BF16 : DT>;
+    store_act4<E>(base, row_elems, col, v.x, v.y, v.z, v.w, split);
+  }
+}
+template <int DT>
+__device__ __forceinline__ void store_out8(unsigned char* base, long long row_elems, int col, const float4& f0, const float4& f1, int out_esz,
+                                           int split) {
+  if (out_esz == 4) {
+    float4* dst = reinterpret_cast<float4*>(base + (row_elems + col) * 4);
+    dst[0] = f0;
+    dst[1] = f1;
+  } else {
+    using E = Elem<DT == NESTI_F32 ? NESTI_BF16 : DT>;
+    store_act8<E>(base, row_elems, col, f0, f1, split);
+  }
 }
 
 // ---- e4m3 planes of the FP8 cross terms (kernels.h: ConvParams::aux8_out; conv8n.hip X8) ----------------------------------------

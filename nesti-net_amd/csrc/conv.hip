@@ -112,12 +112,10 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvParams& p, const unsig
 
   // XCD-aware block -> tile map: the 8 blocks of a dispatch group land on the 8 XCDs; each XCD
   // keeps its M tile and walks the N tiles, so the staged input stays in that XCD's L2.
-  const int xcd = bid & 7, grp = bid >> 3;
-  const int n_tile = grp % p.n_tiles;
-  const int m_tile = (grp / p.n_tiles) * 8 + xcd;
+  const TileId t = tile_id(bid, p.n_tiles);
+  const int n_tile = t.sub, m_tile = t.m_tile;
   if (m_tile >= p.m_tiles) return;
-  int npts = p.npoints;
-  if (p.npoints_ptr) npts = min(npts, *p.npoints_ptr);
+  const int npts = live_points(p);
   const int remap = KPIPE ? 0 : p.remap;
   const SwzKey swz_key(remap, p.log2S);
   const int log2S = p.log2S, log2V = 3 * log2S;
@@ -574,14 +572,6 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvParams& p, const unsig
     // 4-channel group.  max(relu(x + b)) is taken on the final values, exactly like pooling the stored tensor.
     unsigned char* mp_b = reinterpret_cast<unsigned char*>(p.mp_out);
     const int Vo = V >> 3, So = S >> 1, log2So = log2S - 1;
-    auto cvt_store = [&](unsigned char* base, long long row_elems, int col, const float4& v) __attribute__((always_inline)) {
-      if (out_esz == 4) {
-        *reinterpret_cast<float4*>(base + (row_elems + col) * 4) = v;
-      } else {
-        using E = Elem<DT == NESTI_F32 ? NESTI_BF16 : DT>;
-        store_act4<E>(base, row_elems, col, v.x, v.y, v.z, v.w, p.split);
-      }
-    };
     auto mp_half = [&](auto NH) __attribute__((always_inline)) {
       constexpr int nh = decltype(NH)::value;
 #pragma unroll
@@ -606,7 +596,7 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvParams& p, const unsig
           const long long gr = r0 + row;
           if (gr < total_rows) {
             const float4 v4 = *reinterpret_cast<const float4*>(smem + row * kPoolStride + cg * 16);
-            cvt_store(out_b, gr * p.out_cstride, out_col0 + nh * 64 + cg * 4, v4);
+            store_out4<DT>(out_b, gr * p.out_cstride, out_col0 + nh * 64 + cg * 4, v4, out_esz, p.split);
             if (p.aux8_out && p.x8_fmt != 6)   // the e4m3 planes of conv1's outputs for the FP8 cross terms of the block's tap layers (conv8n.hip X8)
               store_aux8_4(reinterpret_cast<unsigned char*>(p.aux8_out) + gr * p.aux8_stride, n_local * TN + nh * 64 + cg * 4,
                            v4.x, v4.y, v4.z, v4.w, aux_mul_lo, aux_mul_hi);
@@ -643,7 +633,7 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvParams& p, const unsig
         }
         const long long go = (r0 >> 3) + orow;
         if (go < (total_rows >> 3))
-          cvt_store(mp_b, go * p.mp_cstride, out_col0 + nh * 64 + cg * 4, m);
+          store_out4<DT>(mp_b, go * p.mp_cstride, out_col0 + nh * 64 + cg * 4, m, out_esz, p.split);
       }
       __syncthreads();
     };

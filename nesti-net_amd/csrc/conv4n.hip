@@ -37,7 +37,11 @@
 //
 // X3 (pair modes, model.hip: PackedLayer::x3n): the K chunk is 16 channels -- an LDS row holds [hi k0..15 | lo k0..15] and a
 // weight row [W_hi k0..15 | W_lo k0..15]; the K = 32 MFMA multiplies [hi | lo] x [W_hi ; W_hi] (= hi W_hi + lo W_hi) and
-// [hi | lo] x [W_lo ; 0] (= hi W_lo; the zero half comes from an out-of-range LDS address, which reads as zeros on gfx950).
+// [hi | lo] x [W_lo ; 0] (= hi W_lo; the zero half comes from an out-of-range LDS address, which reads as zeros on gfx950:
+// mma.h, kLdsOob).
+//
+// Shared with conv8n.hip: the block -> tile map and the launch refusals (kernels.h), the LDS reads (mma.h), the K chunk's place in an
+// activation row and the output stores (common.h).
 #include <type_traits>
 
 #include "kernels.h"
@@ -46,27 +50,17 @@
 namespace nesti {
 namespace {
 
-constexpr int kThreads4 = 512;
 constexpr int kPts4 = 16;                    // points per workgroup
 constexpr int kTile4 = 1024;                 // 16 rows x 64 B
 constexpr int kBTap4 = 4 * kTile4;           // one tap's weights: 64 columns x 64 B
 constexpr int kABuf4 = 64 * kTile4;          // one input chunk: 64 voxel tiles = 64 KiB
-constexpr int kEpiStride4 = 144;             // bytes per row of the fp32 [1024][32] epilogue tile (+16 B pad)
-constexpr int kEpi4 = 1024 * kEpiStride4;    // 144 KiB
+constexpr int kEpi4 = 1024 * kEpiStride;    // 144 KiB
 // LDS of the instantiation for kernel edge K: two weight slots of one tap row each (K taps x 4 KiB), then the input chunk --
 // double-buffered where that fits 160 KiB (K <= 4: 32 + 128 KiB for K = 4), single otherwise (K = 5: 40 + 64 KiB)
 template <int K> constexpr bool dba4() { return 2 * K * kBTap4 + 2 * kABuf4 <= 163840; }
 template <int K> constexpr int lds4() {
   constexpr int loop = 2 * K * kBTap4 + (dba4<K>() ? 2 : 1) * kABuf4;
   return loop > kEpi4 ? loop : kEpi4;
-}
-constexpr unsigned kOob4 = 0x40000u;         // beyond any LDS allocation: ds_read returns 0
-
-typedef unsigned u32x4q_t __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(3))) u32x4q_t* lds_u32x4q_ptr;
-__device__ __forceinline__ uint4 lds128q(unsigned addr) {
-  const u32x4q_t v = *(lds_u32x4q_ptr)(size_t)addr;
-  return make_uint4(v.x, v.y, v.z, v.w);
 }
 
 // 16-B slot swizzle key of row r of a 16-row tile (see the header): with it the four row quads a ds_read_b128 lane group
@@ -97,11 +91,11 @@ __device__ __forceinline__ void conv4n_tile(const ConvParams& p, const unsigned 
   const int cw = wave & 3, h = wave >> 2;    // Latin class and z half of this wave's two lines
 
   // XCD-aware block -> tile map: the column tiles of a group of 16 points stay on one XCD's L2
-  const int xcd = bid & 7, grp = bid >> 3;
-  const int n_tile = grp % p.n_tiles;
-  const int m_tile = (grp / p.n_tiles) * 8 + xcd;
+  const TileId t = tile_id(bid, p.n_tiles);
+  const int n_tile = t.sub, m_tile = t.m_tile;
   if (m_tile >= p.m_tiles) return;
-  int npts = p.npoints;
+  int npts = p.npoints;                      // live_points(p), spelled out: through the helper hipcc allocates the scalar registers of
+                                             // every instantiation of this kernel differently (profiles/refactor_isa_tiles.txt)
   if (p.npoints_ptr) npts = min(npts, *p.npoints_ptr);
   const int p0 = m_tile * kPts4;
   if (p0 >= npts) return;
@@ -116,11 +110,10 @@ __device__ __forceinline__ void conv4n_tile(const ConvParams& p, const unsigned 
   const int st_slot = (lane & 3) ^ swz4(st_row);                   // inverse swizzle on the SOURCE (LDS-DMA writes lane-linear)
   const bool st_ok = st_row < np_here;
   const size_t st_off = (size_t)st_row * 64 * p.in_cstride * kEsz +
-                        (X3 ? (size_t)((st_slot & 1) * 16 + (st_slot >> 1) * (2 * kSplitGroup)) : (size_t)st_slot * 16);
+                        (size_t)tap_slot_offset<X3>(st_slot);
   // tiles q0 .. q0 + nq - 1 of this wave's eight, chunk c, into input buffer `buf`
   auto stage_a = [&](int c, int buf, int q0, int nq) __attribute__((always_inline)) {
-    const size_t coff = X3 ? (size_t)(c >> 2) * (2 * kPairPlanes * kSplitGroup) + (size_t)(c & 3) * 32
-                           : p.in_pair ? (size_t)(c >> 1) * (2 * kPairPlanes * kSplitGroup) + (size_t)(c & 1) * 64 : (size_t)c * 64;
+    const size_t coff = tap_chunk_offset<X3>(c, p.in_pair);
 #pragma unroll
     for (int qq = 0; qq < nq; ++qq) {
       const int s = wave * 8 + q0 + qq;                            // slot -> voxel: x = s & 3, line L = s >> 2 = 4 class + z
@@ -144,7 +137,7 @@ __device__ __forceinline__ void conv4n_tile(const ConvParams& p, const unsigned 
   unsigned b_lane[NB];
   if (X3) {
     b_lane[0] = lds0 + (unsigned)(r16 * 64 + (((kb & 1) ^ swz4(r16)) << 4));
-    b_lane[NB - 1] = kb < 2 ? lds0 + (unsigned)(r16 * 64 + (((2 + (kb & 1)) ^ swz4(r16)) << 4)) : kOob4;
+    b_lane[NB - 1] = kb < 2 ? lds0 + (unsigned)(r16 * 64 + (((2 + (kb & 1)) ^ swz4(r16)) << 4)) : kLdsOob;
   } else {
     b_lane[0] = lds0 + frag;
   }
@@ -182,13 +175,13 @@ __device__ __forceinline__ void conv4n_tile(const ConvParams& p, const unsigned 
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-      for (int x = 0; x < 4; ++x) dst[j][x] = lds128q(base + (4 * j + x) * kTile4);
+      for (int x = 0; x < 4; ++x) dst[j][x] = lds_read16(base + (4 * j + x) * kTile4);
   };
   auto load_b = [&](uint4 (&dst)[4][NB], unsigned off) __attribute__((always_inline)) {
 #pragma unroll
     for (int n = 0; n < 4; ++n)
 #pragma unroll
-      for (int s = 0; s < NB; ++s) dst[n][s] = lds128q(b_lane[s] + off + n * kTile4);
+      for (int s = 0; s < NB; ++s) dst[n][s] = lds_read16(b_lane[s] + off + n * kTile4);
   };
 
   // The layer is ONE stream of G = n_chunks * K^2 tap rows.  Row g multiplies out of weight slot g & 1 and input buffer
@@ -282,20 +275,11 @@ __device__ __forceinline__ void conv4n_tile(const ConvParams& p, const unsigned 
   __syncthreads();                           // nobody still reads A / B: the LDS becomes the epilogue tile
 
   // ---- epilogue: bias + ReLU in fp32 through an LDS tile [16 pts x 64 voxels][32], one pass per 32 columns ------------------
+  // (behind a pass's first barrier this is conv8n.hip's epilogue with another row <-> voxel map: see the note there)
   const int out_esz = p.out_f32 ? 4 : kEsz;
   const float act_floor = p.relu ? 0.f : -INFINITY;
   unsigned char* out_b = reinterpret_cast<unsigned char*>(p.out);
   unsigned char* mp_b = reinterpret_cast<unsigned char*>(p.mp_out);
-  auto cvt_store8 = [&](unsigned char* base, long long row_elems, int col, const float4& f0, const float4& f1) __attribute__((always_inline)) {
-    if (out_esz == 4) {
-      float4* dst = reinterpret_cast<float4*>(base + (row_elems + col) * 4);
-      dst[0] = f0;
-      dst[1] = f1;
-    } else {
-      using E = Elem<DT == NESTI_F32 ? NESTI_BF16 : DT>;
-      store_act8<E>(base, row_elems, col, f0, f1, p.split);
-    }
-  };
   auto epi_pass = [&](auto PP) __attribute__((always_inline)) {
     constexpr int pass = decltype(PP)::value;
     const int out_col0 = p.out_coff + n_tile * 64 + pass * 32;
@@ -312,7 +296,7 @@ __device__ __forceinline__ void conv4n_tile(const ConvParams& p, const unsigned 
 #pragma unroll
           for (int r = 0; r < 4; ++r) {        // D: column = lane & 15, row (point) = 4 (lane >> 4) + r
             const int row = (4 * kb + r) * 64 + v;
-            *reinterpret_cast<float*>(smem + row * kEpiStride4 + (n2 * 16 + r16) * 4) = fmaxf(fmaf(acc[j][x][n][r], p.acc_scale, bv), act_floor);
+            *reinterpret_cast<float*>(smem + row * kEpiStride + (n2 * 16 + r16) * 4) = fmaxf(fmaf(acc[j][x][n][r], p.acc_scale, bv), act_floor);
           }
         }
       }
@@ -321,13 +305,13 @@ __device__ __forceinline__ void conv4n_tile(const ConvParams& p, const unsigned 
     if (p.mp_mode != 1) {                    // full-resolution rows: 4 lanes x 8 channels = one 32-channel row segment
 #pragma unroll 2
       for (int it = 0; it < 8; ++it) {
-        const int item = it * kThreads4 + tid;
+        const int item = it * kTapThreads + tid;
         const int row = item >> 2, seg = item & 3;
         const int ptl = row >> 6, vox = row & 63;
         if (ptl < np_here) {
-          const float4 f0 = *reinterpret_cast<const float4*>(smem + row * kEpiStride4 + seg * 32);
-          const float4 f1 = *reinterpret_cast<const float4*>(smem + row * kEpiStride4 + seg * 32 + 16);
-          cvt_store8(out_b, ((long long)(p0 + ptl) * 64 + vox) * p.out_cstride, out_col0 + seg * 8, f0, f1);
+          const float4 f0 = *reinterpret_cast<const float4*>(smem + row * kEpiStride + seg * 32);
+          const float4 f1 = *reinterpret_cast<const float4*>(smem + row * kEpiStride + seg * 32 + 16);
+          store_out8<DT>(out_b, ((long long)(p0 + ptl) * 64 + vox) * p.out_cstride, out_col0 + seg * 8, f0, f1, out_esz, p.split);
         }
       }
     }
@@ -338,13 +322,13 @@ __device__ __forceinline__ void conv4n_tile(const ConvParams& p, const unsigned 
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
         const int row = ptl * 64 + (2 * cz + (q >> 2)) * 16 + (2 * cy + ((q >> 1) & 1)) * 4 + 2 * cx + (q & 1);
-        const float4 f0 = *reinterpret_cast<const float4*>(smem + row * kEpiStride4 + seg * 32);
-        const float4 f1 = *reinterpret_cast<const float4*>(smem + row * kEpiStride4 + seg * 32 + 16);
+        const float4 f0 = *reinterpret_cast<const float4*>(smem + row * kEpiStride + seg * 32);
+        const float4 f1 = *reinterpret_cast<const float4*>(smem + row * kEpiStride + seg * 32 + 16);
         m0.x = fmaxf(m0.x, f0.x); m0.y = fmaxf(m0.y, f0.y); m0.z = fmaxf(m0.z, f0.z); m0.w = fmaxf(m0.w, f0.w);
         m1.x = fmaxf(m1.x, f1.x); m1.y = fmaxf(m1.y, f1.y); m1.z = fmaxf(m1.z, f1.z); m1.w = fmaxf(m1.w, f1.w);
       }
       if (ptl < np_here)
-        cvt_store8(mp_b, ((long long)(p0 + ptl) * 8 + (cz * 4 + cy * 2 + cx)) * p.mp_cstride, out_col0 + seg * 8, m0, m1);
+        store_out8<DT>(mp_b, ((long long)(p0 + ptl) * 8 + (cz * 4 + cy * 2 + cx)) * p.mp_cstride, out_col0 + seg * 8, m0, m1, out_esz, p.split);
     }
     __syncthreads();
   };
@@ -353,7 +337,7 @@ __device__ __forceinline__ void conv4n_tile(const ConvParams& p, const unsigned 
 }
 
 template <int DT, int K, bool X3, bool WALK>
-__global__ __launch_bounds__(kThreads4) void conv4n_kernel(const ConvParams p) {
+__global__ __launch_bounds__(kTapThreads) void conv4n_kernel(const ConvParams p) {
   if constexpr (!WALK) {
     conv4n_tile<DT, K, X3>(p, blockIdx.x, threadIdx.x);
   } else {
@@ -365,7 +349,7 @@ __global__ __launch_bounds__(kThreads4) void conv4n_kernel(const ConvParams p) {
 
 template <int DT, int K, bool X3>
 int launch_conv4n_one(const ConvParams& p, hipStream_t stream) {
-  return launch_tiles<conv4n_kernel<DT, K, X3, false>, conv4n_kernel<DT, K, X3, true>>(p, lds4<K>(), kThreads4,
+  return launch_tiles<conv4n_kernel<DT, K, X3, false>, conv4n_kernel<DT, K, X3, true>>(p, lds4<K>(), kTapThreads,
                                                                                       tile_rows8(p.m_tiles) * p.n_tiles, stream);
 }
 
@@ -401,10 +385,7 @@ int launch_conv4n(const ConvParams& p, int dtype, int k, hipStream_t stream) {
     if (p.tap[t][0] != t / (k * k) - lo || p.tap[t][1] != (t / k) % k - lo || p.tap[t][2] != t % k - lo)
       NESTI_FAIL("launch_conv4n: taps must be in (dz, dy, dx) order, x fastest");
   }
-  if (p.point_index) NESTI_FAIL("launch_conv4n: no input gather (k^3 layers never read the routed MuPS tensor)");
-  if (p.pool_k > 1 || p.split_tile != p.n_tiles) NESTI_FAIL("launch_conv4n: no fused avg-pool / merged layers");
-  if (p.mp_mode == 2) NESTI_FAIL("launch_conv4n: max-pool mode 2 is conv1's (a 1x1x1 layer)");
-  if (p.mp_mode != 0 && !p.mp_out) NESTI_FAIL("launch_conv4n: fused max-pool needs an output");
+  if (check_tap_launch(p, "launch_conv4n")) return 1;
   return with_elem_type(dtype, "launch_conv4n", [&](auto dt) { return launch_conv4n_dt<decltype(dt)::value>(p, k, stream); });
 }
 

@@ -15,7 +15,8 @@
 //   * the K chunk is 64 bytes per row (32 x 16-bit or 16 x f32 channels), so the 4 points' chunk stays resident in LDS for
 //     all k^3 taps and a tap's weight tile serves 4 points instead of one: a quarter of the weight stream per output;
 //   * the only per-lane padding test left is x + dx: an out-of-range lane reads an LDS address beyond the allocation, which
-//     returns zeros on gfx950 (scripts/lds_oob_probe.hip; checked at model creation, conv8_selftest), so no zero rows are kept;
+//     returns zeros on gfx950 (mma.h: kLdsOob; scripts/lds_oob_probe.hip; checked at model creation, conv8_selftest), so no zero
+//     rows are kept;
 //   * a wave owns FOUR x-line tiles x TWO 32-column tiles, so that every A fragment read from LDS feeds two 32x32x16 MFMAs or
 //     three + three (pair modes): 0.75 / 0.5 KB of LDS reads per 32x32x16-sized product (round 3: 1.125 / 0.75 with eight tiles x
 //     one column tile per wave, 2-5 % slower same-box; these kernels sit within ~10 % of the matrix pipe's own rate on such data,
@@ -79,20 +80,10 @@
 namespace nesti {
 namespace {
 
-constexpr int kThreadsN = 512;
 constexpr int kPtsN = 4;
 constexpr int kTileN = 2048;                 // 32 rows x 64 B
 constexpr int kBTileN = 2 * kTileN;          // one tap's weights: two 32-column tiles
 constexpr int kAOffN = 65536;
-constexpr unsigned kOobN = 0x40000u;         // beyond any LDS allocation: ds_read returns 0
-constexpr int kEpiStrideN = 144;             // bytes per row of the fp32 [1024][32] epilogue tile (+16 B pad)
-
-typedef unsigned u32x4n_t __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(3))) u32x4n_t* lds_u32x4n_ptr;
-__device__ __forceinline__ uint4 lds128n(unsigned addr) {
-  const u32x4n_t v = *(lds_u32x4n_ptr)(size_t)addr;
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
 
 // X6: the second 16 bytes of an FP6 block hold two data dwords, the scale byte's dword and padding.  Read as 8 + 4 bytes the six data
 // dwords of an operand are a 16-byte and an 8-byte result, which hipcc allocates as ONE six-register tuple; read as 16 + 16 it assembles
@@ -107,7 +98,7 @@ __device__ __forceinline__ uint4 lds_hi16n(unsigned addr) {
     const unsigned sc = *(lds_u32n_ptr)(size_t)(addr + 8u);
     return make_uint4(d.x, d.y, sc, 0u);
   } else {
-    return lds128n(addr);
+    return lds_read16(addr);
   }
 }
 
@@ -137,14 +128,10 @@ __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
   // XCD-aware block -> tile map: the 2 halves x n_tiles column pairs of a group of 4 points stay on one XCD's L2
-  const int xcd = bid & 7, grp = bid >> 3;
-  const int per_m = 2 * p.n_tiles;                       // p.n_tiles = 64-column pairs
-  const int sub = grp % per_m;
-  const int n_pair = sub >> 1, half = sub & 1;
-  const int m_tile = (grp / per_m) * 8 + xcd;
+  const TileId t = tile_id(bid, 2 * p.n_tiles);          // p.n_tiles = 64-column pairs
+  const int n_pair = t.sub >> 1, half = t.sub & 1, m_tile = t.m_tile;
   if (m_tile >= p.m_tiles) return;
-  int npts = p.npoints;
-  if (p.npoints_ptr) npts = min(npts, *p.npoints_ptr);
+  const int npts = live_points(p);
   const int p0 = m_tile * kPtsN;
   if (p0 >= npts) return;
   const int np_here = min(kPtsN, npts - p0);
@@ -168,7 +155,7 @@ __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned 
   for (int h = 0; h < 2; ++h) {
     const int pt = 2 * h + (st_row >> 3), x = st_row & 7;
     const int kslot = (lane & 3) ^ pt;                   // inverse swizzle on the SOURCE (LDS-DMA writes lane-linear)
-    a_voff[h] = (unsigned)((pt * 512 + x) * p.in_cstride * kEsz + (X3 ? (kslot & 1) * 16 + (kslot >> 1) * (2 * kSplitGroup) : kslot * 16));
+    a_voff[h] = (unsigned)((pt * 512 + x) * p.in_cstride * kEsz + tap_slot_offset<X3>(kslot));
     a_is8[h] = X8 && kslot >= 2;
     if (a_is8[h]) a_voff[h] = (unsigned)((pt * 512 + x) * p.aux8_stride + (kslot - 2) * kSplitGroup);
     a_ok[h] = pt < np_here;
@@ -178,17 +165,16 @@ __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned 
     for (int jz = 0; jz < NZ; ++jz) {
       const int zp = zlo + jz, yp = (wave - zp) & 7;     // source tile (y', z') of this wave's run: (y' + z') & 7 == wave
       if constexpr (X8) {
-        // chunk c = 16 channels: the hi plane of the pair row group [hi 64 | lo 64] (32 B at (c & 3) * 32) and 16 B of each e4m3
-        // plane of the side row group [lo8 64 | hi8 64]
+        // chunk c = 16 channels: the hi plane of the pair row group [hi 64 | lo 64] (32 B at (c & 3) * 32: tap_chunk_offset<true>,
+        // written out here because hipcc emits one more instruction per chunk when the sum is grouped the helper's way) and 16 B of
+        // each e4m3 plane of the side row group [lo8 64 | hi8 64]
         const size_t off16 = (size_t)((zp * 64 + yp * 8) * p.in_cstride) * kEsz + (size_t)(c >> 2) * (2 * kPairPlanes * kSplitGroup) + (size_t)(c & 3) * 32;
         const size_t off8 = (size_t)(zp * 64 + yp * 8) * p.aux8_stride + (size_t)(c >> 2) * (2 * kSplitGroup) + (size_t)(c & 3) * 16;
 #pragma unroll
         for (int h = 0; h < 2; ++h)
           if (a_ok[h]) glds16((a_is8[h] ? aux_b + off8 : in_b + off16) + a_voff[h], lds0 + kAOffN + (wave * NZ + jz) * kTileN + h * 1024);
       } else {
-      const unsigned char* src = in_b + (size_t)((zp * 64 + yp * 8) * p.in_cstride) * kEsz +
-                                 (X3 ? (size_t)(c >> 2) * (2 * kPairPlanes * kSplitGroup) + (size_t)(c & 3) * 32
-                                     : p.in_pair ? (size_t)(c >> 1) * (2 * kPairPlanes * kSplitGroup) + (size_t)(c & 1) * 64 : (size_t)c * 64);
+      const unsigned char* src = in_b + (size_t)((zp * 64 + yp * 8) * p.in_cstride) * kEsz + tap_chunk_offset<X3>(c, p.in_pair);
 #pragma unroll
       for (int h = 0; h < 2; ++h)
         if (a_ok[h]) glds16(src + a_voff[h], lds0 + kAOffN + (wave * NZ + jz) * kTileN + h * 1024);
@@ -240,7 +226,7 @@ __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned 
   // addresses are K precomputed VGPRs.
   unsigned pa[K];                                        // per-lane A read address for x shift d - LO, or out of range
 #pragma unroll
-  for (int d = 0; d < K; ++d) pa[d] = ((unsigned)(rx + d - LO) < 8u) ? a_lane + (unsigned)((d - LO) * 64) : kOobN;
+  for (int d = 0; d < K; ++d) pa[d] = ((unsigned)(rx + d - LO) < 8u) ? a_lane + (unsigned)((d - LO) * 64) : kLdsOob;
   // X8: one FP8 instruction takes a PAIR of taps -- K block khalf (lanes 0-31 / 32-63) is the pair's tap khalf, and a lane's 32
   // operand bytes are slots 2, 3 ([lo8 | hi8] / [W_hi8 | W_lo8]) of ITS tap's row.  The taps of a chunk are paired as one flat
   // sequence (K is odd: rows alternate between (0 1)(2 3)(4 | next row's 0) and (1 2)(3 4)), so a chunk issues K^3 / 2 FP8
@@ -280,8 +266,8 @@ __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned 
   auto load_b = [&](uint4 (&dst)[2][2], unsigned src) __attribute__((always_inline)) {
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
-      dst[n][0] = lds128n(src + n * kTileN);
-      dst[n][1] = lds128n(src + n * kTileN + b_d1);
+      dst[n][0] = lds_read16(src + n * kTileN);
+      dst[n][1] = lds_read16(src + n * kTileN + b_d1);
     }
   };
   auto tile_mma = [&](int j, const uint4 (&bc)[2][2]) __attribute__((always_inline)) {
@@ -335,8 +321,8 @@ __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned 
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (__builtin_expect((m_mm & (1u << j)) != 0, 1)) tile_mma(j, bc);
-        a[j][0] = lds128n(nb0 + j * kTileN);
-        a[j][1] = lds128n(nb1 + j * kTileN);
+        a[j][0] = lds_read16(nb0 + j * kTileN);
+        a[j][1] = lds_read16(nb1 + j * kTileN);
       }
     }
     if (R == 1) {
@@ -377,10 +363,10 @@ __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned 
     unsigned selA = 0u, selB = 0u, lv = 0u;
     if (T == 0) {
       selA = (khalf ? pa[0] + (unsigned)base_n : pa[K - 1] + (unsigned)base_g) + dslot_a;
-      selB = khalf ? (more ? b8k - (unsigned)kBTileN + boff_n : kOobN) : b8k + (unsigned)((K - 1) * kBTileN) + boff_g;
+      selB = khalf ? (more ? b8k - (unsigned)kBTileN + boff_n : kLdsOob) : b8k + (unsigned)((K - 1) * kBTileN) + boff_g;
       lv = khalf ? mask_n : mask_g;
     }
-    auto a8_x = [&](int j) __attribute__((always_inline)) -> unsigned { return ((lv >> j) & 1u) ? selA : kOobN; };
+    auto a8_x = [&](int j) __attribute__((always_inline)) -> unsigned { return ((lv >> j) & 1u) ? selA : kLdsOob; };
     const unsigned m_mm = (unsigned)__builtin_amdgcn_readfirstlane((int)mask_g);   // scalars: the tile skips are s_cbranch, not exec masks
     const unsigned m_x = (unsigned)__builtin_amdgcn_readfirstlane((int)(mask_g | mask_n));
 #pragma unroll
@@ -419,13 +405,13 @@ __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned 
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         if (__builtin_expect((m0 & (1u << j)) != 0, 1)) mma<DT>(acc[j][0], a[j][0], b[0][0][0]);
-      b[0][0][0] = lds128n(bsrc);
+      b[0][0][0] = lds_read16(bsrc);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (__builtin_expect((m1 & (1u << j)) != 0, 1)) mma<DT>(acc[j][1], a[j][0], b[0][1][0]);
-        a[j][0] = lds128n(nb0 + j * kTileN);
+        a[j][0] = lds_read16(nb0 + j * kTileN);
       }
-      b[0][1][0] = lds128n(bsrc + kTileN);
+      b[0][1][0] = lds_read16(bsrc + kTileN);
       if (cross) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -435,14 +421,14 @@ __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned 
           }
           // tiles 2 / 3 of THIS pair behind tiles 0 / 1, tiles 0 / 1 of the NEXT pair behind tiles 2 / 3
           const unsigned src8 = j < 2 ? (xrow ? a8_x(j + 2) : cb8) + (j + 2) * kTileN : (next_x ? a8_x(j - 2) : nb8) + (j - 2) * kTileN;
-          a8[j & 1][0] = lds128n(src8);
+          a8[j & 1][0] = lds_read16(src8);
           a8[j & 1][1] = lds_hi16n<X6>(src8 + a8_d1);
         }
       }
       if (cross) {
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
-          b8[n][0] = lds128n(bsrc8 + n * kTileN);
+          b8[n][0] = lds_read16(bsrc8 + n * kTileN);
           b8[n][1] = lds_hi16n<X6>(bsrc8 + b8_d1 + n * kTileN);
         }
       }
@@ -468,15 +454,15 @@ __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned 
         const unsigned nb8 = a8_same(0, (unsigned)base_of(0, 0));      // row 0 is of type 0: its first pair is (0 | 1)
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
-          b[0][n][0] = lds128n(b_lane + n * kTileN);
-          b8[n][0] = lds128n(b8k + n * kTileN);
+          b[0][n][0] = lds_read16(b_lane + n * kTileN);
+          b8[n][0] = lds_read16(b8k + n * kTileN);
           b8[n][1] = lds_hi16n<X6>(b8k + b8_d1 + n * kTileN);
         }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) a[j][0] = lds128n(nb0 + j * kTileN);
+        for (int j = 0; j < 4; ++j) a[j][0] = lds_read16(nb0 + j * kTileN);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          a8[j][0] = lds128n(nb8 + j * kTileN);
+          a8[j][0] = lds_read16(nb8 + j * kTileN);
           a8[j][1] = lds_hi16n<X6>(nb8 + a8_d1 + j * kTileN);
         }
       } else {
@@ -484,8 +470,8 @@ __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned 
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         if (m0 & (1u << j)) {
-          a[j][0] = lds128n(nb0 + j * kTileN);
-          a[j][1] = lds128n(nb1 + j * kTileN);
+          a[j][0] = lds_read16(nb0 + j * kTileN);
+          a[j][1] = lds_read16(nb1 + j * kTileN);
         }
       }
     }
@@ -527,20 +513,12 @@ __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned 
   __syncthreads();                                       // nobody still reads A / B: the LDS becomes the epilogue tile
 
   // ---- epilogue: bias + ReLU in fp32 through an LDS tile [4 pts x 256 voxels of the half][32], one pass per column tile --
+  // (the part of a pass behind its first barrier is conv4n.hip's with another row <-> voxel map; one function for both changes the
+  // code hipcc emits for the stores of every instantiation -- profiles/refactor_isa_tiles.txt -- so each kernel keeps its own)
   const int out_esz = p.out_f32 ? 4 : kEsz;
   const float act_floor = p.relu ? 0.f : -INFINITY;
   unsigned char* out_b = reinterpret_cast<unsigned char*>(p.out);
   unsigned char* mp_b = reinterpret_cast<unsigned char*>(p.mp_out);
-  auto cvt_store8 = [&](unsigned char* base, long long row_elems, int col, const float4& f0, const float4& f1) __attribute__((always_inline)) {
-    if (out_esz == 4) {
-      float4* dst = reinterpret_cast<float4*>(base + (row_elems + col) * 4);
-      dst[0] = f0;
-      dst[1] = f1;
-    } else {
-      using E = Elem<DT == NESTI_F32 ? NESTI_BF16 : DT>;
-      store_act8<E>(base, row_elems, col, f0, f1, p.split);
-    }
-  };
   auto epi_pass = [&](auto NN) __attribute__((always_inline)) {
     constexpr int n = decltype(NN)::value;
     const int n_tile = 2 * n_pair + n;
@@ -559,7 +537,7 @@ __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned 
             for (int r = 0; r < 4; ++r) {
               const int m = 16 * h + 4 * (lane >> 4) + r;          // MFMA row = 8 pt + x
               const int row = ((((m >> 3) * 4 + j) * 8 + y) << 3) + (m & 7);
-              *reinterpret_cast<float*>(smem + row * kEpiStrideN + col * 4) =
+              *reinterpret_cast<float*>(smem + row * kEpiStride + col * 4) =
                   fmaxf(fmaf(acc4[j][h][2 * n + k][r], p.acc_scale, bv), act_floor);
             }
         }
@@ -573,7 +551,7 @@ __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned 
         for (int r = 0; r < 16; ++r) {
           const int m = (r & 3) + 8 * (r >> 2) + 4 * khalf;    // MFMA row = 8 pt + x
           const int row = ((((m >> 3) * 4 + j) * 8 + y) << 3) + (m & 7);
-          *reinterpret_cast<float*>(smem + row * kEpiStrideN + l31 * 4) = fmaxf(fmaf(acc[j][n][r], p.acc_scale, bv), act_floor);
+          *reinterpret_cast<float*>(smem + row * kEpiStride + l31 * 4) = fmaxf(fmaf(acc[j][n][r], p.acc_scale, bv), act_floor);
         }
       }
     }
@@ -581,13 +559,13 @@ __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned 
     if (p.mp_mode != 1) {                                // full-resolution rows: 4 lanes x 8 channels = one 32-channel row segment
 #pragma unroll 2
       for (int it = 0; it < 8; ++it) {
-        const int item = it * kThreadsN + tid;
+        const int item = it * kTapThreads + tid;
         const int row = item >> 2, seg = item & 3;
         const int ptl = row >> 8, vox = z0 * 64 + (row & 255);
         if (ptl < np_here) {
-          const float4 f0 = *reinterpret_cast<const float4*>(smem + row * kEpiStrideN + seg * 32);
-          const float4 f1 = *reinterpret_cast<const float4*>(smem + row * kEpiStrideN + seg * 32 + 16);
-          cvt_store8(out_b, ((long long)(p0 + ptl) * 512 + vox) * p.out_cstride, out_col0 + seg * 8, f0, f1);
+          const float4 f0 = *reinterpret_cast<const float4*>(smem + row * kEpiStride + seg * 32);
+          const float4 f1 = *reinterpret_cast<const float4*>(smem + row * kEpiStride + seg * 32 + 16);
+          store_out8<DT>(out_b, ((long long)(p0 + ptl) * 512 + vox) * p.out_cstride, out_col0 + seg * 8, f0, f1, out_esz, p.split);
         }
       }
     }
@@ -598,14 +576,14 @@ __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned 
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
         const int row = ((ptl * 4 + 2 * cz + (q >> 2)) * 8 + 2 * cy + ((q >> 1) & 1)) * 8 + 2 * cx + (q & 1);
-        const float4 f0 = *reinterpret_cast<const float4*>(smem + row * kEpiStrideN + seg * 32);
-        const float4 f1 = *reinterpret_cast<const float4*>(smem + row * kEpiStrideN + seg * 32 + 16);
+        const float4 f0 = *reinterpret_cast<const float4*>(smem + row * kEpiStride + seg * 32);
+        const float4 f1 = *reinterpret_cast<const float4*>(smem + row * kEpiStride + seg * 32 + 16);
         m0.x = fmaxf(m0.x, f0.x); m0.y = fmaxf(m0.y, f0.y); m0.z = fmaxf(m0.z, f0.z); m0.w = fmaxf(m0.w, f0.w);
         m1.x = fmaxf(m1.x, f1.x); m1.y = fmaxf(m1.y, f1.y); m1.z = fmaxf(m1.z, f1.z); m1.w = fmaxf(m1.w, f1.w);
       }
       if (ptl < np_here) {
         const int ovox = ((2 * half + cz) * 4 + cy) * 4 + cx;
-        cvt_store8(mp_b, ((long long)(p0 + ptl) * 64 + ovox) * p.mp_cstride, out_col0 + seg * 8, m0, m1);
+        store_out8<DT>(mp_b, ((long long)(p0 + ptl) * 64 + ovox) * p.mp_cstride, out_col0 + seg * 8, m0, m1, out_esz, p.split);
       }
     }
     __syncthreads();
@@ -615,7 +593,7 @@ __device__ __forceinline__ void conv8n_tile(const ConvParams& p, const unsigned 
 }
 
 template <int DT, int K, int MODE, bool WALK>
-__global__ __launch_bounds__(kThreadsN) void conv8n_kernel(const ConvParams p) {
+__global__ __launch_bounds__(kTapThreads) void conv8n_kernel(const ConvParams p) {
   if constexpr (!WALK) {
     conv8n_tile<DT, K, MODE>(p, blockIdx.x, threadIdx.x);
   } else {
@@ -628,8 +606,8 @@ __global__ __launch_bounds__(kThreadsN) void conv8n_kernel(const ConvParams p) {
 template <int DT, int K, int MODE>
 int launch_conv8n_one(const ConvParams& p, hipStream_t stream) {
   constexpr int lds = lds_bytes_n<K>();
-  static_assert(lds <= 163840 && 1024 * kEpiStrideN <= lds, "LDS budget");
-  return launch_tiles<conv8n_kernel<DT, K, MODE, false>, conv8n_kernel<DT, K, MODE, true>>(p, lds, kThreadsN,
+  static_assert(lds <= 163840 && 1024 * kEpiStride <= lds, "LDS budget");
+  return launch_tiles<conv8n_kernel<DT, K, MODE, false>, conv8n_kernel<DT, K, MODE, true>>(p, lds, kTapThreads,
                                                                                           tile_rows8(p.m_tiles) * 2 * p.n_tiles, stream);
 }
 
@@ -657,13 +635,13 @@ int launch_conv8n_dt(const ConvParams& p, int k, hipStream_t stream) {
   NESTI_FAIL("launch_conv8n: kernel size must be 3 or 5");
 }
 
-// reads 16 B at kOobN from a workgroup that allocated `lds` bytes of dynamic LDS filled with a non-zero pattern
+// reads 16 B at kLdsOob from a workgroup that allocated `lds` bytes of dynamic LDS filled with a non-zero pattern
 __global__ void lds_oob_probe_kernel(unsigned* out, unsigned lds) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   for (unsigned i = threadIdx.x; i < lds / 4; i += blockDim.x) reinterpret_cast<unsigned*>(smem)[i] = 0xA5A50000u + i;
   __syncthreads();
-  const uint4 v = lds128n(kOobN + 16u * threadIdx.x);
-  const uint4 w = lds128n((unsigned)(size_t)(lptr_t)smem + 16u * threadIdx.x);      // in range: must read the pattern back
+  const uint4 v = lds_read16(kLdsOob + 16u * threadIdx.x);
+  const uint4 w = lds_read16((unsigned)(size_t)(lptr_t)smem + 16u * threadIdx.x);      // in range: must read the pattern back
   atomicOr(&out[0], v.x | v.y | v.z | v.w);
   atomicOr(&out[1], w.x == 0xA5A50000u + 4u * threadIdx.x ? 0u : 1u);
 }
@@ -711,10 +689,7 @@ int launch_conv8n(const ConvParams& p, int dtype, int k, hipStream_t stream) {
   if (p.m_tiles <= 0 || p.n_tiles <= 0) return 0;
   if (p.log2S != 3 || p.s_real) NESTI_FAIL("launch_conv8n: the 8^3 volume only");
   if (p.n_taps != k * k * k) NESTI_FAIL("launch_conv8n: all k^3 taps must be present");
-  if (p.point_index) NESTI_FAIL("launch_conv8n: no input gather (k^3 layers never read the routed MuPS tensor)");
-  if (p.pool_k > 1 || p.split_tile != p.n_tiles) NESTI_FAIL("launch_conv8n: no fused avg-pool / merged layers");
-  if (p.mp_mode == 2) NESTI_FAIL("launch_conv8n: max-pool mode 2 is conv1's (a 1x1x1 layer)");
-  if (p.mp_mode != 0 && !p.mp_out) NESTI_FAIL("launch_conv8n: fused max-pool needs an output");
+  if (check_tap_launch(p, "launch_conv8n")) return 1;
   return with_elem_type(dtype, "launch_conv8n", [&](auto dt) { return launch_conv8n_dt<decltype(dt)::value>(p, k, stream); });
 }
 

@@ -112,10 +112,19 @@ int conv8_selftest();
 // 8 * (its group) + (b & 7), so a row tile's column tiles stay on one XCD's L2.  On the host for the capacity, in a walking kernel
 // for the live points
 __host__ __device__ __forceinline__ unsigned tile_rows8(unsigned m_tiles) { return (m_tiles + 7) / 8 * 8; }
-__device__ __forceinline__ int live_points(const ConvParams& p) {
+template <class Params>               // ConvParams, PoolParams
+__device__ __forceinline__ int live_points(const Params& p) {
   int npts = p.npoints;
   if (p.npoints_ptr) npts = min(npts, *p.npoints_ptr);
   return npts;
+}
+// Workgroup `bid` of such a grid -> its row tile and which of that row tile's `per_m` workgroups it is (column tile; conv8n: z half too)
+struct TileId {
+  int sub, m_tile;
+};
+__device__ __forceinline__ TileId tile_id(const unsigned bid, const int per_m) {
+  const int xcd = bid & 7, grp = bid >> 3;
+  return {grp % per_m, (grp / per_m) * 8 + xcd};
 }
 // A walking launch (ConvParams::walk) is a kernel of its own, so that the one-tile-per-workgroup kernel keeps its register
 // allocation: `for (bid = blockIdx.x; bid < live tiles; bid += gridDim.x) tile(p, bid, walk_trip(bid))`.  walk_trip returns the thread
@@ -126,6 +135,20 @@ __device__ __forceinline__ int walk_trip(const unsigned bid) {
   int tid = threadIdx.x;
   asm volatile("" : "+v"(tid));
   return tid;
+}
+
+// The k^3-tap kernels (conv8n.hip, conv4n.hip) run kTapThreads threads and pass their activated outputs, 32 columns at a time,
+// through an fp32 LDS tile of 1024 rows (4 points x a z half of 8^3; 16 points x 4^3) on the way to memory
+constexpr int kTapThreads = 512;
+constexpr int kEpiStride = 144;   // bytes per row of the fp32 [1024][32] epilogue tile (+16 B pad)
+// What the k^3-tap kernels (launch_conv8n, launch_conv4n) refuse alike; `who` names the launcher in the message
+inline int check_tap_launch(const ConvParams& p, const char* who) {
+  const std::string w(who);
+  if (p.point_index) NESTI_FAIL(w + ": no input gather (k^3 layers never read the routed MuPS tensor)");
+  if (p.pool_k > 1 || p.split_tile != p.n_tiles) NESTI_FAIL(w + ": no fused avg-pool / merged layers");
+  if (p.mp_mode == 2) NESTI_FAIL(w + ": max-pool mode 2 is conv1's (a 1x1x1 layer)");
+  if (p.mp_mode != 0 && !p.mp_out) NESTI_FAIL(w + ": fused max-pool needs an output");
+  return 0;
 }
 
 // One launch of a tile kernel with `lds` bytes of dynamic LDS; the opt-in to that much LDS is a per-device function attribute: one

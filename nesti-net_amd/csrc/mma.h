@@ -55,5 +55,15 @@ __device__ __forceinline__ void glds16(const unsigned char* src, unsigned lds_ds
 }
 __device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
+// 16 B from an LDS byte address (ds_read_b128).  kLdsOob lies beyond any LDS allocation: a read there returns zeros on gfx950
+// (scripts/lds_oob_probe.hip; checked at model creation, conv8_selftest) -- the tap kernels take their x padding and the zero
+// halves of the pair loop's weight fragments from it instead of keeping zero rows
+constexpr unsigned kLdsOob = 0x40000u;
+typedef unsigned lds_u32x4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uint4 lds_read16(unsigned addr) {
+  const lds_u32x4_t v = *(const __attribute__((address_space(3))) lds_u32x4_t*)(size_t)addr;
+  return make_uint4(v.x, v.y, v.z, v.w);
+}
+
 }  // namespace
 }  // namespace nesti

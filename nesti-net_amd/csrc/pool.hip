@@ -75,8 +75,7 @@ __device__ __forceinline__ void store_vec(unsigned char* base, long long row_ele
 template <int DT>
 __global__ __launch_bounds__(kThreads) void maxpool2_kernel(const PoolParams p) {
   using V = Vec16<DT>;
-  int npts = p.npoints;
-  if (p.npoints_ptr) npts = min(npts, *p.npoints_ptr);
+  const int npts = live_points(p);
   const int log2S = p.log2S, log2V = 3 * log2S;
   const int log2So = log2S - 1, So = 1 << log2So, log2Vo = 3 * log2So;
   const int vecs = p.C / V::N;
@@ -111,8 +110,7 @@ __global__ __launch_bounds__(kThreads) void maxpool2_kernel(const PoolParams p) 
 template <int DT>
 __global__ __launch_bounds__(kThreads) void maxpool3s2_kernel(const PoolParams p) {
   using V = Vec16<DT>;
-  int npts = p.npoints;
-  if (p.npoints_ptr) npts = min(npts, *p.npoints_ptr);
+  const int npts = live_points(p);
   const int nv = p.C / V::N;
   const long long total = (long long)npts * 8 * nv;
   const unsigned char* in_b = reinterpret_cast<const unsigned char*>(p.in);

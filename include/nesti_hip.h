@@ -463,6 +463,24 @@ int nesti_debug_tower_step(const nesti_model_t* m, int tower, const nesti_debug_
                            const int32_t* point_index_dev, const int32_t* npoints_dev, int walk, void* ws_dev, size_t ws_bytes,
                            void* stream);
 
+/* The weight packer without a device (tests/test_pack.py): builds the graph and packs ONE layer (index `layer` of the model, as
+ * nesti_debug_op_t::layer) on the host, with the very code nesti_model_create uploads from.  form: the packing of a launch form --
+ * NESTI_DEBUG_FORM_PLAIN, _PAIR, _X8 or _X6; _X2 runs on the pair packing and means _PAIR.  A form the layer or the dtype cannot
+ * take is refused with a message.  info is always filled; w / bias may be NULL (sizes only: info->w_bytes, info->n_bias), max_w is
+ * in bytes and max_bias in floats. */
+typedef struct {
+  int kind;            /* kernel family the bytes are laid out for: 0 conv_igemm_kernel, 2 conv8n_kernel, 3 conv4n_kernel   */
+  int TN, n_tiles, split_tile, n_chunks, n_taps;   /* image = [n_tiles][n_chunks][n_taps][TN rows][128 or 64 bytes]            */
+  int x3n;             /* rows are [W_hi | W_lo] K chunks                                                                    */
+  float acc_scale;     /* 2^-s when the weights carry a 2^s scale                                                            */
+  int x8_sb;           /* X8 / X6: power-of-two pre-scale of the e4m3 weight planes                                          */
+  int x8_sc;           /* the pre-scale of the activation planes this layer would write as an X8 / X6 producer              */
+  int64_t w_bytes, n_bias;
+  int8_t tap[125][4];  /* dz, dy, dx, 0 of the n_taps kept taps                                                              */
+} nesti_debug_pack_t;
+int nesti_debug_pack_layer(const nesti_config_t* cfg, const nesti_tensor_t* tensors, int n_tensors, int dtype, int form, int layer,
+                           nesti_debug_pack_t* info, void* w, size_t max_w, float* bias, size_t max_bias);
+
 /* ---- measurement support (bench.py's roofline leg; no reference counterpart) ------------
  * nesti_profile_enable(1) makes every kernel launch of the forward path record a pair of
  * hipEvents on its stream; nesti_profile_read() synchronises on them and returns, per

@@ -62,6 +62,13 @@ class CDebugOp(ctypes.Structure):
                                             "C")]
 
 
+class CDebugPack(ctypes.Structure):
+    """Mirror of ``nesti_debug_pack_t``."""
+    _fields_ = [(n, ctypes.c_int) for n in ("kind", "TN", "n_tiles", "split_tile", "n_chunks", "n_taps", "x3n")] + \
+               [("acc_scale", ctypes.c_float), ("x8_sb", ctypes.c_int), ("x8_sc", ctypes.c_int),
+                ("w_bytes", ctypes.c_int64), ("n_bias", ctypes.c_int64), ("tap", ctypes.c_int8 * 4 * 125)]
+
+
 X8_GUARD_BAR, X8_GUARD_WIDEN, X8_GUARD_DEFAULT = 2.5e-6, 1.5, 0.25   # NESTI_X8_GUARD_* (include/nesti_hip.h)
 GATE_WIDEN = 1.5      # NESTI_GATE_WIDEN (include/nesti_hip.h)
 GATE_WIDEN_PASSES = 3  # NESTI_GATE_WIDEN_PASSES
@@ -123,6 +130,7 @@ SIGNATURES = {
                                    ctypes.POINTER(CDebugOp), _i, ctypes.POINTER(_i), _vp, _i, ctypes.POINTER(_i),
                                    ctypes.POINTER(_sz)]),
     "nesti_debug_tower_step": (_i, [_vp, _i, ctypes.POINTER(CDebugPass), _i, _vp, _i, _vp, _vp, _i, _vp, _sz, _vp]),
+    "nesti_debug_pack_layer": (_i, [_cfgp, ctypes.POINTER(CTensor), _i, _i, _i, _i, ctypes.POINTER(CDebugPack), _vp, _sz, _vp, _sz]),
     "nesti_write_text_f32": (_i, [ctypes.c_char_p, _vp, ctypes.c_int64, _i]),
     "nesti_write_text_i32": (_i, [ctypes.c_char_p, _vp, ctypes.c_int64]),
     "nesti_estimate_normals_multi": (_i, [_vp, ctypes.POINTER(CShapeQueries), _i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),

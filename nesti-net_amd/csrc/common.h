@@ -1,15 +1,11 @@
 // Shared helpers for libnesti_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <stdio.h>
-#include <string>
 
-#include "../../include/nesti_hip.h"
+#include "host.h"
 
 namespace nesti {
-
-void set_error(const std::string& msg);
 
 #define NESTI_CHECK_HIP(expr)                                                         \
   do {                                                                                \
@@ -20,25 +16,6 @@ void set_error(const std::string& msg);
     }                                                                                 \
   } while (0)
 
-#define NESTI_FAIL(msg)           \
-  do {                            \
-    ::nesti::set_error(msg);      \
-    return 1;                     \
-  } while (0)
-
-static inline size_t dtype_size(int dt) { return dt == NESTI_F32 ? 4 : 2; }
-// NESTI_BF16X3: the kernels are the bf16 ones with the pair K loop (conv.hip / conv8n.hip: X3); an activation row holds, per
-// group of 64 channels, the two 64-element planes [hi | lo] (128 elements), a packed weight row [W_hi | W_lo] per K chunk,
-// and one set of fragment reads feeds hi*W_hi + lo*W_hi + hi*W_lo.  Writers emit the planes (split_col / split_pack2 below).
-// NESTI_F16X3: the same with f16 pairs and the f16 kernels.
-// NESTI_F16X3C is NESTI_F16X3 everywhere except in the gating net's first pass (model.hip: gate_cascade)
-static inline int main_dtype(int dt) { return (dt == NESTI_F16X3C || dt == NESTI_F16X8 || dt == NESTI_F16X8C) ? NESTI_F16X3 : dt; }
-static inline bool dtype_cascade(int dt) { return dt == NESTI_F16X3C || dt == NESTI_F16X8C; }
-static inline bool dtype_x8(int dt) { return dt == NESTI_F16X8 || dt == NESTI_F16X8C; }
-static inline int kernel_dtype(int dt) { return dt == NESTI_BF16X3 ? NESTI_BF16 : dt == NESTI_F16X3 ? NESTI_F16 : dt; }
-constexpr int kPairPlanes = 2;    // hi, lo
-static inline int act_planes(int dt) { return (dt == NESTI_BF16X3 || dt == NESTI_F16X3) ? kPairPlanes : 1; }
-constexpr int kSplitGroup = 64;
 __host__ __device__ __forceinline__ int split_col(int col) { return (col >> 6) * (kPairPlanes * kSplitGroup) + (col & (kSplitGroup - 1)); }
 // Where the tap kernels (conv8n.hip, conv4n.hip) find a 64-byte K chunk in an activation row, in bytes.  Plain rows: chunk c
 // of 32 channels at 64 c.  Pair-layout rows [hi 64 | lo 64] per 64-channel group: the pair loop's chunk c is 16 channels of
@@ -55,7 +32,6 @@ template <bool PAIR>
 __device__ __forceinline__ int tap_slot_offset(int slot) {
   return PAIR ? (slot & 1) * 16 + (slot >> 1) * (2 * kSplitGroup) : slot * 16;
 }
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // ---- element conversion (device) ------------------------------------------
 // gfx950 converts in hardware (v_cvt_pk_bf16_f32, round-to-nearest-even, quiet NaN): no branches per element.
@@ -221,11 +197,6 @@ __device__ __forceinline__ void store_aux6_16(unsigned char* aux_row, int col, c
 template <> struct Elem<NESTI_BF16X3> : Elem<NESTI_BF16> {};
 template <> struct Elem<NESTI_F16X3> : Elem<NESTI_F16> {};
 template <int DT> constexpr bool is_x3 = (DT == NESTI_BF16X3 || DT == NESTI_F16X3);
-
-// host-side conversions used by the weight repacker
-uint16_t host_f32_to_bf16(float f);
-uint16_t host_f32_to_f16(float f);
-float host_f16_to_f32(uint16_t h);
 
 // ---- optional kernel timing (model.hip) -----------------------------------------
 void prof_phase(int phase);                                 // NESTI_PHASE_*: what the following launches are booked under

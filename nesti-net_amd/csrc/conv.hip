@@ -4,7 +4,7 @@
 // (utils/tf_util.py:298-311, 491-494), tf.matmul + bias (+BN, ReLU)
 // (utils/tf_util.py:340-351) and -- fused into the epilogue -- the k^3 stride-1 SAME
 // tf.nn.avg_pool3d of the inception pool branch (utils/tf_util.py:450-454,
-// models/experts_n_est.py:307-310).  BN is folded into weights/bias on the host (model.hip).
+// models/experts_n_est.py:307-310).  BN is folded into weights/bias on the host (pack.cpp).
 //
 // Decomposition (one 512-thread workgroup = 8 wave64):
 //   M tile  = 512 GEMM rows = whole points (1 point at 8^3, 8 at 4^3, 64 at 2^3, 512 for FC),

@@ -35,7 +35,7 @@
 // ds_read_b128 lane group of a 16-row fragment read conflict-free.  The epilogue reuses the LDS as an fp32 staging tile (two
 // passes of 32 columns).
 //
-// X3 (pair modes, model.hip: PackedLayer::x3n): the K chunk is 16 channels -- an LDS row holds [hi k0..15 | lo k0..15] and a
+// X3 (pair modes, pack.h: PackMeta::x3n): the K chunk is 16 channels -- an LDS row holds [hi k0..15 | lo k0..15] and a
 // weight row [W_hi k0..15 | W_lo k0..15]; the K = 32 MFMA multiplies [hi | lo] x [W_hi ; W_hi] (= hi W_hi + lo W_hi) and
 // [hi | lo] x [W_lo ; 0] (= hi W_lo; the zero half comes from an out-of-range LDS address, which reads as zeros on gfx950:
 // mma.h, kLdsOob).
@@ -358,7 +358,7 @@ int launch_conv4n_dt(const ConvParams& p, int k, hipStream_t stream) {
   if constexpr (DT != NESTI_F32) {
     if (p.x3native) {
       // pair modes: k = 2 and 4 (experts_n_est); the odd kernels of the ablation towers stay on conv_igemm_kernel there (their
-      // pair-loop instantiations of this kernel need more than 256 registers), model.hip: use_conv4
+      // pair-loop instantiations of this kernel need more than 256 registers), pack.cpp: use_conv4
       if (k == 2) return launch_conv4n_one<DT, 2, true>(p, stream);
       if (k == 4) return launch_conv4n_one<DT, 4, true>(p, stream);
       NESTI_FAIL("launch_conv4n: the pair K loop is built for k = 2 and k = 4");
@@ -375,7 +375,7 @@ int launch_conv4n_dt(const ConvParams& p, int k, hipStream_t stream) {
 }  // namespace
 
 // p.m_tiles = groups of 16 points, p.n_tiles = 64-column tiles, p.n_chunks = 64-byte K chunks, weights packed
-// [n tile][chunk][tap][64 rows][64 B] (model.hip: pack_layer, kind 3)
+// [n tile][chunk][tap][64 rows][64 B] (pack.cpp: pack_layer, kind 3)
 int launch_conv4n(const ConvParams& p, int dtype, int k, hipStream_t stream) {
   if (p.m_tiles <= 0 || p.n_tiles <= 0) return 0;
   if (p.log2S != 2 || p.s_real) NESTI_FAIL("launch_conv4n: the 4^3 volume only");

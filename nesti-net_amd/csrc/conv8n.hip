@@ -48,7 +48,7 @@
 // the DMA source address, which makes every ds_read_b128 lane group conflict-free (M16: with the K-slot order of its per-lane
 // coordinates below).  The epilogue reuses the LDS as an fp32 staging tile.
 //
-// X3 (pair modes, model.hip: PackedLayer::x3n): the K chunk is 16 channels -- an LDS row holds [hi k0..15 | lo k0..15] of the
+// X3 (pair modes, pack.h: PackMeta::x3n): the K chunk is 16 channels -- an LDS row holds [hi k0..15 | lo k0..15] of the
 // activation pair (staged from the two planes of the [hi 64 | lo 64] row groups) and a weight row [W_hi k0..15 | W_lo k0..15]
 // -- and a tap multiplies hi * W_hi + lo * W_hi + hi * W_lo from ONE set of fragment reads.
 //

@@ -1,5 +1,5 @@
 // Kernel parameter blocks and launchers shared between the .hip files and the
-// host-side graph executor (model.hip).
+// host-side graph executor (model.hip).  kRowBytes and kMaxTaps, which the weight packer shares, are host.h's.
 #pragma once
 #include <algorithm>
 #include <type_traits>
@@ -11,10 +11,6 @@ namespace nesti {
 constexpr int kTileM = 512;       // GEMM rows (voxels x points) per workgroup
 constexpr unsigned kWalkGrid = 1024;   // workgroups of a walking launch (ConvParams::walk): a multiple of 8, so a workgroup's tiles stay
                                        // on its XCD (tile & 7 == blockIdx.x & 7); four per CU, enough to run a non-empty round
-constexpr int kRowBytes = 128;    // bytes of one K-chunk row in LDS (64 x 16-bit or 32 x f32)
-constexpr int kMaxTaps = 125;     // 5^3
-
-static inline int chunk_elems(int dt) { return kRowBytes / (int)dtype_size(dt); }  // KC
 
 // One conv3d / fully-connected layer as an implicit GEMM:
 //   out[r, n] = act( sum_{tap, c} in[shift(r, tap), c] * W[tap, c, n] + bias[n] )
@@ -73,7 +69,7 @@ struct ConvParams {
                        // of 32 channels: 64-byte A rows, 128-byte B rows; n_chunks / acc_scale / wpk are the pair packing's.  These layers
                        // are fill-bound, so the second product is nearly free, and it removes the weight-rounding half of the filter's error
   int x3native;        // pair modes: the kernels' pair K loop (conv.hip / conv8n.hip: X3) -- K chunks [hi | lo] x [W_hi | W_lo], three MFMAs
-                       // per fragment set; the packed weights follow (model.hip: PackedLayer::x3n)
+                       // per fragment set; the packed weights follow (pack.h: PackMeta::x3n)
   // FP8 cross terms (NESTI_F16X8 / NESTI_F16X8C; conv8n.hip X8).  Producer side (a 1x1x1 layer, conv.hip): aux8_out != NULL makes the
   // FIRST tile group (conv1) also write the e4m3 planes of its activated outputs v = hi + lo into the side buffer -- per row and
   // 64-channel group [lo8 64 B | hi8 64 B] with lo8 = e4m3(lo 2^x8_sa), hi8 = e4m3(v 2^x8_sc), saturated at +-448; aux8_stride = bytes
@@ -87,7 +83,7 @@ struct ConvParams {
   // bytes of a row's 16-channel chunk (16 where lo8 went, 16 where hi8 went) now hold 32 six-bit elements -- slot 2i = e2m3(lo_i 2^11 / s),
   // slot 2i + 1 = e2m3(hi_i / s) -- then the block's own scale s = 2^(E - 2), E = exponent of the chunk's largest |hi|, as an E8M0 byte
   // (byte 24), zeros after it; |lo_i 2^11| <= |hi_i| element by element, so one scale serves both halves.  The weight rows follow the
-  // same pattern (model.hip: pack_layer_x6, the 2^-11 folded into their scale byte); x8_sa / x8_sc / x8_scale_* are not used.
+  // same pattern (pack.cpp: cross_rows, the 2^-11 folded into their scale byte); x8_sa / x8_sc / x8_scale_* are not used.
   int x8_fmt;
   float acc_scale;     // the accumulators are multiplied by this before the bias (1, or 2^-s when the layer's packed weights
                        // carry a 2^s scale: NESTI_F16X3 keeps the weight pairs in f16's normal range that way)

@@ -1,20 +1,19 @@
-// Host side of libnesti_hip.so: C-ABI entry points, the Nesti-Net graph
-// (models/experts_n_est.py:40-314) expressed as a list of kernel launches, batch-norm folding
-// and weight repacking for the MFMA kernels, and the workspace planner.
+// Host side of libnesti_hip.so that touches the device: C-ABI entry points, the kernel profiler, the form of every launch, the
+// workspace planner, the tower runner and the forward paths.  The graph (graph.cpp) and batch-norm folding and weight repacking
+// for the MFMA kernels (pack.cpp) are host-only units of their own.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
-#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
-#include <regex>
 #include <string>
 #include <vector>
 
 #include "kernels.h"
+#include "pack.h"
 
 #ifndef NESTI_GUARD_WALK_GRID     // measurement builds may override it (scripts/ab_guard.sh); 1 = the default walking grid (kWalkGrid)
 #define NESTI_GUARD_WALK_GRID 64
@@ -103,379 +102,26 @@ static void prof_collect() {
   }
 }
 
-uint16_t host_f32_to_bf16(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-uint16_t host_f32_to_f16(float f) {
-  _Float16 h = (_Float16)f;   // clang host: IEEE RNE conversion
-  uint16_t b;
-  memcpy(&b, &h, 2);
-  return b;
-}
-
-float host_f16_to_f32(uint16_t b) {
-  _Float16 h;
-  memcpy(&h, &b, 2);
-  return (float)h;
-}
-
 namespace {
-
-constexpr int kPad = 64;   // channel segments are zero-padded to multiples of this
-inline int pad_to(int c, int a) { return (c + a - 1) / a * a; }
-inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-
-// ------------------------------------------------------------------------------------------
-// graph description
-// ------------------------------------------------------------------------------------------
-struct LayerDesc {
-  std::string scope;
-  std::string scope2;        // non-empty: a second 1x1 layer on the same input, fused into this launch
-  int pool_k = 1;            // avg-pool window applied to scope2's pre-activation (conv4 of an inception)
-  bool is_fc = false;
-  int k = 1;                 // kernel size (1 for fc)
-  int log2S = 0;             // spatial index space the layer runs at
-  int s_real = 0;            // 3: the 3^3 Gaussian grid embedded in the 4^3 index space (0: the volume is 2^log2S)
-  int cin = 0, cout = 0;     // real channel counts (TF variable shapes); scope2 has the same shape
-  std::vector<int> in_pos;   // real input channel -> position inside the padded input slice
-  int Cin_p = 0, Cout_p = 0;
-  bool bn = true, relu = true;
-};
-
-struct BufSpec { int log2S; int C; bool f32; bool aux8 = false; };   // aux8: side buffer of e4m3 planes, 2 bytes per channel (conv8n.hip X8)
-
-struct Op {
-  enum Kind { CONV, MAX, MAX3 } kind;   // MAX3: max_pool3d [3,3,3] stride 2 SAME, 3^3 (embedded) -> 2^3
-  int in_buf = 0, in_coff = 0, out_buf = 0, out_coff = 0, out_coff2 = 0;
-  int in_cstride = 0;          // 0: the input buffer's channel count; else a flattened view (FC on S^3 x C)
-  int mp_buf = -1, mp_mode = 0; // fused 2^3 max-pool of the first tile group into this buffer (1: pooled only, 2: both)
-  int mp_mode2 = 0;             // 1: the conv4 half writes only its pooled tensor too (kernels.h: ConvParams::mp_mode2)
-  int layer = -1;
-  int C = 0, k = 0, log2S = 0;
-  bool out_f32 = false;
-  // FP8 cross terms (expert towers of NESTI_F16X8 / NESTI_F16X8C models): a block's conv1 (aux_out_buf >= 0) can also write the e4m3
-  // planes of its outputs; the block's tap layers (aux_in_buf >= 0, x8_bit = their bit of nesti_model::x8_mask) read them.
-  // x8_bits (producer) = the bits of the tap layers that read its planes; aux_layer (consumer) = the producer's layer index
-  int aux_out_buf = -1, aux_in_buf = -1, x8_bit = -1, x8_bits = 0, aux_layer = -1;
-};
-
-struct Tower {
-  std::vector<BufSpec> bufs;   // bufs[0] = MuPS X0 (external)
-  std::vector<Op> ops;
-  int out_buf = -1;            // f32 [NB, 64]
-  int n_out = 0;               // real outputs (E or 3)
-};
-
-struct ChanMap { std::vector<int> pos; int C = 0; };   // real channel -> padded position, padded width
-
-struct Graph {
-  nesti_config_t cfg;
-  int gate_x0_log2S() const { return cfg.grid_n == 3 ? 2 : 3; }   // index space of the MuPS rows of one point
-  int mups_cstride = 64;
-  bool x8 = false;           // NESTI_F16X8 / NESTI_F16X8C: the expert towers carry side buffers for the FP8 cross terms
-  std::vector<LayerDesc> layers;
-  Tower gate;
-  std::vector<Tower> experts;
-};
-
-struct Builder {
-  Graph& g;
-  bool x8 = false;           // expert towers of an NESTI_F16X8 / NESTI_F16X8C model: side buffers for the 8^3 blocks' tap layers
-  int x8_block = 0;          // ... and which 8^3 inception block of the tower is being built (0, 1)
-  int s_real = 0;            // stamped on the layers built while it is set (conv_net_3g)
-  explicit Builder(Graph& gg) : g(gg) {}
-
-  int add_layer(const LayerDesc& d) { g.layers.push_back(d); return (int)g.layers.size() - 1; }
-
-  int conv(Tower& T, const std::string& scope, int k, int log2S, int in_buf, int in_coff, const ChanMap& in,
-           int cout, int out_buf, int out_coff, bool bn = true, bool relu = true, bool fc = false, bool out_f32 = false,
-           const std::string& scope2 = "", int out_coff2 = 0, int pool_k = 1) {
-    LayerDesc d;
-    d.scope = scope; d.scope2 = scope2; d.pool_k = pool_k; d.is_fc = fc; d.k = k; d.log2S = log2S;
-    d.s_real = fc ? 0 : s_real;
-    d.cin = (int)in.pos.size(); d.cout = cout; d.in_pos = in.pos; d.Cin_p = in.C;
-    d.Cout_p = pad_to(cout, kPad) * (scope2.empty() ? 1 : 2); d.bn = bn; d.relu = relu;
-    Op op; op.kind = Op::CONV; op.in_buf = in_buf; op.in_coff = in_coff; op.out_buf = out_buf; op.out_coff = out_coff;
-    op.out_coff2 = out_coff2;
-    op.layer = add_layer(d); op.log2S = log2S; op.out_f32 = out_f32;
-    T.ops.push_back(op);
-    return d.Cout_p;
-  }
-
-  // models/experts_n_est.py:294-314.  conv1 and conv4 read the same tensor (avg_pool3d commutes with the
-  // 1x1x1 convolution), so they are one launch; conv4's columns are averaged in the kernel epilogue.
-  // then_maxpool: the block is followed by tf_util.max_pool3d 2^3/2 (e.g. models/experts_n_est.py:198).  conv1
-  // stores full resolution (conv2/conv3 read it) AND its pooled tensor, conv2/conv3 store only the pooled tensor
-  // (nobody reads them at full resolution); conv4's columns come out of the avg-pool epilogue at full resolution
-  // and are max-pooled by the small standalone kernel, restricted to their channel range.  Returns the buffer the
-  // next block reads.
-  int inception(Tower& T, const std::string& scope, int in_buf, const ChanMap& in, int F, int k0, int k1, int log2S,
-                ChanMap* out_map, bool then_maxpool = false) {
-    const int H = F / 2;   // int(n_filters/2)  :299
-    const int Fp = pad_to(F, kPad), Hp = pad_to(H, kPad);
-    const int C = Fp + Hp + Hp + Fp;
-    T.bufs.push_back({log2S, C, false});
-    const int ob = (int)T.bufs.size() - 1;
-    int pb = -1;
-    if (then_maxpool) {
-      T.bufs.push_back({log2S - 1, C, false});
-      pb = (int)T.bufs.size() - 1;
-    }
-    ChanMap c1; c1.C = Fp; for (int i = 0; i < F; ++i) c1.pos.push_back(i);
-    conv(T, scope + "_conv1", 1, log2S, in_buf, 0, in, F, ob, 0, true, true, false, false,
-         scope + "_conv4", Fp + Hp + Hp, k0);
-    // conv4 behind a max-pool: when its avg-pool runs in the epilogue (k0 > 1) the 2^3 max is taken there as well and
-    // its full-resolution columns are never written; with k0 == 1 (plain columns) the small standalone kernel pools them
-    const bool fuse4 = then_maxpool && k0 > 1 && !s_real;
-    if (then_maxpool) { T.ops.back().mp_buf = pb; T.ops.back().mp_mode = 2; T.ops.back().mp_mode2 = fuse4 ? 1 : 0; }
-    const size_t conv1_op = T.ops.size() - 1;
-    int ab = -1;
-    if (x8 && log2S == 3 && !s_real && x8_block < 2 && (k0 == 3 || k0 == 5) && (k1 == 3 || k1 == 5)) {
-      BufSpec ax{log2S, Fp, false};
-      ax.aux8 = true;
-      T.bufs.push_back(ax);
-      ab = (int)T.bufs.size() - 1;
-      T.ops[conv1_op].aux_out_buf = ab;
-      T.ops[conv1_op].x8_bits = 3 << (2 * x8_block);
-    }
-    conv(T, scope + "_conv2", k0, log2S, ob, 0, c1, H, ob, Fp);
-    if (then_maxpool) { T.ops.back().mp_buf = pb; T.ops.back().mp_mode = 1; }
-    if (ab >= 0) { T.ops.back().aux_in_buf = ab; T.ops.back().x8_bit = 2 * x8_block; T.ops.back().aux_layer = T.ops[conv1_op].layer; }
-    conv(T, scope + "_conv3", k1, log2S, ob, 0, c1, H, ob, Fp + Hp);
-    if (then_maxpool) { T.ops.back().mp_buf = pb; T.ops.back().mp_mode = 1; }
-    if (ab >= 0) { T.ops.back().aux_in_buf = ab; T.ops.back().x8_bit = 2 * x8_block + 1; T.ops.back().aux_layer = T.ops[conv1_op].layer; ++x8_block; }
-    out_map->pos.clear();
-    for (int i = 0; i < F; ++i) out_map->pos.push_back(i);
-    for (int i = 0; i < H; ++i) out_map->pos.push_back(Fp + i);
-    for (int i = 0; i < H; ++i) out_map->pos.push_back(Fp + Hp + i);
-    for (int i = 0; i < F; ++i) out_map->pos.push_back(Fp + Hp + Hp + i);
-    out_map->C = C;
-    if (then_maxpool) {
-      if (!fuse4) {
-        Op op; op.kind = Op::MAX; op.in_buf = ob; op.out_buf = pb; op.in_coff = op.out_coff = Fp + Hp + Hp;
-        op.C = Fp; op.log2S = log2S;
-        T.ops.push_back(op);
-      }
-      return pb;
-    }
-    return ob;
-  }
-
-  // fully connected stack on a [NB,1,C] feature (utils/tf_util.py:314-351)
-  int fc_stack(Tower& T, int in_buf, ChanMap m, const std::vector<std::string>& scopes, const std::vector<int>& widths,
-               bool last_relu, int first_in_cstride = 0) {
-    int buf = in_buf;
-    for (size_t i = 0; i < scopes.size(); ++i) {
-      const bool last = (i + 1 == scopes.size());
-      const int Cp = pad_to(widths[i], kPad);
-      T.bufs.push_back({0, Cp, last});
-      const int ob = (int)T.bufs.size() - 1;
-      conv(T, scopes[i], 1, 0, buf, 0, m, widths[i], ob, 0, /*bn=*/!last, /*relu=*/last ? last_relu : true, /*fc=*/true,
-           /*out_f32=*/last);
-      if (i == 0) T.ops.back().in_cstride = first_in_cstride;
-      m.pos.clear(); m.C = Cp;
-      for (int c = 0; c < widths[i]; ++c) m.pos.push_back(c);
-      buf = ob;
-    }
-    return buf;
-  }
-
-  void init_tower(Tower& T) {
-    T.bufs.clear(); T.ops.clear();
-    T.bufs.push_back({g.cfg.grid_n == 3 ? 2 : 3, g.mups_cstride, false});   // 0: X0 (3^3 grid: rows in a 4^3 index space)
-  }
-
-  // conv_net_3g (models/experts_n_est.py:217-240): four inception blocks on the 3^3 grid (kernel sizes [2,3], [2,3],
-  // [1,2], [1,2]; k0 = 1 makes conv2 a 1x1x1 layer and the avg-pool of the conv4 branch the identity), then
-  // max_pool3d [3,3,3] stride 2 SAME -> 2^3 x 1536, flattened voxel-major.  The 27 voxels live in a 4^3 index space
-  // (kernels.h: ConvParams::s_real).  Returns the pooled buffer; *flat describes it as one FC input row.
-  int conv_net_3g(Tower& T, const std::string& s, ChanMap m, ChanMap* flat) {
-    s_real = 3;
-    int b = inception(T, "inception1" + s, 0, m, 128, 2, 3, 2, &m);
-    b = inception(T, "inception2" + s, b, m, 256, 2, 3, 2, &m);
-    b = inception(T, "inception3" + s, b, m, 256, 1, 2, 2, &m);
-    b = inception(T, "inception4" + s, b, m, 512, 1, 2, 2, &m);
-    s_real = 0;
-    T.bufs.push_back({1, m.C, false});
-    const int pb = (int)T.bufs.size() - 1;
-    Op op; op.kind = Op::MAX3; op.in_buf = b; op.out_buf = pb; op.in_coff = op.out_coff = 0; op.C = m.C; op.log2S = 2;
-    T.ops.push_back(op);                                                    // maxpool5  :238
-    flat->pos.clear(); flat->C = 8 * m.C;
-    for (int v = 0; v < 8; ++v)
-      for (size_t c = 0; c < m.pos.size(); ++c) flat->pos.push_back(v * m.C + m.pos[c]);
-    return pb;
-  }
-
-  // scale_manager_net + conv_net_8g (models/experts_n_est.py:155-215)
-  void build_gate() {
-    Tower& T = g.gate;
-    init_tower(T);
-    const int S = g.cfg.n_scales;
-    ChanMap m; m.C = g.mups_cstride;
-    for (int c = 0; c < 20 * S; ++c) m.pos.push_back(c);
-    const std::string s = "gating_conv";
-    if (g.cfg.grid_n == 3) {   // models/experts_n_est.py:162-163
-      ChanMap flat;
-      const int pb = conv_net_3g(T, s, m, &flat);
-      T.out_buf = fc_stack(T, pb, flat, {"fc1noise", "fc2noise", "fc3noise", "fc4noise"}, {1024, 256, 128, g.cfg.n_experts},
-                           /*last_relu=*/true, flat.C);
-      T.n_out = g.cfg.n_experts;
-      return;
-    }
-    int b = inception(T, "inception1" + s, 0, m, 128, 3, 5, 3, &m);
-    b = inception(T, "inception2" + s, b, m, 256, 3, 5, 3, &m);
-    b = inception(T, "inception3" + s, b, m, 256, 3, 5, 3, &m, true);    // + maxpool4  :198
-    b = inception(T, "inception5" + s, b, m, 512, 2, 4, 2, &m);
-    b = inception(T, "inception6" + s, b, m, 512, 2, 4, 2, &m, true);    // + maxpool7  :206
-    b = inception(T, "inception8" + s, b, m, 512, 1, 2, 1, &m, true);    // + maxpool9  :211
-    T.out_buf = fc_stack(T, b, m, {"fc1noise", "fc2noise", "fc3noise", "fc4noise"}, {1024, 256, 128, g.cfg.n_experts},
-                         /*last_relu=*/true);   // relu on fc4: models/experts_n_est.py:174
-    T.n_out = g.cfg.n_experts;
-  }
-
-  // The "ss" tower shared by the ablation models: inception x3 @8^3 [3,5] -> maxpool -> inception x2 @4^3
-  // [3,k1_small] -> maxpool -> flatten 2^3 x 1536 voxel-major (tf.reshape) -> fc 1024/256/128/n_out.  Used by
-  // ss_norm_est.get_model (models/ss_norm_est.py:35-92), ms_norm_est.get_model (models/ms_norm_est.py:45-140) and
-  // the three towers of ms_sw_n_est (models/ms_sw_n_est.py:139-215).  Dropout is the identity at inference.  fc1
-  // is an FC over a flattened view of the pooled buffer.
-  void build_ss_tower(Tower& T, int scale_lo, int scale_cnt, const std::function<std::string(int)>& name,
-                      const std::string& fc_suffix, int n_out, bool last_relu, int k1_small) {
-    init_tower(T);
-    ChanMap m; m.C = g.mups_cstride;
-    for (int c = 0; c < 20 * scale_cnt; ++c) m.pos.push_back(20 * scale_lo + c);
-    int b = inception(T, name(1), 0, m, 128, 3, 5, 3, &m);
-    b = inception(T, name(2), b, m, 256, 3, 5, 3, &m);
-    b = inception(T, name(3), b, m, 256, 3, 5, 3, &m, true);
-    b = inception(T, name(5), b, m, 512, 3, k1_small, 2, &m);
-    b = inception(T, name(6), b, m, 512, 3, k1_small, 2, &m, true);
-    ChanMap flat; flat.C = 8 * m.C;
-    for (int v = 0; v < 8; ++v)
-      for (size_t c = 0; c < m.pos.size(); ++c) flat.pos.push_back(v * m.C + m.pos[c]);
-    T.out_buf = fc_stack(T, b, flat, {"fc1" + fc_suffix, "fc2" + fc_suffix, "fc3" + fc_suffix, "fc4" + fc_suffix},
-                         {1024, 256, 128, n_out}, last_relu, flat.C);
-    T.n_out = n_out;
-  }
-
-  // ss_norm_est (one scale, 4^3 kernels [3,5], scopes 'inception<L>') / ms_norm_est (S scales concatenated on
-  // channels, 4^3 kernels [3,4], scopes 'inception_s<S-1>_l_<L>')
-  void build_single() {
-    const bool multi = g.cfg.arch == NESTI_ARCH_MULTI;
-    const int S = g.cfg.n_scales;
-    auto name = [=](int layer) {
-      return multi ? "inception_s" + std::to_string(S - 1) + "_l_" + std::to_string(layer) : "inception" + std::to_string(layer);
-    };
-    build_ss_tower(g.experts[0], 0, S, name, "", 3, /*last_relu=*/false, multi ? 4 : 5);
-  }
-
-  // ms_sw_n_est.get_model (models/ms_sw_n_est.py:41-89): noise_est_net on the LARGE scale (scale 1) with a ReLU on
-  // its single output (:172), normal_est_net 'small' on scale 0 and 'large' on scale 1 (:77-78); the driver keeps
-  // n_est_small where noise_est < 0.015 (:80-82).  Here: gate = the noise tower, expert 0 = small, expert 1 = large.
-  void build_switch() {
-    auto scoped = [](const std::string& sfx) {
-      return [sfx](int layer) { return "inception" + std::to_string(layer) + sfx; };
-    };
-    build_ss_tower(g.gate, 1, 1, scoped("noise"), "noise", 1, /*last_relu=*/true, 5);
-    build_ss_tower(g.experts[0], 0, 1, scoped("small"), "small", 3, /*last_relu=*/false, 5);
-    build_ss_tower(g.experts[1], 1, 1, scoped("large"), "large", 3, /*last_relu=*/false, 5);
-  }
-
-  // normal_est_net, 8^3 branch (models/experts_n_est.py:243-291)
-  void build_expert(int i) {
-    Tower& T = g.experts[i];
-    init_tower(T);
-    const int lo = g.cfg.expert_scale_lo[i], cnt = g.cfg.expert_scale_cnt[i];
-    ChanMap m; m.C = g.mups_cstride;
-    for (int c = 0; c < 20 * cnt; ++c) m.pos.push_back(20 * lo + c);   // MuPS[..., start:end]  :100-102
-    const std::string s = "Expert_" + std::to_string(i);
-    if (g.cfg.grid_n == 3) {   // models/experts_n_est.py:275-276: the 3^3 branch ignores `divider`
-      ChanMap flat;
-      const int pb = conv_net_3g(T, s + "_expert_conv", m, &flat);
-      T.out_buf = fc_stack(T, pb, flat, {"fc1" + s, "fc2" + s, "fc3" + s, "fc4" + s}, {512, 128, 64, 3}, /*last_relu=*/false, flat.C);
-      T.n_out = 3;
-      return;
-    }
-    const int F1 = 128 / cnt;   // np.round(128 / divider) under Python-2 integer division  :254
-    x8 = g.x8; x8_block = 0;
-    int b = inception(T, "inception1" + s, 0, m, F1, 3, 5, 3, &m);
-    b = inception(T, "inception2" + s, b, m, 256, 3, 5, 3, &m, true);    // + maxpool3  :261
-    x8 = false;
-    b = inception(T, "inception4" + s, b, m, 256, 2, 4, 2, &m, true);    // + maxpool5  :266
-    b = inception(T, "inception6" + s, b, m, 512, 2, 4, 1, &m, true);    // + maxpool7  :271
-    T.out_buf = fc_stack(T, b, m, {"fc1" + s, "fc2" + s, "fc3" + s, "fc4" + s}, {512, 128, 64, 3}, /*last_relu=*/false);
-    T.n_out = 3;
-  }
-};
-
-int build_graph(const nesti_config_t* cfg, Graph* g, bool x8 = false) {
-  if (cfg->arch != NESTI_ARCH_EXPERTS && cfg->arch != NESTI_ARCH_SINGLE && cfg->arch != NESTI_ARCH_MULTI &&
-      cfg->arch != NESTI_ARCH_SWITCH)
-    NESTI_FAIL("unknown arch");
-  if (cfg->arch == NESTI_ARCH_SWITCH && cfg->n_scales != 2)
-    NESTI_FAIL("NESTI_ARCH_SWITCH (ms_sw_n_est) takes exactly two scales (models/ms_sw_n_est.py:50)");
-  if (cfg->arch == NESTI_ARCH_SINGLE && cfg->n_scales != 1) NESTI_FAIL("NESTI_ARCH_SINGLE (ss_norm_est) takes exactly one scale");
-  if (cfg->grid_n != 8 && !(cfg->grid_n == 3 && cfg->arch == NESTI_ARCH_EXPERTS))
-    NESTI_FAIL("the Gaussian grid must be 8^3 (any model) or 3^3 (experts_n_est only: the ablation models are 8^3-only, "
-               "models/ms_sw_n_est.py:183)");
-  if (cfg->n_scales < 1 || cfg->n_scales > NESTI_MAX_SCALES) NESTI_FAIL("bad n_scales");
-  if (cfg->n_experts < 1 || cfg->n_experts > NESTI_MAX_EXPERTS) NESTI_FAIL("bad n_experts");
-  for (int i = 0; i < cfg->n_experts && cfg->arch == NESTI_ARCH_EXPERTS; ++i) {
-    if (cfg->expert_scale_cnt[i] < 1 || cfg->expert_scale_lo[i] < 0 ||
-        cfg->expert_scale_lo[i] + cfg->expert_scale_cnt[i] > cfg->n_scales)
-      NESTI_FAIL("expert scale range outside [0, n_scales)");
-  }
-  g->cfg = *cfg;
-  g->x8 = x8 && cfg->arch == NESTI_ARCH_EXPERTS && cfg->grid_n == 8;
-  g->mups_cstride = pad_to(20 * cfg->n_scales, kPad);
-  g->layers.clear();
-  Builder b(*g);
-  g->gate = Tower();
-  if (cfg->arch == NESTI_ARCH_SINGLE || cfg->arch == NESTI_ARCH_MULTI) {
-    g->cfg.n_experts = 1;
-    g->experts.assign(1, Tower());
-    b.build_single();
-    return 0;
-  }
-  if (cfg->arch == NESTI_ARCH_SWITCH) {
-    g->cfg.n_experts = 2;
-    g->cfg.expert_scale_lo[0] = 0; g->cfg.expert_scale_lo[1] = 1;
-    g->cfg.expert_scale_cnt[0] = g->cfg.expert_scale_cnt[1] = 1;
-    g->experts.assign(2, Tower());
-    b.build_switch();
-    return 0;
-  }
-  b.build_gate();
-  g->experts.assign(cfg->n_experts, Tower());
-  for (int i = 0; i < cfg->n_experts; ++i) b.build_expert(i);
-  return 0;
-}
 
 // ------------------------------------------------------------------------------------------
 // device-resident packed layers
 // ------------------------------------------------------------------------------------------
-struct PackedLayer {
+// A packed layer in device memory (upload): the packer's metadata and where its bytes went
+struct PackedLayer : PackMeta {
   void* wpk = nullptr;
   float* bias = nullptr;
-  int TN = 64, n_tiles = 0, split_tile = 0, n_chunks = 0, n_taps = 0;
-  int kind = 0;              // 0: conv_igemm_kernel (conv.hip), 2: conv8n_kernel (conv8n.hip: 4 points x a z half x 64 columns
-                             // per workgroup), 3: conv4n_kernel (conv4n.hip: 16 points x 64 voxels x 64 columns)
-  bool x3n = false;          // pair modes: K chunks [hi | lo] / [W_hi | W_lo], three MFMAs per fragment set
-  float acc_scale = 1.0f;    // 2^-s when the packed weights carry a 2^s scale (NESTI_F16X3)
-  int x8_sb = 0;             // X8 / X6 entries (rows [W_hi f16 16 ch | W_hi8 16 ch | W_lo8 16 ch], conv8n.hip X8): W_hi8 = e4m3(W_hi 2^sb),
-                             // W_lo8 = e4m3(W_lo 2^(sb + 11))
-  int x8_sc = 0;             // producer layers (an 8^3 block's conv1): hi8 = e4m3(v 2^sc), lo8 = e4m3(lo 2^(sc + 11))
-  int8_t tap[kMaxTaps][4];
 };
 
-// The form of a launch (launch_form): the NESTI_DEBUG_FORM_* values of include/nesti_hip.h and, EXPERIMENT
-// (nesti_model_set_expert_mix / _gate_mix), a tap layer of a pair-mode tower in plain f16 / bf16 -- it reads the hi
-// planes of its pair-layout input, multiplies ONE product and writes its outputs as pairs again
-constexpr int kFormMix = NESTI_DEBUG_FORM_X6 + 1;
-// ... and the packed weights it runs on: its own, except that X2 multiplies by the pair packing
-inline int form_packing(int form) { return form == NESTI_DEBUG_FORM_X2 ? NESTI_DEBUG_FORM_PAIR : form; }
+// The one place packed bytes go to the device: the image pack_form made of a layer, for every form
+int upload(const PackedImage& img, PackedLayer* pl) {
+  static_cast<PackMeta&>(*pl) = img;
+  NESTI_CHECK_HIP(hipMalloc(&pl->wpk, img.w.size()));
+  NESTI_CHECK_HIP(hipMemcpy(pl->wpk, img.w.data(), img.w.size(), hipMemcpyHostToDevice));
+  NESTI_CHECK_HIP(hipMalloc((void**)&pl->bias, img.bias.size() * sizeof(float)));
+  NESTI_CHECK_HIP(hipMemcpy(pl->bias, img.bias.data(), img.bias.size() * sizeof(float), hipMemcpyHostToDevice));
+  return 0;
+}
 
 }  // namespace
 }  // namespace nesti
@@ -552,91 +198,6 @@ struct nesti_model {
 namespace nesti {
 namespace {
 
-struct TensorTable {
-  std::map<std::string, const nesti_tensor_t*> by_name;
-  const nesti_tensor_t* get(const std::string& n) const {
-    auto it = by_name.find(n);
-    return it == by_name.end() ? nullptr : it->second;
-  }
-};
-
-bool shape_is(const nesti_tensor_t* t, std::initializer_list<int64_t> dims) {
-  if (!t || !t->data || t->ndim != (int)dims.size()) return false;
-  int i = 0;
-  for (int64_t d : dims) if (t->dims[i++] != d) return false;
-  return true;
-}
-
-// Expected variables of one layer, in TF naming (utils/tf_util.py:289-302, 332-342, 473-479).
-void layer_tensors(const LayerDesc& d, std::vector<std::pair<std::string, std::vector<int64_t>>>* out) {
-  for (const std::string* sc : {&d.scope, &d.scope2}) {
-    if (sc->empty()) continue;
-    if (d.is_fc) out->push_back({*sc + "/weights", {d.cin, d.cout}});
-    else out->push_back({*sc + "/weights", {d.k, d.k, d.k, d.cin, d.cout}});
-    out->push_back({*sc + "/biases", {d.cout}});
-    if (d.bn) {
-      for (const char* n : {"beta", "gamma", "mean", "var"}) out->push_back({*sc + "/bn/" + n, {d.cout}});
-    }
-  }
-}
-
-// BN-folded weights/bias of one TF layer (utils/tf_util.py:298-311, 491-494)
-struct Folded {
-  const float* w = nullptr;        // [taps][cin][cout]
-  std::vector<float> scale, bias;  // per real output channel
-};
-
-int fold_layer(const LayerDesc& d, const std::string& scope, const TensorTable& tt, Folded* f) {
-  const nesti_tensor_t* w = tt.get(scope + "/weights");
-  const nesti_tensor_t* b = tt.get(scope + "/biases");
-  const bool wok = d.is_fc ? shape_is(w, {d.cin, d.cout}) : shape_is(w, {d.k, d.k, d.k, d.cin, d.cout});
-  if (!wok) NESTI_FAIL("missing or mis-shaped tensor " + scope + "/weights");
-  if (!shape_is(b, {d.cout})) NESTI_FAIL("missing or mis-shaped tensor " + scope + "/biases");
-  f->w = w->data;
-  f->scale.assign(d.cout, 1.0f);
-  f->bias.resize(d.cout);
-  for (int n = 0; n < d.cout; ++n) f->bias[n] = b->data[n];
-  if (d.bn) {
-    const nesti_tensor_t* beta = tt.get(scope + "/bn/beta");
-    const nesti_tensor_t* gamma = tt.get(scope + "/bn/gamma");
-    const nesti_tensor_t* mean = tt.get(scope + "/bn/mean");
-    const nesti_tensor_t* var = tt.get(scope + "/bn/var");
-    if (!shape_is(beta, {d.cout}) || !shape_is(gamma, {d.cout}) || !shape_is(mean, {d.cout}) || !shape_is(var, {d.cout}))
-      NESTI_FAIL("missing or mis-shaped batch-norm tensors under " + scope + "/bn/");
-    for (int n = 0; n < d.cout; ++n) {
-      // tf.nn.batch_normalization(x, mean, var, beta, gamma, 1e-3)  (utils/tf_util.py:494)
-      const double inv = (double)gamma->data[n] / sqrt((double)var->data[n] + 1e-3);
-      f->scale[n] = (float)inv;
-      f->bias[n] = (float)(((double)b->data[n] - (double)mean->data[n]) * inv + (double)beta->data[n]);
-    }
-  }
-  return 0;
-}
-
-// Which layers run on conv8n_kernel (conv8n.hip): the k^3 taps (k = 3, 5) on the 8^3 volume; everything else is
-// conv_igemm_kernel's (conv.hip)
-bool use_conv8(const LayerDesc& d) {
-  if (d.is_fc || d.log2S != 3 || d.s_real || !d.scope2.empty()) return false;
-  return d.k == 5 || d.k == 3;
-}
-// ... and on conv4n_kernel (conv4n.hip): the k^3 taps (k = 2 .. 5) on the 4^3 volume (not the 3^3 grid embedded in 4^3)
-bool use_conv4(const LayerDesc& d, int dtype) {
-  if (d.is_fc || d.log2S != 2 || d.s_real || !d.scope2.empty() || d.k < 2 || d.k > 5) return false;
-  return act_planes(dtype) == 1 || !(d.k & 1);   // pair modes: the even kernels only (conv4n.hip: launch_conv4n_dt)
-}
-
-// PackedLayer::kind of a layer packed for `dtype` (pack_layer)
-int layer_kind(const LayerDesc& d, int dtype) { return use_conv8(d) ? 2 : use_conv4(d, dtype) ? 3 : 0; }
-// PackedLayer::n_taps: the k^3 taps that can land inside the volume (pack_layer keeps only those)
-int layer_taps(const LayerDesc& d) {
-  const int S = d.s_real ? d.s_real : (1 << d.log2S), lo = (d.k - 1) / 2;
-  int n = 0;
-  for (int a = 0; a < d.k; ++a)
-    for (int bb = 0; bb < d.k; ++bb)
-      for (int c = 0; c < d.k; ++c) n += abs(a - lo) < S && abs(bb - lo) < S && abs(c - lo) < S;
-  return n;
-}
-
 // ------------------------------------------------------------------------------------------
 // the form of a launch
 // ------------------------------------------------------------------------------------------
@@ -694,335 +255,6 @@ LaunchForm launch_form(const Graph& g, const Op& op, const Pass& ps, int mdt) {
     f.family = layer_kind(d, mdt);
   }
   return f;
-}
-
-// Error attribution in the pair modes (scripts/exp_attribution.py), ONLY in builds made with -DNESTI_ATTRIBUTION (the product
-// library has no such switch): NESTI_X3_PLAIN = "regex,regex,..." -- a layer whose scope matches drops the hi * W_lo product
-// (its W_lo weights are packed as zeros: the layer then sees its weights rounded to 16 bits).  Round 3's full sweep
-// (profiles/r03_attribution_sweep.txt) also switched off lo * W_hi per layer; that needed the three-plane layout
-// [hi | lo | hi] x [W_hi ; W_hi ; W_lo] of commit 6f246d7 and is not available in the two-plane layout.
-#ifdef NESTI_ATTRIBUTION
-int x3_drop_mask(const LayerDesc& d) {
-  const char* e = getenv("NESTI_X3_PLAIN");
-  if (!e || !*e) return 0;
-  std::string spec(e);
-  size_t pos = 0;
-  while (pos <= spec.size()) {
-    size_t end = spec.find(',', pos);
-    if (end == std::string::npos) end = spec.size();
-    const std::string item = spec.substr(pos, end - pos);
-    pos = end + 1;
-    if (item.empty()) continue;
-    try {
-      const std::regex re(item);
-      if (std::regex_search(d.scope, re) || (!d.scope2.empty() && std::regex_search(d.scope2, re))) {
-        fprintf(stderr, "libnesti_hip (attribution build): layer %s packed WITHOUT its W_lo plane\n", d.scope.c_str());
-        return 2;
-      }
-    } catch (const std::regex_error&) {
-      fprintf(stderr, "libnesti_hip (attribution build): bad regex '%s' in NESTI_X3_PLAIN\n", item.c_str());
-    }
-  }
-  return 0;
-}
-#else
-inline int x3_drop_mask(const LayerDesc&) { return 0; }
-#endif
-
-// OCP e4m3 (1-4-3, bias 7, no infinities, largest finite 448) of a float, round to nearest even, saturating; subnormals kept
-uint8_t host_f32_to_e4m3(float f) {
-  const uint8_t sign = std::signbit(f) ? 0x80 : 0;
-  float a = fabsf(f);
-  if (!(a == a)) return 0x7f;
-  a = std::min(a, 448.f);
-  if (a == 0.f) return sign;
-  int e;
-  (void)frexpf(a, &e);                       // a = m 2^e, m in [0.5, 1)
-  e = std::max(e - 1, -6);                   // exponent of the leading bit, not below the smallest normal's
-  const float quantum = ldexpf(1.f, e - 3);
-  float q = nearbyintf(a / quantum);         // default rounding mode: to nearest, ties to even
-  float v = q * quantum;
-  if (v == 0.f) return sign;
-  if (v < ldexpf(1.f, -6)) return (uint8_t)(sign | (uint8_t)nearbyintf(v / ldexpf(1.f, -9)));   // subnormal: exponent field 0
-  int e2;
-  (void)frexpf(v, &e2);
-  e2 -= 1;
-  const int mant = (int)nearbyintf(v / ldexpf(1.f, e2 - 3)) - 8;
-  return (uint8_t)(sign | ((e2 + 7) << 3) | mant);
-}
-
-// The FP8 cross-term packing of one k^3 tap layer at 8^3 (conv8n.hip X8; NESTI_F16X8 / NESTI_F16X8C): per (column pair, 16-channel
-// chunk, tap) 64 rows x 64 B = [W_hi f16 k0..15 | W_hi8 k0..15 | W_lo8 k0..15] of the SAME scaled weights the pair packing holds
-// (W 2^e, |W| 2^e < 2^14): W_hi8 = e4m3(W_hi 2^sb), W_lo8 = e4m3((W - W_hi) 2^(sb + 11)) with sb = -6 (both below 256).
-// e2m3 (1-2-3, bias 1, largest finite 7.5) code of a non-negative magnitude already divided by its block scale: round to nearest even,
-// saturating.  The code is monotone in the value and the grid is piecewise uniform: [0, 1) step 1/8 (subnormals), [1, 2) 1/8, [2, 4) 1/4,
-// [4, 7.5] 1/2; a value that rounds up to the next binade's first point gets that point's code.
-uint8_t host_mag_to_e2m3(float a) {
-  if (!(a == a)) return 31;
-  int code;
-  if (a < 2.f) code = (int)nearbyintf(a * 8.f);                    // 0 .. 16 (16 = 2.0)
-  else if (a < 4.f) code = 16 + (int)nearbyintf((a - 2.f) * 4.f);    // .. 24 (= 4.0)
-  else code = 24 + (int)nearbyintf((std::min(a, 8.f) - 4.f) * 2.f);
-  return (uint8_t)std::min(code, 31);
-}
-inline uint8_t host_f32_to_e2m3(float f, float inv_scale) {
-  return (uint8_t)(host_mag_to_e2m3(fabsf(f) * inv_scale) | (std::signbit(f) ? 32 : 0));
-}
-
-// fmt == 6: the block-scaled FP6 form of the same rows (conv8n.hip X6; kernels.h: ConvParams::x8_fmt): the 32 bytes that hold
-// [W_hi8 | W_lo8] hold instead 32 e2m3 elements -- slot 2i = W_hi[i] / s, slot 2i + 1 = W_lo[i] 2^11 / s of the chunk's 16 input channels
-// (the order the producer's conversion instruction writes [lo | hi] activations in, so that slot products are lo W_hi and hi W_lo) -- and
-// in byte 24 the E8M0 code of s 2^-11 (s = 2^(E - 2), E = exponent of the chunk's largest |W_hi|; the 2^-11 undoes BOTH 2^11 pre-scales,
-// the activations' and the weights', since every product carries exactly one of them).
-int pack_layer_x8(const LayerDesc& d, const TensorTable& tt, PackedLayer* pl, int fmt) {
-  if (!use_conv8(d) || !d.scope2.empty()) NESTI_FAIL("internal: pack_layer_x8 is for the k^3 tap layers at 8^3");
-  Folded f;
-  if (fold_layer(d, d.scope, tt, &f)) return 1;
-  const int lo = (d.k - 1) / 2;
-  pl->n_taps = 0;
-  std::vector<int> tap_widx;
-  for (int a = 0; a < d.k; ++a)
-    for (int bb = 0; bb < d.k; ++bb)
-      for (int c = 0; c < d.k; ++c) {
-        pl->tap[pl->n_taps][0] = (int8_t)(a - lo); pl->tap[pl->n_taps][1] = (int8_t)(bb - lo);
-        pl->tap[pl->n_taps][2] = (int8_t)(c - lo); pl->tap[pl->n_taps][3] = 0;
-        tap_widx.push_back((a * d.k + bb) * d.k + c);
-        ++pl->n_taps;
-      }
-  pl->kind = 2; pl->x3n = false; pl->TN = 64;
-  if (d.Cout_p % 64 || d.Cin_p % kSplitGroup) NESTI_FAIL("internal: pack_layer_x8 needs 64-aligned channel counts");
-  pl->n_tiles = d.Cout_p / 64; pl->split_tile = pl->n_tiles;
-  constexpr int chunk_ch = 16;
-  pl->n_chunks = d.Cin_p / chunk_ch;
-  float wmax = 0.f;
-  for (size_t t = 0; t < tap_widx.size(); ++t) {
-    const float* wt = f.w + (size_t)tap_widx[t] * d.cin * d.cout;
-    for (int c = 0; c < d.cin; ++c)
-      for (int n = 0; n < d.cout; ++n) wmax = std::max(wmax, fabsf(wt[(size_t)c * d.cout + n] * f.scale[n]));
-  }
-  int e = 0;
-  if (wmax > 0.f && std::isfinite(wmax)) {
-    (void)frexpf(wmax, &e);
-    e = std::min(24, std::max(-8, 14 - e));      // as pack_layer: wmax 2^e in [2^13, 2^14)
-  }
-  const float wmul = ldexpf(1.0f, e);
-  pl->acc_scale = ldexpf(1.0f, -e);
-  pl->x8_sb = -6;
-  const float mul_hi8 = ldexpf(1.f, pl->x8_sb), mul_lo8 = ldexpf(1.f, pl->x8_sb + 11);
-  std::vector<int> inv(d.Cin_p, -1);
-  for (int c = 0; c < d.cin; ++c) inv[d.in_pos[c]] = c;
-  const size_t tile_bytes = (size_t)64 * 64;
-  const size_t total = (size_t)pl->n_tiles * pl->n_chunks * pl->n_taps * tile_bytes;
-  std::vector<unsigned char> host(total, 0);
-  for (int nt = 0; nt < pl->n_tiles; ++nt)
-    for (int ch = 0; ch < pl->n_chunks; ++ch)
-      for (int t = 0; t < pl->n_taps; ++t) {
-        unsigned char* tile = host.data() + (((size_t)nt * pl->n_chunks + ch) * pl->n_taps + t) * tile_bytes;
-        const float* wt = f.w + (size_t)tap_widx[t] * d.cin * d.cout;
-        float whi[16][64] = {}, wlo[16][64] = {};          // fmt 6: the chunk's pair split, per column
-        for (int kc = 0; kc < chunk_ch; ++kc) {
-          const int cr = inv[ch * chunk_ch + kc];
-          if (cr < 0) continue;
-          const float* wrow = wt + (size_t)cr * d.cout;
-          for (int nl = 0; nl < 64; ++nl) {
-            const int n = nt * 64 + nl;
-            if (n >= d.cout) break;
-            const float v = wrow[n] * f.scale[n] * wmul;
-            const uint16_t h = host_f32_to_f16(v);
-            const float hf = host_f16_to_f32(h);
-            const int key = (nl >> 2) & 3;               // conv8n_kernel's weight-row swizzle
-            unsigned char* row = tile + (size_t)nl * 64;
-            memcpy(row + (((kc >> 3) ^ key) << 4) + (kc & 7) * 2, &h, 2);
-            if (fmt == 6) { whi[kc][nl] = hf; wlo[kc][nl] = (v - hf) * 2048.f; continue; }
-            row[((2 ^ key) << 4) + kc] = host_f32_to_e4m3(hf * mul_hi8);
-            row[((3 ^ key) << 4) + kc] = host_f32_to_e4m3((v - hf) * mul_lo8);
-          }
-        }
-        if (fmt == 6)
-          for (int nl = 0; nl < 64; ++nl) {
-            float amax = 0.f;
-            for (int kc = 0; kc < chunk_ch; ++kc) amax = std::max(amax, fabsf(whi[kc][nl]));
-            if (!(amax > 0.f) || !std::isfinite(amax)) continue;          // an all-zero (padding) block: codes 0, scale byte 0
-            int e;
-            (void)frexpf(amax, &e);                                        // amax = m 2^e, m in [0.5, 1): leading exponent e - 1
-            const int sexp = e - 1 - 2;                                    // s = 2^sexp: the largest element lands in [4, 8)
-            const float inv_s = ldexpf(1.f, -sexp);
-            unsigned char blk[32] = {};
-            for (int kc = 0; kc < chunk_ch; ++kc) {
-              const unsigned c2[2] = {host_f32_to_e2m3(whi[kc][nl], inv_s), host_f32_to_e2m3(wlo[kc][nl], inv_s)};
-              for (int j = 0; j < 2; ++j) {
-                const int pos = 6 * (2 * kc + j);
-                const unsigned w = c2[j] << (pos & 7);
-                blk[pos >> 3] |= (unsigned char)w;
-                blk[(pos >> 3) + 1] |= (unsigned char)(w >> 8);
-              }
-            }
-            const int sbyte = sexp - 11 + 127;
-            if (sbyte < 1 || sbyte > 254) NESTI_FAIL("internal: FP6 weight block scale out of the E8M0 range");
-            blk[24] = (unsigned char)sbyte;
-            const int key = (nl >> 2) & 3;
-            unsigned char* row = tile + (size_t)nl * 64;
-            memcpy(row + ((2 ^ key) << 4), blk, 16);
-            memcpy(row + ((3 ^ key) << 4), blk + 16, 16);
-          }
-      }
-  std::vector<float> bias_p((size_t)pl->n_tiles * 64, 0.f);
-  for (int n = 0; n < d.cout; ++n) bias_p[n] = f.bias[n];
-  NESTI_CHECK_HIP(hipMalloc(&pl->wpk, total));
-  NESTI_CHECK_HIP(hipMemcpy(pl->wpk, host.data(), total, hipMemcpyHostToDevice));
-  NESTI_CHECK_HIP(hipMalloc((void**)&pl->bias, bias_p.size() * sizeof(float)));
-  NESTI_CHECK_HIP(hipMemcpy(pl->bias, bias_p.data(), bias_p.size() * sizeof(float), hipMemcpyHostToDevice));
-  return 0;
-}
-
-// Power-of-two pre-scale of the e4m3 activation planes a block's conv1 writes for the FP8 cross terms: hi8 = e4m3(v 2^sc) must stay
-// below the format's 448.  A data-free bound from the layer's own batch-norm: after tf.nn.batch_normalization the pre-activation of
-// channel n is beta_n + gamma_n z with z ~ N(0, 1) on the data the statistics were taken from, so |v| <= |beta_n| + 8 |gamma_n| but for
-// 8-sigma events; 2^sc brings that bound into (128, 256].  A larger value saturates and loses only its own cross terms.
-int x8_activation_exponent(const LayerDesc& d, const TensorTable& tt) {
-  float amax = 16.f;
-  const nesti_tensor_t* beta = tt.get(d.scope + "/bn/beta");
-  const nesti_tensor_t* gamma = tt.get(d.scope + "/bn/gamma");
-  if (d.bn && beta && gamma && beta->data && gamma->data) {
-    amax = 0.f;
-    for (int n = 0; n < d.cout; ++n) amax = std::max(amax, fabsf(beta->data[n]) + 8.f * fabsf(gamma->data[n]));
-  }
-  if (!(amax > 0.f) || !std::isfinite(amax)) amax = 16.f;
-  int e;
-  (void)frexpf(amax, &e);                        // amax = m 2^e, m in [0.5, 1): amax <= 2^e
-  return std::min(20, std::max(-8, 8 - e));
-}
-
-int pack_layer(const LayerDesc& d, const TensorTable& tt, int dtype, PackedLayer* pl) {
-  const int n_parts = d.scope2.empty() ? 1 : 2;
-  Folded parts[2];
-  if (fold_layer(d, d.scope, tt, &parts[0])) return 1;
-  if (n_parts == 2 && fold_layer(d, d.scope2, tt, &parts[1])) return 1;
-  const int part_p = d.Cout_p / n_parts;   // padded width of one part
-  const int S = d.s_real ? d.s_real : (1 << d.log2S);
-  const int lo = (d.k - 1) / 2;   // TF SAME, stride 1
-  pl->n_taps = 0;
-  std::vector<int> tap_widx;
-  for (int a = 0; a < d.k; ++a)
-    for (int bb = 0; bb < d.k; ++bb)
-      for (int c = 0; c < d.k; ++c) {
-        const int dz = a - lo, dy = bb - lo, dx = c - lo;
-        if (abs(dz) >= S || abs(dy) >= S || abs(dx) >= S) continue;   // never lands inside the volume
-        pl->tap[pl->n_taps][0] = (int8_t)dz; pl->tap[pl->n_taps][1] = (int8_t)dy;
-        pl->tap[pl->n_taps][2] = (int8_t)dx; pl->tap[pl->n_taps][3] = 0;
-        tap_widx.push_back((a * d.k + bb) * d.k + c);
-        ++pl->n_taps;
-      }
-  const size_t esz = dtype_size(dtype);
-  // NESTI_BF16X3 / NESTI_F16X3 (common.h): a K chunk of a packed weight row is [W_hi | W_lo] for half as many channels as the
-  // plain chunk holds (the kernels' pair K loop multiplies hi*W_hi + lo*W_hi + hi*W_lo from it: conv.hip / conv8n.hip, X3)
-  const int planes = act_planes(dtype);
-  const int drop = planes > 1 ? x3_drop_mask(d) : 0;
-  pl->kind = layer_kind(d, dtype);
-  if (pl->kind >= 2 && d.Cout_p % 64) NESTI_FAIL("internal: conv8n_kernel / conv4n_kernel need 64-column tiles");
-  pl->x3n = planes > 1;
-  const int K_phys = d.Cin_p * planes;
-  const int row_bytes = pl->kind >= 1 ? 64 : kRowBytes;   // bytes of one K chunk of one row
-  const int KC = row_bytes / (int)esz;
-  const int chunk_ch = KC / planes;                       // input channels per K chunk
-  pl->TN = pl->kind >= 2 ? 64 : (part_p % 128 == 0) ? 128 : 64;   // a tile never straddles the two parts
-  pl->n_tiles = d.Cout_p / pl->TN;
-  pl->split_tile = part_p / pl->TN * (n_parts == 2 ? 1 : n_parts);
-  if (n_parts == 1) pl->split_tile = pl->n_tiles;
-  pl->n_chunks = K_phys / KC;
-  if (K_phys % KC || d.Cin_p % kSplitGroup) NESTI_FAIL("internal: Cin_p not a multiple of the K chunk");
-  if (n_parts == 2 && pl->n_taps != 1) NESTI_FAIL("internal: fused layers must be 1x1x1");
-  // NESTI_F16X3: one power-of-two scale per layer brings the largest folded weight to ~2^14, so that the lo halves of the
-  // weight pairs (2^-12 of a weight) are normal f16 numbers; the epilogue multiplies the accumulators by 2^-s (exact)
-  float wmul = 1.0f;
-  pl->acc_scale = 1.0f;
-  if (dtype == NESTI_F16X3) {
-    float wmax = 0.f;
-    for (int part = 0; part < n_parts; ++part) {
-      const Folded& f = parts[part];
-      for (size_t t = 0; t < tap_widx.size(); ++t) {
-        const float* wt = f.w + (size_t)tap_widx[t] * d.cin * d.cout;
-        for (int c = 0; c < d.cin; ++c)
-          for (int n = 0; n < d.cout; ++n) wmax = std::max(wmax, fabsf(wt[(size_t)c * d.cout + n] * f.scale[n]));
-      }
-    }
-    int e = 0;
-    if (wmax > 0.f && std::isfinite(wmax)) {
-      (void)frexpf(wmax, &e);                  // wmax = m 2^e, m in [0.5, 1)
-      e = std::min(24, std::max(-8, 14 - e));  // wmax 2^s in [2^13, 2^14)
-    }
-    wmul = ldexpf(1.0f, e);
-    pl->acc_scale = ldexpf(1.0f, -e);
-  }
-  std::vector<int> inv(d.Cin_p, -1);
-  for (int c = 0; c < d.cin; ++c) inv[d.in_pos[c]] = c;
-  const size_t tile_bytes = (size_t)pl->TN * row_bytes;
-  const size_t total = (size_t)pl->n_tiles * pl->n_chunks * pl->n_taps * tile_bytes;
-  std::vector<unsigned char> host(total, 0);
-  const int per_slot = 16 / (int)esz;
-  for (int nt = 0; nt < pl->n_tiles; ++nt) {
-    const int part = (nt * pl->TN) / part_p;
-    const int n_base = nt * pl->TN - part * part_p;    // first real channel of this tile within its part
-    const Folded& f = parts[part];
-    for (int ch = 0; ch < pl->n_chunks; ++ch)
-      for (int t = 0; t < pl->n_taps; ++t) {
-        unsigned char* tile = host.data() + (((size_t)nt * pl->n_chunks + ch) * pl->n_taps + t) * tile_bytes;
-        const float* wt = f.w + (size_t)tap_widx[t] * d.cin * d.cout;
-        for (int kc = 0; kc < KC; ++kc) {
-          // which half of the row this K position is (0: W_hi, 1: W_lo) and the padded input channel it multiplies
-          const int plane = kc / chunk_ch;
-          const int cr = inv[ch * chunk_ch + kc % chunk_ch];
-          if (cr < 0) continue;
-          if (plane == 1 && (drop & 2)) continue;
-          const float* wrow = wt + (size_t)cr * d.cout;
-          const int slot = kc / per_slot, within = kc % per_slot;
-          for (int nl = 0; nl < pl->TN; ++nl) {
-            const int n = n_base + nl;
-            if (n >= d.cout) break;
-            const float v = wrow[n] * f.scale[n] * wmul;
-            // the kernels' LDS image: row nl, 16-B slot XOR-swizzled (conv8n_kernel: 64-B rows, key (row >> 2) & 3;
-            // conv4n_kernel: 64-B rows, key {0, 2, 3, 1}[(row >> 2) & 3])
-            const int key64 = pl->kind == 3 ? (0x78 >> (2 * ((nl >> 2) & 3))) & 3 : (nl >> 2) & 3;
-            unsigned char* dst = pl->kind >= 1
-                ? tile + (size_t)nl * 64 + ((slot ^ key64) << 4) + within * esz
-                : tile + (size_t)nl * kRowBytes + ((slot ^ ((nl >> 1) & 7)) << 4) + within * esz;
-            if (dtype == NESTI_F32) memcpy(dst, &v, 4);
-            else if (planes > 1) {
-              const bool b16 = dtype == NESTI_BF16X3;
-              uint16_t h = b16 ? host_f32_to_bf16(v) : host_f32_to_f16(v);
-              if (plane == 1) {                              // W_lo = rne(W - W_hi)
-                float hf;
-                if (b16) { const uint32_t hb = (uint32_t)h << 16; memcpy(&hf, &hb, 4); } else hf = host_f16_to_f32(h);
-                h = b16 ? host_f32_to_bf16(v - hf) : host_f32_to_f16(v - hf);
-              }
-              memcpy(dst, &h, 2);
-            } else {
-              const uint16_t h = (dtype == NESTI_BF16) ? host_f32_to_bf16(v) : host_f32_to_f16(v);
-              memcpy(dst, &h, 2);
-            }
-          }
-        }
-      }
-  }
-  std::vector<float> bias_p((size_t)pl->n_tiles * pl->TN, 0.f);
-  for (int part = 0; part < n_parts; ++part)
-    for (int n = 0; n < d.cout; ++n) bias_p[(size_t)part * part_p + n] = parts[part].bias[n];
-  NESTI_CHECK_HIP(hipMalloc(&pl->wpk, total));
-  NESTI_CHECK_HIP(hipMemcpy(pl->wpk, host.data(), total, hipMemcpyHostToDevice));
-  NESTI_CHECK_HIP(hipMalloc((void**)&pl->bias, bias_p.size() * sizeof(float)));
-  NESTI_CHECK_HIP(hipMemcpy(pl->bias, bias_p.data(), bias_p.size() * sizeof(float), hipMemcpyHostToDevice));
-  return 0;
-}
-
-// The packing of a layer for the launches of one form (form_packing), in a model whose main dtype is mdt
-int pack_form(const LayerDesc& d, const TensorTable& tt, int form, int mdt, PackedLayer* pl) {
-  switch (form) {
-    case NESTI_DEBUG_FORM_X8: return pack_layer_x8(d, tt, pl, 8);
-    case NESTI_DEBUG_FORM_X6: return pack_layer_x8(d, tt, pl, 6);
-    case kFormMix: return pack_layer(d, tt, kernel_dtype(mdt), pl);
-    case NESTI_DEBUG_FORM_PLAIN: return pack_layer(d, tt, act_planes(mdt) > 1 ? NESTI_F16 : mdt, pl);   // pair models: the filter pass
-    default: return pack_layer(d, tt, mdt, pl);
-  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1553,7 +785,8 @@ int nesti_model_create(const nesti_config_t* cfg, const nesti_tensor_t* tensors,
         const LaunchForm f = launch_form(m->graph, op, ps, dtype);
         const int packing = form_packing(f.form);
         PackedLayer& pl = m->packed[{packing, op.layer}];
-        if (!pl.wpk && pack_form(d, tt, packing, dtype, &pl)) return 1;
+        PackedImage img;
+        if (!pl.wpk && (pack_form(d, tt, packing, dtype, &img) || upload(img, &pl))) return 1;
         if (f.producer) pl.x8_sc = x8_activation_exponent(d, tt);   // the pre-scale of the planes it writes
       }
     }
@@ -1606,8 +839,6 @@ int nesti_model_set_x8_layers(nesti_model_t* m, int mask) {
   m->x8_mask = mask;
   return 0;
 }
-
-int nesti_f32_to_e2m3(float value, float inv_scale) { return (int)host_f32_to_e2m3(value, inv_scale); }
 
 int nesti_model_set_x8_format(nesti_model_t* m, int bits) {
   if (!m) NESTI_FAIL("nesti_model_set_x8_format: null model");
@@ -1944,13 +1175,9 @@ int nesti_model_macs(const nesti_model_t* m, int tower, int kind, double* nomina
     const LayerDesc& d = m->graph.layers[op.layer];
     const PackedLayer& pl = m->main_packing(op.layer);
     if (kind >= 0 && conv_category(d, pl) != kind) continue;
-    const int S = d.s_real ? d.s_real : (1 << d.log2S), V = S * S * S, lo = (d.k - 1) / 2;
-    long long valid = 0;   // sum over output voxels of the taps that land inside the volume
-    for (int z = 0; z < S; ++z) for (int y = 0; y < S; ++y) for (int x = 0; x < S; ++x)
-      for (int a = 0; a < d.k; ++a) for (int b = 0; b < d.k; ++b) for (int c = 0; c < d.k; ++c) {
-        const int zz = z + a - lo, yy = y + b - lo, xx = x + c - lo;
-        if (zz >= 0 && zz < S && yy >= 0 && yy < S && xx >= 0 && xx < S) ++valid;
-      }
+    const int S = d.s_real ? d.s_real : (1 << d.log2S), V = S * S * S;
+    long long valid = 0;   // sum over output voxels of the taps that land inside the volume: a kept tap does at S - |offset| per axis
+    for (int t = 0; t < pl.n_taps; ++t) valid += (long long)(S - abs(pl.tap[t][0])) * (S - abs(pl.tap[t][1])) * (S - abs(pl.tap[t][2]));
     const int parts = d.scope2.empty() ? 1 : 2;
     nom += (double)parts * V * d.k * d.k * d.k * d.cin * d.cout;
     use += (double)parts * valid * d.cin * d.cout;
@@ -1976,6 +1203,38 @@ int nesti_model_macs(const nesti_model_t* m, int tower, int kind, double* nomina
 
 // ---- test hooks: one tower, launch by launch (include/nesti_hip.h) ----------------------------------------------------------
 static const nesti_debug_pass_t kMainPass = {0, 0, 0};
+
+int nesti_debug_pack_layer(const nesti_config_t* cfg, const nesti_tensor_t* tensors, int n_tensors, int dtype, int form, int layer,
+                           nesti_debug_pack_t* info, void* w, size_t max_w, float* bias, size_t max_bias) {
+  if (!cfg || !tensors || !info) NESTI_FAIL("nesti_debug_pack_layer: null argument");
+  if (dtype < NESTI_F32 || dtype > NESTI_F16X8C) NESTI_FAIL("nesti_debug_pack_layer: bad dtype");
+  Graph g;
+  if (build_graph(cfg, &g, dtype_x8(dtype))) return 1;
+  if (layer < 0 || layer >= (int)g.layers.size()) NESTI_FAIL("nesti_debug_pack_layer: layer index outside the model");
+  const LayerDesc& d = g.layers[layer];
+  const int mdt = main_dtype(dtype), packing = form_packing(form);
+  const bool x8 = packing == NESTI_DEBUG_FORM_X8 || packing == NESTI_DEBUG_FORM_X6;
+  if (packing != NESTI_DEBUG_FORM_PLAIN && packing != NESTI_DEBUG_FORM_PAIR && !x8) NESTI_FAIL("nesti_debug_pack_layer: form is NESTI_DEBUG_FORM_*");
+  if (packing == NESTI_DEBUG_FORM_PAIR && act_planes(mdt) == 1)
+    NESTI_FAIL("nesti_debug_pack_layer: the pair packing is for the pair dtypes (NESTI_BF16X3, NESTI_F16X3 and the modes built on it)");
+  if (x8 && !(g.x8 && use_conv8(d)))
+    NESTI_FAIL("nesti_debug_pack_layer: the X8 / X6 packings are for the k^3 tap layers at 8^3 of NESTI_F16X8 / NESTI_F16X8C models; " + d.scope +
+               " is not one");
+  TensorTable tt;
+  for (int i = 0; i < n_tensors; ++i) if (tensors[i].name) tt.by_name[tensors[i].name] = &tensors[i];
+  PackedImage img;
+  if (pack_form(d, tt, packing, mdt, &img)) return 1;
+  memset(info, 0, sizeof(*info));
+  info->kind = img.kind; info->TN = img.TN; info->n_tiles = img.n_tiles; info->split_tile = img.split_tile;
+  info->n_chunks = img.n_chunks; info->n_taps = img.n_taps; info->x3n = img.x3n ? 1 : 0; info->acc_scale = img.acc_scale;
+  info->x8_sb = img.x8_sb; info->x8_sc = x8_activation_exponent(d, tt);
+  info->w_bytes = (int64_t)img.w.size(); info->n_bias = (int64_t)img.bias.size();
+  memcpy(info->tap, img.tap, sizeof(info->tap));
+  if ((w && max_w < img.w.size()) || (bias && max_bias < img.bias.size())) NESTI_FAIL("nesti_debug_pack_layer: output arrays too small");
+  if (w) memcpy(w, img.w.data(), img.w.size());
+  if (bias) memcpy(bias, img.bias.data(), img.bias.size() * sizeof(float));
+  return 0;
+}
 
 // the pass arguments of the two hooks against the graph (cascade: a model with the two-stage gate); `who` prefixes the message
 static int check_pass(const std::string& who, const Graph& g, bool cascade, int tower, const nesti_debug_pass_t& ps) {

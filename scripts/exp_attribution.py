@@ -2,7 +2,7 @@
 
 1. f32 / f16 / f16x3 on all 100 000 queries -> gpurun_out/attr_probs.npz (probs, expert, normals per mode): the data the
    gate-cascade margin is derived from (f16-vs-exact logit error against the top-2 margin).
-2. Sweep: the f16x3 model with ONE layer group at a time computed as plain f16 (NESTI_X3_PLAIN, model.hip: the lo * W_hi
+2. Sweep: the f16x3 model with ONE layer group at a time computed as plain f16 (NESTI_X3_PLAIN, pack.cpp: the lo * W_hi
    and hi * W_lo weight planes of the matching layers are packed as zeros), 10 240 strided queries against the f32 mode.
    NOTE: the committed results (profiles/r03_attribution_sweep.txt) were produced at commit 6f246d7, whose pair modes ran
    three activation planes [hi | lo | hi] against weights [W_hi ; W_hi ; W_lo] -- there each product has its own weight

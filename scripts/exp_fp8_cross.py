@@ -8,7 +8,7 @@ power-of-two scales per layer with sa + sb = sc + sd (one E8M0 block scale per o
 
 This script is an EMULATION in torch on the GPU (no new kernel): the expert towers of models/experts_n_est.py:243-291 with
 every layer's arithmetic spelled out the way the library does it -- BN folded (utils/tf_util.py:491-494), weights scaled by the
-packer's power of two (model.hip pack_layer), activations and weights as f16 pairs, products exact, fp32 accumulation, bias +
+packer's power of two (pack.cpp pack_layer), activations and weights as f16 pairs, products exact, fp32 accumulation, bias +
 ReLU in fp32, outputs split into pairs again -- and, for the layers of a variant, the cross terms rounded to e4m3
 (torch.float8_e4m3fn) or, for information, to a block-scaled e2m3 (FP6) with one scale per 16 channels.
 For every query of the bench's 100k cloud (calibrated gate, the library's f16x3 gate decisions) the routed expert is evaluated
@@ -130,7 +130,7 @@ class Layer:
         w = w.astype(np.float32)
         wmax = float(np.abs(w).max())
         m, e = np.frexp(wmax)
-        e = int(min(24, max(-8, 14 - e)))                  # model.hip pack_layer: wmax 2^e in [2^13, 2^14)
+        e = int(min(24, max(-8, 14 - e)))                  # pack.cpp pack_layer: wmax 2^e in [2^13, 2^14)
         self.acc_scale = float(2.0 ** -e)
         ws = torch.as_tensor(w * np.float32(2.0 ** e), device=dev)
         self.k = w.shape[0] if w.ndim == 5 else 1

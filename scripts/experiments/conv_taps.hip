@@ -205,7 +205,7 @@ __global__ __launch_bounds__(kThreads) void conv_taps_kernel(const ConvParams p)
   for (int kk = 0; kk < 4; ++kk) b[kk] = bn[kk];
   __syncthreads();
   if (p.n_chunks > 1) stage_a(1, 1);
-  // taps are enumerated dz-major over the clipped range [lo, hi]^3 (model.hip: pack_layer), so the offsets are
+  // taps are enumerated dz-major over the clipped range [lo, hi]^3 (pack.cpp: tap_list), so the offsets are
   // counted instead of being fetched from the kernel arguments per tap
   const int d_lo = p.tap[0][0], d_hi = p.tap[n_taps - 1][0];
   int c = 0, t = 0, dz = d_lo, dy = d_lo, dx = d_lo;

@@ -3,7 +3,7 @@
 ``tower_ops`` reads a tower's buffers and launches from the library (``nesti_debug_tower_ops``).  ``TowerChecker`` compares
 ONE launch, run alone by ``nesti_debug_tower_step``, with an fp64 evaluation of the same layer on the launch's own input
 buffer, decoded from the workspace.  The effective weights are emulated here from the TF tensors with the packer's VALUE rules
-(model.hip: fold_layer, pack_layer), not read back from the packed buffers, so a packing bug and a kernel bug both show up.
+(pack.cpp: fold_layer, pack_layer), not read back from the packed buffers, so a packing bug and a kernel bug both show up.
 
 Bound per output element: ``|gpu - ref| <= r_out(ref) + c 2^-24 S`` with ``S = sum |a w| + |b|`` over the products the form
 multiplies, r_out the rounding of the output format, and ``c`` one constant per (kernel family, arithmetic form) -- ``C_BOUND``,
@@ -52,7 +52,7 @@ def f16_rne(x):
 
 
 def bf16_rne(x):
-    """float32 array -> float32 values rounded to bf16 (RNE; model.hip: host_f32_to_bf16)."""
+    """float32 array -> float32 values rounded to bf16 (RNE; pack.cpp: host_f32_to_bf16)."""
     u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
     nan = (u & 0x7FFFFFFF) > 0x7F800000
     r = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) & 0xFFFF
@@ -70,7 +70,7 @@ def e2m3_grid():
 
 
 def e2m3_encode(x, inv_scale=1.0):
-    """Vectorised model.hip host_f32_to_e2m3: code of x * inv_scale (float32 product), RNE on the piecewise-uniform grid,
+    """Vectorised pack.cpp host_f32_to_e2m3: code of x * inv_scale (float32 product), RNE on the piecewise-uniform grid,
     saturating at 7.5, sign in bit 5, NaN -> 31."""
     x = np.asarray(x, np.float32)
     a = np.abs(x) * np.float32(inv_scale)
@@ -95,7 +95,7 @@ def e4m3_decode(code):
 
 def e4m3_encode(x):
     """Vectorised OCP e4m3 encoder: round to nearest even on the format's grid, saturating at 448, NaN -> 0x7f
-    (model.hip: host_f32_to_e4m3)."""
+    (pack.cpp: host_f32_to_e4m3)."""
     x = np.asarray(x, np.float64)
     pos = e4m3_decode(np.arange(0x7F))                                  # codes 0 .. 126, increasing
     a = np.minimum(np.abs(x), 448.0)
@@ -109,7 +109,7 @@ def e4m3_encode(x):
 
 # ---- the packer's value rules -----------------------------------------------------------------------------------------
 def fold(W, scope, bn):
-    """(w float32 [..., cin, cout] * scale, bias) as model.hip fold_layer + pack_layer: scale and bias in double cast to
+    """(w float32 [..., cin, cout] * scale, bias) as pack.cpp fold_layer + pack_layer: scale and bias in double cast to
     float, the weight times the scale in float."""
     w = np.asarray(W[scope + "/weights"], np.float32)
     b = np.asarray(W[scope + "/biases"], np.float32)
@@ -310,7 +310,7 @@ def e2m3_decode(code):
 
 
 def x8_activation_exponent(W, scope, bn):
-    """model.hip x8_activation_exponent: the pre-scale 2^sc of a producer's planes, from its batch norm."""
+    """pack.cpp x8_activation_exponent: the pre-scale 2^sc of a producer's planes, from its batch norm."""
     amax = np.float32(16.0)
     if bn:
         beta, gamma = np.asarray(W[scope + "/bn/beta"], np.float32), np.asarray(W[scope + "/bn/gamma"], np.float32)
@@ -322,7 +322,7 @@ def x8_activation_exponent(W, scope, bn):
 
 
 def x8_cross_weights(hi, v, in_pos, fmt):
-    """The two cross-term weight operands of model.hip pack_layer_x8 as the values the MFMA multiplies, per real input channel:
+    """The two cross-term weight operands of pack.cpp cross_rows as the values the MFMA multiplies, per real input channel:
     (B0 ~ W_hi, paired with the activations' lo; B1 ~ W_lo, paired with the activations' full value), each with its block scale
     folded in and in the units the decoded activation operands below use.  hi = f16(v), v = the pair packing's scaled weight."""
     if fmt == 8:                                          # W_hi8 = e4m3(W_hi 2^-6), W_lo8 = e4m3((v - W_hi) 2^5), block scale 2^6

@@ -212,7 +212,7 @@ def test_x8_dtypes_are_refused_where_they_do_not_apply():
 
 
 def test_e2m3_encoder_rounds_to_nearest_even_and_saturates():
-    """The host-side FP6 encoder of the weight packing (model.hip: host_f32_to_e2m3) against the format's definition: every code decodes and
+    """The host-side FP6 encoder of the weight packing (pack.cpp: host_f32_to_e2m3) against the format's definition: every code decodes and
     encodes back to itself, a value between two grid points goes to the nearer one, an exact midpoint to the even mantissa, everything
     beyond 7.5 saturates, the sign rides in bit 5, the scale divides."""
     from nesti_net_amd import _lib

@@ -158,7 +158,7 @@ def test_vectorised_encoders_match_the_library_and_the_format():
 
 def test_side_buffer_decoding():
     """layer_ref.aux_decode on side-buffer rows built by hand: e4m3 planes [lo8 64 B | hi8 64 B] per 64-channel group, and FP6 blocks --
-    32 six-bit elements packed little-endian (model.hip: pack_layer_x8's bit layout), slot 2i = lo, 2i + 1 = hi, E8M0 scale in byte 24,
+    32 six-bit elements packed little-endian (pack.cpp: cross_rows' bit layout), slot 2i = lo, 2i + 1 = hi, E8M0 scale in byte 24,
     the block's first 16 bytes where lo8 went and its second 16 where hi8 went."""
     import torch
     rng = np.random.default_rng(3)

@@ -16,7 +16,11 @@
  *     thread-local message for the last failing call on this thread;
  *   - model handles are immutable after creation (except the NESTI_F16X3C gate margin, which must not be changed while
  *     forward calls are in flight, and its device-side counters, which forward calls update atomically): concurrent
- *     forward calls on different streams are safe provided they use different workspaces.
+ *     forward calls on different streams are safe provided they use different workspaces.  In the default mode those
+ *     counters also DECIDE: the gate margin and the conditioning guard's threshold follow what a model has measured, so the
+ *     outputs of a NESTI_F16X3C / NESTI_F16X8 / NESTI_F16X8C model depend on the calls it has seen since its counters were
+ *     reset.  nesti_model_set_reproducible (below) freezes both thresholds: the counters then only measure, and a query's
+ *     outputs are a function of the weights, the thresholds, the cloud, the seed and its patch row.
  */
 #ifndef NESTI_HIP_H
 #define NESTI_HIP_H
@@ -239,6 +243,33 @@ int nesti_model_cascade_stats(const nesti_model_t* m, nesti_cascade_stats_t* out
 int nesti_model_gate_error_export(const nesti_model_t* m, float* dst_dev, void* stream);
 int nesti_model_gate_error_import(nesti_model_t* m, const float* src_dev, int n, void* stream);
 
+/* ---- REPRODUCIBLE MODE (off by default; no reference counterpart) ------------------------------------------------------------
+ * on != 0 freezes the two thresholds that otherwise follow the model's measurements:
+ *   - the two-stage gate filters with exactly tau (nothing folds max_margin_err in) and enqueues no widening pass;
+ *   - the conditioning guard re-evaluates exactly the rows with |n| in [0, thr) and enqueues no further pass (thr < 0 still
+ *     switches it off, +inf still re-evaluates everything).
+ * Everything that MEASURES keeps running -- max_margin_err, the squared-pair sums, max_dn, the counts, the _import calls -- but no
+ * decision reads a counter, so the three outputs of a query no longer depend on the batch, the stream, the lane, a captured graph
+ * or the calls that came before.  tau_eff / thr_eff of the stats structs then report tau / thr.  What the default mode would have
+ * ACTED on is counted instead, in a 64-byte device block of its own:
+ *   gate_violations   rows decided twice whose NESTI_GATE_WIDEN x error exceeds the call's tau,
+ *   guard_violations  rows re-evaluated whose NESTI_X8_GUARD_WIDEN x |dn| / sqrt(2 x NESTI_X8_GUARD_BAR) exceeds thr,
+ * and a caller that wants today's 1.5 x guarantee raises tau / thr from the reported maxima and runs the WHOLE range again
+ * (nesti-net_amd/pipeline.py: NormalEstimator.run_verified) -- each pass is then a function of (thresholds, query set).
+ * Accepted on every model (a no-op without two-stage gate and guard); the frozen path has fewer launches than the default one and
+ * stays capturable into a hipGraph (a captured graph keeps the mode and the thresholds it was captured with).  Must not be changed
+ * while forward calls are in flight.
+ * nesti_model_reproducible_stats synchronises `stream` and reads the counters; reset != 0 clears this block TOGETHER with the
+ * gate's and the guard's (nesti_model_cascade_stats / nesti_model_x8_guard_stats).  tau = 0 without a two-stage gate, thr = -1
+ * without a guard. */
+typedef struct {
+  int on;
+  uint64_t gate_violations, guard_violations, guard_dropped;
+  float max_margin_err, max_dn, tau, thr;
+} nesti_reproducible_stats_t;
+int nesti_model_set_reproducible(nesti_model_t* m, int on);
+int nesti_model_reproducible_stats(const nesti_model_t* m, nesti_reproducible_stats_t* out, int reset, void* stream);
+
 /* EXPERIMENT (pair-mode experts_n_est models, 8^3 grid, created after nesti_experiment_mix_enable(1); no reference counterpart): which of the experts' k^3 tap layers run ONE
  * 16-bit product (hi * W_hi, reading only the hi planes of their pair-layout input, writing pairs again) instead of three.
  * Bits: 0 / 1 = inception1 conv2 (3^3) / conv3 (5^3), 2 / 3 = inception2 conv2 / conv3, 4 / 5 = inception4 conv2 (2^3) / conv3 (4^3).
@@ -274,7 +305,10 @@ int nesti_model_set_x8_format(nesti_model_t* m, int bits);
  * margin: calibrate.calibrate_x8_guard), thr < 0 switches the guard off, +inf re-evaluates everything (calibration).  Must not be
  * changed while forward calls are in flight.  Because thr_eff follows what the model has measured so far, WHICH rows are re-evaluated
  * (hence the last bits of a few normals near the threshold, never the expert index) depends on the order and partition of the batches
- * a model has seen since its counters were last reset (nesti_model_x8_guard_stats with reset = 1). */
+ * a model has seen since its counters were last reset (nesti_model_x8_guard_stats with reset = 1) -- in the default mode.  With
+ * nesti_model_set_reproducible on, thr_eff IS thr: the rows re-evaluated are those with |n| < thr, whatever has been measured, and a
+ * |dn| that would have raised the threshold is counted in guard_violations (nesti_model_reproducible_stats).
+ * nesti_model_guard_error_export / _import are the twins of the gate pair above for max_dn: one tiny kernel each on `stream`. */
 #define NESTI_X8_GUARD_BAR 2.5e-6f
 #define NESTI_X8_GUARD_WIDEN 1.5f
 #ifndef NESTI_X8_GUARD_WIDEN_PASSES
@@ -290,6 +324,8 @@ typedef struct {
 } nesti_x8_guard_stats_t;
 int nesti_model_set_x8_guard(nesti_model_t* m, float thr);
 int nesti_model_x8_guard_stats(const nesti_model_t* m, nesti_x8_guard_stats_t* out, int reset, void* stream);
+int nesti_model_guard_error_export(const nesti_model_t* m, float* dst_dev, void* stream);
+int nesti_model_guard_error_import(nesti_model_t* m, const float* src_dev, int n, void* stream);
 
 /* Workspace of ONE tower for `batch` queries, from the configuration alone (no device needed): tower = -1 the gating
  * net, 0..E-1 an expert.  dtype as nesti_model_create (NESTI_F16X3C: the gate figure is the f16 filter's). */

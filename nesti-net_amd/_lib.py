@@ -40,6 +40,13 @@ class CX8GuardStats(ctypes.Structure):
                 ("max_dn", ctypes.c_float), ("thr", ctypes.c_float), ("thr_eff", ctypes.c_float)]
 
 
+class CReproducibleStats(ctypes.Structure):
+    """Mirror of ``nesti_reproducible_stats_t``."""
+    _fields_ = [("on", ctypes.c_int), ("gate_violations", ctypes.c_uint64), ("guard_violations", ctypes.c_uint64),
+                ("guard_dropped", ctypes.c_uint64), ("max_margin_err", ctypes.c_float), ("max_dn", ctypes.c_float),
+                ("tau", ctypes.c_float), ("thr", ctypes.c_float)]
+
+
 class CDebugPass(ctypes.Structure):
     """Mirror of ``nesti_debug_pass_t``."""
     _fields_ = [("fast", ctypes.c_int), ("x8_mask", ctypes.c_int), ("x8_fmt", ctypes.c_int)]
@@ -105,6 +112,10 @@ SIGNATURES = {
     "nesti_model_cascade_stats": (_i, [_vp, ctypes.POINTER(CCascadeStats), _i, _vp]),
     "nesti_model_gate_error_export": (_i, [_vp, _vp, _vp]),
     "nesti_model_gate_error_import": (_i, [_vp, _vp, _i, _vp]),
+    "nesti_model_set_reproducible": (_i, [_vp, _i]),
+    "nesti_model_reproducible_stats": (_i, [_vp, ctypes.POINTER(CReproducibleStats), _i, _vp]),
+    "nesti_model_guard_error_export": (_i, [_vp, _vp, _vp]),
+    "nesti_model_guard_error_import": (_i, [_vp, _vp, _i, _vp]),
     "nesti_experiment_mix_enable": (_i, [_i]),
     "nesti_model_set_expert_mix": (_i, [_vp, _i]),
     "nesti_model_set_gate_mix": (_i, [_vp, _i]),

@@ -52,7 +52,26 @@ GATE_MARGIN_OVER_MAX = 1.5   # ... and at least this x the largest such error se
 GATE_MARGIN_MIN_QUERIES = 256   # fewer calibration queries than this: no filtering (every query is decided by the f16x3 gate)
 
 
-def calibrate_gate_margin(net, points, n_eff, sigmas=GATE_MARGIN_SIGMAS, over_max=GATE_MARGIN_OVER_MAX, floor=1e-3):
+def reproducible_gate_margin(max_err, sample_pairs, shape_queries, n_experts, floor=1e-3, widen=GATE_MARGIN_OVER_MAX):
+    """The gate margin of the reproducible mode: a pure function of an order-independent maximum and three integers.
+
+        tau = max(floor, widen x growth x max_err),   growth = sqrt(ln(n_t) / ln(n_s)),
+        n_s = sample_pairs,   n_t = max(n_s, (E - 1) x shape_queries)
+
+    ``max_err`` is the largest error of the f16 gate on a logit difference over the ``sample_pairs`` (row, expert) pairs of the
+    calibration sample; the shape will show ``(E - 1) x shape_queries`` such pairs.  The errors are rounding noise close to
+    Gaussian (:func:`calibrate_gate_margin`), and the maximum of n Gaussian draws grows like sqrt(2 ln n), so ``growth`` scales
+    the sample's maximum to the one expected on the whole shape; ``widen`` = NESTI_GATE_WIDEN keeps the library's factor on top.
+    sigma -- a double sum of atomics whose order differs from run to run -- does not enter."""
+    import math
+    n_s = int(sample_pairs)
+    n_t = max(n_s, (int(n_experts) - 1) * int(shape_queries))
+    growth = math.sqrt(math.log(n_t) / math.log(n_s)) if n_s > 1 else 1.0
+    return max(float(floor), float(widen) * growth * float(max_err))
+
+
+def calibrate_gate_margin(net, points, n_eff, sigmas=GATE_MARGIN_SIGMAS, over_max=GATE_MARGIN_OVER_MAX, floor=1e-3,
+                          reproducible=False, shape_queries=None):
     """Set the gate margin tau of an 'f16x3c' :class:`NestiNet` (``nesti_model_set_gate_margin``) from a sample of queries
     (``points`` [B,S*P,3] / ``n_eff`` [B,S] device tensors).
 
@@ -66,7 +85,9 @@ def calibrate_gate_margin(net, points, n_eff, sigmas=GATE_MARGIN_SIGMAS, over_ma
     rows in between in the same call (include/nesti_hip.h: NESTI_GATE_WIDEN; :meth:`NestiNet.cascade_stats` reports
     ``widened`` / ``widen_events`` / ``tau_eff``).  The counters are reset here, so the threshold starts at tau.  Returns tau.
     A sample of fewer than ``GATE_MARGIN_MIN_QUERIES`` queries cannot carry a 7-sigma statement: the margin is then left at
-    infinity, which makes the mode plain f16x3 (always safe, no filter gain)."""
+    infinity, which makes the mode plain f16x3 (always safe, no filter gain).
+    ``reproducible=True``: tau = :func:`reproducible_gate_margin` of the sample's largest error, its pair count and
+    ``shape_queries`` (the number of queries the margin has to hold for; default: the sample's) -- the same bits on every run."""
     if int(points.shape[0]) < GATE_MARGIN_MIN_QUERIES:
         net.cascade_stats(reset=True)         # the counters start from zero for this shape here too (ADVICE r04)
         net.set_gate_margin(1e30)
@@ -75,7 +96,12 @@ def calibrate_gate_margin(net, points, n_eff, sigmas=GATE_MARGIN_SIGMAS, over_ma
     net.set_gate_margin(1e30)
     net.gate(net.mups(points, n_eff))
     st = net.cascade_stats(reset=True)
-    tau = max(float(sigmas) * st["sigma"], float(over_max) * st["max_margin_err"], float(floor))
+    if reproducible:
+        E = net.cfg.n_gate_out
+        tau = reproducible_gate_margin(st["max_margin_err"], st["rechecked"] * (E - 1),
+                                       st["rechecked"] if shape_queries is None else shape_queries, E, floor=floor, widen=over_max)
+    else:
+        tau = max(float(sigmas) * st["sigma"], float(over_max) * st["max_margin_err"], float(floor))
     net.set_gate_margin(tau)
     return tau
 
@@ -83,7 +109,7 @@ def calibrate_gate_margin(net, points, n_eff, sigmas=GATE_MARGIN_SIGMAS, over_ma
 X8_GUARD_MIN_QUERIES = 256
 
 
-def calibrate_x8_guard(net, points, n_eff, floor=0.05):
+def calibrate_x8_guard(net, points, n_eff, floor=0.05, reproducible=False):
     """Set the conditioning guard's threshold of an 'f16x8' / 'f16x8c' :class:`NestiNet` (``nesti_model_set_x8_guard``) from a sample
     of queries (``points`` [B,S*P,3] / ``n_eff`` [B,S] device tensors).
 
@@ -93,7 +119,9 @@ def calibrate_x8_guard(net, points, n_eff, floor=0.05):
     threshold to ``_lib.X8_GUARD_WIDEN`` x the largest |dn| seen / sqrt(2 x ``_lib.X8_GUARD_BAR``) by itself.  The threshold set here
     is that formula on the sample's largest |dn| (at least ``floor``); the counters are reset, so it starts un-widened.  A sample
     of fewer than ``X8_GUARD_MIN_QUERIES`` queries leaves the library default in place.  The gate margin of an 'f16x8c' model is
-    calibrated separately (:func:`calibrate_gate_margin`); call this one afterwards -- it runs a full forward pass.  Returns thr."""
+    calibrated separately (:func:`calibrate_gate_margin`); call this one afterwards -- it runs a full forward pass.  Returns thr.
+    The threshold is a function of a maximum, hence of the sample alone.  ``reproducible=True`` additionally requires that the
+    maximum was taken over the WHOLE sample -- no flagged row dropped, every query evaluated twice -- and raises otherwise."""
     from . import _lib
     if int(points.shape[0]) < X8_GUARD_MIN_QUERIES:
         net.x8_guard_stats(reset=True)
@@ -103,6 +131,10 @@ def calibrate_x8_guard(net, points, n_eff, floor=0.05):
     net.set_x8_guard(float("inf"))
     net.forward(points, n_eff)
     st = net.x8_guard_stats(reset=True)
+    if reproducible and (st["dropped"] != 0 or st["rechecked"] != st["queries"]):
+        raise _lib.NestiError("calibrate_x8_guard: the sample's largest |dn| is not over the whole sample (%d of %d queries evaluated "
+                              "twice, %d dropped): the threshold would depend on which rows were left out" %
+                              (st["rechecked"], st["queries"], st["dropped"]))
     thr = max(float(floor), _lib.X8_GUARD_WIDEN * st["max_dn"] / (2.0 * _lib.X8_GUARD_BAR) ** 0.5)
     net.set_x8_guard(thr)
     return thr

@@ -61,6 +61,12 @@ def build_parser():
                         "round 6 (ball sizes counted on the device, the stream replayed natively on the host from the sizes, the balls "
                         "sorted into tree order in LDS); reference_host = the same rows by scipy + numpy on the host "
                         "(nesti-net_amd/refsample.py), several times slower")
+    p.add_argument("--reproducible", type=int, default=0, choices=[0, 1],
+                   help="1: the written files are a function of the model and the cloud alone -- not of --batch_size, --lib_batch, "
+                        "the free device memory or what ran before.  The gate margin and the cross-term guard's threshold are calibrated "
+                        "without floating-point sums and frozen, every shape is checked against them after it ran and runs again as a "
+                        "whole with wider ones if the check fails (the log names the passes).  Default 0: the thresholds follow the "
+                        "measurements on the device while a shape runs, which is a little faster")
     p.add_argument("--synthetic_weights", action="store_true", help="use seeded synthetic weights if model.nstw is absent")
     return p
 
@@ -144,7 +150,10 @@ def main(argv=None):
     if (FLAGS.x8_layers is not None or FLAGS.x8_format is not None) and dtype not in ("f16x8", "f16x8c"):
         raise SystemExit("--x8_layers / --x8_format belong to --dtype f16x8 / f16x8c")
     est = NormalEstimator(cfg, W, dtype=dtype, device=device, batch=batch, n_streams=2, subsample=FLAGS.subsample,
-                          x8_layers=FLAGS.x8_layers, x8_format=FLAGS.x8_format)
+                          x8_layers=FLAGS.x8_layers, x8_format=FLAGS.x8_format, reproducible=bool(FLAGS.reproducible))
+    repro = bool(FLAGS.reproducible)
+    if repro and FLAGS.subsample != "hash":
+        raise SystemExit("--reproducible 1 needs --subsample hash")
     printout("Model restored.")
 
     for ind, name in enumerate(dataset.shape_names):
@@ -155,15 +164,24 @@ def main(argv=None):
             # printed below are this shape's
             from .calibrate import calibrate_gate_margin
             sp, sn = cloud.build(0, min(1024, cloud.patch_count))
-            printout("gate margin for %s: tau = %.4g" % (name, calibrate_gate_margin(est.net, sp, sn)))
+            printout("gate margin for %s: tau = %.4g" % (name, calibrate_gate_margin(est.net, sp, sn, reproducible=repro,
+                                                                                     shape_queries=cloud.patch_count)))
             del sp, sn
         if dtype in ("f16x8", "f16x8c"):
             # the conditioning guard of the FP6 / FP8 cross-term layers: its |n| threshold from the same sample of THIS shape
             from .calibrate import calibrate_x8_guard
             sp, sn = cloud.build(0, min(1024, cloud.patch_count))
-            printout("cross-term guard threshold for %s: |n| < %.4g" % (name, calibrate_x8_guard(est.net, sp, sn)))
+            printout("cross-term guard threshold for %s: |n| < %.4g" % (name, calibrate_x8_guard(est.net, sp, sn, reproducible=repro)))
             del sp, sn
-        normals, expert, probs = est.run(cloud)
+        if repro:
+            normals, expert, probs = est.run_verified(cloud)
+            lv, rs = est.last_verified, est.net.reproducible_stats()
+            printout("reproducible run of %s: %d pass%s, thresholds used: tau %.9g, |n| < %.9g; violations == 0: %s "
+                     "(largest gate error %.4g, largest |dn| %.3g)"
+                     % (name, lv["passes"], "" if lv["passes"] == 1 else "es", lv["tau"], lv["thr"],
+                        rs["gate_violations"] + rs["guard_violations"] == 0, lv["max_margin_err"], lv["max_dn"]))
+        else:
+            normals, expert, probs = est.run(cloud)
         torch.cuda.synchronize()
         # byte-identical to the reference's np.savetxt calls (test_n_est_w_experts.py:182-188), ~6x faster
         textio.write_f32(os.path.join(output_dir, name + ".normals"), normals.cpu().numpy())

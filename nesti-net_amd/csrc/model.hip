@@ -180,6 +180,12 @@ struct nesti_model {
   int gate_mix = 0;          // EXPERIMENT (nesti_model_set_gate_mix): the f16x3 gating passes run their tap layers single-product
   float tau = 0.25f;
   unsigned long long* cstat = nullptr;
+  // nesti_model_set_reproducible: rstat = the mode's own 64-byte counter block ([0] gate_violations, [1] guard_violations), allocated
+  // with cstat / gstat; forward calls hand it to the kernels only while the mode is on (frozen() below), and then no decision of
+  // theirs reads cstat / gstat
+  bool reproducible = false;
+  unsigned long long* rstat = nullptr;
+  unsigned long long* frozen() const { return reproducible ? rstat : nullptr; }
   ~nesti_model() {
     for (auto& p : packed) {
       if (p.second.wpk) (void)hipFree(p.second.wpk);
@@ -187,6 +193,7 @@ struct nesti_model {
     }
     if (cstat) (void)hipFree(cstat);
     if (gstat) (void)hipFree(gstat);
+    if (rstat) (void)hipFree(rstat);
     for (auto& gl : glane) {
       if (gl.gstream) (void)hipStreamDestroy(gl.gstream);
       for (auto& ev : gl.gev_done) if (ev) (void)hipEventDestroy(ev);
@@ -533,14 +540,15 @@ int gate_cascade(const nesti_model* m, const void* X0, int B, unsigned char* ws,
   if (run_tower(fast, m->graph.gate, X0, tower_ws, tower_bytes_, &logits)) return 1;
   prof_phase(NESTI_PHASE_RECHECK);
   const int cap = std::min(cascade_cap(NB), B), rounds = (B + cap - 1) / cap;
+  unsigned long long* rstat = m->frozen();   // reproducible mode: the threshold is tau itself and pass 0 is the only pass
   if (launch_gate_flag(logits, lstride, B, E, m->tau, NESTI_GATE_WIDEN, probs, expert, keep, fcounts, flag_list, cap, rounds,
-                       m->cstat, stream))
+                       m->cstat, rstat, stream))
     return 1;
   // pass 0: the rows below the call's threshold; passes 1 .. NESTI_GATE_WIDEN_PASSES: widening passes -- the band between the
   // threshold reached so far and NESTI_GATE_WIDEN x the largest error measured up to the start of the pass, so an error first
   // seen inside a widening pass is covered by the next one of the SAME call (normally every pass is empty: its launches find a
   // zero row count on the device and return; no host synchronisation, so the whole call stays graph-capturable)
-  for (int pass = 0; pass <= NESTI_GATE_WIDEN_PASSES; ++pass) {
+  for (int pass = 0; pass <= (rstat ? 0 : NESTI_GATE_WIDEN_PASSES); ++pass) {
     if (pass >= 1 && launch_gate_widen(keep, B, E, NESTI_GATE_WIDEN, fcounts, flag_list, cap, rounds, m->cstat, stream)) return 1;
     const int32_t* round_counts = fcounts + (pass == 0 ? kRoundCountsOff : kWidenRoundsOff);
     for (int r = 0; r < rounds; ++r) {
@@ -549,7 +557,7 @@ int gate_cascade(const nesti_model* m, const void* X0, int B, unsigned char* ws,
                                     pass >= 1 ? NESTI_GATE_WIDEN_WALK_GRID : r >= 1 ? 1 : 0);
       if (run_tower(exact, m->graph.gate, X0, tower_ws, tower_bytes_, &logits)) return 1;
       if (launch_gate_recheck(logits, lstride, flag_list + (size_t)r * cap, round_counts + r, cap, E, keep, probs, expert,
-                              m->cstat, stream))
+                              m->cstat, fcounts, NESTI_GATE_WIDEN, rstat, stream))
         return 1;
     }
   }
@@ -589,6 +597,7 @@ int experts_impl(const nesti_model* m, const void* X0, int B, int NB, unsigned c
   float* gslot = guard ? reinterpret_cast<float*>(ecounts + kGuardSlotOff) : nullptr;
   int32_t* gcount = guard ? ecounts + kGuardCountOff : nullptr;                 // [E]
   const float gscale = NESTI_X8_GUARD_WIDEN / sqrtf(2.f * NESTI_X8_GUARD_BAR);
+  unsigned long long* rstat = m->frozen();   // reproducible mode: the band is [0, thr) and pass 0 is the only pass
   size_t main_bytes = 0, guard_bytes = 0;
   for (int e = 0; e < E && guard; ++e) {
     main_bytes = std::max(main_bytes, align_up(tower_bytes(m->graph.experts[e], cap, m->dtype), 256));
@@ -607,9 +616,9 @@ int experts_impl(const nesti_model* m, const void* X0, int B, int NB, unsigned c
     float* out = nullptr;
     const RunCtx rc = pass_ctx(m, e, false, /*x8_mask=*/0, gcap, gcount + e, gl, st, walk_grid);   // a small walking grid (a few dozen rows)
     if (run_tower(rc, T, X0, arena, arena_bytes, &out)) return 1;
-    return launch_x8_guard_fix(out, T.bufs[T.out_buf].C, gl, gcount + e, gcap, normals, m->gstat, st);
+    return launch_x8_guard_fix(out, T.bufs[T.out_buf].C, gl, gcount + e, gcap, normals, m->gstat, m->x8_guard_thr, gscale, rstat, st);
   };
-  if (guard && launch_x8_guard_begin(0, m->x8_guard_thr, gscale, B, m->gstat, gslot, stream)) return 1;
+  if (guard && launch_x8_guard_begin(0, m->x8_guard_thr, gscale, B, m->gstat, gslot, rstat, stream)) return 1;
   for (int e = 0; e < E; ++e) {
     const Tower& T = m->graph.experts[e];
     const int ostride = T.bufs[T.out_buf].C;
@@ -648,8 +657,8 @@ int experts_impl(const nesti_model* m, const void* X0, int B, int NB, unsigned c
       glk.unlock();
     }
     prof_phase(NESTI_PHASE_GUARD);
-    for (int pass = 1; pass <= NESTI_X8_GUARD_WIDEN_PASSES; ++pass) {
-      if (launch_x8_guard_begin(pass, m->x8_guard_thr, gscale, B, m->gstat, gslot, stream)) return 1;
+    for (int pass = 1; pass <= (rstat ? 0 : NESTI_X8_GUARD_WIDEN_PASSES); ++pass) {
+      if (launch_x8_guard_begin(pass, m->x8_guard_thr, gscale, B, m->gstat, gslot, nullptr, stream)) return 1;
       for (int e = 0; e < E; ++e)
         if (guard_expert(e, stream, tower_ws, tower_bytes_, NESTI_GUARD_WIDEN_WALK_GRID)) return 1;
     }
@@ -805,6 +814,10 @@ int nesti_model_create(const nesti_config_t* cfg, const nesti_tensor_t* tensors,
     NESTI_CHECK_HIP(hipMalloc((void**)&m->cstat, 64));
     NESTI_CHECK_HIP(hipMemset(m->cstat, 0, 64));
   }
+  if (m->cstat || m->gstat) {   // the reproducible mode's own counters (nesti_model_set_reproducible)
+    NESTI_CHECK_HIP(hipMalloc((void**)&m->rstat, 64));
+    NESTI_CHECK_HIP(hipMemset(m->rstat, 0, 64));
+  }
   NESTI_CHECK_HIP(hipDeviceSynchronize());
   *out = m.release();
   return 0;
@@ -865,7 +878,7 @@ int nesti_model_x8_guard_stats(const nesti_model_t* m, nesti_x8_guard_stats_t* o
   const uint32_t bits = (uint32_t)h[2];
   memcpy(&out->max_dn, &bits, 4);
   out->thr = m->x8_guard_thr;
-  out->thr_eff = m->x8_guard_thr < 0.f ? m->x8_guard_thr
+  out->thr_eff = m->x8_guard_thr < 0.f || m->reproducible ? m->x8_guard_thr
                                        : std::max(m->x8_guard_thr, NESTI_X8_GUARD_WIDEN * out->max_dn / sqrtf(2.f * NESTI_X8_GUARD_BAR));
   return 0;
 }
@@ -896,18 +909,57 @@ int nesti_model_cascade_stats(const nesti_model_t* m, nesti_cascade_stats_t* out
   out->pairs = h[5];
   out->widened = h[6];
   out->widen_events = h[7];
-  out->tau_eff = std::max(m->tau, NESTI_GATE_WIDEN * out->max_margin_err);
+  out->tau_eff = m->reproducible ? m->tau : std::max(m->tau, NESTI_GATE_WIDEN * out->max_margin_err);
+  return 0;
+}
+
+int nesti_model_set_reproducible(nesti_model_t* m, int on) {
+  if (!m) NESTI_FAIL("nesti_model_set_reproducible: null model");
+  m->reproducible = on != 0;   // a model with neither two-stage gate nor guard has no rstat: frozen() stays null, nothing changes
+  return 0;
+}
+
+int nesti_model_reproducible_stats(const nesti_model_t* m, nesti_reproducible_stats_t* out, int reset, void* stream) {
+  if (!m || !out) NESTI_FAIL("nesti_model_reproducible_stats: null model / null argument");
+  unsigned long long r[8] = {}, c[8] = {}, g[8] = {};
+  NESTI_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
+  if (m->rstat) NESTI_CHECK_HIP(hipMemcpy(r, m->rstat, sizeof(r), hipMemcpyDeviceToHost));
+  if (m->cstat) NESTI_CHECK_HIP(hipMemcpy(c, m->cstat, sizeof(c), hipMemcpyDeviceToHost));
+  if (m->gstat) NESTI_CHECK_HIP(hipMemcpy(g, m->gstat, sizeof(g), hipMemcpyDeviceToHost));
+  if (reset) {
+    if (m->rstat) NESTI_CHECK_HIP(hipMemset(m->rstat, 0, 64));
+    if (m->cstat) NESTI_CHECK_HIP(hipMemset(m->cstat, 0, 64));
+    if (m->gstat) NESTI_CHECK_HIP(hipMemset(m->gstat, 0, 64));
+  }
+  memset(out, 0, sizeof(*out));
+  out->on = m->reproducible ? 1 : 0;
+  out->gate_violations = r[0]; out->guard_violations = r[1]; out->guard_dropped = g[3];
+  const uint32_t eb = (uint32_t)c[3], db = (uint32_t)g[2];
+  memcpy(&out->max_margin_err, &eb, 4);
+  memcpy(&out->max_dn, &db, 4);
+  out->tau = m->cascade ? m->tau : 0.f;
+  out->thr = m->gstat ? m->x8_guard_thr : -1.f;
   return 0;
 }
 
 int nesti_model_gate_error_export(const nesti_model_t* m, float* dst_dev, void* stream) {
   if (!m || !m->cascade || !dst_dev) NESTI_FAIL("nesti_model_gate_error_export: not a NESTI_F16X3C model / null argument");
-  return launch_gate_error_export(m->cstat, dst_dev, (hipStream_t)stream);
+  return launch_stat_max_export(m->cstat + 3, dst_dev, (hipStream_t)stream);
 }
 
 int nesti_model_gate_error_import(nesti_model_t* m, const float* src_dev, int n, void* stream) {
   if (!m || !m->cascade || (n > 0 && !src_dev)) NESTI_FAIL("nesti_model_gate_error_import: not a NESTI_F16X3C model / null argument");
-  return launch_gate_error_import(m->cstat, src_dev, n, (hipStream_t)stream);
+  return launch_stat_max_import(m->cstat + 3, src_dev, n, (hipStream_t)stream);
+}
+
+int nesti_model_guard_error_export(const nesti_model_t* m, float* dst_dev, void* stream) {
+  if (!m || !m->gstat || !dst_dev) NESTI_FAIL("nesti_model_guard_error_export: not an NESTI_F16X8 / NESTI_F16X8C model / null argument");
+  return launch_stat_max_export(m->gstat + 2, dst_dev, (hipStream_t)stream);
+}
+
+int nesti_model_guard_error_import(nesti_model_t* m, const float* src_dev, int n, void* stream) {
+  if (!m || !m->gstat || (n > 0 && !src_dev)) NESTI_FAIL("nesti_model_guard_error_import: not an NESTI_F16X8 / NESTI_F16X8C model / null argument");
+  return launch_stat_max_import(m->gstat + 2, src_dev, n, (hipStream_t)stream);
 }
 
 size_t nesti_tower_workspace_bytes(const nesti_config_t* cfg, int dtype, int tower, int batch) {

@@ -178,13 +178,18 @@ __global__ void gate_finish_kernel(const float* __restrict__ logits, int lstride
 // Unrechecked rows therefore keep a margin of at least NESTI_GATE_WIDEN x the largest error seen on any row decided twice up to
 // the start of the call's last widening pass.  The guarantee is per call: two calls in flight on two streams share the
 // counters, and an error one of them measures after the other's last snapshot protects the other only from its next call on.
+//
+// REPRODUCIBLE MODE (nesti_model_set_reproducible): the kernels below that take `rstat` -- the model's third 64-byte counter block,
+// [0] gate_violations, [1] guard_violations -- get a null pointer in the default mode and behave as described above.  With the
+// block, no DECISION reads a counter: the call's threshold is tau itself, no widening pass is enqueued, and a row decided twice
+// whose error would have widened the margin is counted in rstat[0] instead.  Everything that measures keeps running.
 __global__ void gate_begin_kernel(int32_t* __restrict__ fcounts, const unsigned long long* __restrict__ cstat, float tau,
-                                  float widen) {
+                                  float widen, const unsigned long long* __restrict__ rstat) {
   if (threadIdx.x != 0) return;
   fcounts[0] = 0;                                    // flag count of the filter pass
   fcounts[kWidenCountOff] = 0;                       // ... of the widening round
   const float m = __uint_as_float((unsigned)cstat[3]);
-  reinterpret_cast<float*>(fcounts)[kTauEffOff] = fmaxf(tau, widen * m);
+  reinterpret_cast<float*>(fcounts)[kTauEffOff] = rstat ? tau : fmaxf(tau, widen * m);
 }
 
 __device__ __forceinline__ float top2_margin(const float* l, int E, bool* has_nan) {
@@ -275,15 +280,16 @@ __global__ void gate_widen_end_kernel(int32_t* __restrict__ fcounts, int cap, in
   }
 }
 
-// multi-GPU: the largest error of the f16 gate as a device float, and the other ranks' values folded back in (dist.py)
-__global__ void gate_error_export_kernel(const unsigned long long* __restrict__ cstat, float* __restrict__ dst) {
-  if (threadIdx.x == 0) dst[0] = __uint_as_float((unsigned)cstat[3]);
+// multi-GPU: the largest error of the f16 gate as a device float, and the other ranks' values folded back in (dist.py); word = the
+// counter that holds the float's bits (cstat[3]: max_margin_err; gstat[2]: the conditioning guard's max_dn)
+__global__ void stat_max_export_kernel(const unsigned long long* __restrict__ word, float* __restrict__ dst) {
+  if (threadIdx.x == 0) dst[0] = __uint_as_float((unsigned)word[0]);
 }
-__global__ void gate_error_import_kernel(unsigned long long* __restrict__ cstat, const float* __restrict__ src, int n) {
+__global__ void stat_max_import_kernel(unsigned long long* __restrict__ word, const float* __restrict__ src, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float v = src[i];
-  if (v > 0.f && v < INFINITY) atomicMax(&cstat[3], (unsigned long long)__float_as_uint(v));   // NaN compares false
+  if (v > 0.f && v < INFINITY) atomicMax(word, (unsigned long long)__float_as_uint(v));   // NaN compares false
 }
 
 // rows [r * cap, r * cap + cap) of list i are one round of a tower that runs `cap` rows at a time:
@@ -298,7 +304,8 @@ __global__ void round_counts_kernel(const int32_t* __restrict__ counts, int n_li
 __global__ void gate_recheck_kernel(const float* __restrict__ logits, int lstride, const int32_t* __restrict__ flag_list,
                                     const int32_t* __restrict__ count_ptr, int cap, int E, const float* __restrict__ keep,
                                     float* __restrict__ probs, int32_t* __restrict__ expert,
-                                    unsigned long long* __restrict__ cstat) {
+                                    unsigned long long* __restrict__ cstat, const int32_t* __restrict__ fcounts, float widen,
+                                    unsigned long long* __restrict__ rstat) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= min(cap, *count_ptr)) return;
   const int b = flag_list[j];
@@ -327,6 +334,8 @@ __global__ void gate_recheck_kernel(const float* __restrict__ logits, int lstrid
     atomicMax(&cstat[3], (unsigned long long)__float_as_uint(err));
     atomicAdd(reinterpret_cast<double*>(&cstat[4]), (double)sq);
     atomicAdd(&cstat[5], (unsigned long long)(E - 1));
+    // reproducible mode: the error that would have widened the call's margin is counted, not acted on
+    if (rstat && widen * err > reinterpret_cast<const float*>(fcounts)[kTauEffOff]) atomicAdd(&rstat[0], 1ull);
   }
 }
 
@@ -423,10 +432,10 @@ int launch_gate_finish(const float* logits, int lstride, int B, int E, float* pr
 
 int launch_gate_flag(const float* logits, int lstride, int B, int E, float tau, float widen, float* probs, int32_t* expert,
                      float* keep, int32_t* fcounts, int32_t* flag_list, int cap, int n_rounds, unsigned long long* cstat,
-                     hipStream_t stream) {
+                     const unsigned long long* rstat, hipStream_t stream) {
   if (B <= 0) return 0;
   if (E > NESTI_MAX_EXPERTS || n_rounds > kMaxCascadeRounds) NESTI_FAIL("gate_flag: too many experts / rounds");
-  hipLaunchKernelGGL(gate_begin_kernel, dim3(1), dim3(64), 0, stream, fcounts, cstat, tau, widen);
+  hipLaunchKernelGGL(gate_begin_kernel, dim3(1), dim3(64), 0, stream, fcounts, cstat, tau, widen, rstat);
   hipLaunchKernelGGL(gate_flag_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, logits, lstride, B, E, probs,
                      expert, keep, fcounts, flag_list, cstat);
   hipLaunchKernelGGL(round_counts_kernel, dim3(1), dim3(64), 0, stream, fcounts, 1, cap, n_rounds, fcounts + kRoundCountsOff);
@@ -445,14 +454,14 @@ int launch_gate_widen(const float* keep, int B, int E, float widen, int32_t* fco
   return 0;
 }
 
-int launch_gate_error_export(const unsigned long long* cstat, float* dst, hipStream_t stream) {
-  hipLaunchKernelGGL(gate_error_export_kernel, dim3(1), dim3(64), 0, stream, cstat, dst);
+int launch_stat_max_export(const unsigned long long* word, float* dst, hipStream_t stream) {
+  hipLaunchKernelGGL(stat_max_export_kernel, dim3(1), dim3(64), 0, stream, word, dst);
   NESTI_CHECK_HIP(hipGetLastError());
   return 0;
 }
-int launch_gate_error_import(unsigned long long* cstat, const float* src, int n, hipStream_t stream) {
+int launch_stat_max_import(unsigned long long* word, const float* src, int n, hipStream_t stream) {
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(gate_error_import_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, cstat, src, n);
+  hipLaunchKernelGGL(stat_max_import_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, word, src, n);
   NESTI_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -465,10 +474,11 @@ int launch_round_counts(const int32_t* counts, int n_lists, int cap, int n_round
 }
 
 int launch_gate_recheck(const float* logits, int lstride, const int32_t* flag_list, const int32_t* count_ptr, int cap, int E,
-                        const float* keep, float* probs, int32_t* expert, unsigned long long* cstat, hipStream_t stream) {
+                        const float* keep, float* probs, int32_t* expert, unsigned long long* cstat, const int32_t* fcounts,
+                        float widen, unsigned long long* rstat, hipStream_t stream) {
   if (cap <= 0) return 0;
   hipLaunchKernelGGL(gate_recheck_kernel, dim3((cap + 255) / 256), dim3(256), 0, stream, logits, lstride, flag_list,
-                     count_ptr, cap, E, keep, probs, expert, cstat);
+                     count_ptr, cap, E, keep, probs, expert, cstat, fcounts, widen, rstat);
   NESTI_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -491,9 +501,12 @@ int launch_switch_finish(const float* logits, int lstride, int B, float threshol
 // threshold follows the measurement like the two-stage gate's margin does.
 //   gstat (device, per model): [0] queries, [1] rows re-evaluated, [2] largest |dn| (float bits), [3] rows dropped because a list was full
 //   slot  (device, per call):  [0] lower, [1] upper end of the current pass's |n| band (floats)
-__global__ void x8_guard_begin_kernel(int pass, float thr, float scale, int B, unsigned long long* __restrict__ gstat, float* __restrict__ slot) {
+// Reproducible mode (rstat != null, see the two-stage gate above): the band of pass 0 is [0, thr) whatever has been measured, no
+// further pass is enqueued, and a re-evaluated row whose |dn| would have raised the threshold is counted in rstat[1].
+__global__ void x8_guard_begin_kernel(int pass, float thr, float scale, int B, unsigned long long* __restrict__ gstat, float* __restrict__ slot,
+                                      const unsigned long long* __restrict__ rstat) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const float hi = fmaxf(thr, scale * __uint_as_float((unsigned)gstat[2]));      // scale = widen / theta
+  const float hi = rstat ? thr : fmaxf(thr, scale * __uint_as_float((unsigned)gstat[2]));      // scale = widen / theta
   if (pass == 0) {
     slot[0] = 0.f;
     slot[1] = hi;
@@ -521,7 +534,8 @@ __global__ void x8_guard_flag_kernel(const int32_t* __restrict__ list, const int
 // the f16x3 results of the flagged rows replace the X8 ones; |dn| is measured on the way
 __global__ void x8_guard_fix_kernel(const float* __restrict__ src, int sstride, const int32_t* __restrict__ glist,
                                     const int32_t* __restrict__ gcount, int cap, float* __restrict__ normals,
-                                    unsigned long long* __restrict__ gstat) {
+                                    unsigned long long* __restrict__ gstat, float thr, float scale,
+                                    unsigned long long* __restrict__ rstat) {
   const int n = min(cap, *gcount);
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j == 0 && n > 0) atomicAdd(&gstat[1], (unsigned long long)n);
@@ -536,10 +550,12 @@ __global__ void x8_guard_fix_kernel(const float* __restrict__ src, int sstride, 
   }
   const float dn = sqrtf(d2);
   if (dn > 0.f && dn < INFINITY) atomicMax(&gstat[2], (unsigned long long)__float_as_uint(dn));
+  if (rstat && dn < INFINITY && scale * dn > thr) atomicAdd(&rstat[1], 1ull);
 }
 
-int launch_x8_guard_begin(int pass, float thr, float scale, int B, unsigned long long* gstat, float* slot, hipStream_t stream) {
-  hipLaunchKernelGGL(x8_guard_begin_kernel, dim3(1), dim3(64), 0, stream, pass, thr, scale, B, gstat, slot);
+int launch_x8_guard_begin(int pass, float thr, float scale, int B, unsigned long long* gstat, float* slot,
+                          const unsigned long long* rstat, hipStream_t stream) {
+  hipLaunchKernelGGL(x8_guard_begin_kernel, dim3(1), dim3(64), 0, stream, pass, thr, scale, B, gstat, slot, rstat);
   NESTI_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -553,10 +569,11 @@ int launch_x8_guard_flag(const int32_t* list, const int32_t* count_ptr, int coun
   return 0;
 }
 int launch_x8_guard_fix(const float* src, int sstride, const int32_t* glist, const int32_t* gcount, int cap, float* normals,
-                        unsigned long long* gstat, hipStream_t stream) {
+                        unsigned long long* gstat, float thr, float scale, unsigned long long* rstat, hipStream_t stream) {
   if (cap <= 0) return 0;
   // a walking-size grid: the list is normally a few dozen rows; a full one is walked by the same threads
-  hipLaunchKernelGGL(x8_guard_fix_kernel, dim3((cap + 255) / 256), dim3(256), 0, stream, src, sstride, glist, gcount, cap, normals, gstat);
+  hipLaunchKernelGGL(x8_guard_fix_kernel, dim3((cap + 255) / 256), dim3(256), 0, stream, src, sstride, glist, gcount, cap, normals, gstat,
+                     thr, scale, rstat);
   NESTI_CHECK_HIP(hipGetLastError());
   return 0;
 }

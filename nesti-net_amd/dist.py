@@ -15,7 +15,13 @@ measured.  Scope of that guarantee: the imported maximum lives in t
 measurements, so (a) it lasts until the counters are reset -- ``calibrate_gate_margin`` resets them for every shape, after which
 the ranks re-converge with the next gather -- and (b) ``cascade_stats()['max_margin_err']`` of a rank reads the largest error ANY
 rank has measured since the last reset, not that rank's alone.  The export runs on the caller's current stream after
-``NormalEstimator.run`` / ``run_many`` have joined their lane streams (they end with ``main.wait_stream(lane)``)."""
+``NormalEstimator.run`` / ``run_many`` have joined their lane streams (they end with ``main.wait_stream(lane)``).
+
+Reproducible estimators (``NormalEstimator(..., reproducible=True)``): the shards run frozen and the verified loop of
+``pipeline.verified_passes`` runs over the GLOBAL maxima -- after the usual gather ONE extra ``all_reduce(MAX)`` of four floats
+[max_margin_err, max_dn, violations > 0, dropped > 0], read on the host, so every rank takes the same decision and, if needed,
+re-runs its shard with the same raised thresholds.  The result equals the one-rank ``run_verified`` of the whole shape bit for
+bit.  The extra collective exists only in that mode."""
 import torch
 import torch.distributed as dist
 
@@ -112,13 +118,28 @@ def gather_shards(normals, expert, probs, n_rows, group=None, net=None):
     return unpack_results(torch.cat(outs), gated)
 
 
+def _verified(estimator, run_once, group):
+    """``run_once`` (this rank's shards frozen + the gather) under the verified loop of a reproducible estimator."""
+    from .pipeline import verified_passes
+    if getattr(estimator, "subsample", "hash") != "hash":
+        raise ValueError("a reproducible sharded run needs subsample='hash': a second pass would draw from the shared reference stream again")
+    reduce = None
+    if dist.is_initialized() and dist.get_world_size(group) > 1:
+        def reduce(flags):
+            dist.all_reduce(flags, op=dist.ReduceOp.MAX, group=group)     # the mode's own collective: four floats
+    return verified_passes(estimator, run_once, reduce)
+
+
 def estimate_sharded(estimator, cloud, group=None):
     """Run this rank's block of ``cloud``'s patch rows and gather everyone's results."""
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     lo, hi = shard_range(cloud.patch_count, rank, world)
-    normals, expert, probs = estimator.run(cloud, lo, hi - lo)
-    return gather_shards(normals, expert, probs, cloud.patch_count, group, net=_cascade_net(estimator))
+
+    def run_once():
+        normals, expert, probs = estimator.run(cloud, lo, hi - lo)
+        return gather_shards(normals, expert, probs, cloud.patch_count, group, net=_cascade_net(estimator))
+    return _verified(estimator, run_once, group) if getattr(estimator, "reproducible", False) else run_once()
 
 
 def estimate_sharded_many(estimator, clouds, group=None):
@@ -126,6 +147,12 @@ def estimate_sharded_many(estimator, clouds, group=None):
     (``NormalEstimator.run_many``: at 8 ranks a 100k cloud leaves 12.5k rows per rank -- eight such blocks fill the gate
     and expert launches like one whole cloud does) and ONE all-gather carries every cloud's results.  Returns one
     (normals, expert, probs) triple of full-length tensors per cloud, on every rank."""
+    if getattr(estimator, "reproducible", False):
+        return _verified(estimator, lambda: _estimate_sharded_many(estimator, clouds, group), group)
+    return _estimate_sharded_many(estimator, clouds, group)
+
+
+def _estimate_sharded_many(estimator, clouds, group):
     inited = dist.is_initialized()
     world = dist.get_world_size(group) if inited else 1
     rank = dist.get_rank(group) if inited else 0

@@ -96,6 +96,7 @@ class NestiNet:
                                                    ctypes.byref(self._handle)), "nesti_model_create")
         self._keep = None
         self.cascade = dtype in CASCADE_DTYPES
+        self.reproducible = False
         self.mups_cstride = self.lib.nesti_model_mups_cstride(self._handle)
         self._ws = None
         self._ws_batch = 0
@@ -177,6 +178,41 @@ class NestiNet:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.nesti_model_gate_error_import(self._handle, _lib.ptr(src), int(src.numel()), self._stream(stream)),
                        "nesti_model_gate_error_import")
+
+    def export_guard_error(self, dst, stream=None):
+        """dtype 'f16x8' / 'f16x8c': write the conditioning guard's ``max_dn`` into the one-element f32 device tensor ``dst`` (no
+        synchronisation) -- the twin of :meth:`export_gate_error`."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.nesti_model_guard_error_export(self._handle, _lib.ptr(dst), self._stream(stream)),
+                       "nesti_model_guard_error_export")
+
+    def import_guard_error(self, src, stream=None):
+        """Raise ``max_dn`` to the largest finite value of the contiguous f32 device tensor ``src`` (the twin of
+        :meth:`import_gate_error`)."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.nesti_model_guard_error_import(self._handle, _lib.ptr(src), int(src.numel()), self._stream(stream)),
+                       "nesti_model_guard_error_import")
+
+    # -- reproducible mode (include/nesti_hip.h: nesti_model_set_reproducible) -----------------
+    def set_reproducible(self, on=True):
+        """Freeze the gate margin and the conditioning guard's threshold: forward calls filter with exactly ``tau`` and re-evaluate
+        exactly the outputs with ``|n| < thr``, run no widening pass, and COUNT what the default mode would have acted on
+        (:meth:`reproducible_stats`).  A query's outputs then do not depend on batches, streams or earlier calls.  Accepted on every
+        model; not while forward calls are in flight."""
+        _lib.check(self.lib.nesti_model_set_reproducible(self._handle, int(bool(on))), "nesti_model_set_reproducible")
+        self.reproducible = bool(on)
+
+    def reproducible_stats(self, reset=False, stream=None):
+        """Synchronises the stream.  Dict with on, gate_violations (rows decided twice with 1.5 x error > tau), guard_violations (rows
+        re-evaluated with 1.5 x |dn| / sqrt(2 x 2.5e-6) > thr), guard_dropped, max_margin_err, max_dn, tau (0 without a two-stage gate)
+        and thr (-1 without a guard).  ``reset`` clears these counters together with the gate's and the guard's."""
+        st = _lib.CReproducibleStats()
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.nesti_model_reproducible_stats(self._handle, ctypes.byref(st), int(bool(reset)), self._stream(stream)),
+                       "nesti_model_reproducible_stats")
+        return {"on": bool(st.on), "gate_violations": int(st.gate_violations), "guard_violations": int(st.guard_violations),
+                "guard_dropped": int(st.guard_dropped), "max_margin_err": float(st.max_margin_err), "max_dn": float(st.max_dn),
+                "tau": float(st.tau), "thr": float(st.thr)}
 
     # -- workspace -------------------------------------------------------------------------
     def reserve(self, batch):

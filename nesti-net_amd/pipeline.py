@@ -13,13 +13,47 @@ from .model import NestiNet
 from .provider import CloudPatches
 
 
+def verified_passes(est, run_once, reduce=None):
+    """The loop of the reproducible mode's verified run (:meth:`NormalEstimator.run_verified`; ``dist.estimate_sharded`` passes an
+    all-reduce as ``reduce``).  ``run_once()`` runs the WHOLE query set frozen; ``est.verify_flags()`` then returns the 4-float
+    tensor [max_margin_err, max_dn, violations > 0, dropped > 0] of that pass, ``reduce`` folds the other ranks' in (MAX), and
+    every rank takes the same decision from the same four numbers: done, or raise the thresholds to 1.5 x the maxima and run
+    everything again -- at most ``1 + NESTI_GATE_WIDEN_PASSES`` passes.  The maxima of a pass are taken over a set of rows fixed by
+    (thresholds, query set), so the thresholds of the next pass, and with them the result, are a function of (model, calibrated
+    tau / thr, cloud, query set).  The calibrated thresholds are restored on the way out, also on error."""
+    saved = est.verify_begin()
+    try:
+        for passes in range(1, 2 + _lib.GATE_WIDEN_PASSES):
+            res = run_once()
+            flags = est.verify_flags()
+            if reduce is not None:
+                reduce(flags)
+            err, dn, violated, dropped = (float(v) for v in flags.tolist())
+            if dropped > 0:
+                raise _lib.NestiError("reproducible run: flagged outputs did not fit the conditioning guard's lists (guard_dropped > 0): "
+                                      "the guard threshold is absurd for this shape, or the library batch too small for it")
+            if not violated > 0:
+                est.verify_record(passes, err, dn)
+                return res
+            est.verify_raise(err, dn)
+        raise _lib.NestiError("reproducible run: the measured errors still exceed the thresholds after %d passes "
+                              "(max_margin_err %.4g, max_dn %.4g)" % (passes, err, dn))
+    finally:
+        est.verify_end(saved)
+
+
 class NormalEstimator:
     """``use_graph=True`` captures the forward pass of a full batch (MuPS + gate + routing + experts,
     ~250 launches whose sizes depend only on the batch size -- expert counts are read on the device) into a
-    hipGraph once and replays it; only worthwhile for small batches where launch gaps matter."""
+    hipGraph once and replays it; only worthwhile for small batches where launch gaps matter.
+
+    ``reproducible=True`` (``nesti_model_set_reproducible``): the gate margin and the conditioning guard's threshold are frozen, so
+    ``run`` / ``run_many`` / ``estimate`` give results that do not depend on ``batch``, ``n_streams``, ``use_graph`` or on what the
+    estimator ran before; :meth:`run_verified` adds the check that the default mode performs on the device."""
 
     def __init__(self, cfg: NestiConfig, weights, dtype="bf16", device="cuda:0", batch=4096, seed=3627473,
-                 use_graph=False, n_streams=1, gate_margin=None, subsample="hash", x8_layers=None, x8_format=None):
+                 use_graph=False, n_streams=1, gate_margin=None, subsample="hash", x8_layers=None, x8_format=None,
+                 reproducible=False):
         self.cfg, self.device, self.batch, self.seed = cfg, torch.device(device), int(batch), seed
         # subsample='reference': balls larger than P are thinned exactly like the reference does (scipy cKDTree traversal
         # order + ONE numpy RandomState stream over all patches in visiting order, utils/pcpnet_dataset.py:304-321), on the
@@ -54,6 +88,11 @@ class NormalEstimator:
             self.net.set_x8_layers(x8_layers)
         if x8_format is not None:                         # ... and in which format (NestiNet.set_x8_format: 6 = block-scaled e2m3, the default; 8 = e4m3)
             self.net.set_x8_format(x8_format)
+        self.reproducible = bool(reproducible)
+        self._has_guard = dtype in ("f16x8", "f16x8c")
+        self.last_verified = None
+        if self.reproducible:
+            self.net.set_reproducible(True)
         S, P, E = cfg.n_scales, cfg.num_point, max(1, cfg.n_gate_out)
         self._graph = None
         if self._fused:
@@ -164,6 +203,70 @@ class NormalEstimator:
         if single_tower:
             return normals, None, None
         return normals, expert, probs
+
+    # -- reproducible mode -------------------------------------------------------------------
+    def run_verified(self, cloud, first=0, count=None, out=None):
+        """:meth:`run` with the 1.5 x guarantee of the default mode, as a pure function of (model, calibrated tau / thr, cloud, query
+        set).  SYNCHRONISES the device after every pass (it reads the counters on the host).  The range runs frozen; if a row decided
+        twice shows 1.5 x its error above a threshold, tau <- max(tau, 1.5 x max_margin_err) and thr <- max(thr, 1.5 x max_dn /
+        sqrt(2 x 2.5e-6)) and the WHOLE range runs again, at most ``1 + _lib.GATE_WIDEN_PASSES`` passes (then ``NestiError``, as for
+        ``guard_dropped > 0``).  The calibrated thresholds are back in place afterwards; ``self.last_verified`` = {passes, tau, thr,
+        max_margin_err, max_dn} of the pass whose results are returned.  Resets the model's counters.  Two calls over two halves of
+        a range need not equal one call over the whole: the query sets differ."""
+        if not self.reproducible:
+            raise ValueError("run_verified belongs to NormalEstimator(..., reproducible=True)")
+        if self.subsample != "hash":
+            raise ValueError("run_verified needs subsample='hash': a second pass would draw from the shared reference stream again")
+        return verified_passes(self, lambda: self.run(cloud, first, count, out))
+
+    def _set_thresholds(self, tau, thr):
+        if self.net.cascade:
+            self.net.set_gate_margin(tau)
+        if self._has_guard:
+            self.net.set_x8_guard(thr)
+        self._graph = None          # a captured forward pass carries the thresholds it was captured with
+
+    def verify_begin(self):
+        """Remember (tau, thr) and reset the three counter blocks (synchronises)."""
+        torch.cuda.synchronize(self.device)
+        st = self.net.reproducible_stats(reset=True)
+        self._verify_thr = (st["tau"], st["thr"])
+        return self._verify_thr
+
+    def verify_flags(self):
+        """[max_margin_err, max_dn, violations > 0, dropped > 0] of everything run since the last reset, as a 4-float device tensor --
+        the first two written by the export kernels (synchronises; the counters stay, so the stats of the last pass can be read)."""
+        t = torch.zeros(4, dtype=torch.float32, device=self.device)
+        if self.net.cascade:
+            self.net.export_gate_error(t[0:1])
+        if self._has_guard:
+            self.net.export_guard_error(t[1:2])
+        torch.cuda.synchronize(self.device)
+        st = self.net.reproducible_stats()
+        t[2] = float(st["gate_violations"] + st["guard_violations"] > 0)
+        t[3] = float(st["guard_dropped"] > 0)
+        return t
+
+    def verify_raise(self, max_margin_err, max_dn):
+        """The thresholds of the next pass, in the device's own float32 arithmetic (the violation tests compare 1.5f x err with tau
+        and 1.5f / sqrtf(2 x bar) x dn with thr: the same products here, so the row that caused a pass cannot cause the next)."""
+        f = np.float32
+        tau, thr = self._verify_thr
+        tau = max(f(tau), f(_lib.GATE_WIDEN) * f(max_margin_err))
+        if self._has_guard and thr >= 0.0:
+            scale = f(_lib.X8_GUARD_WIDEN) / np.sqrt(f(2.0) * f(_lib.X8_GUARD_BAR))
+            thr = max(f(thr), scale * f(max_dn))
+        self._verify_thr = (float(tau), float(thr))
+        self._set_thresholds(*self._verify_thr)
+        self.net.reproducible_stats(reset=True)
+
+    def verify_record(self, passes, max_margin_err, max_dn):
+        self.last_verified = {"passes": passes, "tau": self._verify_thr[0], "thr": self._verify_thr[1],
+                              "max_margin_err": max_margin_err, "max_dn": max_dn}
+
+    def verify_end(self, saved):
+        torch.cuda.synchronize(self.device)
+        self._set_thresholds(*saved)
 
     def _prefetch(self, spans, make, consume):
         """Producer / consumer over ``spans`` with two buffers in flight: ``make(i, span)`` runs in ONE worker thread, span after

@@ -154,6 +154,21 @@ int nesti_patches_query(const nesti_config_t* cfg, const float* cloud_dev, int N
                         int32_t* n_eff_out_dev, int32_t* nbr_idx_out_dev,
                         int32_t* n_ball_out_dev, const void* grid_ws_dev,
                         size_t grid_ws_bytes, void* stream);
+/* Step 2 for query POSITIONS: generalises utils/pcpnet_dataset.py:304, where the reference hands cKDTree.query_ball_point the
+ * cloud point pts[center_point_ind] although the tree answers for any position.  Like nesti_patches_query with
+ * query_xyz_dev [M,3] f32 (device) in place of query_idx_dev: query i's centre is query_xyz_dev[i], which need not be a cloud
+ * point, may lie outside the cloud's bounding box and may be non-finite (its balls are then empty).  Everything else is
+ * unchanged: the fp64 ball test, the f32 (p - c) / r, the subsample key hash(seed, query_row0 + i, scale, index) -- the patch
+ * ROW, not the position, so results do not depend on batching -- and the key order.  query_row0 >= 0 is only that row.
+ * EMPTY BALLS (the library's convention; the reference divides by zero there): a scale whose ball is empty has n_eff = 0
+ * and all-zero patch rows, and contributes zero MuPS channels (as nesti_mups_forward writes for n_eff = 0); a query whose
+ * balls are empty at EVERY scale has no neighbourhood, see nesti_mask_empty_queries. */
+int nesti_patches_query_at(const nesti_config_t* cfg, const float* cloud_dev, int N,
+                           const float* query_xyz_dev, int M, const double* r_abs,
+                           uint64_t seed, int query_row0, float* points_out_dev,
+                           int32_t* n_eff_out_dev, int32_t* nbr_idx_out_dev,
+                           int32_t* n_ball_out_dev, const void* grid_ws_dev,
+                           size_t grid_ws_bytes, void* stream);
 /* Steps 1 + 2 in one call. */
 int nesti_patches_build(const nesti_config_t* cfg, const float* cloud_dev, int N,
                         const int32_t* query_idx_dev, int M, const double* r_abs,
@@ -390,6 +405,23 @@ int nesti_estimate_normals(const nesti_model_t* m, const float* cloud_dev, int N
                            float* normals_out_dev, int32_t* expert_out_dev, float* probs_out_dev,
                            void* stream);
 
+/* nesti_estimate_normals for query POSITIONS (generalises utils/pcpnet_dataset.py:304: the ball query's centre is any
+ * position, see nesti_patches_query_at): query_xyz_dev [M,3] f32 in place of query_idx_dev; query_row0 >= 0 is the patch row of
+ * the first query (the subsample key).  Both Gaussian grids.  n_ball_out_dev (optional) [M,S] int32: the uncapped ball sizes.
+ * Rows without a neighbourhood carry the sentinel of nesti_mask_empty_queries on return. */
+int nesti_estimate_normals_at(const nesti_model_t* m, const float* cloud_dev, int N,
+                              const float* query_xyz_dev, int M, const double* r_abs, uint64_t seed,
+                              int query_row0, int batch, int build_grid, void* grid_ws_dev,
+                              size_t grid_ws_bytes, void* ws_dev, size_t ws_bytes,
+                              float* normals_out_dev, int32_t* expert_out_dev, float* probs_out_dev,
+                              int32_t* n_ball_out_dev, void* stream);
+/* The sentinel alone, for callers of the unfused path (nesti_patches_query_at -> nesti_forward; the reference has no such
+ * rows: utils/pcpnet_dataset.py:304 always finds the centre itself): every row i of [0, M) whose n_eff_dev[i, 0..S) is 0 at
+ * every scale gets normal (0, 0, 0), expert -1 and probabilities 0 (E columns); other rows are untouched.  expert_dev and
+ * probs_dev may be NULL.  Enqueue it after everything that writes the rows (nesti_forward ends ordered on its stream). */
+int nesti_mask_empty_queries(const int32_t* n_eff_dev, int M, int S, float* normals_dev, int32_t* expert_dev,
+                             float* probs_dev, int E, void* stream);
+
 /* Several shapes in flight (BASELINE config 4; also every rank of a multi-GPU job, which holds a block of rows of
  * every shape): the queries of all items are processed as ONE stream of `batch`-sized batches, so small shapes / small
  * shards share the gate and expert launches instead of each paying for its own partially filled rounds.  Item i
@@ -409,6 +441,23 @@ typedef struct {
 int nesti_estimate_normals_multi(const nesti_model_t* m, const nesti_shape_queries_t* items, int n_items, int batch,
                                  void* ws_dev, size_t ws_bytes, float* normals_out_dev, int32_t* expert_out_dev,
                                  float* probs_out_dev, void* stream);
+
+/* nesti_estimate_normals_multi for query POSITIONS (generalises utils/pcpnet_dataset.py:304, see nesti_patches_query_at): what
+ * sharded and multi-shape runs call.  Rows without a neighbourhood carry the sentinel of nesti_mask_empty_queries. */
+typedef struct {
+  const float* cloud_dev;        /* [n_points, 3] f32 */
+  int n_points;
+  const float* query_xyz_dev;    /* [n_queries, 3] f32 */
+  int n_queries;
+  double r_abs[NESTI_MAX_SCALES];
+  uint64_t seed;
+  int query_row0;                /* patch row of the item's first query: the subsample key */
+  const void* grid_ws_dev;       /* from nesti_patches_grid on this shape */
+  size_t grid_ws_bytes;
+} nesti_shape_positions_t;
+int nesti_estimate_normals_multi_at(const nesti_model_t* m, const nesti_shape_positions_t* items, int n_items, int batch,
+                                    void* ws_dev, size_t ws_bytes, float* normals_out_dev, int32_t* expert_out_dev,
+                                    float* probs_out_dev, void* stream);
 
 /* ---- the reference's own subsample stream, replayed on the host (refreplay.cpp) ----------
  * utils/pcpnet_dataset.py:237-240, 320-321: ONE numpy RandomState(seed) shared by every patch and scale of every shape, one

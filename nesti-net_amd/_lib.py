@@ -26,6 +26,14 @@ class CShapeQueries(ctypes.Structure):
                 ("grid_ws_dev", ctypes.c_void_p), ("grid_ws_bytes", ctypes.c_size_t)]
 
 
+class CShapePositions(ctypes.Structure):
+    """Mirror of ``nesti_shape_positions_t``."""
+    _fields_ = [("cloud_dev", ctypes.c_void_p), ("n_points", ctypes.c_int),
+                ("query_xyz_dev", ctypes.c_void_p), ("n_queries", ctypes.c_int),
+                ("r_abs", ctypes.c_double * 4), ("seed", ctypes.c_uint64), ("query_row0", ctypes.c_int),
+                ("grid_ws_dev", ctypes.c_void_p), ("grid_ws_bytes", ctypes.c_size_t)]
+
+
 class CCascadeStats(ctypes.Structure):
     """Mirror of ``nesti_cascade_stats_t``."""
     _fields_ = [("queries", ctypes.c_uint64), ("rechecked", ctypes.c_uint64), ("changed", ctypes.c_uint64),
@@ -99,6 +107,8 @@ SIGNATURES = {
     "nesti_patches_grid": (_i, [_cfgp, _vp, _i, ctypes.POINTER(ctypes.c_double), _vp, _sz, _vp]),
     "nesti_patches_query": (_i, [_cfgp, _vp, _i, _vp, _i, ctypes.POINTER(ctypes.c_double), _u64, _i,
                                  _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "nesti_patches_query_at": (_i, [_cfgp, _vp, _i, _vp, _i, ctypes.POINTER(ctypes.c_double), _u64, _i,
+                                    _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "nesti_patches_build": (_i, [_cfgp, _vp, _i, _vp, _i, ctypes.POINTER(ctypes.c_double), _u64, _i,
                                  _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "nesti_patches_count": (_i, [_cfgp, _vp, _i, _vp, _i, ctypes.POINTER(ctypes.c_double), _i, _vp, _vp, _sz, _vp]),
@@ -135,6 +145,10 @@ SIGNATURES = {
     "nesti_estimate_workspace_bytes_for_config": (_sz, [_cfgp, _i, _i]),
     "nesti_estimate_normals": (_i, [_vp, _vp, _i, _vp, _i, ctypes.POINTER(ctypes.c_double), _u64, _i, _i, _i, _vp, _sz,
                                     _vp, _sz, _vp, _vp, _vp, _vp]),
+    "nesti_estimate_normals_at": (_i, [_vp, _vp, _i, _vp, _i, ctypes.POINTER(ctypes.c_double), _u64, _i, _i, _i, _vp, _sz,
+                                       _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "nesti_mask_empty_queries": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "nesti_estimate_normals_multi_at": (_i, [_vp, ctypes.POINTER(CShapePositions), _i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
     "nesti_crc32c": (ctypes.c_uint32, [_vp, _sz, ctypes.c_uint32]),
     "nesti_f32_to_e2m3": (_i, [ctypes.c_float, ctypes.c_float]),
     "nesti_debug_tower_ops": (_i, [_cfgp, _i, _i, _i, ctypes.POINTER(CDebugPass), ctypes.POINTER(CDebugBuf), _i, ctypes.POINTER(_i),

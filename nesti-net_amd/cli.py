@@ -1,6 +1,6 @@
 """Command-line drop-in for the reference's ``test_n_est_w_experts.py``: same flags
 (``:19-29``), same inputs (``<dataset_path>/<testset>`` shape list, ``<shape>.xyz``, optional
-``<shape>.pidx``) and same outputs (``<results_path>/<dataset_name>_results/<shape>.normals``,
+``<shape>.pidx``; ``--query_positions 1``: ``<shape>.qxyz``, the positions to estimate at) and same outputs (``<results_path>/<dataset_name>_results/<shape>.normals``,
 ``.experts``, ``.experts_probs`` written with ``np.savetxt`` like ``:182-188``, plus ``log.txt``).
 
 The trained-model directory holds either ``model.nstw`` (variables + hyper-parameters, see
@@ -67,6 +67,11 @@ def build_parser():
                         "without floating-point sums and frozen, every shape is checked against them after it ran and runs again as a "
                         "whole with wider ones if the check fails (the log names the passes).  Default 0: the thresholds follow the "
                         "measurements on the device while a shape runs, which is a little faster")
+    p.add_argument("--query_positions", type=int, default=0, choices=[0, 1],
+                   help="1: estimate at the positions listed in <shape>.qxyz (M rows of x y z, read like .xyz) instead of at the cloud's "
+                        "own points; neighbourhoods and radii still come from <shape>.xyz.  The three output files then have M rows; a "
+                        "position with no cloud point inside any of its balls is written as normal 0 0 0, expert -1, probabilities 0.  "
+                        "Mutually exclusive with --sparse_patches 1; needs --subsample hash")
     p.add_argument("--synthetic_weights", action="store_true", help="use seeded synthetic weights if model.nstw is absent")
     return p
 
@@ -90,7 +95,12 @@ def fit_batch(cfg, dtype, batch, device, lanes=2, reserve=2 << 30):
 
 
 def main(argv=None):
-    FLAGS = build_parser().parse_args(argv)
+    parser = build_parser()
+    FLAGS = parser.parse_args(argv)
+    if FLAGS.query_positions and FLAGS.sparse_patches:
+        parser.error("--query_positions 1 and --sparse_patches 1 are mutually exclusive: the queries are positions or cloud points")
+    if FLAGS.query_positions and FLAGS.subsample != "hash":
+        parser.error("--query_positions 1 needs --subsample hash: the reference's subsample order is defined for cloud points only")
     archs = {"experts_n_est": ARCH_EXPERTS, "ss_norm_est": ARCH_SINGLE, "ms_norm_est": ARCH_MULTI,
              "ms_sw_n_est": ARCH_SWITCH}      # test_n_est_w_experts.py / test_n_est.py / test_n_est_w_switching.py
     if FLAGS.model not in archs:
@@ -135,7 +145,7 @@ def main(argv=None):
     if dtype in ("f16x8", "f16x8c") and cfg.n_gaussians != 8:
         raise SystemExit("--dtype %s needs the 8^3 Gaussian grid; use f16x3c" % dtype)
     dataset = PointcloudPatchDataset(pc_path, FLAGS.testset, cfg, seed=3627473, sparse_patches=FLAGS.sparse_patches,
-                                     device=device)
+                                     device=device, query_positions=bool(FLAGS.query_positions))
     # two library batches in flight on two HIP streams; a batch is half the largest shape (rounded up to 256 rows) unless
     # that exceeds what the workspace of the dtype allows (~2 MB per query in f16x3c, twice that in the full pair modes)
     lib_batch = FLAGS.lib_batch or {"f16x3c": 50000, "f16x8c": 50000, "f16": 50000, "bf16": 50000, "f32": 8192}.get(dtype, 25000)
@@ -183,6 +193,11 @@ def main(argv=None):
         else:
             normals, expert, probs = est.run(cloud)
         torch.cuda.synchronize()
+        if FLAGS.query_positions:
+            # the sentinel (pool.hip: mask_empty_queries_kernel): expert -1; the single-tower models have only the (0, 0, 0) normal
+            alone = (expert == -1) if expert is not None else (normals == 0).all(dim=1)
+            printout("query positions of %s: %d, of which %d had no neighbourhood (no cloud point inside any ball: written as 0 0 0 / -1 / 0)"
+                     % (name, cloud.patch_count, int(alone.sum().item())))
         # byte-identical to the reference's np.savetxt calls (test_n_est_w_experts.py:182-188), ~6x faster
         textio.write_f32(os.path.join(output_dir, name + ".normals"), normals.cpu().numpy())
         printout("saved normals for " + name)

@@ -240,6 +240,9 @@ int launch_x8_guard_flag(const int32_t* list, const int32_t* count_ptr, int coun
                          int32_t* glist, int32_t* gcount, int cap, unsigned long long* gstat, hipStream_t stream);
 int launch_x8_guard_fix(const float* src, int sstride, const int32_t* glist, const int32_t* gcount, int cap, float* normals,
                         unsigned long long* gstat, float thr, float scale, unsigned long long* rstat, hipStream_t stream);
+// position queries: rows whose n_eff is 0 at every scale get the sentinel normal (0,0,0), expert -1, probs 0 (expert / probs may be NULL)
+int launch_mask_empty_queries(const int32_t* n_eff, int M, int S, float* normals, int32_t* expert, float* probs, int E,
+                              hipStream_t stream);
 // build routing lists from a caller-supplied expert assignment
 int launch_route(const int32_t* expert, int B, int E, int32_t* counts, int32_t* lists,
                  hipStream_t stream);

@@ -1087,23 +1087,28 @@ size_t nesti_estimate_workspace_bytes_for_config(const nesti_config_t* cfg, int 
   return nesti_estimate_workspace_bytes(&shell, batch);
 }
 
-int nesti_estimate_normals(const nesti_model_t* m, const float* cloud_dev, int N, const int32_t* query_idx_dev, int M,
-                           const double* r_abs, uint64_t seed, int query_row0, int batch, int build_grid,
-                           void* grid_ws_dev, size_t grid_ws_bytes, void* ws_dev, size_t ws_bytes,
-                           float* normals_out_dev, int32_t* expert_out_dev, float* probs_out_dev, void* stream) {
+// nesti_estimate_normals (centres = cloud points) and nesti_estimate_normals_at (centres = positions, `at`): one body.  The
+// position form also applies the sentinel of queries without a neighbourhood, after each batch's outputs are complete
+// (forward_tail ends with the conditioning guard joined on `st`), and can hand out the uncapped ball sizes.
+static int estimate_impl(const char* who, bool at, const nesti_model_t* m, const float* cloud_dev, int N, const int32_t* query_idx_dev,
+                         const float* query_xyz_dev, int M, const double* r_abs, uint64_t seed, int query_row0, int batch,
+                         int build_grid, void* grid_ws_dev, size_t grid_ws_bytes, void* ws_dev, size_t ws_bytes, float* normals_out_dev,
+                         int32_t* expert_out_dev, float* probs_out_dev, int32_t* n_ball_out_dev, void* stream) {
+  const std::string w(who);
   if (M <= 0) return 0;   // no queries: nothing to do
-  if (!m || !cloud_dev || !r_abs || !grid_ws_dev || !ws_dev || !normals_out_dev)
-    NESTI_FAIL("nesti_estimate_normals: null argument");
-  if (N <= 0) NESTI_FAIL("nesti_estimate_normals: empty cloud");
-  if (batch <= 0) NESTI_FAIL("nesti_estimate_normals: batch must be positive");
-  if (query_row0 < 0 || (!query_idx_dev && (long long)query_row0 + M > (long long)N))
-    NESTI_FAIL("nesti_estimate_normals: query rows [query_row0, query_row0 + M) exceed the cloud (N points)");
+  if (!m || !cloud_dev || !r_abs || !grid_ws_dev || !ws_dev || !normals_out_dev) NESTI_FAIL(w + ": null argument");
+  if (at && !query_xyz_dev) NESTI_FAIL(w + ": null query_xyz_dev");
+  if (N <= 0) NESTI_FAIL(w + ": empty cloud");
+  if (batch <= 0) NESTI_FAIL(w + ": batch must be positive");
+  if (at && query_row0 < 0) NESTI_FAIL(w + ": query_row0 must be >= 0");
+  if (!at && (query_row0 < 0 || (!query_idx_dev && (long long)query_row0 + M > (long long)N)))
+    NESTI_FAIL(w + ": query rows [query_row0, query_row0 + M) exceed the cloud (N points)");
   if (nesti_estimate_workspace_bytes(m, batch) > ws_bytes)
-    NESTI_FAIL("nesti_estimate_normals: workspace too small (see nesti_estimate_workspace_bytes)");
-  if (grid_ws_bytes < nesti_patches_workspace_bytes(N)) NESTI_FAIL("nesti_estimate_normals: grid workspace too small");
+    NESTI_FAIL(w + ": workspace too small (see nesti_estimate_workspace_bytes)");
+  if (grid_ws_bytes < nesti_patches_workspace_bytes(N)) NESTI_FAIL(w + ": grid workspace too small");
   const nesti_config_t* cfg = &m->graph.cfg;
   for (int s = 0; s < cfg->n_scales; ++s)
-    if (!(r_abs[s] > 0.0)) NESTI_FAIL("nesti_estimate_normals: radii must be positive");
+    if (!(r_abs[s] > 0.0)) NESTI_FAIL(w + ": radii must be positive");
   hipStream_t st = (hipStream_t)stream;
   unsigned char* ws = (unsigned char*)ws_dev;
   float* points = (float*)ws;
@@ -1112,26 +1117,140 @@ int nesti_estimate_normals(const nesti_model_t* m, const float* cloud_dev, int N
   const WsLayout L = ws_layout(m, batch);
   if (build_grid && nesti_patches_grid(cfg, cloud_dev, N, r_abs, grid_ws_dev, grid_ws_bytes, stream)) return 1;
   const int E = m->graph.cfg.arch == NESTI_ARCH_SWITCH ? 1 : m->graph.cfg.n_experts;   // columns of probs_out
+  const int S = cfg->n_scales;
   const bool fused = cfg->grid_n == 8;
   for (int done = 0; done < M; done += batch) {
     const int take = std::min(batch, M - done);
     const int32_t* qidx = query_idx_dev ? query_idx_dev + done : nullptr;
+    const float* qxyz = at ? query_xyz_dev + (size_t)done * 3 : nullptr;
+    int32_t* b_out = n_ball_out_dev ? n_ball_out_dev + (size_t)done * S : nullptr;
     float* n_out = normals_out_dev + (size_t)done * 3;
     int32_t* e_out = expert_out_dev ? expert_out_dev + done : nullptr;
     float* p_out = probs_out_dev ? probs_out_dev + (size_t)done * E : nullptr;
     if (fused) {
       const int tok = prof_begin(NESTI_PROF_MUPS, st);
-      const int rcf = launch_patches_mups(cfg, cloud_dev, N, qidx, take, r_abs, seed, query_row0 + done, grid_ws_dev,
-                                          fwd_ws + L.x0, m->dtype, mups_stride(m), n_eff, st);
+      const int rcf = launch_patches_mups(cfg, cloud_dev, N, qidx, qxyz, take, r_abs, seed, query_row0 + done, grid_ws_dev,
+                                          fwd_ws + L.x0, m->dtype, mups_stride(m), n_eff, b_out, st);
       prof_end(NESTI_PROF_MUPS, tok, st);
       if (rcf) return 1;
       if (forward_tail(m, fwd_ws + L.x0, take, batch, fwd_ws, L, n_out, e_out, p_out, st)) return 1;
     } else {
-      if (nesti_patches_query(cfg, cloud_dev, N, qidx, take, r_abs, seed, query_row0 + done, points, n_eff, nullptr, nullptr,
-                              grid_ws_dev, grid_ws_bytes, stream))
+      if (at ? nesti_patches_query_at(cfg, cloud_dev, N, qxyz, take, r_abs, seed, query_row0 + done, points, n_eff, nullptr, b_out,
+                                      grid_ws_dev, grid_ws_bytes, stream)
+             : nesti_patches_query(cfg, cloud_dev, N, qidx, take, r_abs, seed, query_row0 + done, points, n_eff, nullptr, nullptr,
+                                   grid_ws_dev, grid_ws_bytes, stream))
         return 1;
       if (nesti_forward(m, points, n_eff, take, fwd_ws, L.total, n_out, e_out, p_out, stream)) return 1;
     }
+    if (at && launch_mask_empty_queries(n_eff, take, S, n_out, e_out, p_out, E, st)) return 1;
+  }
+  return 0;
+}
+
+int nesti_estimate_normals(const nesti_model_t* m, const float* cloud_dev, int N, const int32_t* query_idx_dev, int M,
+                           const double* r_abs, uint64_t seed, int query_row0, int batch, int build_grid,
+                           void* grid_ws_dev, size_t grid_ws_bytes, void* ws_dev, size_t ws_bytes,
+                           float* normals_out_dev, int32_t* expert_out_dev, float* probs_out_dev, void* stream) {
+  return estimate_impl("nesti_estimate_normals", false, m, cloud_dev, N, query_idx_dev, nullptr, M, r_abs, seed, query_row0, batch,
+                       build_grid, grid_ws_dev, grid_ws_bytes, ws_dev, ws_bytes, normals_out_dev, expert_out_dev, probs_out_dev,
+                       nullptr, stream);
+}
+
+int nesti_estimate_normals_at(const nesti_model_t* m, const float* cloud_dev, int N, const float* query_xyz_dev, int M,
+                              const double* r_abs, uint64_t seed, int query_row0, int batch, int build_grid,
+                              void* grid_ws_dev, size_t grid_ws_bytes, void* ws_dev, size_t ws_bytes,
+                              float* normals_out_dev, int32_t* expert_out_dev, float* probs_out_dev, int32_t* n_ball_out_dev,
+                              void* stream) {
+  return estimate_impl("nesti_estimate_normals_at", true, m, cloud_dev, N, nullptr, query_xyz_dev, M, r_abs, seed, query_row0, batch,
+                       build_grid, grid_ws_dev, grid_ws_bytes, ws_dev, ws_bytes, normals_out_dev, expert_out_dev, probs_out_dev,
+                       n_ball_out_dev, stream);
+}
+
+int nesti_mask_empty_queries(const int32_t* n_eff_dev, int M, int S, float* normals_dev, int32_t* expert_dev, float* probs_dev, int E,
+                             void* stream) {
+  if (M <= 0) return 0;   // no rows: nothing to do
+  if (!n_eff_dev || !normals_dev) NESTI_FAIL("nesti_mask_empty_queries: null argument");
+  if (S < 1 || S > NESTI_MAX_SCALES) NESTI_FAIL("nesti_mask_empty_queries: bad n_scales");
+  if (probs_dev && E < 1) NESTI_FAIL("nesti_mask_empty_queries: probs_dev needs E >= 1 columns");
+  return launch_mask_empty_queries(n_eff_dev, M, S, normals_dev, expert_dev, probs_dev, E, (hipStream_t)stream);
+}
+
+// one item of nesti_estimate_normals_multi / _multi_at
+struct EstItem {
+  const float* cloud_dev;
+  int n_points;
+  const int32_t* query_idx_dev;
+  const float* query_xyz_dev;
+  int n_queries;
+  const double* r_abs;
+  uint64_t seed;
+  int query_row0;
+  const void* grid_ws_dev;
+  size_t grid_ws_bytes;
+};
+
+static int estimate_multi_impl(const char* who, bool at, const nesti_model_t* m, const std::vector<EstItem>& items, int batch,
+                               void* ws_dev, size_t ws_bytes, float* normals_out_dev, int32_t* expert_out_dev, float* probs_out_dev,
+                               void* stream) {
+  const std::string w(who);
+  const int n_items = (int)items.size();
+  if (!m || !ws_dev || !normals_out_dev) NESTI_FAIL(w + ": null argument");
+  if (batch <= 0) NESTI_FAIL(w + ": batch must be positive");
+  const nesti_config_t* cfg = &m->graph.cfg;
+  if (cfg->grid_n != 8) NESTI_FAIL(w + ": the 8^3 Gaussian grid only (use nesti_estimate_normals per shape)");
+  if (nesti_estimate_workspace_bytes(m, batch) > ws_bytes)
+    NESTI_FAIL(w + ": workspace too small (see nesti_estimate_workspace_bytes)");
+  long long total = 0;
+  for (int i = 0; i < n_items; ++i) {
+    const EstItem& it = items[i];
+    if (it.n_queries < 0 || (it.n_queries > 0 && (!it.cloud_dev || !it.grid_ws_dev || it.n_points <= 0)))
+      NESTI_FAIL(w + ": bad item");
+    if (at && it.n_queries > 0 && !it.query_xyz_dev) NESTI_FAIL(w + ": null query_xyz_dev in an item");
+    if (at && it.query_row0 < 0) NESTI_FAIL(w + ": query_row0 of an item must be >= 0");
+    if (!at && (it.query_row0 < 0 || (!it.query_idx_dev && (long long)it.query_row0 + it.n_queries > (long long)it.n_points)))
+      NESTI_FAIL(w + ": query rows of an item exceed its cloud");
+    if (it.n_queries > 0 && it.grid_ws_bytes < nesti_patches_workspace_bytes(it.n_points))
+      NESTI_FAIL(w + ": grid workspace of an item too small");
+    for (int s = 0; s < cfg->n_scales; ++s)
+      if (it.n_queries > 0 && !(it.r_abs[s] > 0.0)) NESTI_FAIL(w + ": radii must be positive");
+    total += it.n_queries;
+  }
+  if (total == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  int32_t* n_eff = (int32_t*)((unsigned char*)ws_dev + est_points_bytes(m, batch));   // [batch, S]: position queries only
+  unsigned char* fwd_ws = (unsigned char*)ws_dev + est_points_bytes(m, batch) + est_neff_bytes(m, batch);
+  const WsLayout L = ws_layout(m, batch);
+  unsigned char* X0 = fwd_ws + L.x0;
+  const size_t row_bytes = (size_t)nesti_model_mups_rows(m) * mups_stride(m) * dtype_size(m->dtype);   // one query's MuPS
+  const int E = m->graph.cfg.arch == NESTI_ARCH_SWITCH ? 1 : m->graph.cfg.n_experts;
+  const int S = cfg->n_scales;
+  long long done = 0;           // rows emitted so far
+  int item = 0, item_done = 0;  // cursor into the items
+  while (done < total) {
+    int fill = 0;
+    const int tok = prof_begin(NESTI_PROF_MUPS, st);
+    while (fill < batch && item < n_items) {
+      const EstItem& it = items[item];
+      const int take = std::min(batch - fill, it.n_queries - item_done);
+      if (take > 0 &&
+          launch_patches_mups(cfg, it.cloud_dev, it.n_points, it.query_idx_dev ? it.query_idx_dev + item_done : nullptr,
+                              at ? it.query_xyz_dev + (size_t)item_done * 3 : nullptr, take, it.r_abs, it.seed,
+                              it.query_row0 + item_done, it.grid_ws_dev, X0 + (size_t)fill * row_bytes, m->dtype, mups_stride(m),
+                              at ? n_eff + (size_t)fill * S : nullptr, nullptr, st)) {
+        prof_end(NESTI_PROF_MUPS, tok, st);      // close the timing span on the error path too
+        return 1;
+      }
+      fill += take;
+      item_done += take;
+      if (item_done >= it.n_queries) { ++item; item_done = 0; }
+    }
+    prof_end(NESTI_PROF_MUPS, tok, st);
+    float* n_out = normals_out_dev + (size_t)done * 3;
+    int32_t* e_out = expert_out_dev ? expert_out_dev + done : nullptr;
+    float* p_out = probs_out_dev ? probs_out_dev + (size_t)done * E : nullptr;
+    if (forward_tail(m, X0, fill, batch, fwd_ws, L, n_out, e_out, p_out, st)) return 1;
+    if (at && launch_mask_empty_queries(n_eff, fill, S, n_out, e_out, p_out, E, st)) return 1;
+    done += fill;
   }
   return 0;
 }
@@ -1144,58 +1263,30 @@ int nesti_estimate_normals_multi(const nesti_model_t* m, const nesti_shape_queri
     for (int i = 0; items && i < n_items; ++i) any += items[i].n_queries > 0 ? items[i].n_queries : 0;
     if (any == 0) return 0;   // no queries: nothing to do
   }
-  if (!m || !items || !ws_dev || !normals_out_dev) NESTI_FAIL("nesti_estimate_normals_multi: null argument");
-  if (batch <= 0) NESTI_FAIL("nesti_estimate_normals_multi: batch must be positive");
-  const nesti_config_t* cfg = &m->graph.cfg;
-  if (cfg->grid_n != 8) NESTI_FAIL("nesti_estimate_normals_multi: the 8^3 Gaussian grid only (use nesti_estimate_normals per shape)");
-  if (nesti_estimate_workspace_bytes(m, batch) > ws_bytes)
-    NESTI_FAIL("nesti_estimate_normals_multi: workspace too small (see nesti_estimate_workspace_bytes)");
-  long long total = 0;
-  for (int i = 0; i < n_items; ++i) {
-    const nesti_shape_queries_t& it = items[i];
-    if (it.n_queries < 0 || (it.n_queries > 0 && (!it.cloud_dev || !it.grid_ws_dev || it.n_points <= 0)))
-      NESTI_FAIL("nesti_estimate_normals_multi: bad item");
-    if (it.query_row0 < 0 || (!it.query_idx_dev && (long long)it.query_row0 + it.n_queries > (long long)it.n_points))
-      NESTI_FAIL("nesti_estimate_normals_multi: query rows of an item exceed its cloud");
-    if (it.n_queries > 0 && it.grid_ws_bytes < nesti_patches_workspace_bytes(it.n_points))
-      NESTI_FAIL("nesti_estimate_normals_multi: grid workspace of an item too small");
-    for (int s = 0; s < cfg->n_scales; ++s)
-      if (it.n_queries > 0 && !(it.r_abs[s] > 0.0)) NESTI_FAIL("nesti_estimate_normals_multi: radii must be positive");
-    total += it.n_queries;
+  if (!items) NESTI_FAIL("nesti_estimate_normals_multi: null argument");
+  std::vector<EstItem> v;
+  for (int i = 0; i < n_items; ++i)
+    v.push_back({items[i].cloud_dev, items[i].n_points, items[i].query_idx_dev, nullptr, items[i].n_queries, items[i].r_abs,
+                 items[i].seed, items[i].query_row0, items[i].grid_ws_dev, items[i].grid_ws_bytes});
+  return estimate_multi_impl("nesti_estimate_normals_multi", false, m, v, batch, ws_dev, ws_bytes, normals_out_dev, expert_out_dev,
+                             probs_out_dev, stream);
+}
+
+int nesti_estimate_normals_multi_at(const nesti_model_t* m, const nesti_shape_positions_t* items, int n_items, int batch,
+                                    void* ws_dev, size_t ws_bytes, float* normals_out_dev, int32_t* expert_out_dev,
+                                    float* probs_out_dev, void* stream) {
+  {
+    long long any = 0;
+    for (int i = 0; items && i < n_items; ++i) any += items[i].n_queries > 0 ? items[i].n_queries : 0;
+    if (any == 0) return 0;   // no queries: nothing to do
   }
-  if (total == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  unsigned char* fwd_ws = (unsigned char*)ws_dev + est_points_bytes(m, batch) + est_neff_bytes(m, batch);
-  const WsLayout L = ws_layout(m, batch);
-  unsigned char* X0 = fwd_ws + L.x0;
-  const size_t row_bytes = (size_t)nesti_model_mups_rows(m) * mups_stride(m) * dtype_size(m->dtype);   // one query's MuPS
-  const int E = m->graph.cfg.arch == NESTI_ARCH_SWITCH ? 1 : m->graph.cfg.n_experts;
-  long long done = 0;           // rows emitted so far
-  int item = 0, item_done = 0;  // cursor into the items
-  while (done < total) {
-    int fill = 0;
-    const int tok = prof_begin(NESTI_PROF_MUPS, st);
-    while (fill < batch && item < n_items) {
-      const nesti_shape_queries_t& it = items[item];
-      const int take = std::min(batch - fill, it.n_queries - item_done);
-      if (take > 0 &&
-          launch_patches_mups(cfg, it.cloud_dev, it.n_points, it.query_idx_dev ? it.query_idx_dev + item_done : nullptr, take,
-                              it.r_abs, it.seed, it.query_row0 + item_done, it.grid_ws_dev, X0 + (size_t)fill * row_bytes,
-                              m->dtype, mups_stride(m), nullptr, st)) {
-        prof_end(NESTI_PROF_MUPS, tok, st);      // close the timing span on the error path too
-        return 1;
-      }
-      fill += take;
-      item_done += take;
-      if (item_done >= it.n_queries) { ++item; item_done = 0; }
-    }
-    prof_end(NESTI_PROF_MUPS, tok, st);
-    if (forward_tail(m, X0, fill, batch, fwd_ws, L, normals_out_dev + (size_t)done * 3, expert_out_dev ? expert_out_dev + done : nullptr,
-                     probs_out_dev ? probs_out_dev + (size_t)done * E : nullptr, st))
-      return 1;
-    done += fill;
-  }
-  return 0;
+  if (!items) NESTI_FAIL("nesti_estimate_normals_multi_at: null argument");
+  std::vector<EstItem> v;
+  for (int i = 0; i < n_items; ++i)
+    v.push_back({items[i].cloud_dev, items[i].n_points, nullptr, items[i].query_xyz_dev, items[i].n_queries, items[i].r_abs,
+                 items[i].seed, items[i].query_row0, items[i].grid_ws_dev, items[i].grid_ws_bytes});
+  return estimate_multi_impl("nesti_estimate_normals_multi_at", true, m, v, batch, ws_dev, ws_bytes, normals_out_dev, expert_out_dev,
+                             probs_out_dev, stream);
 }
 
 int nesti_profile_enable(int on) {

@@ -491,9 +491,10 @@ int launch_mups(const nesti_config_t* cfg, const float* points, const int32_t* n
   return 0;
 }
 
-int launch_patches_mups(const nesti_config_t* cfg, const float* cloud_dev, int N, const int32_t* query_idx_dev, int M,
-                        const double* r_abs, uint64_t seed, int query_row0, const void* grid_ws_dev, void* out, int out_dtype,
-                        int out_cstride, int32_t* n_eff_out_dev, hipStream_t stream) {
+int launch_patches_mups(const nesti_config_t* cfg, const float* cloud_dev, int N, const int32_t* query_idx_dev,
+                        const float* query_xyz_dev, int M, const double* r_abs, uint64_t seed, int query_row0, const void* grid_ws_dev,
+                        void* out, int out_dtype, int out_cstride, int32_t* n_eff_out_dev, int32_t* n_ball_out_dev,
+                        hipStream_t stream) {
   if (cfg->grid_n != kR) NESTI_FAIL("launch_patches_mups: the fused kernel serves the 8^3 Gaussian grid");
   if (cfg->points_per_scale < 1 || 2 * cfg->points_per_scale > kListCap) NESTI_FAIL("launch_patches_mups: points_per_scale must be in [1, 512]");
   const bool x3 = act_planes(out_dtype) > 1;
@@ -502,7 +503,9 @@ int launch_patches_mups(const nesti_config_t* cfg, const float* cloud_dev, int N
   if (M <= 0) return 0;
   PatchParams p;
   patch_params_fill(&p, cfg, cloud_dev, N, query_idx_dev, M, r_abs, seed, query_row0, grid_ws_dev);
+  p.query_xyz = query_xyz_dev;       // positions instead of cloud points (nesti_estimate_normals_at)
   p.n_eff_out = n_eff_out_dev;
+  p.n_ball_out = n_ball_out_dev;     // the uncapped ball sizes: the kernel holds them in LDS anyway
   const float sigma = (float)sqrt(cfg->variance);
   const float w = 1.0f / (float)kG;
   dim3 grid(M), block(kThreads);

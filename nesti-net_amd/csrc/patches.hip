@@ -353,34 +353,55 @@ int nesti_patches_grid(const nesti_config_t* cfg, const float* cloud_dev, int N,
   return 0;
 }
 
-int nesti_patches_query(const nesti_config_t* cfg, const float* cloud_dev, int N, const int32_t* query_idx_dev, int M,
-                        const double* r_abs, uint64_t seed, int query_row0, float* points_out_dev,
-                        int32_t* n_eff_out_dev, int32_t* nbr_idx_out_dev, int32_t* n_ball_out_dev,
-                        const void* grid_ws_dev, size_t grid_ws_bytes, void* stream) {
-  if (!cfg || !cloud_dev || !r_abs || !grid_ws_dev) NESTI_FAIL("nesti_patches_query: null argument");
-  if (N <= 0) NESTI_FAIL("nesti_patches_query: empty cloud");
-  if (cfg->n_scales < 1 || cfg->n_scales > NESTI_MAX_SCALES) NESTI_FAIL("nesti_patches_query: bad n_scales");
+// nesti_patches_query (centres = cloud points, by index or row) and nesti_patches_query_at (centres = positions): one body
+static int patches_query_impl(const char* who, bool at, const nesti_config_t* cfg, const float* cloud_dev, int N,
+                              const int32_t* query_idx_dev, const float* query_xyz_dev, int M, const double* r_abs, uint64_t seed,
+                              int query_row0, float* points_out_dev, int32_t* n_eff_out_dev, int32_t* nbr_idx_out_dev,
+                              int32_t* n_ball_out_dev, const void* grid_ws_dev, size_t grid_ws_bytes, void* stream) {
+  const std::string w(who);
+  if (!cfg || !cloud_dev || !r_abs || !grid_ws_dev) NESTI_FAIL(w + ": null argument");
+  if (N <= 0) NESTI_FAIL(w + ": empty cloud");
+  if (cfg->n_scales < 1 || cfg->n_scales > NESTI_MAX_SCALES) NESTI_FAIL(w + ": bad n_scales");
   if (cfg->points_per_scale < 1 || 2 * cfg->points_per_scale > kListCap)
-    NESTI_FAIL("nesti_patches_query: points_per_scale must be in [1, 512]");
+    NESTI_FAIL(w + ": points_per_scale must be in [1, 512]");
   const WsLayout L = patch_ws_layout(N);
-  if (grid_ws_bytes < L.total) NESTI_FAIL("nesti_patches_query: grid workspace too small");
+  if (grid_ws_bytes < L.total) NESTI_FAIL(w + ": grid workspace too small");
   if (M <= 0) return 0;
   // 'full' sampler (query_idx NULL): patch row == point index, so the row range must lie inside the cloud.  With a
   // query list the indices live on the device; the host mirror (provider.CloudPatches) validates them once at upload
   // and the kernel clamps defensively (a bad index then yields a wrong patch, never an out-of-bounds read).
-  if (query_row0 < 0) NESTI_FAIL("nesti_patches_query: query_row0 must be >= 0");
-  if (!query_idx_dev && (long long)query_row0 + M > (long long)N)
-    NESTI_FAIL("nesti_patches_query: query rows [query_row0, query_row0 + M) exceed the cloud (N points)");
+  // Positions: query_row0 is only the subsample key's row; any position is served (cell_coords, patches_dev.h).
+  if (query_row0 < 0) NESTI_FAIL(w + ": query_row0 must be >= 0");
+  if (at && !query_xyz_dev) NESTI_FAIL(w + ": null query_xyz_dev");
+  if (!at && !query_idx_dev && (long long)query_row0 + M > (long long)N)
+    NESTI_FAIL(w + ": query rows [query_row0, query_row0 + M) exceed the cloud (N points)");
   for (int s = 0; s < cfg->n_scales; ++s)
-    if (!(r_abs[s] > 0.0)) NESTI_FAIL("nesti_patches_query: radii must be positive");
+    if (!(r_abs[s] > 0.0)) NESTI_FAIL(w + ": radii must be positive");
   PatchParams p;
   patch_params_fill(&p, cfg, cloud_dev, N, query_idx_dev, M, r_abs, seed, query_row0, grid_ws_dev);
+  p.query_xyz = at ? query_xyz_dev : nullptr;
   p.points_out = points_out_dev; p.n_eff_out = n_eff_out_dev; p.nbr_out = nbr_idx_out_dev; p.n_ball_out = n_ball_out_dev;
   const int tok = prof_begin(NESTI_PROF_PATCHES, (hipStream_t)stream);
   hipLaunchKernelGGL(patches_kernel, dim3(M), dim3(kThreads), 0, (hipStream_t)stream, p);
   prof_end(NESTI_PROF_PATCHES, tok, (hipStream_t)stream);
   NESTI_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+int nesti_patches_query(const nesti_config_t* cfg, const float* cloud_dev, int N, const int32_t* query_idx_dev, int M,
+                        const double* r_abs, uint64_t seed, int query_row0, float* points_out_dev,
+                        int32_t* n_eff_out_dev, int32_t* nbr_idx_out_dev, int32_t* n_ball_out_dev,
+                        const void* grid_ws_dev, size_t grid_ws_bytes, void* stream) {
+  return patches_query_impl("nesti_patches_query", false, cfg, cloud_dev, N, query_idx_dev, nullptr, M, r_abs, seed, query_row0,
+                            points_out_dev, n_eff_out_dev, nbr_idx_out_dev, n_ball_out_dev, grid_ws_dev, grid_ws_bytes, stream);
+}
+
+int nesti_patches_query_at(const nesti_config_t* cfg, const float* cloud_dev, int N, const float* query_xyz_dev, int M,
+                           const double* r_abs, uint64_t seed, int query_row0, float* points_out_dev,
+                           int32_t* n_eff_out_dev, int32_t* nbr_idx_out_dev, int32_t* n_ball_out_dev,
+                           const void* grid_ws_dev, size_t grid_ws_bytes, void* stream) {
+  return patches_query_impl("nesti_patches_query_at", true, cfg, cloud_dev, N, nullptr, query_xyz_dev, M, r_abs, seed, query_row0,
+                            points_out_dev, n_eff_out_dev, nbr_idx_out_dev, n_ball_out_dev, grid_ws_dev, grid_ws_bytes, stream);
 }
 
 static int check_query_args(const char* who, const nesti_config_t* cfg, const float* cloud_dev, int N, const int32_t* query_idx_dev,

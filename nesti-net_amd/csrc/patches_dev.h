@@ -37,10 +37,21 @@ inline WsLayout patch_ws_layout(int N) {
   return L;
 }
 
+// Cell of a coordinate, clamped to the grid IN DOUBLE before the integer conversion: a far-away coordinate gets a defined
+// border cell instead of an undefined conversion.  For a cloud point the result is its cell.  A non-finite query centre never
+// gets here: patch_query_setup tests the BIT PATTERNS of the centre and gives such a query empty spans -- mups.hip is built
+// with -fno-honor-nans, under which neither fmax(NaN, 0) nor an ordered compare against NaN can be relied on.
+// A query POSITION (PatchParams::query_xyz) may lie outside the bounding box: the cell edge is >= 1.0001 x the largest
+// radius, so a centre whose true cell index is -1 or dims has its whole ball inside cells [-2, 0] resp. [dims - 1, dims + 1],
+// of which only the border cell holds points, and the 3 x 3 x 3 block around the CLAMPED cell contains that border cell;
+// a centre further out has an empty ball, which the distance test finds (no candidate passes it).
+__device__ __forceinline__ int cell_axis(double v, double minv, double inv_cell, int dim) {
+  return (int)fmin((double)(dim - 1), fmax(0.0, floor((v - minv) * inv_cell)));
+}
 __device__ __forceinline__ void cell_coords(const GridHeader& h, float x, float y, float z, int* ix, int* iy, int* iz) {
-  *ix = min(h.dims[0] - 1, max(0, (int)floor(((double)x - h.minv[0]) * h.inv_cell)));
-  *iy = min(h.dims[1] - 1, max(0, (int)floor(((double)y - h.minv[1]) * h.inv_cell)));
-  *iz = min(h.dims[2] - 1, max(0, (int)floor(((double)z - h.minv[2]) * h.inv_cell)));
+  *ix = cell_axis((double)x, h.minv[0], h.inv_cell, h.dims[0]);
+  *iy = cell_axis((double)y, h.minv[1], h.inv_cell, h.dims[1]);
+  *iz = cell_axis((double)z, h.minv[2], h.inv_cell, h.dims[2]);
 }
 __device__ __forceinline__ int cell_flat(const GridHeader& h, int ix, int iy, int iz) {
   return (iz * h.dims[1] + iy) * h.dims[0] + ix;   // x fastest: a row of cells is one contiguous span
@@ -62,6 +73,7 @@ struct PatchParams {
   const int* start;
   const GridHeader* header;
   const int32_t* query_idx;
+  const float* query_xyz;          // [M,3] query POSITIONS (nesti_*_at): the centre is query_xyz[q], not a cloud point
   int M, N, S, P, row0;
   unsigned long long seed;
   double r2[NESTI_MAX_SCALES];     // r*r, like cKDTree's upper_bound for p = 2
@@ -82,23 +94,42 @@ struct PatchShared {
   int sel[kListCap];
 };
 
+// exponent all ones: +-inf or NaN, tested on the bits.  The empty asm makes the word opaque: without it the compiler
+// recognises the mask test as a floating-point class test of v and, under -fno-honor-nans, drops the NaN half of it
+// (it became v_cmp_eq_f32 |v|, inf, which a NaN fails).
+__device__ __forceinline__ bool non_finite_bits(float v) {
+  unsigned u = __float_as_uint(v);
+  asm volatile("" : "+s"(u));       // the centre is uniform over the workgroup: a scalar register
+  return (u & 0x7f800000u) == 0x7f800000u;
+}
+
 // The query point, the 3 x 3 cell block as nine contiguous x-spans of the cell-ordered copy, and the ball sizes of
 // every scale (pass A).  Ends with a barrier: sh.s_count[] is valid on return.
 __device__ __forceinline__ void patch_query_setup(const PatchParams& p, PatchShared& sh, int q, int t, float (&cf)[3]) {
-  int qi = p.query_idx ? p.query_idx[q] : p.row0 + q;         // 'full' sampler: patch row == point index
-  qi = min(max(qi, 0), p.N - 1);
+  const float* centre;
+  if (p.query_xyz) {                                          // position query (uniform per launch): need not be in its own ball
+    centre = p.query_xyz + (size_t)q * 3;
+  } else {
+    int qi = p.query_idx ? p.query_idx[q] : p.row0 + q;       // 'full' sampler: patch row == point index
+    qi = min(max(qi, 0), p.N - 1);
+    centre = p.cloud + (size_t)qi * 3;
+  }
   const GridHeader h = *p.header;
-  cf[0] = p.cloud[(size_t)qi * 3]; cf[1] = p.cloud[(size_t)qi * 3 + 1]; cf[2] = p.cloud[(size_t)qi * 3 + 2];
+  cf[0] = centre[0]; cf[1] = centre[1]; cf[2] = centre[2];
   const double cx = cf[0], cy = cf[1], cz = cf[2];
+  // a centre with an infinite or NaN coordinate has empty balls: it visits no cell, so no distance is ever formed from it
+  const bool lost = non_finite_bits(cf[0]) || non_finite_bits(cf[1]) || non_finite_bits(cf[2]);
   if (t < 9) {
-    int ix, iy, iz;
-    cell_coords(h, cf[0], cf[1], cf[2], &ix, &iy, &iz);
-    const int zz = iz + t / 3 - 1, yy = iy + t % 3 - 1;
     int b = 0, e = 0;
-    if (zz >= 0 && zz < h.dims[2] && yy >= 0 && yy < h.dims[1]) {
-      const int x0 = max(ix - 1, 0), x1 = min(ix + 1, h.dims[0] - 1);
-      b = p.start[cell_flat(h, x0, yy, zz)];
-      e = p.start[cell_flat(h, x1, yy, zz) + 1];
+    if (!lost) {
+      int ix, iy, iz;
+      cell_coords(h, cf[0], cf[1], cf[2], &ix, &iy, &iz);
+      const int zz = iz + t / 3 - 1, yy = iy + t % 3 - 1;
+      if (zz >= 0 && zz < h.dims[2] && yy >= 0 && yy < h.dims[1]) {
+        const int x0 = max(ix - 1, 0), x1 = min(ix + 1, h.dims[0] - 1);
+        b = p.start[cell_flat(h, x0, yy, zz)];
+        e = p.start[cell_flat(h, x1, yy, zz) + 1];
+      }
     }
     sh.span_beg[t] = b;
     sh.span_end[t] = e;

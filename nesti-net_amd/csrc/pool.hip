@@ -578,6 +578,29 @@ int launch_x8_guard_fix(const float* src, int sstride, const int32_t* glist, con
   return 0;
 }
 
+// ---- position queries (nesti_*_at): a query whose balls are empty at EVERY scale has no neighbourhood ----------------------------
+// Its MuPS rows are zeros and went through the towers like any row; what comes out is the sentinel: normal (0, 0, 0), expert -1,
+// probabilities 0.  Element-wise over the rows of a batch, enqueued after everything that writes the batch's outputs.
+__global__ void mask_empty_queries_kernel(const int32_t* __restrict__ n_eff, int M, int S, float* __restrict__ normals,
+                                          int32_t* __restrict__ expert, float* __restrict__ probs, int E) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= M) return;
+  for (int s = 0; s < S; ++s)
+    if (n_eff[(size_t)i * S + s] > 0) return;
+  normals[(size_t)i * 3] = 0.f; normals[(size_t)i * 3 + 1] = 0.f; normals[(size_t)i * 3 + 2] = 0.f;
+  if (expert) expert[i] = -1;
+  if (probs)
+    for (int e = 0; e < E; ++e) probs[(size_t)i * E + e] = 0.f;
+}
+
+int launch_mask_empty_queries(const int32_t* n_eff, int M, int S, float* normals, int32_t* expert, float* probs, int E,
+                              hipStream_t stream) {
+  if (M <= 0) return 0;
+  hipLaunchKernelGGL(mask_empty_queries_kernel, dim3((M + 255) / 256), dim3(256), 0, stream, n_eff, M, S, normals, expert, probs, E);
+  NESTI_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 int launch_route(const int32_t* expert, int B, int E, int32_t* counts, int32_t* lists, hipStream_t stream) {
   if (B <= 0) return 0;
   hipLaunchKernelGGL(zero_counts_kernel, dim3(1), dim3(64), 0, stream, counts, E);

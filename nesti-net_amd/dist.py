@@ -17,6 +17,10 @@ the ranks re-converge with the next gather -- and (b) ``cascade_stats()['max_mar
 rank has measured since the last reset, not that rank's alone.  The export runs on the caller's current stream after
 ``NormalEstimator.run`` / ``run_many`` have joined their lane streams (they end with ``main.wait_stream(lane)``).
 
+Position queries (``CloudPatches(..., queries=)``) are sharded by row exactly like ``pidx`` rows: a rank runs rows [lo, hi) of the
+query list (``NormalEstimator.run`` / ``run_many`` call the ``_at`` entries), the subsample key is the global row, and sentinel
+rows travel through the gather like any other row.
+
 Reproducible estimators (``NormalEstimator(..., reproducible=True)``): the shards run frozen and the verified loop of
 ``pipeline.verified_passes`` runs over the GLOBAL maxima -- after the usual gather ONE extra ``all_reduce(MAX)`` of four floats
 [max_margin_err, max_dn, violations > 0, dropped > 0], read on the host, so every rank takes the same decision and, if needed,

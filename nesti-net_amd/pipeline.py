@@ -125,9 +125,19 @@ class NormalEstimator:
             with torch.cuda.graph(self._graph):
                 self.net.forward(self._points, self._n_eff, out=self._g_out)
 
-    def prepare(self, pts, pidx=None):
-        """Upload a cloud and build its search grid (replaces ``load_shape``)."""
-        return CloudPatches(pts, self.cfg, device=self.device, seed=self.seed, pidx=pidx)
+    def prepare(self, pts, pidx=None, queries=None):
+        """Upload a cloud and build its search grid (replaces ``load_shape``).  ``queries`` [M,3]: estimate at these positions
+        instead of at cloud points (``CloudPatches``)."""
+        return CloudPatches(pts, self.cfg, device=self.device, seed=self.seed, pidx=pidx, queries=queries)
+
+    def _mask_empty(self, n_eff, normals, expert, probs, single_tower):
+        """Position queries on the unfused paths: the sentinel of rows without a neighbourhood (``nesti_mask_empty_queries``), on
+        the current stream, after the forward pass that wrote the rows (never inside the captured graph)."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.net.lib.nesti_mask_empty_queries(
+                _lib.ptr(n_eff), normals.shape[0], self.cfg.n_scales, _lib.ptr(normals), None if single_tower else _lib.ptr(expert),
+                None if single_tower else _lib.ptr(probs), probs.shape[1], _lib.stream_ptr(torch.cuda.current_stream(self.device))),
+                "nesti_mask_empty_queries")
 
     def run(self, cloud: CloudPatches, first=0, count=None, out=None):
         """Normals for patch rows [first, first+count) of a prepared cloud.
@@ -146,6 +156,10 @@ class NormalEstimator:
         single_tower = self.cfg.arch in (ARCH_SINGLE, ARCH_MULTI)      # ss/ms ablations: normals only
         if first < 0 or count < 0 or first + count > cloud.patch_count:
             raise ValueError("patch rows [%d, %d) outside [0, %d)" % (first, first + count, cloud.patch_count))
+        at = cloud.queries is not None
+        if at and self._ref is not None:
+            raise _lib.NestiError("subsample=%r reproduces the reference's subsample order, which is defined for index queries only; "
+                                  "a cloud with position queries needs subsample='hash'" % self.subsample)
         if self._ref is not None:
             if self._ref_failed:
                 raise _lib.NestiError("a reference-order run failed half way: the shared random stream no longer lines up with "
@@ -168,13 +182,22 @@ class NormalEstimator:
                 r0 = first + done
                 qidx = cloud.pidx[r0:r0 + take].contiguous() if cloud.pidx is not None else None
                 with torch.cuda.device(self.device):
-                    _lib.check(self.net.lib.nesti_estimate_normals(
-                        self.net._handle, _lib.ptr(cloud.cloud), cloud.n_points, _lib.ptr(qidx), take, cloud._r,
-                        ctypes.c_uint64(cloud.seed), r0, self.batch, 0, _lib.ptr(cloud._ws), cloud._ws.numel(),
-                        _lib.ptr(arena), arena.numel(), _lib.ptr(normals[done:done + take]),
-                        None if single_tower else _lib.ptr(expert[done:done + take]),
-                        None if single_tower else _lib.ptr(probs[done:done + take]),
-                        ctypes.c_void_p(st.cuda_stream)), "nesti_estimate_normals")
+                    if at:
+                        _lib.check(self.net.lib.nesti_estimate_normals_at(
+                            self.net._handle, _lib.ptr(cloud.cloud), cloud.n_points, _lib.ptr(cloud.queries[r0:r0 + take]), take,
+                            cloud._r, ctypes.c_uint64(cloud.seed), r0, self.batch, 0, _lib.ptr(cloud._ws), cloud._ws.numel(),
+                            _lib.ptr(arena), arena.numel(), _lib.ptr(normals[done:done + take]),
+                            None if single_tower else _lib.ptr(expert[done:done + take]),
+                            None if single_tower else _lib.ptr(probs[done:done + take]), None,
+                            ctypes.c_void_p(st.cuda_stream)), "nesti_estimate_normals_at")
+                    else:
+                        _lib.check(self.net.lib.nesti_estimate_normals(
+                            self.net._handle, _lib.ptr(cloud.cloud), cloud.n_points, _lib.ptr(qidx), take, cloud._r,
+                            ctypes.c_uint64(cloud.seed), r0, self.batch, 0, _lib.ptr(cloud._ws), cloud._ws.numel(),
+                            _lib.ptr(arena), arena.numel(), _lib.ptr(normals[done:done + take]),
+                            None if single_tower else _lib.ptr(expert[done:done + take]),
+                            None if single_tower else _lib.ptr(probs[done:done + take]),
+                            ctypes.c_void_p(st.cuda_stream)), "nesti_estimate_normals")
                 if qidx is not None and lane > 0:
                     qidx.record_stream(st)
                 done += take
@@ -199,6 +222,8 @@ class NormalEstimator:
                 probs[sl].copy_(self._g_out[2])
             else:
                 self.net.forward(p, n, out=(normals[sl], expert[sl], probs[sl]))
+            if at:
+                self._mask_empty(n, normals[sl], expert[sl], probs[sl], single_tower)
             done += take
         if single_tower:
             return normals, None, None
@@ -407,6 +432,10 @@ class NormalEstimator:
         for cloud, first, count in items:
             if first < 0 or count < 0 or first + count > cloud.patch_count:
                 raise ValueError("patch rows [%d, %d) outside [0, %d)" % (first, first + count, cloud.patch_count))
+        # a library call serves index items or position items, and one stream of batches is one kind of call
+        if len({c.queries is not None for c, _, _ in items}) > 1:
+            raise ValueError("run_many: clouds with position queries and clouds with index queries cannot share one call; "
+                             "run the two kinds separately")
         # groups of pieces (cloud, first, count): one group = one library call on one lane
         if self.n_streams == 1:
             groups = [list(items)]
@@ -429,7 +458,8 @@ class NormalEstimator:
         for gi, group in enumerate(groups):
             lane = gi % self.n_streams
             st, arena = (main, self._arena) if lane == 0 else self._lanes[lane - 1]
-            arr = (_lib.CShapeQueries * max(1, len(group)))()
+            at = bool(group) and group[0][0].queries is not None
+            arr = ((_lib.CShapePositions if at else _lib.CShapeQueries) * max(1, len(group)))()
             for i, (cloud, first, count) in enumerate(group):
                 qidx = cloud.pidx[first:first + count].contiguous() if cloud.pidx is not None else None
                 if qidx is not None and lane > 0:
@@ -437,7 +467,10 @@ class NormalEstimator:
                 keep.append(qidx)
                 arr[i].cloud_dev = cloud.cloud.data_ptr()
                 arr[i].n_points = cloud.n_points
-                arr[i].query_idx_dev = qidx.data_ptr() if qidx is not None and count > 0 else None
+                if at:
+                    arr[i].query_xyz_dev = cloud.queries[first:first + count].data_ptr() if count > 0 else None
+                else:
+                    arr[i].query_idx_dev = qidx.data_ptr() if qidx is not None and count > 0 else None
                 arr[i].n_queries = count
                 for s, r in enumerate(cloud.r_abs):
                     arr[i].r_abs[s] = r
@@ -446,11 +479,12 @@ class NormalEstimator:
                 arr[i].grid_ws_dev = cloud._ws.data_ptr()
                 arr[i].grid_ws_bytes = cloud._ws.numel()
             rows = sum(c for _, _, c in group)
+            entry = "nesti_estimate_normals_multi_at" if at else "nesti_estimate_normals_multi"
             with torch.cuda.device(self.device):
-                _lib.check(self.net.lib.nesti_estimate_normals_multi(
+                _lib.check(getattr(self.net.lib, entry)(
                     self.net._handle, arr, len(group), self.batch, _lib.ptr(arena), arena.numel(), _lib.ptr(normals[o:o + rows]),
                     None if single_tower else _lib.ptr(expert[o:o + rows]), None if single_tower else _lib.ptr(probs[o:o + rows]),
-                    ctypes.c_void_p(st.cuda_stream)), "nesti_estimate_normals_multi")
+                    ctypes.c_void_p(st.cuda_stream)), entry)
             o += rows
         for st, _ in self._lanes:
             main.wait_stream(st)
@@ -460,9 +494,10 @@ class NormalEstimator:
             o += n
         return out
 
-    def estimate(self, pts, pidx=None):
-        """Convenience: numpy cloud in, numpy results out (synchronises)."""
-        cloud = self.prepare(np.asarray(pts, dtype=np.float32), pidx)
+    def estimate(self, pts, pidx=None, queries=None):
+        """Convenience: numpy cloud in, numpy results out (synchronises).  ``queries`` [M,3]: positions instead of cloud points;
+        a position without a neighbourhood comes back as normal (0, 0, 0), expert -1, probabilities 0."""
+        cloud = self.prepare(np.asarray(pts, dtype=np.float32), pidx, queries)
         normals, expert, probs = self.run(cloud)
         torch.cuda.synchronize(self.device)
         if expert is None:

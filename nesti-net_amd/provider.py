@@ -35,11 +35,46 @@ def load_xyz(path):
     return pts
 
 
+def load_qxyz(path):
+    """``<shape>.qxyz``: the query positions of a shape, a text file of M rows x 3 read like ``.xyz`` (no cache file)."""
+    q = np.loadtxt(path).astype("float32")
+    if q.ndim == 1:
+        q = q.reshape(1, -1) if q.size else q.reshape(0, 3)
+    return np.ascontiguousarray(q[:, :3])
+
+
+def check_queries(queries):
+    """``queries`` as a contiguous float32 [M,3] host array, or a float32 [M,3] torch tensor left where it is.  ``ValueError``
+    for another shape, and for a host array with a non-finite entry (the first bad row is named): a position without
+    coordinates is a mistake of the caller.  The kernels themselves serve any bit pattern (such a query has empty balls)."""
+    if isinstance(queries, torch.Tensor):
+        if queries.dim() != 2 or queries.shape[1] != 3:
+            raise ValueError("queries must be [M,3]: got %s" % (tuple(queries.shape),))
+        return queries.to(torch.float32)
+    q = np.asarray(queries)
+    if q.ndim != 2 or q.shape[1] != 3:
+        raise ValueError("queries must be [M,3]: got %s" % (q.shape,))
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    bad = np.flatnonzero(~np.isfinite(q).all(axis=1))
+    if len(bad):
+        raise ValueError("queries row %d is not finite: %s" % (bad[0], q[bad[0]].tolist()))
+    return q
+
+
 class CloudPatches:
     """One shape: the cloud in HBM + its uniform search grid (replaces ``load_shape`` /
-    ``cKDTree``, ``utils/pcpnet_dataset.py:13-39``).  ``build(rows)`` extracts patches."""
+    ``cKDTree``, ``utils/pcpnet_dataset.py:13-39``).  ``build(rows)`` extracts patches.
 
-    def __init__(self, pts, cfg: NestiConfig, device="cuda:0", seed=3627473, pidx=None):
+    ``queries`` ([M,3], converted to float32; mutually exclusive with ``pidx``): the patch centres are these POSITIONS instead
+    of cloud points -- a downsampled copy, mesh vertices, voxel centres, another sweep -- while the neighbourhoods come from
+    this cloud and ``r_abs`` from ITS bounding box.  Patch row i is ``queries[i]``; a position whose balls are all empty gets
+    the sentinel outputs."""
+
+    def __init__(self, pts, cfg: NestiConfig, device="cuda:0", seed=3627473, pidx=None, queries=None):
+        if pidx is not None and queries is not None:
+            raise ValueError("pidx and queries are mutually exclusive: a query is a cloud point (pidx) or a position (queries)")
+        if queries is not None:
+            queries = check_queries(queries)
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.NestiError("CloudPatches needs a GPU: libnesti_hip.so has no CPU path")
@@ -57,6 +92,10 @@ class CloudPatches:
                 raise ValueError("pidx entries must lie in [0, %d): got [%d, %d]" % (self.n_points, pidx.min(), pidx.max()))
         self.pidx = None if pidx is None else torch.as_tensor(pidx, dtype=torch.int32, device=self.device)
         self.patch_count = self.n_points if pidx is None else len(pidx)     # :276-279
+        self.queries = None
+        if queries is not None:
+            self.queries = (queries if isinstance(queries, torch.Tensor) else torch.from_numpy(queries)).to(self.device).contiguous()
+            self.patch_count = self.queries.shape[0]
         nbytes = self.lib.nesti_patches_workspace_bytes(self.n_points)
         self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self._c = cfg.to_c()
@@ -82,7 +121,7 @@ class CloudPatches:
         S, P = self.cfg.n_scales, self.cfg.num_point
         if first < 0 or count < 0 or first + count > self.patch_count:
             raise ValueError("patch rows [%d, %d) outside [0, %d)" % (first, first + count, self.patch_count))
-        # sparse: <shape>.pidx rows; full: NULL -> the kernel uses point index = patch row
+        # sparse: <shape>.pidx rows; full: NULL -> the kernel uses point index = patch row; positions: rows of queries
         qidx = self.pidx[first:first + count].contiguous() if self.pidx is not None else None
         if out is None:
             points = torch.empty((count, S * P, 3), dtype=torch.float32, device=self.device)
@@ -92,12 +131,14 @@ class CloudPatches:
         nbr = torch.empty((count, S * P), dtype=torch.int32, device=self.device) if want_idx else None
         n_ball = torch.empty((count, S), dtype=torch.int32, device=self.device) if want_idx else None
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        at = self.queries is not None
+        entry = "nesti_patches_query_at" if at else "nesti_patches_query"
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.nesti_patches_query(
-                ctypes.byref(self._c), _lib.ptr(self.cloud), self.n_points, _lib.ptr(qidx), count, self._r,
-                ctypes.c_uint64(self.seed), ctypes.c_int(first), _lib.ptr(points), _lib.ptr(n_eff), _lib.ptr(nbr),
+            _lib.check(getattr(self.lib, entry)(
+                ctypes.byref(self._c), _lib.ptr(self.cloud), self.n_points, _lib.ptr(self.queries[first:first + count] if at else qidx),
+                count, self._r, ctypes.c_uint64(self.seed), ctypes.c_int(first), _lib.ptr(points), _lib.ptr(n_eff), _lib.ptr(nbr),
                 _lib.ptr(n_ball), _lib.ptr(self._ws), self._ws.numel(), ctypes.c_void_p(st.cuda_stream)),
-                "nesti_patches_query")
+                entry)
         if want_idx:
             return points, n_eff, nbr, n_ball
         return points, n_eff
@@ -118,10 +159,17 @@ class CloudPatches:
             self._tree_rank = torch.from_numpy(rank).to(self.device)
         return self._tree_rank, self._tree_order
 
+    def _index_queries_only(self, what):
+        """The reference-order entries exist to diff against a reference run, which has only index queries."""
+        if self.queries is not None:
+            raise _lib.NestiError("%s: the reference's subsample order is defined for index queries only; a cloud with position "
+                                  "queries uses subsample='hash'" % what)
+
     def count_balls(self, first, count, stream=None):
         """Ball sizes [count, S] int32 (device) of patch rows [first, first + count): what the reference's random stream needs
         (``nesti_patches_count``)."""
         S = self.cfg.n_scales
+        self._index_queries_only("count_balls")
         if first < 0 or count < 0 or first + count > self.patch_count:
             raise ValueError("patch rows [%d, %d) outside [0, %d)" % (first, first + count, self.patch_count))
         qidx = self.pidx[first:first + count].contiguous() if self.pidx is not None else None
@@ -139,6 +187,7 @@ class CloudPatches:
         tensor, any 2-byte dtype) at ``pick_offsets`` [count * S] int64 (device; -1 = the ball holds <= P points) -- the table
         ``refsample.RefStream.picks`` replays from the ball sizes of :meth:`count_balls`."""
         S, P = self.cfg.n_scales, self.cfg.num_point
+        self._index_queries_only("build_reference_order")
         if first < 0 or count < 0 or first + count > self.patch_count:
             raise ValueError("patch rows [%d, %d) outside [0, %d)" % (first, first + count, self.patch_count))
         rank, order = self.ensure_tree_order()
@@ -168,9 +217,13 @@ class PointcloudPatchDataset:
     (``utils/pcpnet_dataset.py:179-282``), for the inference configuration only."""
 
     def __init__(self, root, shape_list_filename, cfg: NestiConfig, seed=3627473, sparse_patches=False,
-                 device="cuda:0", cache_capacity=100):
+                 device="cuda:0", cache_capacity=100, query_positions=False):
         self.root, self.cfg, self.seed, self.device = root, cfg, seed, device
         self.sparse_patches = bool(sparse_patches)
+        # query_positions: the rows of <shape>.qxyz (M rows x 3, read like .xyz) are the queries instead of cloud points
+        self.query_positions = bool(query_positions)
+        if self.sparse_patches and self.query_positions:
+            raise ValueError("sparse_patches and query_positions are mutually exclusive")
         with open(os.path.join(root, shape_list_filename)) as f:
             self.shape_names = [x.strip() for x in f.readlines()]
         self.shape_names = list(filter(None, self.shape_names))       # :221-224
@@ -191,7 +244,8 @@ class PointcloudPatchDataset:
             pidx = None
             if self.sparse_patches:
                 pidx = np.loadtxt(os.path.join(self.root, name + ".pidx")).astype("int")   # :267-270
-            self._cache[ind] = [CloudPatches(pts, self.cfg, self.device, self.seed, pidx), self._tick]
+            queries = load_qxyz(os.path.join(self.root, name + ".qxyz")) if self.query_positions else None
+            self._cache[ind] = [CloudPatches(pts, self.cfg, self.device, self.seed, pidx, queries=queries), self._tick]
         self._cache[ind][1] = self._tick
         return self._cache[ind][0]
 
@@ -238,7 +292,7 @@ class _Loader:
 def get_data_loader(dataset_name, batchSize, indir, patch_radius, points_per_patch, outputs=(), patch_point_count_std=0,
                     seed=3627473, identical_epochs=False, use_pca=False, patch_center="point", point_tuple=1,
                     cache_capacity=100, patch_sample_order="full", workers=0, dataset_type="test", sparse_patches=False,
-                    cfg: NestiConfig = None, device="cuda:0"):
+                    cfg: NestiConfig = None, device="cuda:0", query_positions=False):
     """Keyword-compatible with ``utils/provider.py:319-429`` for the inference settings of
     ``test_n_est_w_experts.py:109-116``; anything outside that configuration raises, as it is
     outside the hot path."""
@@ -249,5 +303,5 @@ def get_data_loader(dataset_name, batchSize, indir, patch_radius, points_per_pat
     cfg = NestiConfig(**{**cfg.__dict__, "patch_radius": list(patch_radius), "num_point": int(points_per_patch)})
     listfile = os.path.relpath(dataset_name, indir) if os.path.isabs(dataset_name) else dataset_name
     ds = PointcloudPatchDataset(indir, listfile, cfg, seed=seed, sparse_patches=sparse_patches, device=device,
-                                cache_capacity=cache_capacity)
+                                cache_capacity=cache_capacity, query_positions=query_positions)
     return _Loader(ds, batchSize), ds

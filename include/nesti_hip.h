@@ -422,6 +422,47 @@ int nesti_estimate_normals_at(const nesti_model_t* m, const float* cloud_dev, in
 int nesti_mask_empty_queries(const int32_t* n_eff_dev, int M, int S, float* normals_dev, int32_t* expert_dev,
                              float* probs_dev, int E, void* stream);
 
+/* ---- consistent orientation of estimated normals (orient.hip; DESIGN.md 2 "Orientation") ------------------------------------
+ * No reference call site: Nesti-Net is trained with an unoriented loss and its .normals are lines, not vectors.  The consumer is
+ * the reference's "RMS oriented" figure (utils/evaluate.py:151); the conventions below are the library's own.
+ * Hoppe's propagation made unique, as a post-pass over positions xyz_dev [M,3] f32 and their normals [M,3] f32:
+ *   eligible rows: all three normal components finite and one non-zero (tested on the bits); other rows are left untouched and
+ *     are nobody's neighbour.  PRECONDITION: the positions of eligible rows are finite.
+ *   nbr(i): the eligible j != i with fp64 d2 = (dx dx + dy dy) + dz dz <= radius^2, the K (1 .. 16) smallest by (d2, j), in order.
+ *   edge {a < b}: b in nbr(a) or a in nbr(b); id = a K + slot of b in nbr(a) if b in nbr(a), else b K + slot of a in nbr(b).
+ *     In fp64, every operation rounded on its own: d = (na.x nb.x + na.y nb.y) + na.z nb.z, q_i = |n_i|^2, flip bit f = d < 0,
+ *     weight w = (float)max(0, 1 - (d d) / (q_a q_b)); key = (bits of w) << 32 | id.  Keys are distinct, so the minimum spanning
+ *     forest under this order is unique.
+ *   root of each tree: the vertex with the largest z (ties: smaller index), signed so that the first non-zero of (n_z, n_y, n_x)
+ *     is positive; with a viewpoint v the vertex with the smallest fp64 d2 to v, flipped iff the fp64 n . (v - p) < 0.
+ *   vertex x is flipped iff (root flipped) xor (xor of f over the tree path root -> x).  A flip negates the three floats: sign
+ *     bits only, nothing is normalised.
+ * NESTI_ORIENT_VIEWPOINT: no graph; every eligible row is flipped iff the fp64 n . (v - p) < 0 (viewpoint required).
+ * Each tree is oriented on its own: a graph that falls apart (tiny radius, K = 1) gives trees whose root rule may pick the inner
+ * side; n_components tells.  grid_ws_dev: nesti_patches_workspace_bytes(M) bytes (the call builds the search grid over xyz_dev);
+ * ws_dev: nesti_orient_workspace_bytes(M, K) bytes.  M = 0 is a no-op.  Argument errors (null pointers, K outside 1 .. 16, a
+ * radius that is not finite or <= 0, an unknown mode, NESTI_ORIENT_VIEWPOINT without a viewpoint, a non-finite viewpoint, a
+ * short workspace, M K >= 2^32) are reported before any device call.  The calls enqueue on `stream` and neither synchronise nor
+ * read anything back; the result is a pure function of the inputs. */
+enum { NESTI_ORIENT_MST = 0, NESTI_ORIENT_VIEWPOINT = 1 };
+typedef struct {
+  int32_t n_eligible, n_components, n_flipped, n_edges;   /* NESTI_ORIENT_VIEWPOINT: n_components = n_edges = 0 */
+} nesti_orient_stats_t;
+/* host only; 0 for M <= 0 (and for K outside 1 .. 16) */
+size_t nesti_orient_workspace_bytes(int M, int K);
+/* The parity entry: neighbour lists and edges only.  Any output may be NULL: nbr_out_dev [M,K] int32, -1 padded; edge_u_dev /
+ * edge_v_dev [M K] int32 indexed by edge id, -1 = no edge in this slot; edge_wbits_dev [M K] the bits of w; edge_flip_dev [M K] f. */
+int nesti_orient_graph(const float* xyz_dev, int M, const float* normals_dev, double radius, int K,
+                       void* grid_ws_dev, size_t grid_ws_bytes, void* ws_dev, size_t ws_bytes,
+                       int32_t* nbr_out_dev, int32_t* edge_u_dev, int32_t* edge_v_dev,
+                       uint32_t* edge_wbits_dev, uint8_t* edge_flip_dev, void* stream);
+/* Orients normals_dev in place.  viewpoint: 3 doubles on the HOST, or NULL.  tree_edge_out_dev (optional) [M K] uint8: 1 for the
+ * edge ids of the spanning forest.  stats_dev (optional): on the DEVICE, written on the stream. */
+int nesti_orient_normals(const float* xyz_dev, int M, float* normals_dev, int mode, double radius, int K,
+                         const double* viewpoint, void* grid_ws_dev, size_t grid_ws_bytes,
+                         void* ws_dev, size_t ws_bytes, uint8_t* tree_edge_out_dev,
+                         nesti_orient_stats_t* stats_dev, void* stream);
+
 /* Several shapes in flight (BASELINE config 4; also every rank of a multi-GPU job, which holds a block of rows of
  * every shape): the queries of all items are processed as ONE stream of `batch`-sized batches, so small shapes / small
  * shards share the gate and expert launches instead of each paying for its own partially filled rounds.  Item i

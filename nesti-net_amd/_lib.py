@@ -55,6 +55,11 @@ class CReproducibleStats(ctypes.Structure):
                 ("tau", ctypes.c_float), ("thr", ctypes.c_float)]
 
 
+class COrientStats(ctypes.Structure):
+    """Mirror of ``nesti_orient_stats_t``."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("n_eligible", "n_components", "n_flipped", "n_edges")]
+
+
 class CDebugPass(ctypes.Structure):
     """Mirror of ``nesti_debug_pass_t``."""
     _fields_ = [("fast", ctypes.c_int), ("x8_mask", ctypes.c_int), ("x8_fmt", ctypes.c_int)]
@@ -87,6 +92,7 @@ class CDebugPack(ctypes.Structure):
 X8_GUARD_BAR, X8_GUARD_WIDEN, X8_GUARD_DEFAULT = 2.5e-6, 1.5, 0.25   # NESTI_X8_GUARD_* (include/nesti_hip.h)
 GATE_WIDEN = 1.5      # NESTI_GATE_WIDEN (include/nesti_hip.h)
 GATE_WIDEN_PASSES = 3  # NESTI_GATE_WIDEN_PASSES
+ORIENT_MST, ORIENT_VIEWPOINT = 0, 1   # NESTI_ORIENT_*
 
 
 class NestiError(RuntimeError):
@@ -148,6 +154,10 @@ SIGNATURES = {
     "nesti_estimate_normals_at": (_i, [_vp, _vp, _i, _vp, _i, ctypes.POINTER(ctypes.c_double), _u64, _i, _i, _i, _vp, _sz,
                                        _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "nesti_mask_empty_queries": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "nesti_orient_workspace_bytes": (_sz, [_i, _i]),
+    "nesti_orient_graph": (_i, [_vp, _i, _vp, ctypes.c_double, _i, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "nesti_orient_normals": (_i, [_vp, _i, _vp, _i, ctypes.c_double, _i, ctypes.POINTER(ctypes.c_double), _vp, _sz, _vp, _sz,
+                                  _vp, _vp, _vp]),
     "nesti_estimate_normals_multi_at": (_i, [_vp, ctypes.POINTER(CShapePositions), _i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
     "nesti_crc32c": (ctypes.c_uint32, [_vp, _sz, ctypes.c_uint32]),
     "nesti_f32_to_e2m3": (_i, [ctypes.c_float, ctypes.c_float]),

@@ -72,6 +72,16 @@ def build_parser():
                         "own points; neighbourhoods and radii still come from <shape>.xyz.  The three output files then have M rows; a "
                         "position with no cloud point inside any of its balls is written as normal 0 0 0, expert -1, probabilities 0.  "
                         "Mutually exclusive with --sparse_patches 1; needs --subsample hash")
+    p.add_argument("--orient", default="0", choices=["0", "mst", "viewpoint"],
+                   help="orient the written normals consistently (only signs in <shape>.normals change; .experts and .experts_probs "
+                        "do not).  0 (default): signs as the experts produced them.  mst: propagate signs along the minimum spanning "
+                        "tree of the --orient_k nearest-neighbour graph inside the largest patch radius, from the highest point "
+                        "(made to point up) or, with --viewpoint, from the point nearest to it (made to face it); every connected "
+                        "piece is oriented on its own, the log line names their number.  viewpoint: every normal faces --viewpoint "
+                        "(a single-sensor scan)")
+    p.add_argument("--orient_k", type=int, default=8, help="--orient mst: neighbours per point, 1 .. 16 [default: 8]")
+    p.add_argument("--viewpoint", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"),
+                   help="--orient viewpoint (required) / --orient mst (optional): the sensor position in the cloud's coordinates")
     p.add_argument("--synthetic_weights", action="store_true", help="use seeded synthetic weights if model.nstw is absent")
     return p
 
@@ -101,6 +111,12 @@ def main(argv=None):
         parser.error("--query_positions 1 and --sparse_patches 1 are mutually exclusive: the queries are positions or cloud points")
     if FLAGS.query_positions and FLAGS.subsample != "hash":
         parser.error("--query_positions 1 needs --subsample hash: the reference's subsample order is defined for cloud points only")
+    if FLAGS.orient == "viewpoint" and FLAGS.viewpoint is None:
+        parser.error("--orient viewpoint needs --viewpoint X Y Z")
+    if FLAGS.orient == "0" and FLAGS.viewpoint is not None:
+        parser.error("--viewpoint belongs to --orient mst / --orient viewpoint")
+    if not 1 <= FLAGS.orient_k <= 16:
+        parser.error("--orient_k must be in 1 .. 16")
     archs = {"experts_n_est": ARCH_EXPERTS, "ss_norm_est": ARCH_SINGLE, "ms_norm_est": ARCH_MULTI,
              "ms_sw_n_est": ARCH_SWITCH}      # test_n_est_w_experts.py / test_n_est.py / test_n_est_w_switching.py
     if FLAGS.model not in archs:
@@ -192,6 +208,13 @@ def main(argv=None):
                         rs["gate_violations"] + rs["guard_violations"] == 0, lv["max_margin_err"], lv["max_dn"]))
         else:
             normals, expert, probs = est.run(cloud)
+        if FLAGS.orient != "0":
+            # after the whole shape is estimated (in the reproducible mode: after its last verified pass); only signs change
+            from .orient import stats_dict
+            ost = stats_dict(est.orient(cloud, normals, FLAGS.orient, FLAGS.viewpoint, FLAGS.orient_k))
+            printout("orientation of %s (%s): %d of %d rows oriented, %d flipped, %d connected piece%s, %d edges"
+                     % (name, FLAGS.orient, ost["n_eligible"], cloud.patch_count, ost["n_flipped"], ost["n_components"],
+                        "" if ost["n_components"] == 1 else "s", ost["n_edges"]))
         torch.cuda.synchronize()
         if FLAGS.query_positions:
             # the sentinel (pool.hip: mask_empty_queries_kernel): expert -1; the single-tower models have only the (0, 0, 0) normal

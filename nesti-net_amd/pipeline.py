@@ -494,11 +494,39 @@ class NormalEstimator:
             o += n
         return out
 
-    def estimate(self, pts, pidx=None, queries=None):
+    def orient(self, cloud, normals, mode="mst", viewpoint=None, k=8):
+        """Orient the normals of a prepared cloud's patch rows IN PLACE (``orient.orient_device``: minimum-spanning-tree propagation,
+        or ``mode='viewpoint'``), on the current stream, after everything that wrote them.  ``normals`` [patch_count, 3]: what
+        :meth:`run` / :meth:`run_verified` returned for the whole range.  Positions are the cloud, ``cloud[pidx]`` or the query
+        positions; the radius is the largest patch radius ``cloud.r_abs[-1]``, the scale at which the network itself looks.  Rows
+        without a neighbourhood (the (0, 0, 0) sentinel) stay as they are.  Returns the stats as an int32[4] device tensor
+        (``orient.stats_dict``); nothing synchronises."""
+        from . import orient as _orient
+        if normals.shape[0] != cloud.patch_count:
+            raise ValueError("orientation needs the normals of all %d patch rows, got %d" % (cloud.patch_count, normals.shape[0]))
+        if cloud.queries is not None:
+            pos = _orient.harmless_positions(cloud.queries)      # a non-finite position has no neighbourhood: its row is the sentinel
+        elif cloud.pidx is not None:
+            pos = cloud.cloud[cloud.pidx.long()].contiguous()
+        else:
+            pos = cloud.cloud
+        if not normals.is_contiguous():
+            raise ValueError("orientation works in place on a contiguous [M, 3] tensor")
+        return _orient.orient_device(pos, normals, float(cloud.r_abs[-1]), k, viewpoint, mode,
+                                     torch.cuda.current_stream(self.device))
+
+    def estimate(self, pts, pidx=None, queries=None, orient=None, viewpoint=None, orient_k=8):
         """Convenience: numpy cloud in, numpy results out (synchronises).  ``queries`` [M,3]: positions instead of cloud points;
-        a position without a neighbourhood comes back as normal (0, 0, 0), expert -1, probabilities 0."""
+        a position without a neighbourhood comes back as normal (0, 0, 0), expert -1, probabilities 0.  ``orient`` = ``'mst'`` /
+        ``'viewpoint'`` (default None: signs as the experts produced them): :meth:`orient` runs over the estimated rows, only signs
+        change, and ``self.last_orient`` holds the stats dict."""
+        if orient not in (None, "mst", "viewpoint"):
+            raise ValueError("orient must be None, 'mst' or 'viewpoint'")
         cloud = self.prepare(np.asarray(pts, dtype=np.float32), pidx, queries)
         normals, expert, probs = self.run(cloud)
+        if orient is not None:
+            from .orient import stats_dict
+            self.last_orient = stats_dict(self.orient(cloud, normals, orient, viewpoint, orient_k))
         torch.cuda.synchronize(self.device)
         if expert is None:
             return normals.cpu().numpy(), None, None

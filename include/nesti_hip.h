@@ -463,6 +463,66 @@ int nesti_orient_normals(const float* xyz_dev, int M, float* normals_dev, int mo
                          void* ws_dev, size_t ws_bytes, uint8_t* tree_edge_out_dev,
                          nesti_orient_stats_t* stats_dev, void* stream);
 
+/* ---- depth images in, normal images out (depth.hip; DESIGN.md 2 "Depth images") --------------------------------------------------
+ * The two ends of the reference's Kinect route: MATLAB/ScanNet_depth2xyz.m (depth + intrinsics + pose -> cloud) before
+ * test_n_est_w_experts.py, and MATLAB/ScanNet_world2cam_normals.m / MATLAB/export_visualizations_nyu.m:146-153 (per-point results
+ * -> image) after it.  The conventions are the library's own, because the reference's are MATLAB's:
+ *   - pixel coordinates are 0-BASED, u = column, v = row.  The MATLAB files are 1-based: a caller with MATLAB-convention intrinsics
+ *     passes cx - 1, cy - 1;
+ *   - the pose is applied as a proper rigid transform, translation included.  ScanNet_depth2xyz.m:14 multiplies with a homogeneous
+ *     coordinate of 0 and thereby drops the translation; that is not reproduced;
+ *   - where several rows project onto one pixel the NEAREST wins and among equals the smaller row index (the reference lets the last
+ *     row win).
+ * nesti_camera_t lives on the HOST.  pose: row-major 3 x 4 [R | t], read only when has_pose != 0 -- camera -> world for
+ * nesti_depth_to_cloud, world -> camera (the caller inverts) for nesti_project_to_image.  z_near / z_far: 0 and +inf keep everything.
+ *
+ * nesti_depth_to_cloud: depth_dev [H,W] uint16 or float32 (NESTI_DEPTH_*).  A pixel is VALID iff z = (double)raw * depth_scale is
+ * finite (a float's finiteness is tested on its bits), > 0 and inside [z_near, z_far].  In fp64, every operation rounded on its own:
+ *     xc = ((u - cx) * z) / fx,  yc = ((v - cy) * z) / fy,  zc = z,
+ *     with a pose X_r = ((T[r][0] * xc + T[r][1] * yc) + T[r][2] * zc) + T[r][3],
+ * then ONE rounding to float32.  Outputs, all in row-major pixel order (the order of the reference's loop):
+ *   xyz_dev [n_valid,3] f32 and pix_dev [n_valid] int32 (pixel index v W + u): the caller provides room for H W rows;
+ *   rank_dev [H W] int32 (optional): the cloud row of a pixel, or -1;
+ *   qidx_dev (optional; room for ceil(H / stride) ceil(W / stride) entries): the cloud rows of the valid pixels with v % stride == 0
+ *     and u % stride == 0, in pixel order -- what nesti_estimate_normals takes as query_idx_dev;
+ *   counts_dev [2] int32 = {n_valid, n_queries}, on the DEVICE.
+ * The compaction is deterministic and atomic-free: per-block counts, one single-workgroup scan over them, a scatter; no workgroup
+ * waits on another.
+ *
+ * nesti_image_scatter: rows_dev [M,C] of 4-byte elements (f32 or int32) are written to image_dev [H,W,C] at the pixels pix_dev [M];
+ * every other element is fill[C] (HOST, 4-byte elements).  pix entries must be distinct (they are by construction); an entry outside
+ * [0, H W) is skipped.  M = 0 gives an all-fill image.
+ *
+ * nesti_project_to_image: for a cloud that did not come from nesti_depth_to_cloud.  Per row, in fp64, every operation rounded on its
+ * own: camera coordinates (through `pose` as above if has_pose), u = floor(((xc * fx) / zc + cx) + 0.5), v likewise with fy, cy.  A
+ * row lands iff its three floats and zc are finite, zc > 0 and 0 <= u < W, 0 <= v < H.  Per pixel the smallest key
+ * (bits of (float)zc) << 32 | row wins (64-bit atomicMin); image_dev [H,W,C] gets the winner's values_dev[row, 0:C] (4-byte elements)
+ * or fill[C]; index_image_dev [H,W] int32 (optional) the winning row or -1.  image_dev may be NULL when only the index is wanted.
+ * depth_scale, z_near and z_far are checked but not used.
+ *
+ * ws_dev: nesti_depth_workspace_bytes(H, W) bytes (nesti_depth_to_cloud, nesti_project_to_image).  Argument errors -- null pointers,
+ * H or W <= 0, H W > 2^26, stride < 1, fx or fy zero or not finite, cx / cy / depth_scale / pose not finite, depth_scale <= 0,
+ * z_near > z_far, C outside 1 .. 8, M < 0, a short workspace, an unknown depth type -- are reported before any device call.  The calls
+ * enqueue on `stream` and neither synchronise nor read anything back. */
+enum { NESTI_DEPTH_U16 = 0, NESTI_DEPTH_F32 = 1 };
+typedef struct {
+  double fx, fy, cx, cy;
+  double depth_scale;      /* metres (or any unit) per raw depth value: 1e-3 for uint16 millimetres */
+  double z_near, z_far;
+  int has_pose;
+  double pose[12];
+} nesti_camera_t;
+/* host only; 0 for H or W <= 0 and for H W > 2^26 */
+size_t nesti_depth_workspace_bytes(int H, int W);
+int nesti_depth_to_cloud(const void* depth_dev, int depth_type, int H, int W, const nesti_camera_t* camera, int stride,
+                         float* xyz_dev, int32_t* pix_dev, int32_t* rank_dev, int32_t* qidx_dev, int32_t* counts_dev,
+                         void* ws_dev, size_t ws_bytes, void* stream);
+int nesti_image_scatter(const void* rows_dev, const int32_t* pix_dev, int M, int C, int H, int W, const void* fill,
+                        void* image_dev, void* stream);
+int nesti_project_to_image(const float* xyz_dev, const void* values_dev, int M, int C, int H, int W,
+                           const nesti_camera_t* camera, const void* fill, void* image_dev, int32_t* index_image_dev,
+                           void* ws_dev, size_t ws_bytes, void* stream);
+
 /* Several shapes in flight (BASELINE config 4; also every rank of a multi-GPU job, which holds a block of rows of
  * every shape): the queries of all items are processed as ONE stream of `batch`-sized batches, so small shapes / small
  * shards share the gate and expert launches instead of each paying for its own partially filled rounds.  Item i

@@ -60,6 +60,12 @@ class COrientStats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("n_eligible", "n_components", "n_flipped", "n_edges")]
 
 
+class CCamera(ctypes.Structure):
+    """Mirror of ``nesti_camera_t``."""
+    _fields_ = [(n, ctypes.c_double) for n in ("fx", "fy", "cx", "cy", "depth_scale", "z_near", "z_far")] + \
+               [("has_pose", ctypes.c_int), ("pose", ctypes.c_double * 12)]
+
+
 class CDebugPass(ctypes.Structure):
     """Mirror of ``nesti_debug_pass_t``."""
     _fields_ = [("fast", ctypes.c_int), ("x8_mask", ctypes.c_int), ("x8_fmt", ctypes.c_int)]
@@ -93,6 +99,8 @@ X8_GUARD_BAR, X8_GUARD_WIDEN, X8_GUARD_DEFAULT = 2.5e-6, 1.5, 0.25   # NESTI_X8_
 GATE_WIDEN = 1.5      # NESTI_GATE_WIDEN (include/nesti_hip.h)
 GATE_WIDEN_PASSES = 3  # NESTI_GATE_WIDEN_PASSES
 ORIENT_MST, ORIENT_VIEWPOINT = 0, 1   # NESTI_ORIENT_*
+DEPTH_U16, DEPTH_F32 = 0, 1           # NESTI_DEPTH_*
+DEPTH_MAX_PIXELS = 1 << 26
 
 
 class NestiError(RuntimeError):
@@ -158,6 +166,10 @@ SIGNATURES = {
     "nesti_orient_graph": (_i, [_vp, _i, _vp, ctypes.c_double, _i, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nesti_orient_normals": (_i, [_vp, _i, _vp, _i, ctypes.c_double, _i, ctypes.POINTER(ctypes.c_double), _vp, _sz, _vp, _sz,
                                   _vp, _vp, _vp]),
+    "nesti_depth_workspace_bytes": (_sz, [_i, _i]),
+    "nesti_depth_to_cloud": (_i, [_vp, _i, _i, _i, ctypes.POINTER(CCamera), _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "nesti_image_scatter": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "nesti_project_to_image": (_i, [_vp, _vp, _i, _i, _i, _i, ctypes.POINTER(CCamera), _vp, _vp, _vp, _vp, _sz, _vp]),
     "nesti_estimate_normals_multi_at": (_i, [_vp, ctypes.POINTER(CShapePositions), _i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
     "nesti_crc32c": (ctypes.c_uint32, [_vp, _sz, ctypes.c_uint32]),
     "nesti_f32_to_e2m3": (_i, [ctypes.c_float, ctypes.c_float]),

@@ -1,7 +1,9 @@
 """Command-line drop-in for the reference's ``test_n_est_w_experts.py``: same flags
 (``:19-29``), same inputs (``<dataset_path>/<testset>`` shape list, ``<shape>.xyz``, optional
 ``<shape>.pidx``; ``--query_positions 1``: ``<shape>.qxyz``, the positions to estimate at) and same outputs (``<results_path>/<dataset_name>_results/<shape>.normals``,
-``.experts``, ``.experts_probs`` written with ``np.savetxt`` like ``:182-188``, plus ``log.txt``).
+``.experts``, ``.experts_probs`` written with ``np.savetxt`` like ``:182-188``, plus ``log.txt``).  ``--depth_images 1``: the inputs are
+depth frames (``<name>.depth.npy``, ``<name>.camera``, optional ``<name>.cam2world``), the outputs one row per estimated pixel plus
+``<name>.pix``, ``<name>.normal_map.npy`` and ``<name>.expert_map.npy`` (the reference's MATLAB route, DESIGN.md 2 "Depth images").
 
 The trained-model directory holds either ``model.nstw`` (variables + hyper-parameters, see
 :mod:`.weights`) or the reference's own ``parameters.p`` / ``gmm.p`` / ``model.ckpt.*`` (read by
@@ -72,13 +74,25 @@ def build_parser():
                         "own points; neighbourhoods and radii still come from <shape>.xyz.  The three output files then have M rows; a "
                         "position with no cloud point inside any of its balls is written as normal 0 0 0, expert -1, probabilities 0.  "
                         "Mutually exclusive with --sparse_patches 1; needs --subsample hash")
-    p.add_argument("--orient", default="0", choices=["0", "mst", "viewpoint"],
+    p.add_argument("--depth_images", type=int, default=0, choices=[0, 1],
+                   help="1: every name of the test set is a depth frame -- <name>.depth.npy ([H,W] uint16 or float32), <name>.camera (one "
+                        "line: fx fy cx cy depth_scale; pixel coordinates are 0-based, so MATLAB-convention intrinsics lose 1 from cx and "
+                        "cy) and optionally <name>.cam2world (4 x 4, camera to world, applied with its translation).  The frame is "
+                        "back-projected on the GPU, normals are estimated at its valid pixels (depth finite and > 0) and written as one "
+                        "row per estimated pixel in row-major pixel order, with <name>.pix (the pixel index v W + u of each row), "
+                        "<name>.normal_map.npy ([H,W,3], 0 0 0 where nothing was estimated) and <name>.expert_map.npy ([H,W], -1 "
+                        "there).  --orient defaults to viewpoint, the camera centre; --viewpoint is refused.  Mutually exclusive with "
+                        "--sparse_patches 1 and --query_positions 1")
+    p.add_argument("--depth_stride", type=int, default=1,
+                   help="--depth_images 1: estimate at the valid pixels whose row and column are multiples of S only (neighbourhoods "
+                        "still come from every valid pixel) [default: 1]")
+    p.add_argument("--orient", default=None, choices=["0", "mst", "viewpoint"],
                    help="orient the written normals consistently (only signs in <shape>.normals change; .experts and .experts_probs "
                         "do not).  0 (default): signs as the experts produced them.  mst: propagate signs along the minimum spanning "
                         "tree of the --orient_k nearest-neighbour graph inside the largest patch radius, from the highest point "
                         "(made to point up) or, with --viewpoint, from the point nearest to it (made to face it); every connected "
                         "piece is oriented on its own, the log line names their number.  viewpoint: every normal faces --viewpoint "
-                        "(a single-sensor scan)")
+                        "(a single-sensor scan).  With --depth_images 1 the default is viewpoint and the viewpoint is the camera")
     p.add_argument("--orient_k", type=int, default=8, help="--orient mst: neighbours per point, 1 .. 16 [default: 8]")
     p.add_argument("--viewpoint", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"),
                    help="--orient viewpoint (required) / --orient mst (optional): the sensor position in the cloud's coordinates")
@@ -104,6 +118,54 @@ def fit_batch(cfg, dtype, batch, device, lanes=2, reserve=2 << 30):
     return batch
 
 
+class DepthFrames:
+    """The frames of ``--depth_images 1``: the names of the test set and, from the ``.npy`` headers alone, an upper bound on the rows
+    each can produce (sizes the library batch)."""
+
+    def __init__(self, root, testset, stride):
+        import numpy as np
+        self.root, self.stride = root, int(stride)
+        with open(os.path.join(root, testset)) as f:
+            self.names = list(filter(None, (x.strip() for x in f.readlines())))
+        self.max_rows = []
+        for name in self.names:
+            H, W = np.load(self.path(name, ".depth.npy"), mmap_mode="r").shape
+            self.max_rows.append(((H + self.stride - 1) // self.stride) * ((W + self.stride - 1) // self.stride))
+
+    def path(self, name, ext):
+        return os.path.join(self.root, name + ext)
+
+    def load(self, name):
+        """(depth [H,W], Camera) of a frame; the pose from ``<name>.cam2world`` when that file exists."""
+        import dataclasses
+        from . import depth as _depth
+        cam = _depth.read_camera(self.path(name, ".camera"))
+        if os.path.exists(self.path(name, ".cam2world")):
+            cam = dataclasses.replace(cam, pose=_depth.read_cam2world(self.path(name, ".cam2world")))
+        return _depth.read_depth(self.path(name, ".depth.npy")), cam
+
+
+def run_depth_frame(est, frames, name, FLAGS, output_dir, printout, on_cloud, write_experts=True):
+    """One frame of ``--depth_images 1``: estimate, then the row files, ``.pix`` and the two images."""
+    import numpy as np
+    depth, cam = frames.load(name)
+    res = est.estimate_depth(depth, cam, stride=FLAGS.depth_stride, orient=None if FLAGS.orient == "0" else FLAGS.orient,
+                             orient_k=FLAGS.orient_k, on_cloud=on_cloud)
+    H, W = depth.shape
+    printout("depth frame %s: %d x %d, %d normals estimated (stride %d), oriented: %s"
+             % (name, H, W, len(res["pix"]), FLAGS.depth_stride, FLAGS.orient))
+    textio.write_f32(os.path.join(output_dir, name + ".normals"), res["normals"])
+    textio.write_i32(os.path.join(output_dir, name + ".pix"), res["pix"])
+    np.save(os.path.join(output_dir, name + ".normal_map.npy"), res["normal_map"])
+    printout("saved normals for " + name)
+    if res["expert"] is None or not write_experts:
+        return
+    textio.write_i32(os.path.join(output_dir, name + ".experts"), res["expert"])
+    textio.write_f32(os.path.join(output_dir, name + ".experts_probs"), res["probs"])
+    np.save(os.path.join(output_dir, name + ".expert_map.npy"), res["expert_map"])
+    printout("saved experts for " + name)
+
+
 def main(argv=None):
     parser = build_parser()
     FLAGS = parser.parse_args(argv)
@@ -111,7 +173,19 @@ def main(argv=None):
         parser.error("--query_positions 1 and --sparse_patches 1 are mutually exclusive: the queries are positions or cloud points")
     if FLAGS.query_positions and FLAGS.subsample != "hash":
         parser.error("--query_positions 1 needs --subsample hash: the reference's subsample order is defined for cloud points only")
-    if FLAGS.orient == "viewpoint" and FLAGS.viewpoint is None:
+    if FLAGS.depth_images:
+        if FLAGS.sparse_patches or FLAGS.query_positions:
+            parser.error("--depth_images 1 is mutually exclusive with --sparse_patches 1 and --query_positions 1: the queries are the "
+                         "frame's valid pixels (--depth_stride thins them)")
+        if FLAGS.viewpoint is not None:
+            parser.error("--viewpoint does not go with --depth_images 1: the camera is the viewpoint")
+        if FLAGS.depth_stride < 1:
+            parser.error("--depth_stride must be >= 1")
+    elif FLAGS.depth_stride != 1:
+        parser.error("--depth_stride belongs to --depth_images 1")
+    if FLAGS.orient is None:
+        FLAGS.orient = "viewpoint" if FLAGS.depth_images else "0"
+    if FLAGS.orient == "viewpoint" and FLAGS.viewpoint is None and not FLAGS.depth_images:
         parser.error("--orient viewpoint needs --viewpoint X Y Z")
     if FLAGS.orient == "0" and FLAGS.viewpoint is not None:
         parser.error("--viewpoint belongs to --orient mst / --orient viewpoint")
@@ -160,12 +234,17 @@ def main(argv=None):
                          "--model %s" % (dtype, FLAGS.model))
     if dtype in ("f16x8", "f16x8c") and cfg.n_gaussians != 8:
         raise SystemExit("--dtype %s needs the 8^3 Gaussian grid; use f16x3c" % dtype)
-    dataset = PointcloudPatchDataset(pc_path, FLAGS.testset, cfg, seed=3627473, sparse_patches=FLAGS.sparse_patches,
-                                     device=device, query_positions=bool(FLAGS.query_positions))
+    if FLAGS.depth_images:
+        frames = DepthFrames(pc_path, FLAGS.testset, FLAGS.depth_stride)
+        patch_counts = frames.max_rows
+    else:
+        dataset = PointcloudPatchDataset(pc_path, FLAGS.testset, cfg, seed=3627473, sparse_patches=FLAGS.sparse_patches,
+                                         device=device, query_positions=bool(FLAGS.query_positions))
+        patch_counts = dataset.shape_patch_count
     # two library batches in flight on two HIP streams; a batch is half the largest shape (rounded up to 256 rows) unless
     # that exceeds what the workspace of the dtype allows (~2 MB per query in f16x3c, twice that in the full pair modes)
     lib_batch = FLAGS.lib_batch or {"f16x3c": 50000, "f16x8c": 50000, "f16": 50000, "bf16": 50000, "f32": 8192}.get(dtype, 25000)
-    half = (max(dataset.shape_patch_count + [1]) + 1) // 2
+    half = (max(patch_counts + [1]) + 1) // 2
     batch = max(FLAGS.batch_size, min(lib_batch, max(1024, (half + 255) // 256 * 256)))
     # ... and what the device has free right now: two arenas (one per stream) + the 1024-query calibration workspace must fit
     # (the defaults are sized for an otherwise idle 288 GB MI355X; a shared or smaller device gets smaller batches, not an OOM)
@@ -182,8 +261,7 @@ def main(argv=None):
         raise SystemExit("--reproducible 1 needs --subsample hash")
     printout("Model restored.")
 
-    for ind, name in enumerate(dataset.shape_names):
-        cloud = dataset.get_shape(ind)
+    def calibrate(name, cloud):
         if dtype in CASCADE_DTYPES:
             # the gate margin, from up to 1024 queries of THIS shape (noise level and density change the activation and
             # error statistics from shape to shape); calibrate_gate_margin resets the gate's counters, so the statistics
@@ -199,6 +277,17 @@ def main(argv=None):
             sp, sn = cloud.build(0, min(1024, cloud.patch_count))
             printout("cross-term guard threshold for %s: |n| < %.4g" % (name, calibrate_x8_guard(est.net, sp, sn, reproducible=repro)))
             del sp, sn
+
+    if FLAGS.depth_images:
+        for name in frames.names:
+            run_depth_frame(est, frames, name, FLAGS, output_dir, printout, lambda cloud: calibrate(name, cloud),
+                            write_experts=arch != ARCH_SWITCH)
+        flog.close()
+        return 0
+
+    for ind, name in enumerate(dataset.shape_names):
+        cloud = dataset.get_shape(ind)
+        calibrate(name, cloud)
         if repro:
             normals, expert, probs = est.run_verified(cloud)
             lv, rs = est.last_verified, est.net.reproducible_stats()

@@ -531,3 +531,51 @@ class NormalEstimator:
         if expert is None:
             return normals.cpu().numpy(), None, None
         return normals.cpu().numpy(), expert.cpu().numpy(), probs.cpu().numpy()
+
+    def estimate_depth(self, depth, camera, stride=1, orient="viewpoint", orient_k=8, on_cloud=None):
+        """Depth frame in, normal image out (``depth.py``; DESIGN.md 2 "Depth images"): back-project ``depth`` [H,W] (uint16 or
+        float32) through ``camera`` (``depth.Camera``), prepare the cloud of valid pixels, estimate -- :meth:`run`, or
+        :meth:`run_verified` when the estimator is reproducible -- at every valid pixel, or with ``stride`` > 1 at the valid pixels
+        with ``v % stride == 0 and u % stride == 0`` (``pidx`` = their cloud rows; the neighbourhoods still come from every valid
+        pixel), orient, and scatter the rows into images.  ``orient``: ``'viewpoint'`` (default; the viewpoint is the camera centre:
+        the pose's translation column, or the origin), ``'mst'`` (rooted at the point nearest to the camera) or None.
+        ``on_cloud(cloud)`` (optional) is called with the prepared ``CloudPatches`` before anything runs (per-frame calibration).
+
+        Returns a dict of numpy arrays (synchronises): ``normal_map`` [H,W,3] f32 (fill 0 0 0), ``expert_map`` [H,W] int32 (fill -1)
+        and ``probs_map`` [H,W,E] f32 (fill 0) -- both omitted for the single-tower models -- and per estimated pixel, in pixel
+        order, ``xyz``, ``pix`` (pixel index ``v W + u``), ``normals``, ``expert``, ``probs`` (None for the single-tower models).  A
+        frame without a valid pixel gives all-fill maps and empty rows without touching the network.  The cloud passes through the
+        host once (``CloudPatches`` takes a host array and computes the bounding-box diagonal there)."""
+        from . import depth as _depth
+        if orient not in (None, "mst", "viewpoint"):
+            raise ValueError("orient must be None, 'mst' or 'viewpoint'")
+        single_tower = self.cfg.arch in (ARCH_SINGLE, ARCH_MULTI)
+        E = max(1, self.cfg.n_gate_out)
+        dc = _depth.depth_to_cloud(depth, camera, stride=stride, device=self.device)
+        H, W = dc.H, dc.W
+        rows = dc.n_valid if dc.stride == 1 else dc.n_queries
+        with torch.cuda.device(self.device):
+            if rows == 0:
+                normals = torch.empty((0, 3), dtype=torch.float32, device=self.device)
+                expert = None if single_tower else torch.empty((0,), dtype=torch.int32, device=self.device)
+                probs = None if single_tower else torch.empty((0, E), dtype=torch.float32, device=self.device)
+                xyz, pix = dc.xyz[:0], dc.pix[:0]
+            else:
+                sparse = dc.stride > 1
+                cloud = self.prepare(dc.xyz.cpu().numpy(), pidx=dc.qidx.cpu().numpy() if sparse else None)
+                if on_cloud is not None:
+                    on_cloud(cloud)
+                normals, expert, probs = self.run_verified(cloud) if self.reproducible else self.run(cloud)
+                if orient is not None:
+                    from .orient import stats_dict
+                    self.last_orient = stats_dict(self.orient(cloud, normals, orient, dc.viewpoint, orient_k))
+                sel = dc.qidx.long() if sparse else None
+                xyz = dc.xyz[sel] if sparse else dc.xyz
+                pix = dc.pix[sel].contiguous() if sparse else dc.pix
+            out = {"normal_map": _depth.scatter_to_image(normals, pix, H, W, 0.0)}
+            if not single_tower:
+                out["expert_map"] = _depth.scatter_to_image(expert, pix, H, W, -1)
+                out["probs_map"] = _depth.scatter_to_image(probs, pix, H, W, 0.0)
+            out.update(xyz=xyz, pix=pix, normals=normals, expert=expert, probs=probs)
+            torch.cuda.synchronize(self.device)
+        return {k: None if v is None else v.cpu().numpy() for k, v in out.items()}

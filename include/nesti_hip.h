@@ -463,6 +463,41 @@ int nesti_orient_normals(const float* xyz_dev, int M, float* normals_dev, int mo
                          void* ws_dev, size_t ws_bytes, uint8_t* tree_edge_out_dev,
                          nesti_orient_stats_t* stats_dev, void* stream);
 
+/* ---- plane-fit (PCA) normals and surface variation at every patch scale (pca.hip; DESIGN.md 2 "Plane-fit normals") -------------
+ * The classical estimator: the first row of the paper's comparison tables and the frame of the reference dataset's use_pca step
+ * (utils/pcpnet_dataset.py:357-377, which the test path never takes; the per-scale estimator itself has no reference call site).
+ * No model, no weights.  Queries, radii, grid workspace and query_row0 as for nesti_patches_count / nesti_patches_query_at
+ * (query_idx_dev NULL: row i is cloud point query_row0 + i; positions may lie anywhere and may be non-finite).  Per query and scale s,
+ * over the FULL ball B = {p : fp64 d2(p, c) <= r_s^2} -- the ball test of nesti_patches_query, NOT capped at points_per_scale and not
+ * subsampled -- with d = (double)p - (double)c:
+ *     n = |B|,  m = (sum d) / n,  C = ((sum d d^T) / n - m m^T) / r_s^2     (units of r^2: eigenvalues are scale-free and <= 1)
+ *     eigen-decomposition of C in fp64 (cyclic Jacobi, a fixed number of sweeps: nesti_sym3_eig), eigenvalues w0 <= w1 <= w2.
+ * Outputs (device; any may be NULL):
+ *     normals_out_dev [M,S,3] f32  the eigenvector of w0, normalised in fp64 and rounded to f32 once; then, on the f32 values, signed
+ *                                  so that the first non-zero of (n_z, n_y, n_x) is positive (the root rule of nesti_orient_normals);
+ *                                  zeros are +0
+ *     eig_out_dev     [M,S,3] f32  max(0, w_k), ascending; surface variation = w0 / (w0 + w1 + w2)
+ *     n_ball_out_dev  [M,S] int32  n (what nesti_patches_count writes)
+ * SENTINEL: a scale with n < 3 -- an empty ball, and every scale of a non-finite position -- gets normal 0 0 0 and eigenvalues
+ * 0 0 0; its count is still written.
+ * DETERMINISM: no floating-point atomics; for ONE grid (one nesti_patches_grid call) a row's outputs are identical bits however the
+ * rows are split over calls and streams.  The grid's cell-ordered copy is filled through an atomic cursor, so the order of the points
+ * inside a cell, and with it the last bits of an fp64 sum, may differ between two grid builds: across builds the counts are equal,
+ * eigenvalues agree to ~2^-23 relative + 8 n 2^-53 and directions to 2^-22 + 16 n 2^-53 / (w1 - w0) (tests/test_gpu_pca.py).
+ * Argument errors (null cfg / cloud / radii / workspace, M < 0, a short workspace, n_scales outside 1 .. NESTI_MAX_SCALES, a radius
+ * that is not finite or <= 0, rows beyond the cloud) are reported before any device call; M = 0 is a no-op.  The calls enqueue one
+ * kernel on `stream`, neither synchronise nor read anything back, and can be captured into a graph. */
+int nesti_pca_normals(const nesti_config_t* cfg, const float* cloud_dev, int N, const int32_t* query_idx_dev, int M,
+                      const double* r_abs, int query_row0, float* normals_out_dev, float* eig_out_dev,
+                      int32_t* n_ball_out_dev, const void* grid_ws_dev, size_t grid_ws_bytes, void* stream);
+int nesti_pca_normals_at(const nesti_config_t* cfg, const float* cloud_dev, int N, const float* query_xyz_dev, int M,
+                         const double* r_abs, int query_row0, float* normals_out_dev, float* eig_out_dev,
+                         int32_t* n_ball_out_dev, const void* grid_ws_dev, size_t grid_ws_bytes, void* stream);
+/* Host only: the solver of the two entries above, the same arithmetic on the CPU (csrc/pca_eig.h).  c = {xx, xy, xz, yy, yz, zz};
+ * w[3]: eigenvalues ascending (not clamped); v[9]: v[3 k + i] = component i of the unit eigenvector of w[k].  Only + - x / sqrt,
+ * every operation rounded on its own.  Returns 1 for a null pointer. */
+int nesti_sym3_eig(const double c[6], double w[3], double v[9]);
+
 /* ---- depth images in, normal images out (depth.hip; DESIGN.md 2 "Depth images") --------------------------------------------------
  * The two ends of the reference's Kinect route: MATLAB/ScanNet_depth2xyz.m (depth + intrinsics + pose -> cloud) before
  * test_n_est_w_experts.py, and MATLAB/ScanNet_world2cam_normals.m / MATLAB/export_visualizations_nyu.m:146-153 (per-point results

@@ -8,7 +8,8 @@ depth frames (``<name>.depth.npy``, ``<name>.camera``, optional ``<name>.cam2wor
 The trained-model directory holds either ``model.nstw`` (variables + hyper-parameters, see
 :mod:`.weights`) or the reference's own ``parameters.p`` / ``gmm.p`` / ``model.ckpt.*`` (read by
 :mod:`.tf_ckpt` without TensorFlow); ``--synthetic_weights`` substitutes seeded random weights (no
-checkpoint ships with the reference)."""
+checkpoint ships with the reference).  ``--estimator pca`` needs none of them: the plane-fit normals of :mod:`.pca`, written as
+``<shape>.normals`` (one scale), ``<shape>.pca_eig`` and ``<shape>.pca_count`` (every scale)."""
 import argparse
 import ctypes
 import os
@@ -96,6 +97,17 @@ def build_parser():
     p.add_argument("--orient_k", type=int, default=8, help="--orient mst: neighbours per point, 1 .. 16 [default: 8]")
     p.add_argument("--viewpoint", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"),
                    help="--orient viewpoint (required) / --orient mst (optional): the sensor position in the cloud's coordinates")
+    p.add_argument("--estimator", default="net", choices=["net", "pca"],
+                   help="net (default): Nesti-Net, from the trained model in --results_path.  pca: the classical plane fit at every patch "
+                        "radius of --model's configuration (DESIGN.md 2 'Plane-fit normals'); no model.nstw and no --synthetic_weights "
+                        "are needed or read.  Writes <shape>.normals (the scale --pca_scale), <shape>.pca_eig (M rows of 3 S "
+                        "eigenvalues in units of r^2, ascending per scale; surface variation = the first over the sum of the three) and "
+                        "<shape>.pca_count (M rows of S ball sizes); a scale whose ball holds fewer than 3 points is written as 0 0 0.  "
+                        "Honours --sparse_patches, --query_positions, --orient, --orient_k and --viewpoint (the orientation radius is "
+                        "that of --pca_scale); --depth_images 1, --reproducible 1 and --subsample reference* belong to net")
+    p.add_argument("--pca_scale", type=int, default=-1,
+                   help="--estimator pca: the scale whose normals go to <shape>.normals, an index into the patch radii; negative "
+                        "counts from the end [default: -1, the largest]")
     p.add_argument("--synthetic_weights", action="store_true", help="use seeded synthetic weights if model.nstw is absent")
     return p
 
@@ -166,9 +178,44 @@ def run_depth_frame(est, frames, name, FLAGS, output_dir, printout, on_cloud, wr
     printout("saved experts for " + name)
 
 
+def run_pca(FLAGS, cfg, scale, pc_path, output_dir, printout):
+    """``--estimator pca``: per shape the plane fit at every scale, the optional orientation of the rows of scale ``scale`` (>= 0), and
+    the three files.  No model is loaded."""
+    from . import pca as _pca
+    dataset = PointcloudPatchDataset(pc_path, FLAGS.testset, cfg, seed=3627473, sparse_patches=FLAGS.sparse_patches,
+                                     device="cuda:%d" % FLAGS.gpu, query_positions=bool(FLAGS.query_positions))
+    for ind, name in enumerate(dataset.shape_names):
+        cloud = dataset.get_shape(ind)
+        res = _pca.pca_cloud(cloud, scale, None if FLAGS.orient == "0" else FLAGS.orient, FLAGS.viewpoint, FLAGS.orient_k)
+        short = int((res["n_ball"][:, scale] < 3).sum())
+        printout("plane fit of %s: %d rows, radius %.6g (scale %d of %d); %d rows with fewer than 3 points in that ball (written as 0 0 0)"
+                 % (name, cloud.patch_count, cloud.r_abs[scale], scale, cfg.n_scales, short))
+        if res["orient"] is not None:
+            ost = res["orient"]
+            printout("orientation of %s (%s): %d of %d rows oriented, %d flipped, %d connected piece%s, %d edges"
+                     % (name, FLAGS.orient, ost["n_eligible"], cloud.patch_count, ost["n_flipped"], ost["n_components"],
+                        "" if ost["n_components"] == 1 else "s", ost["n_edges"]))
+        textio.write_f32(os.path.join(output_dir, name + ".normals"), res["normals"])
+        textio.write_f32(os.path.join(output_dir, name + ".pca_eig"), res["eig"].reshape(len(res["eig"]), -1))
+        textio.write_i32_rows(os.path.join(output_dir, name + ".pca_count"), res["n_ball"])
+        printout("saved normals, eigenvalues and ball sizes for " + name)
+    return 0
+
+
 def main(argv=None):
     parser = build_parser()
     FLAGS = parser.parse_args(argv)
+    if FLAGS.estimator == "pca":
+        if FLAGS.depth_images:
+            parser.error("--estimator pca does not take --depth_images 1: depth frames belong to the network path (--estimator net)")
+        if FLAGS.reproducible:
+            parser.error("--estimator pca does not take --reproducible 1: it freezes the network's thresholds (--estimator net); the "
+                         "plane fit has none")
+        if FLAGS.subsample != "hash":
+            parser.error("--estimator pca does not take --subsample %s: the plane fit uses the full ball and subsamples nothing"
+                         % FLAGS.subsample)
+    elif FLAGS.pca_scale != -1:
+        parser.error("--pca_scale belongs to --estimator pca")
     if FLAGS.query_positions and FLAGS.sparse_patches:
         parser.error("--query_positions 1 and --sparse_patches 1 are mutually exclusive: the queries are positions or cloud points")
     if FLAGS.query_positions and FLAGS.subsample != "hash":
@@ -207,6 +254,17 @@ def main(argv=None):
         print(data)
         flog.write(data + "\n")
         sys.stdout.flush()
+
+    if FLAGS.estimator == "pca":
+        from .pca import check_scale
+        cfg = NestiConfig.for_model(FLAGS.model)
+        try:
+            scale = check_scale(FLAGS.pca_scale, cfg.n_scales)
+        except ValueError as e:
+            raise SystemExit("--pca_scale with --model %s: %s" % (FLAGS.model, e))
+        rc = run_pca(FLAGS, cfg, scale, pc_path, output_dir, printout)
+        flog.close()
+        return rc
 
     model_file = os.path.join(results_path, "model.nstw")
     if os.path.exists(model_file):

@@ -1,0 +1,229 @@
+// Plane-fit (PCA) normals and surface variation at every patch scale ("Plane-fit normals"): the classical estimator, the
+// first row of the paper's comparison tables and the frame of the reference dataset's use_pca step (utils/pcpnet_dataset.py:357-377,
+// which the test path never takes).  It needs no model and no weights.
+//
+// Per query and scale s, over the FULL ball B_s = {p : d2(p, c) <= r_s^2} of the search grid (patches.hip; the fp64 ball test of
+// patch_query_setup, not capped at P and not subsampled), with d = (double)p - (double)c:
+//     n = |B_s|,  m = (sum d) / n,  C = ((sum d d^T) / n - m m^T) / r_s^2          (units of r^2: eigenvalues are scale-free, <= 1)
+//     (w, V) = sym3_eig(C)  (pca_eig.h: cyclic Jacobi, fp64, fixed sweeps),  w ascending
+//     normal  = V[0] normalised in fp64, rounded to f32 once, then signed ON THE F32 VALUES so that the first non-zero of
+//               (n_z, n_y, n_x) is positive (the rule orient.hip uses for a tree root); zeros are written as +0
+//     eig     = (float)max(0, w_k)
+// A scale with n < 3 writes normal 0 0 0 and eigenvalues 0 0 0 (the count is still written): an empty ball, a lone point, and every
+// scale of a query whose position is not finite (it visits no cell, so n = 0).
+//
+// One wave per query, four queries per workgroup (the candidates of a query are a few thousand float4: ~50 trips per lane; no LDS, no
+// barrier; the nine fp64 sums and the count of a scale are each reduced by one fixed xor-butterfly of wave shuffles).  A candidate is tested once for all
+// scales: the six products of d are formed once and added to the sums of every scale whose ball holds it.  Lane s then solves scale s.
+//
+// DETERMINISM.  No floating-point atomics and no dependence on which workgroup runs first: candidate i of a span goes to lane
+// (i - span begin) mod 64 and the lanes meet in a fixed tree, so for ONE prepared grid a row's outputs are identical bits however the
+// rows are batched.  The cell-ordered copy of the cloud is filled through an atomic cursor (patches.hip: fill_kernel): the order inside
+// a cell, and with it the last bits of an fp64 sum, may differ between two grid builds.  Across grid builds the outputs agree to the
+// bounds of tests/test_gpu_pca.py (counts exactly), no more is promised.
+#include <string.h>
+
+#include <cmath>
+#include <string>
+
+#include "kernels.h"
+#include "patches_dev.h"
+
+// every product and sum below -- the solver of pca_eig.h included -- is rounded on its own, on the host (nesti_sym3_eig) as on the
+// device: the CPU restatement (tests/_pca_fixture.py) bounds each step
+#pragma clang fp contract(off)
+
+#include "pca_eig.h"
+
+namespace nesti {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWave = 64;
+constexpr int kRowsPerBlock = kThreads / kWave;
+constexpr int kSums = 9;              // sum d (3), sum d d^T (6: xx xy xz yy yz zz)
+
+struct PcaParams {
+  PatchParams p;                      // points_out / n_eff_out / nbr_out unused; n_ball_out optional
+  float* normals_out;                 // [M, S, 3] or NULL
+  float* eig_out;                     // [M, S, 3] or NULL
+};
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) v = v + __shfl_xor(v, off, kWave);
+  return v;
+}
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+  return v;
+}
+
+template <int S>
+__global__ __launch_bounds__(kThreads) void pca_kernel(const PcaParams pp) {
+  const PatchParams& p = pp.p;
+  const int lane = threadIdx.x & (kWave - 1);
+  // the row is the same in every lane of a wave: say so, and the centre and its tests live in scalar registers
+  const int q = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6)));
+  if (q >= p.M) return;                                       // whole waves leave: the shuffles below see full waves
+  const float* centre;
+  if (p.query_xyz) {
+    centre = p.query_xyz + (size_t)q * 3;
+  } else {
+    int qi = p.query_idx ? p.query_idx[q] : p.row0 + q;
+    qi = min(max(qi, 0), p.N - 1);
+    centre = p.cloud + (size_t)qi * 3;
+  }
+  const float cf0 = centre[0], cf1 = centre[1], cf2 = centre[2];
+  // a centre with an infinite or NaN coordinate has empty balls: it visits no cell (patches_dev.h)
+  const bool lost = non_finite_bits(cf0) || non_finite_bits(cf1) || non_finite_bits(cf2);
+  int b = 0, e = 0;
+  if (!lost && lane < 9) {                                    // the nine x-spans of the 3 x 3 x 3 cell block, as patch_query_setup
+    const GridHeader h = *p.header;
+    int ix, iy, iz;
+    cell_coords(h, cf0, cf1, cf2, &ix, &iy, &iz);
+    const int zz = iz + lane / 3 - 1, yy = iy + lane % 3 - 1;
+    if (zz >= 0 && zz < h.dims[2] && yy >= 0 && yy < h.dims[1]) {
+      const int x0 = max(ix - 1, 0), x1 = min(ix + 1, h.dims[0] - 1);
+      b = p.start[cell_flat(h, x0, yy, zz)];
+      e = p.start[cell_flat(h, x1, yy, zz) + 1];
+    }
+  }
+  const double cx = cf0, cy = cf1, cz = cf2;
+  double acc[S][kSums];
+  int cnt[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    cnt[s] = 0;
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) acc[s][k] = 0.0;
+  }
+  for (int sp = 0; sp < 9; ++sp) {
+    const int sb = max(__shfl(b, sp, kWave), 0), se = min(__shfl(e, sp, kWave), p.N);   // a span never leaves the cell-ordered copy
+    for (int i = sb + lane; i < se; i += kWave) {
+      const float4 c = p.sorted[i];
+      const double dx = (double)c.x - cx, dy = (double)c.y - cy, dz = (double)c.z - cz;
+      const double xx = __dmul_rn(dx, dx), yy = __dmul_rn(dy, dy), zz = __dmul_rn(dz, dz);
+      const double d2 = __dadd_rn(__dadd_rn(xx, yy), zz);     // the ball test of pass A (patches_dev.h), operation for operation
+      const double xy = dx * dy, xz = dx * dz, yz = dy * dz;
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        if (d2 <= p.r2[s]) {
+          ++cnt[s];
+          acc[s][0] += dx; acc[s][1] += dy; acc[s][2] += dz;
+          acc[s][3] += xx; acc[s][4] += xy; acc[s][5] += xz;
+          acc[s][6] += yy; acc[s][7] += yz; acc[s][8] += zz;
+        }
+      }
+    }
+  }
+  // every lane ends up with every total; lane s keeps those of scale s (lanes >= S: of the last scale, and write nothing)
+  double sum[kSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  int n = 0;
+  double r2 = 1.0;
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    const int ns = wave_sum(cnt[s]);
+    const bool mine = lane == s || (s == S - 1 && lane >= S);
+    if (mine) { n = ns; r2 = p.r2[s]; }
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) {
+      const double t = wave_sum(acc[s][k]);
+      if (mine) sum[k] = t;
+    }
+  }
+  if (lane >= S) return;
+  float nrm[3] = {0.f, 0.f, 0.f}, ev[3] = {0.f, 0.f, 0.f};
+  if (n >= 3) {
+    const double dn = (double)n;
+    const double mx = sum[0] / dn, my = sum[1] / dn, mz = sum[2] / dn;
+    const double c[6] = {(sum[3] / dn - mx * mx) / r2, (sum[4] / dn - mx * my) / r2, (sum[5] / dn - mx * mz) / r2,
+                         (sum[6] / dn - my * my) / r2, (sum[7] / dn - my * mz) / r2, (sum[8] / dn - mz * mz) / r2};
+    double w[3], vec[3][3];
+    sym3_eig(c, w, vec);
+    const double len = sqrt((vec[0][0] * vec[0][0] + vec[0][1] * vec[0][1]) + vec[0][2] * vec[0][2]);
+    float fx = (float)(vec[0][0] / len), fy = (float)(vec[0][1] / len), fz = (float)(vec[0][2] / len);
+    const float lead = fz != 0.f ? fz : (fy != 0.f ? fy : fx);
+    if (lead < 0.f) { fx = -fx; fy = -fy; fz = -fz; }
+    nrm[0] = fx + 0.f; nrm[1] = fy + 0.f; nrm[2] = fz + 0.f;   // -0 + +0 = +0: no negative zero leaves
+#pragma unroll
+    for (int k = 0; k < 3; ++k) ev[k] = (float)fmax(0.0, w[k]);
+  }
+  const size_t o = (size_t)q * S + lane;
+  if (pp.normals_out) { pp.normals_out[o * 3] = nrm[0]; pp.normals_out[o * 3 + 1] = nrm[1]; pp.normals_out[o * 3 + 2] = nrm[2]; }
+  if (pp.eig_out) { pp.eig_out[o * 3] = ev[0]; pp.eig_out[o * 3 + 1] = ev[1]; pp.eig_out[o * 3 + 2] = ev[2]; }
+  if (p.n_ball_out) p.n_ball_out[o] = n;
+}
+
+// nesti_pca_normals (centres = cloud points, by index or row) and nesti_pca_normals_at (centres = positions): one body
+int pca_impl(const char* who, bool at, const nesti_config_t* cfg, const float* cloud_dev, int N, const int32_t* query_idx_dev,
+             const float* query_xyz_dev, int M, const double* r_abs, int query_row0, float* normals_out_dev, float* eig_out_dev,
+             int32_t* n_ball_out_dev, const void* grid_ws_dev, size_t grid_ws_bytes, void* stream) {
+  const std::string w(who);
+  if (!cfg || !cloud_dev || !r_abs || !grid_ws_dev) NESTI_FAIL(w + ": null argument");
+  if (N <= 0) NESTI_FAIL(w + ": empty cloud");
+  if (M < 0) NESTI_FAIL(w + ": M must be >= 0");
+  if (cfg->n_scales < 1 || cfg->n_scales > NESTI_MAX_SCALES) NESTI_FAIL(w + ": bad n_scales");
+  if (grid_ws_bytes < patch_ws_layout(N).total) NESTI_FAIL(w + ": grid workspace too small");
+  if (query_row0 < 0) NESTI_FAIL(w + ": query_row0 must be >= 0");
+  for (int s = 0; s < cfg->n_scales; ++s)
+    if (!(r_abs[s] > 0.0) || !std::isfinite(r_abs[s])) NESTI_FAIL(w + ": radii must be positive and finite");
+  if (M == 0) return 0;
+  if (at && !query_xyz_dev) NESTI_FAIL(w + ": null query_xyz_dev");
+  if (!at && !query_idx_dev && (long long)query_row0 + M > (long long)N)
+    NESTI_FAIL(w + ": query rows [query_row0, query_row0 + M) exceed the cloud (N points)");
+  PcaParams pp;
+  patch_params_fill(&pp.p, cfg, cloud_dev, N, query_idx_dev, M, r_abs, 0, query_row0, grid_ws_dev);
+  pp.p.query_xyz = at ? query_xyz_dev : nullptr;
+  pp.p.n_ball_out = n_ball_out_dev;
+  pp.normals_out = normals_out_dev;
+  pp.eig_out = eig_out_dev;
+  const dim3 grid((unsigned)((M + kRowsPerBlock - 1) / kRowsPerBlock)), block(kThreads);
+  hipStream_t st = (hipStream_t)stream;
+  const int tok = prof_begin(NESTI_PROF_PATCHES, st);
+  switch (cfg->n_scales) {
+    case 1: hipLaunchKernelGGL(pca_kernel<1>, grid, block, 0, st, pp); break;
+    case 2: hipLaunchKernelGGL(pca_kernel<2>, grid, block, 0, st, pp); break;
+    case 3: hipLaunchKernelGGL(pca_kernel<3>, grid, block, 0, st, pp); break;
+    default: hipLaunchKernelGGL(pca_kernel<4>, grid, block, 0, st, pp); break;
+  }
+  prof_end(NESTI_PROF_PATCHES, tok, st);
+  NESTI_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+}  // namespace nesti
+
+using namespace nesti;
+
+extern "C" {
+
+int nesti_pca_normals(const nesti_config_t* cfg, const float* cloud_dev, int N, const int32_t* query_idx_dev, int M,
+                      const double* r_abs, int query_row0, float* normals_out_dev, float* eig_out_dev, int32_t* n_ball_out_dev,
+                      const void* grid_ws_dev, size_t grid_ws_bytes, void* stream) {
+  return pca_impl("nesti_pca_normals", false, cfg, cloud_dev, N, query_idx_dev, nullptr, M, r_abs, query_row0, normals_out_dev,
+                  eig_out_dev, n_ball_out_dev, grid_ws_dev, grid_ws_bytes, stream);
+}
+
+int nesti_pca_normals_at(const nesti_config_t* cfg, const float* cloud_dev, int N, const float* query_xyz_dev, int M,
+                         const double* r_abs, int query_row0, float* normals_out_dev, float* eig_out_dev, int32_t* n_ball_out_dev,
+                         const void* grid_ws_dev, size_t grid_ws_bytes, void* stream) {
+  return pca_impl("nesti_pca_normals_at", true, cfg, cloud_dev, N, nullptr, query_xyz_dev, M, r_abs, query_row0, normals_out_dev,
+                  eig_out_dev, n_ball_out_dev, grid_ws_dev, grid_ws_bytes, stream);
+}
+
+int nesti_sym3_eig(const double c[6], double w[3], double v[9]) {
+  if (!c || !w || !v) NESTI_FAIL("nesti_sym3_eig: null argument");
+  const double cc[6] = {c[0], c[1], c[2], c[3], c[4], c[5]};
+  double ww[3], vec[3][3];
+  sym3_eig(cc, ww, vec);
+  for (int k = 0; k < 3; ++k) {
+    w[k] = ww[k];
+    for (int i = 0; i < 3; ++i) v[3 * k + i] = vec[k][i];
+  }
+  return 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,89 @@
+"""Plane-fit (PCA) normals and surface variation at every patch scale on the GPU (``csrc/pca.hip``; DESIGN.md 2 "Plane-fit normals"):
+the classical estimator -- the first row of the paper's comparison tables, and the frame of the reference dataset's ``use_pca`` step
+(``utils/pcpnet_dataset.py:357-377``).  It needs no model and no weights: per query and patch radius, the plane fitted to the full
+ball; the normal is the eigenvector of the smallest eigenvalue of the ball's covariance and the three eigenvalues give the surface
+variation ``w0 / (w0 + w1 + w2)``.  There is no CPU fallback."""
+import numpy as np
+
+from . import _lib
+from .config import NestiConfig
+
+ORIENT_MODES = (None, "mst", "viewpoint")
+
+
+def check_scale(scale, n_scales):
+    """``scale`` in [-S, S) -> its non-negative index; ``ValueError`` otherwise."""
+    if int(scale) != scale or not -n_scales <= int(scale) < n_scales:
+        raise ValueError("scale must be in [-%d, %d): got %r" % (n_scales, n_scales, scale))
+    return int(scale) % n_scales
+
+
+def variation(eig):
+    """Surface variation ``w0 / (w0 + w1 + w2)`` of eigenvalues [..., 3] (float32 in, float32 out), 0 where the sum is 0."""
+    eig = np.asarray(eig, np.float32)
+    total = eig.sum(axis=-1, dtype=np.float32)
+    return np.divide(eig[..., 0], total, out=np.zeros_like(total), where=total != 0)
+
+
+def orient_rows(cloud, normals, scale, mode, viewpoint=None, k=8):
+    """Orient the rows ``normals`` [patch_count, 3] (contiguous, on the cloud's device) of a prepared cloud IN PLACE with
+    ``orient.orient_device``, the way ``NormalEstimator.orient`` does: positions are the cloud, ``cloud[pidx]`` or the (harmless) query
+    positions; the radius is ``r_abs[scale]``.  Only sign bits change, sentinel rows stay 0 0 0.  Returns the int32[4] stats tensor."""
+    import torch
+    from . import orient as _orient
+    if cloud.queries is not None:
+        pos = _orient.harmless_positions(cloud.queries)
+    elif cloud.pidx is not None:
+        pos = cloud.cloud[cloud.pidx.long()].contiguous()
+    else:
+        pos = cloud.cloud
+    return _orient.orient_device(pos, normals, float(cloud.r_abs[scale]), k, viewpoint, mode, torch.cuda.current_stream(cloud.device))
+
+
+def pca_cloud(cloud, scale=-1, orient=None, viewpoint=None, orient_k=8):
+    """``pca_normals`` for a prepared ``provider.CloudPatches`` (all of its patch rows); synchronises."""
+    import torch
+    from . import orient as _orient
+    s = check_scale(scale, cloud.cfg.n_scales)
+    if orient not in ORIENT_MODES:
+        raise ValueError("orient must be None, 'mst' or 'viewpoint'")
+    with torch.cuda.device(cloud.device):
+        normals_all, eig, n_ball = cloud.pca(0, cloud.patch_count)
+        normals = normals_all[:, s, :].contiguous()
+        stats = None
+        if orient is not None and cloud.patch_count:
+            stats = orient_rows(cloud, normals, s, orient, viewpoint, orient_k)
+        torch.cuda.current_stream(cloud.device).synchronize()
+    eig_h = eig.cpu().numpy()
+    return {"normals": normals.cpu().numpy(), "normals_all": normals_all.cpu().numpy(), "eig": eig_h, "variation": variation(eig_h),
+            "n_ball": n_ball.cpu().numpy(),
+            "orient": None if orient is None else (_orient.stats_dict(stats) if stats is not None else dict.fromkeys(_orient.STAT_NAMES, 0))}
+
+
+def pca_normals(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, viewpoint=None, orient_k=8, device="cuda:0"):
+    """Plane-fit normals of a cloud: numpy in, a dict of numpy arrays out (synchronises).  Queries are all points, the points
+    ``pidx`` or the positions ``queries`` [M,3] (mutually exclusive), as for ``NormalEstimator.estimate``; the radii are
+    ``cfg.patch_radius`` times the cloud's bounding-box diagonal.
+
+      normals      [M,3]    the normals at ``scale`` (default -1: the largest), after the optional orientation
+      normals_all  [M,S,3]  every scale, unoriented: the first non-zero of (n_z, n_y, n_x) is positive
+      eig          [M,S,3]  eigenvalues of the ball's covariance in units of r^2, ascending
+      variation    [M,S]    w0 / (w0 + w1 + w2), 0 where the sum is 0
+      n_ball       [M,S]    points in the ball (the full ball: not capped at ``cfg.num_point``, not subsampled)
+      orient       the stats dict of ``orient.orient_normals``, or None
+
+    A scale whose ball holds fewer than 3 points has normal 0 0 0 and eigenvalues 0 0 0; the orientation leaves such rows alone.
+    ``orient='mst' | 'viewpoint'`` orients the rows of ``scale`` with radius ``r_abs[scale]`` (only sign bits change).
+    Raises ``ValueError`` for a ``scale`` outside [-S, S) and for ``pidx`` together with ``queries``."""
+    cfg = cfg or NestiConfig()
+    check_scale(scale, cfg.n_scales)
+    if orient not in ORIENT_MODES:
+        raise ValueError("orient must be None, 'mst' or 'viewpoint'")
+    if pidx is not None and queries is not None:
+        raise ValueError("pidx and queries are mutually exclusive: a query is a cloud point (pidx) or a position (queries)")
+    if orient is not None:
+        from .orient import _check_args
+        _check_args(1.0, orient_k, viewpoint, orient)
+    from .provider import CloudPatches
+    cloud = CloudPatches(np.asarray(pts, dtype=np.float32), cfg, device=device, pidx=pidx, queries=queries)
+    return pca_cloud(cloud, scale, orient, viewpoint, orient_k)

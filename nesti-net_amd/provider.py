@@ -181,6 +181,37 @@ class CloudPatches:
                                                     ctypes.c_void_p(st.cuda_stream)), "nesti_patches_count")
         return n_ball
 
+    def pca(self, first, count, out=None, stream=None):
+        """Plane-fit normals of patch rows [first, first + count) at every scale (``nesti_pca_normals`` / ``nesti_pca_normals_at``;
+        DESIGN.md 2 "Plane-fit normals"): device tensors ``(normals [count,S,3] f32, eig [count,S,3] f32, n_ball [count,S] int32)``,
+        or the three of ``out``.  Serves all points, ``pidx`` and ``queries``; asynchronous on ``stream``.  A scale whose ball holds
+        fewer than 3 points has normal 0 0 0 and eigenvalues 0 0 0.  For this grid a row's bits do not depend on the batching."""
+        S = self.cfg.n_scales
+        if first < 0 or count < 0 or first + count > self.patch_count:
+            raise ValueError("patch rows [%d, %d) outside [0, %d)" % (first, first + count, self.patch_count))
+        if out is None:
+            normals = torch.empty((count, S, 3), dtype=torch.float32, device=self.device)
+            eig = torch.empty((count, S, 3), dtype=torch.float32, device=self.device)
+            n_ball = torch.empty((count, S), dtype=torch.int32, device=self.device)
+        else:
+            normals, eig, n_ball = out
+            for t, shape, dt in ((normals, (count, S, 3), torch.float32), (eig, (count, S, 3), torch.float32), (n_ball, (count, S), torch.int32)):
+                if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+                    raise ValueError("out: contiguous (normals [count,S,3] f32, eig [count,S,3] f32, n_ball [count,S] int32) on %s" % self.device)
+        at = self.queries is not None
+        if at:
+            q = self.queries[first:first + count]
+        else:
+            q = self.pidx[first:first + count].contiguous() if self.pidx is not None else None
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        entry = "nesti_pca_normals_at" if at else "nesti_pca_normals"
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(self.lib, entry)(
+                ctypes.byref(self._c), _lib.ptr(self.cloud), self.n_points, _lib.ptr(q), count, self._r, ctypes.c_int(first),
+                _lib.ptr(normals), _lib.ptr(eig), _lib.ptr(n_ball), _lib.ptr(self._ws), self._ws.numel(),
+                ctypes.c_void_p(st.cuda_stream)), entry)
+        return normals, eig, n_ball
+
     def build_reference_order(self, first, count, picks, pick_offsets, want_idx=False, out=None, stream=None):
         """Patch tensors of rows [first, first + count) exactly as the reference's ``PointcloudPatchDataset.__getitem__`` builds
         them (``nesti_patches_query_ref``): balls in cKDTree's visiting order, over-full balls thinned by ``picks`` (uint16 device

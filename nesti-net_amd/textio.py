@@ -17,3 +17,12 @@ def write_i32(path, a):
     """Same bytes as ``np.savetxt(path, a.astype(int), fmt='%i')``."""
     a = np.ascontiguousarray(a, dtype=np.int32).ravel()
     _lib.check(_lib.load().nesti_write_text_i32(path.encode(), _lib.ptr(a), a.shape[0]), "nesti_write_text_i32")
+
+
+def write_i32_rows(path, a):
+    """Rows of integers, ``a`` [M, C]: same bytes as ``np.savetxt(path, a.astype(int), fmt='%i')`` -- for one column, ``write_i32``."""
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    a = a.reshape(a.shape[0], -1) if a.ndim > 1 else a.reshape(-1, 1)
+    if a.shape[1] == 1:
+        return write_i32(path, a)
+    np.savetxt(path, a, fmt="%i")

@@ -33,6 +33,10 @@ __device__ __forceinline__ int tap_slot_offset(int slot) {
   return PAIR ? (slot & 1) * 16 + (slot >> 1) * (2 * kSplitGroup) : slot * 16;
 }
 
+// exponent not all ones: neither +-inf nor NaN, tested on the bits of a per-lane value (an ordered compare would not do where a
+// file is built with -fno-honor-nans).  A wave-uniform query centre: non_finite_bits (patches_dev.h).
+__device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
 // ---- element conversion (device) ------------------------------------------
 // gfx950 converts in hardware (v_cvt_pk_bf16_f32, round-to-nearest-even, quiet NaN): no branches per element.
 typedef __attribute__((ext_vector_type(2))) float nesti_f32x2;

@@ -60,7 +60,7 @@ struct Frame {
   int type, H, W, n, stride;
 };
 
-__device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+using nesti::finite_bits;             // the float form (common.h); a declaration here alone would hide it
 __device__ __forceinline__ bool finite_bits(double v) {
   return ((unsigned long long)__double_as_longlong(v) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
 }

@@ -1,20 +1,8 @@
 // Stand-alone driver of the depth-image entries' host side (depth.hip): the workspace size and every argument refusal, all of which
 // return before any device call.  Built and run by `make asan-depth` against the AddressSanitizer build of the library.
 #include <math.h>
-#include <stdio.h>
-#include <string.h>
 
-#include "../../include/nesti_hip.h"
-
-static int failures = 0;
-
-static void refused(int rc, const char* word, const char* what) {
-  const char* msg = nesti_last_error();
-  if (rc == 0 || !msg || !strstr(msg, word)) {
-    printf("FAIL %s: rc %d, message '%s'\n", what, rc, msg ? msg : "(null)");
-    ++failures;
-  }
-}
+#include "args_main.h"
 
 static nesti_camera_t good_camera(void) {
   nesti_camera_t c;
@@ -108,6 +96,5 @@ int main() {
   }
   // a non-finite pose entry is not read when has_pose is 0: nothing to refuse there, and nothing else is wrong with this camera --
   // but the call would reach the device, so it is not made here
-  printf(failures ? "depth_args: %d failure(s)\n" : "depth_args: ok\n", failures);
-  return failures ? 1 : 0;
+  return finish("depth_args");
 }

@@ -3,9 +3,10 @@
 // "RMS oriented" figure (utils/evaluate.py:151).  The conventions below are the library's own.
 //
 //   grid (patches.hip, one scale of radius R)  ->  eligibility  ->  K nearest eligible neighbours inside R per row (fp64 distances,
-//   the ball test of patches_dev.h; one wave per row)  ->  one edge per unordered neighbour pair with key (bits of 1 - cos^2) << 32 | id
-//   ->  Boruvka's minimum spanning forest over a union-find whose words carry the sign parity to the parent  ->  per tree the root
-//   (largest z, or nearest to the viewpoint) and its sign  ->  sign flips.
+//   dot3 below: five separately rounded operations, NOT the fused ball_d2 of patches_dev.h; one wave per row)  ->  one edge per
+//   unordered neighbour pair with key (bits of 1 - cos^2) << 32 | id  ->  Boruvka's minimum spanning forest over a union-find whose
+//   words carry the sign parity to the parent  ->  per tree the root (largest z, or nearest to the viewpoint) and its sign  ->  sign
+//   flips.
 //
 // One kernel per step, fixed launch counts derived from M, integer atomics only: the result is a pure function of the inputs, no
 // workgroup waits on another and the host neither synchronises nor reads anything back.
@@ -60,7 +61,6 @@ inline OrientLayout orient_layout(int M, int K) {
   return L;
 }
 
-__device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 __device__ __forceinline__ bool nonzero_bits(float v) { return (__float_as_uint(v) & 0x7fffffffu) != 0u; }
 // all three components finite and at least one non-zero, on the bits
 __device__ __forceinline__ bool eligible_normal(const float* n) {
@@ -94,8 +94,8 @@ struct Cand {
 };
 __device__ __forceinline__ bool cand_less(const Cand& a, const Cand& b) { return a.d2 < b.d2 || (a.d2 == b.d2 && a.j < b.j); }
 
-// One wave per row.  The nine x-spans of the 3 x 3 x 3 cell block are those of patch_query_setup; every lane keeps the KC >= K
-// smallest (d2, j) of the candidates it saw, sorted, in registers; K rounds of a wave-wide minimum over the lanes' heads then emit
+// One wave per row.  The nine x-spans of the 3 x 3 x 3 cell block are block_span's (patches_dev.h), written out; every lane keeps the
+// KC >= K smallest (d2, j) of the candidates it saw, sorted, in registers; K rounds of a wave-wide minimum over the lanes' heads then emit
 // the list in order (the winner shifts its list down).  A candidate is seen by exactly one lane, so j identifies the winner.
 template <int KC>
 __global__ __launch_bounds__(kThreads) void orient_knn_kernel(const float* __restrict__ xyz, const unsigned char* __restrict__ elig,

@@ -1,20 +1,8 @@
 // Stand-alone driver of the orientation entries' host side (orient.hip): the workspace size and every argument refusal, all of which
 // return before any device call.  Built and run by `make asan-orient` against the AddressSanitizer build of the library.
 #include <math.h>
-#include <stdio.h>
-#include <string.h>
 
-#include "../../include/nesti_hip.h"
-
-static int failures = 0;
-
-static void refused(int rc, const char* word, const char* what) {
-  const char* msg = nesti_last_error();
-  if (rc == 0 || !msg || !strstr(msg, word)) {
-    printf("FAIL %s: rc %d, message '%s'\n", what, rc, msg ? msg : "(null)");
-    ++failures;
-  }
-}
+#include "args_main.h"
 
 int main() {
   const int M = 1000, K = 8;
@@ -63,6 +51,5 @@ int main() {
     printf("FAIL M = 0 is a no-op\n");
     ++failures;
   }
-  printf(failures ? "orient_args: %d failure(s)\n" : "orient_args: ok\n", failures);
-  return failures ? 1 : 0;
+  return finish("orient_args");
 }

@@ -196,44 +196,28 @@ __global__ __launch_bounds__(kRefThreads) void patches_ref_kernel(const RefParam
   __shared__ int span_beg[9], span_end[9], s_cnt, s_part[kRefThreads];
   const PatchParams& p = rp.p;
   const int q = blockIdx.x, t = threadIdx.x;
-  int qi = p.query_idx ? p.query_idx[q] : p.row0 + q;
-  qi = min(max(qi, 0), p.N - 1);
-  const GridHeader h = *p.header;
-  float cf[3] = {p.cloud[(size_t)qi * 3], p.cloud[(size_t)qi * 3 + 1], p.cloud[(size_t)qi * 3 + 2]};
-  const double cx = cf[0], cy = cf[1], cz = cf[2];
+  const float* centre = query_centre(p, q);
+  const float cf[3] = {centre[0], centre[1], centre[2]};
+  const bool lost = centre_lost(cf[0], cf[1], cf[2]);
   if (t < 9) {
-    int ix, iy, iz;
-    cell_coords(h, cf[0], cf[1], cf[2], &ix, &iy, &iz);
-    const int zz = iz + t / 3 - 1, yy = iy + t % 3 - 1;
-    int b = 0, e = 0;
-    if (zz >= 0 && zz < h.dims[2] && yy >= 0 && yy < h.dims[1]) {
-      const int x0 = max(ix - 1, 0), x1 = min(ix + 1, h.dims[0] - 1);
-      b = p.start[cell_flat(h, x0, yy, zz)];
-      e = p.start[cell_flat(h, x1, yy, zz) + 1];
-    }
-    span_beg[t] = b;
-    span_end[t] = e;
+    Span s = {0, 0};
+    if (!lost) s = block_span(*p.header, p.start, p.N, cf[0], cf[1], cf[2], t);
+    span_beg[t] = s.b;
+    span_end[t] = s.e;
   }
   if (t == 0) s_cnt = 0;
   __syncthreads();
   // ---- collect every point inside at least one ball: key = rank << 4 | mask of the scales whose ball holds it ---------------
-  for (int sp = 0; sp < 9; ++sp) {
-    for (int i = span_beg[sp] + t; i < span_end[sp]; i += kRefThreads) {
-      const float4 c = p.sorted[i];
-      const double dx = (double)c.x - cx, dy = (double)c.y - cy, dz = (double)c.z - cz;
-      double d2 = __dmul_rn(dx, dx);
-      d2 = __dadd_rn(d2, __dmul_rn(dy, dy));
-      d2 = __dadd_rn(d2, __dmul_rn(dz, dz));
-      unsigned mask = 0u;
+  walk_block(p.sorted, LdsSpans{span_beg, span_end}, t, kRefThreads, cf[0], cf[1], cf[2], [&](const float4& c, double d2) {
+    unsigned mask = 0u;
 #pragma unroll
-      for (int s = 0; s < NESTI_MAX_SCALES; ++s)
-        if (s < p.S && d2 <= p.r2[s]) mask |= 1u << s;
-      if (mask) {
-        const int pos = atomicAdd(&s_cnt, 1);
-        if (pos < kRefCap) keys[pos] = ((unsigned)rp.rank[__float_as_int(c.w)] << 4) | mask;
-      }
+    for (int s = 0; s < NESTI_MAX_SCALES; ++s)
+      if (s < p.S && d2 <= p.r2[s]) mask |= 1u << s;
+    if (mask) {
+      const int pos = atomicAdd(&s_cnt, 1);
+      if (pos < kRefCap) keys[pos] = ((unsigned)rp.rank[__float_as_int(c.w)] << 4) | mask;
     }
-  }
+  });
   __syncthreads();
   const int n_all = s_cnt;
   if (n_all > kRefCap) {                 // refused on the host before the launch (nesti_patches_query_ref's caller holds the counts)
@@ -323,11 +307,8 @@ size_t nesti_patches_workspace_bytes(int N) { return N > 0 ? patch_ws_layout(N).
 
 int nesti_patches_grid(const nesti_config_t* cfg, const float* cloud_dev, int N, const double* r_abs,
                        void* grid_ws_dev, size_t grid_ws_bytes, void* stream) {
-  if (!cfg || !cloud_dev || !r_abs || !grid_ws_dev) NESTI_FAIL("nesti_patches_grid: null argument");
-  if (N <= 0) NESTI_FAIL("nesti_patches_grid: empty cloud");
-  if (cfg->n_scales < 1 || cfg->n_scales > NESTI_MAX_SCALES) NESTI_FAIL("nesti_patches_grid: bad n_scales");
+  if (refuse_grid_cloud("nesti_patches_grid", cfg, cloud_dev, N, r_abs, grid_ws_dev, grid_ws_bytes)) return 1;
   const WsLayout L = patch_ws_layout(N);
-  if (grid_ws_bytes < L.total) NESTI_FAIL("nesti_patches_grid: grid workspace too small");
   hipStream_t st = (hipStream_t)stream;
   unsigned char* ws = (unsigned char*)grid_ws_dev;
   GridHeader* header = (GridHeader*)(ws + L.header);
@@ -359,22 +340,11 @@ static int patches_query_impl(const char* who, bool at, const nesti_config_t* cf
                               int query_row0, float* points_out_dev, int32_t* n_eff_out_dev, int32_t* nbr_idx_out_dev,
                               int32_t* n_ball_out_dev, const void* grid_ws_dev, size_t grid_ws_bytes, void* stream) {
   const std::string w(who);
-  if (!cfg || !cloud_dev || !r_abs || !grid_ws_dev) NESTI_FAIL(w + ": null argument");
-  if (N <= 0) NESTI_FAIL(w + ": empty cloud");
-  if (cfg->n_scales < 1 || cfg->n_scales > NESTI_MAX_SCALES) NESTI_FAIL(w + ": bad n_scales");
-  if (cfg->points_per_scale < 1 || 2 * cfg->points_per_scale > kListCap)
-    NESTI_FAIL(w + ": points_per_scale must be in [1, 512]");
-  const WsLayout L = patch_ws_layout(N);
-  if (grid_ws_bytes < L.total) NESTI_FAIL(w + ": grid workspace too small");
-  if (M <= 0) return 0;
-  // 'full' sampler (query_idx NULL): patch row == point index, so the row range must lie inside the cloud.  With a
-  // query list the indices live on the device; the host mirror (provider.CloudPatches) validates them once at upload
-  // and the kernel clamps defensively (a bad index then yields a wrong patch, never an out-of-bounds read).
-  // Positions: query_row0 is only the subsample key's row; any position is served (cell_coords, patches_dev.h).
-  if (query_row0 < 0) NESTI_FAIL(w + ": query_row0 must be >= 0");
+  if (refuse_grid_cloud(w, cfg, cloud_dev, N, r_abs, grid_ws_dev, grid_ws_bytes)) return 1;
+  if (cfg->points_per_scale < 1 || 2 * cfg->points_per_scale > kListCap) NESTI_FAIL(w + ": points_per_scale must be in [1, 512]");
+  if (M <= 0) return 0;                  // no queries: nothing to do, whatever query_row0 and the radii are
+  if (refuse_query_rows(w, N, !at && !query_idx_dev, M, query_row0)) return 1;
   if (at && !query_xyz_dev) NESTI_FAIL(w + ": null query_xyz_dev");
-  if (!at && !query_idx_dev && (long long)query_row0 + M > (long long)N)
-    NESTI_FAIL(w + ": query rows [query_row0, query_row0 + M) exceed the cloud (N points)");
   for (int s = 0; s < cfg->n_scales; ++s)
     if (!(r_abs[s] > 0.0)) NESTI_FAIL(w + ": radii must be positive");
   PatchParams p;
@@ -407,14 +377,9 @@ int nesti_patches_query_at(const nesti_config_t* cfg, const float* cloud_dev, in
 static int check_query_args(const char* who, const nesti_config_t* cfg, const float* cloud_dev, int N, const int32_t* query_idx_dev,
                             int M, const double* r_abs, int query_row0, const void* grid_ws_dev, size_t grid_ws_bytes) {
   const std::string w(who);
-  if (!cfg || !cloud_dev || !r_abs || !grid_ws_dev) NESTI_FAIL(w + ": null argument");
-  if (N <= 0) NESTI_FAIL(w + ": empty cloud");
-  if (cfg->n_scales < 1 || cfg->n_scales > NESTI_MAX_SCALES) NESTI_FAIL(w + ": bad n_scales");
+  if (refuse_grid_cloud(w, cfg, cloud_dev, N, r_abs, grid_ws_dev, grid_ws_bytes)) return 1;
   if (cfg->points_per_scale < 1 || 2 * cfg->points_per_scale > kListCap) NESTI_FAIL(w + ": points_per_scale must be in [1, 512]");
-  if (grid_ws_bytes < patch_ws_layout(N).total) NESTI_FAIL(w + ": grid workspace too small");
-  if (query_row0 < 0) NESTI_FAIL(w + ": query_row0 must be >= 0");
-  if (M > 0 && !query_idx_dev && (long long)query_row0 + M > (long long)N)
-    NESTI_FAIL(w + ": query rows [query_row0, query_row0 + M) exceed the cloud (N points)");
+  if (refuse_query_rows(w, N, !query_idx_dev, M, query_row0)) return 1;
   for (int s = 0; s < cfg->n_scales; ++s)
     if (!(r_abs[s] > 0.0)) NESTI_FAIL(w + ": radii must be positive");
   return 0;

@@ -2,8 +2,8 @@
 // first row of the paper's comparison tables and the frame of the reference dataset's use_pca step (utils/pcpnet_dataset.py:357-377,
 // which the test path never takes).  It needs no model and no weights.
 //
-// Per query and scale s, over the FULL ball B_s = {p : d2(p, c) <= r_s^2} of the search grid (patches.hip; the fp64 ball test of
-// patch_query_setup, not capped at P and not subsampled), with d = (double)p - (double)c:
+// Per query and scale s, over the FULL ball B_s = {p : d2(p, c) <= r_s^2} of the search grid (patches.hip; the fp64 ball test
+// ball_d2 of patches_dev.h, not capped at P and not subsampled), with d = (double)p - (double)c:
 //     n = |B_s|,  m = (sum d) / n,  C = ((sum d d^T) / n - m m^T) / r_s^2          (units of r^2: eigenvalues are scale-free, <= 1)
 //     (w, V) = sym3_eig(C)  (pca_eig.h: cyclic Jacobi, fp64, fixed sweeps),  w ascending
 //     normal  = V[0] normalised in fp64, rounded to f32 once, then signed ON THE F32 VALUES so that the first non-zero of
@@ -27,6 +27,8 @@
 #include <string>
 
 #include "kernels.h"
+// before the pragma below, like patches.hip and mups.hip: the ball of a scale is then the patch kernels' ball, whose d2 hipcc forms
+// with two FMAs (ball_d2, patches_dev.h)
 #include "patches_dev.h"
 
 // every product and sum below -- the solver of pca_eig.h included -- is rounded on its own, on the host (nesti_sym3_eig) as on the
@@ -67,28 +69,13 @@ __global__ __launch_bounds__(kThreads) void pca_kernel(const PcaParams pp) {
   // the row is the same in every lane of a wave: say so, and the centre and its tests live in scalar registers
   const int q = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6)));
   if (q >= p.M) return;                                       // whole waves leave: the shuffles below see full waves
-  const float* centre;
-  if (p.query_xyz) {
-    centre = p.query_xyz + (size_t)q * 3;
-  } else {
-    int qi = p.query_idx ? p.query_idx[q] : p.row0 + q;
-    qi = min(max(qi, 0), p.N - 1);
-    centre = p.cloud + (size_t)qi * 3;
-  }
+  const float* centre = query_centre(p, q);
   const float cf0 = centre[0], cf1 = centre[1], cf2 = centre[2];
-  // a centre with an infinite or NaN coordinate has empty balls: it visits no cell (patches_dev.h)
-  const bool lost = non_finite_bits(cf0) || non_finite_bits(cf1) || non_finite_bits(cf2);
-  int b = 0, e = 0;
-  if (!lost && lane < 9) {                                    // the nine x-spans of the 3 x 3 x 3 cell block, as patch_query_setup
-    const GridHeader h = *p.header;
-    int ix, iy, iz;
-    cell_coords(h, cf0, cf1, cf2, &ix, &iy, &iz);
-    const int zz = iz + lane / 3 - 1, yy = iy + lane % 3 - 1;
-    if (zz >= 0 && zz < h.dims[2] && yy >= 0 && yy < h.dims[1]) {
-      const int x0 = max(ix - 1, 0), x1 = min(ix + 1, h.dims[0] - 1);
-      b = p.start[cell_flat(h, x0, yy, zz)];
-      e = p.start[cell_flat(h, x1, yy, zz) + 1];
-    }
+  WaveSpans spans = {0, 0};                                   // lane t < 9: x-span t of the cell block (block_span, patches_dev.h)
+  if (!centre_lost(cf0, cf1, cf2) && lane < 9) {
+    const Span s = block_span(*p.header, p.start, p.N, cf0, cf1, cf2, lane);
+    spans.b = s.b;
+    spans.e = s.e;
   }
   const double cx = cf0, cy = cf1, cz = cf2;
   double acc[S][kSums];
@@ -99,25 +86,21 @@ __global__ __launch_bounds__(kThreads) void pca_kernel(const PcaParams pp) {
 #pragma unroll
     for (int k = 0; k < kSums; ++k) acc[s][k] = 0.0;
   }
-  for (int sp = 0; sp < 9; ++sp) {
-    const int sb = max(__shfl(b, sp, kWave), 0), se = min(__shfl(e, sp, kWave), p.N);   // a span never leaves the cell-ordered copy
-    for (int i = sb + lane; i < se; i += kWave) {
-      const float4 c = p.sorted[i];
-      const double dx = (double)c.x - cx, dy = (double)c.y - cy, dz = (double)c.z - cz;
-      const double xx = __dmul_rn(dx, dx), yy = __dmul_rn(dy, dy), zz = __dmul_rn(dz, dz);
-      const double d2 = __dadd_rn(__dadd_rn(xx, yy), zz);     // the ball test of pass A (patches_dev.h), operation for operation
-      const double xy = dx * dy, xz = dx * dz, yz = dy * dz;
+  walk_block(p.sorted, spans, lane, kWave, cx, cy, cz, [&](const float4& c, double d2) {
+    // the differences ball_d2 was given, formed again: the same operations, so the same values
+    const double dx = (double)c.x - cx, dy = (double)c.y - cy, dz = (double)c.z - cz;
+    const double xx = __dmul_rn(dx, dx), yy = __dmul_rn(dy, dy), zz = __dmul_rn(dz, dz);
+    const double xy = dx * dy, xz = dx * dz, yz = dy * dz;
 #pragma unroll
-      for (int s = 0; s < S; ++s) {
-        if (d2 <= p.r2[s]) {
-          ++cnt[s];
-          acc[s][0] += dx; acc[s][1] += dy; acc[s][2] += dz;
-          acc[s][3] += xx; acc[s][4] += xy; acc[s][5] += xz;
-          acc[s][6] += yy; acc[s][7] += yz; acc[s][8] += zz;
-        }
+    for (int s = 0; s < S; ++s) {
+      if (d2 <= p.r2[s]) {
+        ++cnt[s];
+        acc[s][0] += dx; acc[s][1] += dy; acc[s][2] += dz;
+        acc[s][3] += xx; acc[s][4] += xy; acc[s][5] += xz;
+        acc[s][6] += yy; acc[s][7] += yz; acc[s][8] += zz;
       }
     }
-  }
+  });
   // every lane ends up with every total; lane s keeps those of scale s (lanes >= S: of the last scale, and write nothing)
   double sum[kSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   int n = 0;
@@ -161,18 +144,13 @@ int pca_impl(const char* who, bool at, const nesti_config_t* cfg, const float* c
              const float* query_xyz_dev, int M, const double* r_abs, int query_row0, float* normals_out_dev, float* eig_out_dev,
              int32_t* n_ball_out_dev, const void* grid_ws_dev, size_t grid_ws_bytes, void* stream) {
   const std::string w(who);
-  if (!cfg || !cloud_dev || !r_abs || !grid_ws_dev) NESTI_FAIL(w + ": null argument");
-  if (N <= 0) NESTI_FAIL(w + ": empty cloud");
+  if (refuse_grid_cloud(w, cfg, cloud_dev, N, r_abs, grid_ws_dev, grid_ws_bytes)) return 1;
   if (M < 0) NESTI_FAIL(w + ": M must be >= 0");
-  if (cfg->n_scales < 1 || cfg->n_scales > NESTI_MAX_SCALES) NESTI_FAIL(w + ": bad n_scales");
-  if (grid_ws_bytes < patch_ws_layout(N).total) NESTI_FAIL(w + ": grid workspace too small");
-  if (query_row0 < 0) NESTI_FAIL(w + ": query_row0 must be >= 0");
+  if (refuse_query_rows(w, N, !at && !query_idx_dev, M, query_row0)) return 1;
   for (int s = 0; s < cfg->n_scales; ++s)
     if (!(r_abs[s] > 0.0) || !std::isfinite(r_abs[s])) NESTI_FAIL(w + ": radii must be positive and finite");
   if (M == 0) return 0;
   if (at && !query_xyz_dev) NESTI_FAIL(w + ": null query_xyz_dev");
-  if (!at && !query_idx_dev && (long long)query_row0 + M > (long long)N)
-    NESTI_FAIL(w + ": query rows [query_row0, query_row0 + M) exceed the cloud (N points)");
   PcaParams pp;
   patch_params_fill(&pp.p, cfg, cloud_dev, N, query_idx_dev, M, r_abs, 0, query_row0, grid_ws_dev);
   pp.p.query_xyz = at ? query_xyz_dev : nullptr;

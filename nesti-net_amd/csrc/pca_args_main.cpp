@@ -2,20 +2,8 @@
 // call, and the eigen-solver behind nesti_sym3_eig on a few matrices.  Built and run by `make asan-pca` against the AddressSanitizer
 // build of the library.
 #include <math.h>
-#include <stdio.h>
-#include <string.h>
 
-#include "../../include/nesti_hip.h"
-
-static int failures = 0;
-
-static void refused(int rc, const char* word, const char* what) {
-  const char* msg = nesti_last_error();
-  if (rc == 0 || !msg || !strstr(msg, word)) {
-    printf("FAIL %s: rc %d, message '%s'\n", what, rc, msg ? msg : "(null)");
-    ++failures;
-  }
-}
+#include "args_main.h"
 
 // eigenvalues ascending, C v = w v and V^T V = I to a small multiple of 2^-53 ||C||
 static void solved(const double (&c)[6], const char* what) {
@@ -112,6 +100,5 @@ int main() {
     printf("FAIL diagonal: w = %g %g %g\n", w[0], w[1], w[2]);
     ++failures;
   }
-  printf(failures ? "pca_args: %d failure(s)\n" : "pca_args: ok\n", failures);
-  return failures ? 1 : 0;
+  return finish("pca_args");
 }

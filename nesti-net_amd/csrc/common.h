@@ -149,7 +149,7 @@ __device__ __forceinline__ void store_out8(unsigned char* base, long long row_el
   }
 }
 
-// ---- e4m3 planes of the FP8 cross terms (kernels.h: ConvParams::aux8_out; conv8n.hip X8) ----------------------------------------
+// ---- e4m3 planes of the FP8 cross terms (host.h: ConvParams::aux8_out; conv8n.hip X8) ----------------------------------------
 // Four values -> four OCP e4m3 bytes (v_cvt_pk_fp8_f32: round to nearest even, subnormals kept), saturated at +-448 (the
 // conversion itself would produce NaN above the format's range).
 __device__ __forceinline__ uint32_t pack4_e4m3(float a, float b, float c, float d) {
@@ -173,7 +173,7 @@ __device__ __forceinline__ void store_aux8_8(unsigned char* aux_row, int col, co
   store_aux8_4(aux_row, col + 4, f1.x, f1.y, f1.z, f1.w, mul_lo, mul_hi);
 }
 
-// The FP6 form of the same side-buffer chunk (kernels.h: ConvParams::x8_fmt == 6): 16 consecutive channels of one row -> 32 e2m3 elements
+// The FP6 form of the same side-buffer chunk (host.h: ConvParams::x8_fmt == 6): 16 consecutive channels of one row -> 32 e2m3 elements
 // under ONE power-of-two scale + that scale as an E8M0 byte.  v_cvt_scalef32_2xpk16_fp6_f32 writes src0[i] to slot 2i and src1[i] to slot
 // 2i + 1, divides by `scale`, rounds to nearest even and saturates at +-7.5 (scripts/fp6_probe.hip).  `col` = logical column, multiple of 16.
 typedef float f32x16c_t __attribute__((ext_vector_type(16)));

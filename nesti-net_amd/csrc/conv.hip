@@ -85,7 +85,7 @@ struct SwzKey {
 // and one set of fragment reads feeds three MFMAs (lo * W_hi, hi * W_hi, hi * W_lo): 1.5x the MFMAs per LDS byte, per
 // staged byte and per barrier of the plain kernel.
 // one (M tile, N tile) of the layer; `bid` is the position in the XCD-aware block order (blockIdx.x of a one-tile-per-workgroup launch)
-// X2 (kernels.h: ConvParams::x2; KPIPE, 16-bit, not X3): plain activations x pair-packed weights.  The A side is the plain loop's:
+// X2 (host.h: ConvParams::x2; KPIPE, 16-bit, not X3): plain activations x pair-packed weights.  The A side is the plain loop's:
 // 64-channel super-chunks, 128-byte rows (whole cache lines), two buffers.  The B side is the pair packing's: 32-channel chunks, rows
 // [W_hi k0..31 | W_lo k0..31], two buffers.  A 32-channel step h of super-chunk C reads the A fragments of slots 4 h .. 4 h + 3 and per
 // 16-channel K-step one A fragment set feeds hi * W_hi and hi * W_lo.
@@ -396,7 +396,7 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvParams& p, const unsig
   const int out_col0 = (second ? p.out_coff2 : p.out_coff) + n_local * TN;
   const float* bias = p.bias + n_tile * TN;
   const float act_floor = p.relu ? 0.f : -INFINITY;      // ReLU as one v_max
-  // kernels.h: ConvParams::aux8_out -- power-of-two pre-scales of the e4m3 planes (exact multiplications)
+  // host.h: ConvParams::aux8_out -- power-of-two pre-scales of the e4m3 planes (exact multiplications)
   const float aux_mul_lo = __builtin_ldexpf(1.f, p.x8_sa), aux_mul_hi = __builtin_ldexpf(1.f, p.x8_sc);
 
   if (KPIPE && second && p.pool_k > 1) {
@@ -727,7 +727,7 @@ int launch_one(const ConvParams& p, hipStream_t stream) {
   return launch_tiles<conv_igemm_kernel<DT, TN, KPIPE, X3, false>, conv_igemm_kernel<DT, TN, KPIPE, X3, true>>(
       p, lds_bytes<TN, KPIPE>(), kThreads, tile_rows8(p.m_tiles) * p.n_tiles, stream);
 }
-// plain activations x pair-packed weights (kernels.h: ConvParams::x2): never a walking launch
+// plain activations x pair-packed weights (host.h: ConvParams::x2): never a walking launch
 template <int DT, int TN>
 int launch_one_x2(const ConvParams& p, hipStream_t stream) {
   return launch_tile_kernel<conv_igemm_kernel<DT, TN, true, false, false, true>>(p, lds_bytes<TN, true>(), kThreads,

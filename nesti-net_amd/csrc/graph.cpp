@@ -119,7 +119,7 @@ struct Builder {
   // conv_net_3g (models/experts_n_est.py:217-240): four inception blocks on the 3^3 grid (kernel sizes [2,3], [2,3],
   // [1,2], [1,2]; k0 = 1 makes conv2 a 1x1x1 layer and the avg-pool of the conv4 branch the identity), then
   // max_pool3d [3,3,3] stride 2 SAME -> 2^3 x 1536, flattened voxel-major.  The 27 voxels live in a 4^3 index space
-  // (kernels.h: ConvParams::s_real).  Returns the pooled buffer; *flat describes it as one FC input row.
+  // (host.h: ConvParams::s_real).  Returns the pooled buffer; *flat describes it as one FC input row.
   int conv_net_3g(Tower& T, const std::string& s, ChanMap m, ChanMap* flat) {
     s_real = 3;
     int b = inception(T, "inception1" + s, 0, m, 128, 2, 3, 2, &m);

@@ -29,7 +29,7 @@ struct Op {
   int in_buf = 0, in_coff = 0, out_buf = 0, out_coff = 0, out_coff2 = 0;
   int in_cstride = 0;          // 0: the input buffer's channel count; else a flattened view (FC on S^3 x C)
   int mp_buf = -1, mp_mode = 0; // fused 2^3 max-pool of the first tile group into this buffer (1: pooled only, 2: both)
-  int mp_mode2 = 0;             // 1: the conv4 half writes only its pooled tensor too (kernels.h: ConvParams::mp_mode2)
+  int mp_mode2 = 0;             // 1: the conv4 half writes only its pooled tensor too (host.h: ConvParams::mp_mode2)
   int layer = -1;
   int C = 0, k = 0, log2S = 0;
   bool out_f32 = false;
@@ -56,6 +56,7 @@ struct Graph {
   std::vector<LayerDesc> layers;
   Tower gate;
   std::vector<Tower> experts;
+  const Tower& tower(int t) const { return t < 0 ? gate : experts[t]; }   // -1: the gating net, else an expert
 };
 
 // x8: an NESTI_F16X8 / NESTI_F16X8C model (only experts_n_est on the 8^3 grid gets the side buffers)

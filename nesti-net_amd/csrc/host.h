@@ -1,6 +1,6 @@
-// What the host-only units of libnesti_hip.so (graph.cpp, pack.cpp) share with the HIP files: the error slot, the dtype
-// predicates and the layout constants the weight packer shares with the kernels.  No HIP header: common.h includes this file,
-// so host and device code see the same definitions.
+// What the host-only units of libnesti_hip.so (graph.cpp, pack.cpp, plan.cpp) share with the HIP files: the error slot, the dtype
+// predicates, the layout constants the weight packer and the planner share with the kernels, and the kernels' parameter blocks
+// (ConvParams, PoolParams).  No HIP header: common.h includes this file, so host and device code see the same definitions.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -34,11 +34,102 @@ constexpr int kSplitGroup = 64;
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 constexpr int kRowBytes = 128;    // bytes of one K-chunk row in LDS (64 x 16-bit or 32 x f32)
+constexpr int kTileM = 512;       // GEMM rows (voxels x points) per workgroup
 constexpr int kMaxTaps = 125;     // 5^3
 
 // host-side conversions used by the weight repacker (pack.cpp)
 uint16_t host_f32_to_bf16(float f);
 uint16_t host_f32_to_f16(float f);
 float host_f16_to_f32(uint16_t h);
+
+// ---- the parameter blocks of the conv and pool kernels: filled by the planner (plan.cpp), launched through kernels.h ------------
+// One conv3d / fully-connected layer as an implicit GEMM:
+//   out[r, n] = act( sum_{tap, c} in[shift(r, tap), c] * W[tap, c, n] + bias[n] )
+// rows r = point * V + voxel (V = S^3, channels-last); a tap that leaves the S^3 volume
+// contributes zero (TF 'SAME', utils/tf_util.py:298-300).
+struct ConvParams {
+  const void* in;      // [points * V, in_cstride] elements of the model dtype
+  void* out;           // [points * V, out_cstride] (model dtype, or f32 if out_f32)
+  const void* wpk;     // packed weights [n_tiles][n_chunks][n_taps][TN][128 B] (pre-swizzled)
+  const float* bias;   // [n_tiles * TN] BN-folded bias
+  const int32_t* npoints_ptr;   // optional device-side point count (top-1 routing); NULL -> npoints
+  const int32_t* point_index;   // optional gather of INPUT points (routing); NULL -> identity
+  int npoints;         // capacity (grid is sized for this)
+  int in_cstride, in_coff;
+  int in_chunk_bytes;  // plain (non-pair) K loop of conv_igemm_kernel: byte distance between consecutive 128-byte K chunks of an
+                       // input row -- 128, or 256 when a plain-f16 layer reads the hi planes of a pair-layout tensor (plan.cpp)
+  int in_pair;         // plain K loop of conv8n_kernel / conv4n_kernel: 1 = the input tensor has the pair layout and only its hi planes
+                       // are read (64-byte chunk c = 32 channels sits at byte (c >> 1) * 256 + (c & 1) * 64 of a row); with
+                       // `split` the outputs are written as pairs again -- a single-product layer inside a pair-mode tower
+  int out_cstride, out_coff;
+  int n_chunks, n_taps;
+  int tap_k;           // kernel edge k when all k^3 taps are present in x-fastest order (conv4n_kernel derives the taps from counters)
+  int log2S;           // S in {1,2,4,8}: the index space rows are laid out in
+  int s_real;          // 0, or the real volume edge when it is smaller than S (3^3 Gaussian grid embedded in 4^3:
+                       // voxels with a coordinate >= s_real are dead rows -- never read as neighbours, contents ignored)
+  int relu, out_f32;
+  int m_tiles, n_tiles;
+  // merged inception conv1|conv4 launch: column tiles >= split_tile are conv4's; they write at
+  // out_coff2 and average the pre-activation over the pool_k^3 SAME window (pool_k == 1: plain).
+  int split_tile;      // == n_tiles for an ordinary layer
+  int out_coff2;
+  int pool_k;
+  // fused tf.nn.max_pool3d 2^3 stride 2 (utils/tf_util.py:424-428) for the FIRST tile group: 1 = write only the pooled
+  // tensor, 2 = write the full-resolution tensor and the pooled one
+  void* mp_out;        // [points * V/8, mp_cstride], same channel offsets as `out`
+  int mp_cstride;
+  int mp_mode;
+  int mp_mode2;        // 1: the conv4 half (fused avg-pool epilogue) writes ONLY its 2^3 / 2 max-pooled tensor, into mp_out at
+                       // out_coff2 -- the block is followed by max_pool3d and nobody reads conv4 at full resolution
+  // k^3-tap layers: 1 = the 16 32-row MFMA tiles of a workgroup are (8x,2y,2z) blocks (8^3) / x-lines of the
+  // 8 points (4^3), dealt to the 4 SIMDs as a Latin square so that the tiles a padding tap skips are spread evenly
+  // over the matrix pipes (conv.hip: tile_row).  0 = tile t holds rows [32t, 32t+32).  2 (2^3 volumes) = a tile is ONE voxel of
+  // 32 points and the chunk sits in LDS in (voxel, point) order: padding skips whole tiles in all three axes.
+  int remap;
+  // A launch that is probably EMPTY (a later round of a routing / flag list walk, a widening pass of the two-stage gate: the row
+  // count sits in device memory) is made with a small fixed grid whose workgroups WALK the tiles (tile = blockIdx.x, += gridDim.x,
+  // bounded by the live row count): an empty launch then costs a few hundred workgroups instead of one per tile of the capacity
+  // (a full-capacity grid of early-exiting workgroups costs ~1.1 ns each: 0.11 ms for 100k).  0 = one tile per workgroup; 1 = kWalkGrid
+  // workgroups; > 1 = that many (a multiple of 8): the conditioning guard's towers see a few dozen rows and use 64.
+  int walk;
+  // NESTI_BF16X3 / NESTI_F16X3 (common.h): in_cstride / in_coff / out_cstride / mp_cstride and n_chunks are PHYSICAL (two planes per
+  // 64-channel group); out_coff / out_coff2 stay logical and every 16-bit store goes through split_col + two planes.
+  int split;
+  int x2;              // 1x1x1 / FC layers of the NESTI_F16X3C filter pass (conv_igemm_kernel, KPIPE): PLAIN 16-bit activations times the
+                       // pair-packed weights [W_hi | W_lo] -- hi * W_hi + hi * W_lo, i.e. the layer multiplies by its exact weights.  K chunks
+                       // of 32 channels: 64-byte A rows, 128-byte B rows; n_chunks / acc_scale / wpk are the pair packing's.  These layers
+                       // are fill-bound, so the second product is nearly free, and it removes the weight-rounding half of the filter's error
+  int x3native;        // pair modes: the kernels' pair K loop (conv.hip / conv8n.hip: X3) -- K chunks [hi | lo] x [W_hi | W_lo], three MFMAs
+                       // per fragment set; the packed weights follow (pack.h: PackMeta::x3n)
+  // FP8 cross terms (NESTI_F16X8 / NESTI_F16X8C; conv8n.hip X8).  Producer side (a 1x1x1 layer, conv.hip): aux8_out != NULL makes the
+  // FIRST tile group (conv1) also write the e4m3 planes of its activated outputs v = hi + lo into the side buffer -- per row and
+  // 64-channel group [lo8 64 B | hi8 64 B] with lo8 = e4m3(lo 2^x8_sa), hi8 = e4m3(v 2^x8_sc), saturated at +-448; aux8_stride = bytes
+  // per row.  Consumer side (conv8n_kernel): x8 = 1, aux8_in = that buffer, x8_scale_a / x8_scale_b = the E8M0 codes (127 - sa,
+  // 127 - sb) of the block scales that undo the pre-scales of the activation and weight planes
+  const void* aux8_in;
+  void* aux8_out;
+  int aux8_stride;
+  int x8, x8_sa, x8_sc, x8_scale_a, x8_scale_b;
+  // x8_fmt == 6: the block-scaled FP6 (e2m3) form of the same cross terms (conv8n.hip X6).  The side buffer keeps its geometry; the 32
+  // bytes of a row's 16-channel chunk (16 where lo8 went, 16 where hi8 went) now hold 32 six-bit elements -- slot 2i = e2m3(lo_i 2^11 / s),
+  // slot 2i + 1 = e2m3(hi_i / s) -- then the block's own scale s = 2^(E - 2), E = exponent of the chunk's largest |hi|, as an E8M0 byte
+  // (byte 24), zeros after it; |lo_i 2^11| <= |hi_i| element by element, so one scale serves both halves.  The weight rows follow the
+  // same pattern (pack.cpp: cross_rows, the 2^-11 folded into their scale byte); x8_sa / x8_sc / x8_scale_* are not used.
+  int x8_fmt;
+  float acc_scale;     // the accumulators are multiplied by this before the bias (1, or 2^-s when the layer's packed weights
+                       // carry a 2^s scale: NESTI_F16X3 keeps the weight pairs in f16's normal range that way)
+  int8_t tap[kMaxTaps][4];   // dz, dy, dx, -
+};
+
+struct PoolParams {
+  const void* in;
+  void* out;
+  const int32_t* npoints_ptr;
+  int npoints;
+  int in_cstride, in_coff, out_cstride, out_coff;
+  int C;               // channels to process (multiple of 8)
+  int log2S;           // input S
+  int split;           // pair modes: cstrides physical, in_coff / out_coff / C logical (split_col), values = hi + lo
+};
 
 }  // namespace nesti

@@ -267,7 +267,7 @@ int x8_activation_exponent(const LayerDesc& d, const TensorTable& tt) {
 // [W_hi f16 k0..15 | W_lo f16 k0..15] of a k^3 tap layer at 8^3 with, where W_lo went, narrow codes of BOTH halves of the same scaled
 // weights (W 2^e, |W| 2^e < 2^14); whi / wlo = W_hi and W - W_hi of the tile's 16 channels x 64 columns, zero on padding.
 // fmt == 8: [W_hi8 k0..15 | W_lo8 k0..15], W_hi8 = e4m3(W_hi 2^sb), W_lo8 = e4m3((W - W_hi) 2^(sb + 11)) with sb = -6 (both below 256).
-// fmt == 6: the block-scaled FP6 form (kernels.h: ConvParams::x8_fmt): the same 32 bytes hold 32 e2m3 elements -- slot 2i = W_hi[i] / s,
+// fmt == 6: the block-scaled FP6 form (host.h: ConvParams::x8_fmt): the same 32 bytes hold 32 e2m3 elements -- slot 2i = W_hi[i] / s,
 // slot 2i + 1 = W_lo[i] 2^11 / s of the chunk's 16 input channels (the order the producer's conversion instruction writes [lo | hi]
 // activations in, so that slot products are lo W_hi and hi W_lo) -- and in byte 24 the E8M0 code of s 2^-11 (s = 2^(E - 2), E = exponent of
 // the chunk's largest |W_hi|; the 2^-11 undoes BOTH 2^11 pre-scales, the activations' and the weights', since every product carries
@@ -402,3 +402,36 @@ int pack_form(const LayerDesc& d, const TensorTable& tt, int form, int mdt, Pack
 
 // include/nesti_hip.h: the FP6 weight encoder, exposed for tests/test_abi.py
 extern "C" int nesti_f32_to_e2m3(float value, float inv_scale) { return (int)nesti::host_f32_to_e2m3(value, inv_scale); }
+
+// include/nesti_hip.h: the packer without a device (tests/test_pack.py)
+extern "C" int nesti_debug_pack_layer(const nesti_config_t* cfg, const nesti_tensor_t* tensors, int n_tensors, int dtype, int form,
+                                      int layer, nesti_debug_pack_t* info, void* w, size_t max_w, float* bias, size_t max_bias) {
+  using namespace nesti;
+  if (!cfg || !tensors || !info) NESTI_FAIL("nesti_debug_pack_layer: null argument");
+  if (dtype < NESTI_F32 || dtype > NESTI_F16X8C) NESTI_FAIL("nesti_debug_pack_layer: bad dtype");
+  Graph g;
+  if (build_graph(cfg, &g, dtype_x8(dtype))) return 1;
+  if (layer < 0 || layer >= (int)g.layers.size()) NESTI_FAIL("nesti_debug_pack_layer: layer index outside the model");
+  const LayerDesc& d = g.layers[layer];
+  const int mdt = main_dtype(dtype), packing = form_packing(form);
+  const bool x8 = packing == NESTI_DEBUG_FORM_X8 || packing == NESTI_DEBUG_FORM_X6;
+  if (packing != NESTI_DEBUG_FORM_PLAIN && packing != NESTI_DEBUG_FORM_PAIR && !x8) NESTI_FAIL("nesti_debug_pack_layer: form is NESTI_DEBUG_FORM_*");
+  if (packing == NESTI_DEBUG_FORM_PAIR && act_planes(mdt) == 1)
+    NESTI_FAIL("nesti_debug_pack_layer: the pair packing is for the pair dtypes (NESTI_BF16X3, NESTI_F16X3 and the modes built on it)");
+  if (x8 && !(g.x8 && use_conv8(d)))
+    NESTI_FAIL("nesti_debug_pack_layer: the X8 / X6 packings are for the k^3 tap layers at 8^3 of NESTI_F16X8 / NESTI_F16X8C models; " + d.scope +
+               " is not one");
+  const TensorTable tt = tensor_table(tensors, n_tensors);
+  PackedImage img;
+  if (pack_form(d, tt, packing, mdt, &img)) return 1;
+  memset(info, 0, sizeof(*info));
+  info->kind = img.kind; info->TN = img.TN; info->n_tiles = img.n_tiles; info->split_tile = img.split_tile;
+  info->n_chunks = img.n_chunks; info->n_taps = img.n_taps; info->x3n = img.x3n ? 1 : 0; info->acc_scale = img.acc_scale;
+  info->x8_sb = img.x8_sb; info->x8_sc = x8_activation_exponent(d, tt);
+  info->w_bytes = (int64_t)img.w.size(); info->n_bias = (int64_t)img.bias.size();
+  memcpy(info->tap, img.tap, sizeof(info->tap));
+  if ((w && max_w < img.w.size()) || (bias && max_bias < img.bias.size())) NESTI_FAIL("nesti_debug_pack_layer: output arrays too small");
+  if (w) memcpy(w, img.w.data(), img.w.size());
+  if (bias) memcpy(bias, img.bias.data(), img.bias.size() * sizeof(float));
+  return 0;
+}

@@ -1,5 +1,5 @@
 // Batch-norm folding and the weight packer (pack.cpp): TF tensors -> the byte image of a layer's weights as the MFMA kernels read
-// it, plus the padded bias.  Host only -- the caller uploads the image (model.hip: upload).
+// it, plus the padded bias.  Host only -- the caller uploads the image (model.hip: upload); nesti_debug_pack_layer hands the same image to tests.
 #pragma once
 #include <map>
 #include <string>
@@ -17,6 +17,11 @@ struct TensorTable {
     return it == by_name.end() ? nullptr : it->second;
   }
 };
+inline TensorTable tensor_table(const nesti_tensor_t* tensors, int n) {
+  TensorTable tt;
+  for (int i = 0; i < n; ++i) if (tensors[i].name) tt.by_name[tensors[i].name] = &tensors[i];
+  return tt;
+}
 
 // Expected variables of one layer, in TF naming (utils/tf_util.py:289-302, 332-342, 473-479).
 void layer_tensors(const LayerDesc& d, std::vector<std::pair<std::string, std::vector<int64_t>>>* out);
@@ -49,7 +54,7 @@ struct PackedImage : PackMeta {
   std::vector<float> bias;
 };
 
-// The form of a launch (model.hip: launch_form): the NESTI_DEBUG_FORM_* values of include/nesti_hip.h and, EXPERIMENT
+// The form of a launch (plan.cpp: launch_form): the NESTI_DEBUG_FORM_* values of include/nesti_hip.h and, EXPERIMENT
 // (nesti_model_set_expert_mix / _gate_mix), a tap layer of a pair-mode tower in plain f16 / bf16 -- it reads the hi
 // planes of its pair-layout input, multiplies ONE product and writes its outputs as pairs again
 constexpr int kFormMix = NESTI_DEBUG_FORM_X6 + 1;

@@ -12,7 +12,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-B = 6000      # > 4096: the recheck runs in four rounds of 1536 rows (model.hip: cascade_cap)
+B = 6000      # > 4096: the recheck runs in four rounds of 1536 rows (plan.h: cascade_cap)
 
 
 @pytest.fixture(scope="module")

@@ -86,7 +86,7 @@ def test_experts_model_every_launch(experts_setup, gpu_device, dtype):
     g = _check_tower(net, W, dtype, -1, mups, B)
     probs, expert = net.gate(mups)
     torch.cuda.synchronize()
-    # nesti_gate_forward leaves the gating net's logits in its tower workspace, the tail of the forward workspace (model.hip:
+    # nesti_gate_forward leaves the gating net's logits in its tower workspace, the tail of the forward workspace (plan.cpp:
     # ws_layout): they must be the stepped tower's, bit for bit
     c = cfg.to_c()
     tower_bytes = max(net.lib.nesti_tower_workspace_bytes(ctypes.byref(c), DTYPES[dtype], t, B) for t in range(-1, cfg.n_experts))

@@ -442,7 +442,7 @@ def test_reference_order_subsample_feeds_the_same_forward(gpu_device, mode):
 @pytest.mark.parametrize("dtype", ["f16", "f16x3"])
 def test_later_expert_rounds_run_through_the_walking_kernels(gpu_device, dtype):
     """A batch larger than 8192 sizes the expert towers for a quarter of it and walks each routing list in four rounds; rounds
-    1 .. 3 are normally empty and are launched as small walking grids (csrc/kernels.h: ConvParams::walk).  With a gate biased towards
+    1 .. 3 are normally empty and are launched as small walking grids (csrc/host.h: ConvParams::walk).  With a gate biased towards
     one expert most queries route to it, so that expert's later rounds are FULL: the walking instantiations of conv_igemm /
     conv8n / conv4n then do real work, and the result must equal the small-batch (single-round) result bit for bit."""
     from nesti_net_amd import synth, weights

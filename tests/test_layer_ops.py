@@ -1,6 +1,9 @@
 """CPU checks of the per-layer test hook (nesti_debug_tower_ops) and of tests/layer_ref.py's emulation of the packer's value
 rules and number formats -- no device needed."""
 import ctypes
+import hashlib
+import json
+import os
 
 import numpy as np
 import pytest
@@ -80,6 +83,50 @@ def test_tower_ops_cover_the_graph_and_keep_buffers_apart(model):
                                     seen[s] = seen.get(s, 0) + (0 if x8 else 1)
         assert sorted(seen) == scopes, (model, dtype, set(scopes) ^ set(seen))
         assert all(v == 1 for v in seen.values()), (model, dtype, [k for k, v in seen.items() if v != 1])
+
+
+PLAN_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plan_digests.json")
+# both sides of cascade_cap's 4096, expert_cap's 8192 and guard_cap's 2048; 100000: a whole cloud as one batch
+PLAN_BATCHES = (1, 37, 1000, 2048, 2049, 4096, 4097, 8192, 8193, 100000)
+
+
+def plan_digests(lib):
+    """{key: SHA-256} of every plan the library makes, folded over PLAN_BATCHES: per (model, dtype) the fused entry's workspace size
+    ("size/..."), per pass of a tower ("plan/...") every field nesti_debug_tower_ops reports for every buffer and launch in the
+    structs' field order, in_pos, the tower workspace and nesti_tower_workspace_bytes.  scripts/record_plan_digests.py writes the
+    golden file from this function and the library of the commit BEFORE the planner was carved out of model.hip."""
+    from nesti_net_amd.config import DTYPES
+    out = {}
+    for model, cfg in sorted(_configs().items()):
+        c = cfg.to_c()
+        for dtype in DTYPES_OF[model]:
+            h = hashlib.sha256()
+            for batch in PLAN_BATCHES:
+                h.update(b"%d=%d;" % (batch, lib.nesti_estimate_workspace_bytes_for_config(ctypes.byref(c), DTYPES[dtype], batch)))
+            out["size/%s/%s" % (model, dtype)] = h.hexdigest()
+            for tower, fast, x8 in _passes(model, dtype):
+                for fmt in ((6, 8) if x8 else (0,)):
+                    h = hashlib.sha256()
+                    for batch in PLAN_BATCHES:
+                        bufs, ops, wsb = layer_ref.tower_ops(lib, c, DTYPES[dtype], tower, batch, fast, x8, fmt)
+                        h.update(b"batch %d ws %d tower %d;" % (batch, wsb, lib.nesti_tower_workspace_bytes(
+                            ctypes.byref(c), DTYPES[dtype], tower, batch)))
+                        for d in bufs + ops:
+                            for k, v in d.items():       # the struct's field order (layer_ref.tower_ops), then in_pos
+                                h.update(("%s=%s;" % (k, v.tolist() if isinstance(v, np.ndarray) else v)).encode())
+                    out["plan/%s/%s/tower%d/fast%d/x8_%x/fmt%d" % (model, dtype, tower, fast, x8, fmt)] = h.hexdigest()
+    return out
+
+
+def test_plans_equal_the_recorded_ones():
+    """Every plan -- buffer placement, launch description, workspace sizes; all six models, every dtype, every pass, ten batch sizes --
+    is the one recorded in tests/golden/plan_digests.json.  No tolerance, no excluded case."""
+    import nesti_net_amd  # noqa: F401
+    from nesti_net_amd import _lib
+    got = plan_digests(_lib.load())
+    want = json.load(open(PLAN_GOLDEN))
+    assert sorted(got) == sorted(want)
+    assert [k for k in sorted(want) if got[k] != want[k]] == []
 
 
 def test_tower_ops_forms_follow_the_pass():

@@ -6,7 +6,8 @@
 // (bbox -> counts -> scan -> fill; points re-ordered into cell order as float4 {x,y,z,index}
 // so a query streams contiguous memory).  One 256-thread workgroup per query visits the
 // 3x3x3 cell block as 9 contiguous x-spans, tests every candidate once against all scales in
-// fp64 exactly as cKDTree does (d2 = dx*dx, += dy*dy, += dz*dz, no FMA; d2 <= r*r), and keeps
+// fp64 with cKDTree's formula (d2 = (dx*dx + dy*dy) + dz*dz, formed with two FMAs under hipcc's
+// default contraction -- ball_d2 in patches_dev.h; d2 <= r*r, the boundary included), and keeps
 // per scale the P hits with the smallest (hash, index) keys, in key order.
 #include <string.h>
 
@@ -318,10 +319,7 @@ int nesti_patches_grid(const nesti_config_t* cfg, const float* cloud_dev, int N,
   int* cursor = (int*)(ws + L.cursor);
   float4* sorted = (float4*)(ws + L.sorted);
   double rmax = 0.0;
-  for (int s = 0; s < cfg->n_scales; ++s) {
-    if (!(r_abs[s] > 0.0)) NESTI_FAIL("nesti_patches_grid: radii must be positive");
-    rmax = fmax(rmax, r_abs[s]);
-  }
+  for (int s = 0; s < cfg->n_scales; ++s) rmax = fmax(rmax, r_abs[s]);
   const int gb = std::min(1024, (N + 255) / 256);
   hipLaunchKernelGGL(bbox_init_kernel, dim3(1), dim3(64), 0, st, bb);
   hipLaunchKernelGGL(bbox_kernel, dim3(gb), dim3(256), 0, st, cloud_dev, N, bb);
@@ -340,13 +338,11 @@ static int patches_query_impl(const char* who, bool at, const nesti_config_t* cf
                               int query_row0, float* points_out_dev, int32_t* n_eff_out_dev, int32_t* nbr_idx_out_dev,
                               int32_t* n_ball_out_dev, const void* grid_ws_dev, size_t grid_ws_bytes, void* stream) {
   const std::string w(who);
-  if (refuse_grid_cloud(w, cfg, cloud_dev, N, r_abs, grid_ws_dev, grid_ws_bytes)) return 1;
+  if (refuse_grid_cloud(w, cfg, cloud_dev, N, r_abs, grid_ws_dev, grid_ws_bytes, M > 0)) return 1;
   if (cfg->points_per_scale < 1 || 2 * cfg->points_per_scale > kListCap) NESTI_FAIL(w + ": points_per_scale must be in [1, 512]");
   if (M <= 0) return 0;                  // no queries: nothing to do, whatever query_row0 and the radii are
   if (refuse_query_rows(w, N, !at && !query_idx_dev, M, query_row0)) return 1;
   if (at && !query_xyz_dev) NESTI_FAIL(w + ": null query_xyz_dev");
-  for (int s = 0; s < cfg->n_scales; ++s)
-    if (!(r_abs[s] > 0.0)) NESTI_FAIL(w + ": radii must be positive");
   PatchParams p;
   patch_params_fill(&p, cfg, cloud_dev, N, query_idx_dev, M, r_abs, seed, query_row0, grid_ws_dev);
   p.query_xyz = at ? query_xyz_dev : nullptr;
@@ -380,8 +376,6 @@ static int check_query_args(const char* who, const nesti_config_t* cfg, const fl
   if (refuse_grid_cloud(w, cfg, cloud_dev, N, r_abs, grid_ws_dev, grid_ws_bytes)) return 1;
   if (cfg->points_per_scale < 1 || 2 * cfg->points_per_scale > kListCap) NESTI_FAIL(w + ": points_per_scale must be in [1, 512]");
   if (refuse_query_rows(w, N, !query_idx_dev, M, query_row0)) return 1;
-  for (int s = 0; s < cfg->n_scales; ++s)
-    if (!(r_abs[s] > 0.0)) NESTI_FAIL(w + ": radii must be positive");
   return 0;
 }
 

@@ -4,6 +4,7 @@
 #pragma once
 #include <string.h>
 
+#include <cmath>
 #include <string>
 
 #include "kernels.h"
@@ -291,13 +292,17 @@ inline void patch_params_fill(PatchParams* p, const nesti_config_t* cfg, const f
   }
 }
 
-// host side: what every entry over a cloud and its grid workspace refuses first, under the entry's name `w`
+// host side: what every entry over a cloud and its grid workspace refuses first, under the entry's name `w`.  The radii come last
+// and only where `radii_used`: an entry that returns early for M <= 0 "whatever the radii are" passes M > 0.  An infinite radius
+// (one infinite coordinate makes the host's bounding-box diagonal infinite) would give header_kernel inv_cell = 0 and a NaN to convert.
 inline int refuse_grid_cloud(const std::string& w, const nesti_config_t* cfg, const float* cloud_dev, int N, const double* r_abs,
-                             const void* grid_ws_dev, size_t grid_ws_bytes) {
+                             const void* grid_ws_dev, size_t grid_ws_bytes, bool radii_used = true) {
   if (!cfg || !cloud_dev || !r_abs || !grid_ws_dev) NESTI_FAIL(w + ": null argument");
   if (N <= 0) NESTI_FAIL(w + ": empty cloud");
   if (cfg->n_scales < 1 || cfg->n_scales > NESTI_MAX_SCALES) NESTI_FAIL(w + ": bad n_scales");
   if (grid_ws_bytes < patch_ws_layout(N).total) NESTI_FAIL(w + ": grid workspace too small");
+  for (int s = 0; radii_used && s < cfg->n_scales; ++s)
+    if (!(r_abs[s] > 0.0) || !std::isfinite(r_abs[s])) NESTI_FAIL(w + ": radii must be positive and finite");
   return 0;
 }
 // ... and of its M queries.  rows_are_centres: the centres are the cloud rows [query_row0, query_row0 + M) -- no index list, no

@@ -147,8 +147,6 @@ int pca_impl(const char* who, bool at, const nesti_config_t* cfg, const float* c
   if (refuse_grid_cloud(w, cfg, cloud_dev, N, r_abs, grid_ws_dev, grid_ws_bytes)) return 1;
   if (M < 0) NESTI_FAIL(w + ": M must be >= 0");
   if (refuse_query_rows(w, N, !at && !query_idx_dev, M, query_row0)) return 1;
-  for (int s = 0; s < cfg->n_scales; ++s)
-    if (!(r_abs[s] > 0.0) || !std::isfinite(r_abs[s])) NESTI_FAIL(w + ": radii must be positive and finite");
   if (M == 0) return 0;
   if (at && !query_xyz_dev) NESTI_FAIL(w + ": null query_xyz_dev");
   PcaParams pp;

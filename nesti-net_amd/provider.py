@@ -75,11 +75,14 @@ class CloudPatches:
             raise ValueError("pidx and queries are mutually exclusive: a query is a cloud point (pidx) or a position (queries)")
         if queries is not None:
             queries = check_queries(queries)
+        pts = np.ascontiguousarray(pts, dtype=np.float32)
+        bad = np.flatnonzero(~np.isfinite(pts).all(axis=1)) if pts.ndim == 2 else []
+        if len(bad):      # one infinite coordinate makes bbdiag, and with it every radius, infinite: no grid can be built for it
+            raise ValueError("cloud row %d is not finite: %s" % (bad[0], pts[bad[0]].tolist()))
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.NestiError("CloudPatches needs a GPU: libnesti_hip.so has no CPU path")
         self.cfg, self.device, self.seed = cfg, torch.device(device), int(seed)
-        pts = np.ascontiguousarray(pts, dtype=np.float32)
         self.host_pts = pts                   # kept for the opt-in reference-order subsample (pipeline.py: subsample='reference')
         self.n_points = pts.shape[0]
         # utils/pcpnet_dataset.py:281-282 -- float64 Python arithmetic on the host, like the reference

@@ -239,3 +239,56 @@ def test_e2m3_encoder_rounds_to_nearest_even_and_saturates():
         assert lib.nesti_f32_to_e2m3(v, 1.0) == 31 and lib.nesti_f32_to_e2m3(-v, 1.0) == 63
     assert lib.nesti_f32_to_e2m3(0.06, 1.0) == 0 and lib.nesti_f32_to_e2m3(0.0626, 1.0) == 1     # the probe's cases (profiles/r06_fp6_probe.txt)
     assert lib.nesti_f32_to_e2m3(24.0, 0.25) == lib.nesti_f32_to_e2m3(6.0, 1.0) == 28
+
+
+def test_patch_entries_refuse_non_finite_radii_before_any_device_call():
+    """nesti_patches_grid / _query / _query_at / _count / _query_ref: an infinite or NaN radius is refused like a non-positive one, with
+    pointers that are never dereferenced.  (An infinite radius would give the grid header inv_cell = 0 and a NaN to convert to a cell.)"""
+    import nesti_net_amd  # noqa: F401
+    from nesti_net_amd import _lib
+    from nesti_net_amd.config import NestiConfig
+    lib, c = _lib.load(), NestiConfig().to_c()
+    p, big, N = ctypes.c_void_p(4096), 1 << 40, 100
+    cfg = ctypes.byref(c)
+
+    def entries(rr, M=5):
+        return {
+            "nesti_patches_grid": lambda: lib.nesti_patches_grid(cfg, p, N, rr, p, big, None),
+            "nesti_patches_query": lambda: lib.nesti_patches_query(cfg, p, N, p, M, rr, 1, 0, None, None, None, None, p, big, None),
+            "nesti_patches_query_at": lambda: lib.nesti_patches_query_at(cfg, p, N, p, M, rr, 1, 0, None, None, None, None, p, big, None),
+            "nesti_patches_count": lambda: lib.nesti_patches_count(cfg, p, N, p, M, rr, 0, p, p, big, None),
+            "nesti_patches_query_ref": lambda: lib.nesti_patches_query_ref(cfg, p, N, p, M, rr, 0, p, p, p, p, None, None, None, p, big, None),
+        }
+
+    for bad in (float("inf"), float("nan"), -float("inf"), 0.0, -1.0):
+        for slot in range(3):
+            r = [0.1, 0.2, 0.3]
+            r[slot] = bad
+            for who, call in entries((ctypes.c_double * 3)(*r)).items():
+                assert call() != 0, (who, r)
+                assert lib.nesti_last_error().decode() == who + ": radii must be positive and finite", (who, r)
+    # no queries: the query entries still return before they look at the radii, as they did
+    inf3 = (ctypes.c_double * 3)(float("inf"), 0.2, 0.3)
+    assert entries(inf3, M=0)["nesti_patches_query"]() == 0 and entries(inf3, M=0)["nesti_patches_query_at"]() == 0
+    # ... and the two that checked the radii first still do
+    assert entries(inf3, M=0)["nesti_patches_count"]() != 0 and entries(inf3, M=0)["nesti_patches_query_ref"]() != 0
+    ok = (ctypes.c_double * 3)(0.1, 0.2, 0.3)
+    assert entries(ok, M=0)["nesti_patches_count"]() == 0 and entries(ok, M=0)["nesti_patches_query_ref"]() == 0
+
+
+def test_cloud_patches_refuses_a_cloud_with_a_non_finite_row():
+    """Raised on the host before the library or a device is asked for: one infinite coordinate makes the bounding-box diagonal, and
+    with it every radius, infinite."""
+    import pytest
+    import nesti_net_amd  # noqa: F401
+    from nesti_net_amd import provider
+    from nesti_net_amd.config import NestiConfig
+    pts = np.random.RandomState(0).rand(50, 3).astype(np.float32)
+    for v in (np.inf, -np.inf, np.nan):
+        bad = pts.copy()
+        bad[7, 2] = v
+        bad[31, 0] = v
+        with pytest.raises(ValueError, match="cloud row 7 is not finite"):
+            provider.CloudPatches(bad, NestiConfig())
+        with pytest.raises(ValueError, match="cloud row 7 is not finite"):
+            provider.CloudPatches(bad.astype(np.float64), NestiConfig(), queries=pts[:3])

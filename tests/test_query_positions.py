@@ -50,7 +50,7 @@ def test_patches_query_at_refusals_before_any_device_call():
     # everything the index form refuses, in its style
     assert _query_at(lib, cfg, FAKE, 5, N=0) != 0 and _last_error(lib) == "nesti_patches_query_at: empty cloud"
     assert _query_at(lib, cfg, FAKE, 5, ws_bytes=16) != 0 and _last_error(lib) == "nesti_patches_query_at: grid workspace too small"
-    assert _query_at(lib, cfg, FAKE, 5, r=(0.1, 0.0, 0.3)) != 0 and _last_error(lib) == "nesti_patches_query_at: radii must be positive"
+    assert _query_at(lib, cfg, FAKE, 5, r=(0.1, 0.0, 0.3)) != 0 and _last_error(lib) == "nesti_patches_query_at: radii must be positive and finite"
     assert _query_at(lib, NestiConfig(num_point=1024), FAKE, 5) != 0
     assert _last_error(lib) == "nesti_patches_query_at: points_per_scale must be in [1, 512]"
     c = cfg.to_c()

@@ -499,6 +499,53 @@ int nesti_pca_normals_at(const nesti_config_t* cfg, const float* cloud_dev, int 
  * every operation rounded on its own.  Returns 1 for a null pointer. */
 int nesti_sym3_eig(const double c[6], double w[3], double v[9]);
 
+/* ---- quadric-fit normals and principal curvatures at every patch scale (quadric.hip; DESIGN.md 2 "Quadric fit") ------------------
+ * The osculating-jet estimator of Cazals and Pouget at degree 2: the second row of the paper's comparison tables, and the source of
+ * the principal curvatures the reference's data layer reads from <shape>.curv (utils/pcpnet_dataset.py:260-263, 349-352, 410-413).
+ * No model, no weights.  Queries, radii, grid workspace and query_row0 as for nesti_pca_normals.  Per query centre c and scale s
+ * (radius r), over the FULL ball of nesti_pca_normals (fp64 d2(p, c) <= r^2, not capped at points_per_scale, not subsampled), with
+ * d = (double)p - (double)c and n the ball size; fp64, every operation rounded on its own:
+ *   1 plane normal  n0 = the normal nesti_pca_normals returns for that ball on the same grid (f32, signed), taken back to fp64, not
+ *                   renormalised
+ *   2 frame         j = the index of the smallest |n0_j| (ties: the first of x, y, z); t1 = (n0 x e_j) / |n0 x e_j|; t2 = n0 x t1,
+ *                   not renormalised.  (The fitted surface does not depend on the rotation inside the tangent plane.)
+ *   3 coordinates   (u, v, h) = ((t . d) / r) for t = t1, t2, n0, the dot product bracketed (t_x d_x + t_y d_y) + t_z d_z;
+ *                   phi = (1, u, v, u^2, u v, v^2)
+ *   4 moments       m[0..14] = sum u^p v^q for (p, q) = (0,0) (1,0) (0,1) (2,0) (1,1) (0,2) (3,0) (2,1) (1,2) (0,3) (4,0) (3,1) (2,2)
+ *                   (1,3) (0,4); m[15..20] = sum h phi_i; m[0] = n
+ *   5 solve         N a = b, N_ij = sum phi_i phi_j read from m, b = m[15..20]: Cholesky without pivoting in a fixed operation order
+ *                   (csrc/quadric_solve.h).  The fit FAILS if n < 6, if n0 is the zero row, or if a pivot
+ *                   s_j = N_jj - sum_k L_jk^2 is not > 2^-44 N_jj (a zero, negative or NaN pivot included), or if a coefficient
+ *                   comes out non-finite (a NaN among the h moments, which no pivot sees)
+ *   6 normal        nu = (n0 - a1 t1) - a2 t2, normalised in fp64, rounded to f32 once; zeros are +0.  nu . n0 > 0: it lies on
+ *                   n0's side, and no second sign rule is applied, because the curvature signs refer to this side
+ *   7 curvatures    the eigenvalues of the shape operator in an orthonormal tangent basis: g = (a1, a2), w = sqrt(1 + g.g),
+ *                   Hh = [[2 a3, a4], [a4, 2 a5]], P = I - g g^T / (w (1 + w)), Sm = P Hh P / w, mean = (Sm00 + Sm11) / 2,
+ *                   dif = (Sm00 - Sm11) / 2, q = (Sm01 + Sm10) / 2, rad = sqrt(dif^2 + q^2); k_max = (mean + rad) / r,
+ *                   k_min = (mean - rad) / r, as f32.  ABSOLUTE units (1 / length), those of a PCPNet .curv file.  Positive where
+ *                   the surface bends toward nu: a sphere of radius R with outward normals has k_max = k_min = -1 / R
+ *   8 failed fit    nu = 0 0 0 and k = 0 0 (also where nu or k would not be finite, which takes an overflow); plane_out and n_ball
+ *                   are written as nesti_pca_normals writes them.  No output is NaN or infinite for finite input; a non-finite
+ *                   position has n = 0 at every scale.
+ * FLIP: replacing n0 by -n0 gives t1 -> -t1, t2 -> t2, (u, v, h) -> (-u, v, -h), a -> (-a0, a1, -a2, -a3, a4, -a5), nu -> -nu
+ * and (k_max, k_min) -> (-k_min, -k_max), all exactly.  Orienting a row is therefore: where the sign bits of nu were flipped, its
+ * curvatures become (-k_min, -k_max).
+ * Outputs (device; any may be NULL): normals_out_dev [M,S,3] f32 nu; curv_out_dev [M,S,2] f32 (k_max, k_min); plane_out_dev [M,S,3]
+ * f32 n0, the bits of nesti_pca_normals' normals_out_dev; n_ball_out_dev [M,S] int32.
+ * DETERMINISM as for nesti_pca_normals: no floating-point atomics; for ONE grid a row's outputs are identical bits however the rows
+ * are split over calls and streams.  The argument errors of nesti_pca_normals are reported before any device call; M = 0 is a no-op.
+ * The calls enqueue one kernel on `stream`, neither synchronise nor read anything back, and can be captured into a graph. */
+int nesti_quadric_fit(const nesti_config_t* cfg, const float* cloud_dev, int N, const int32_t* query_idx_dev, int M,
+                      const double* r_abs, int query_row0, float* normals_out_dev, float* curv_out_dev, float* plane_out_dev,
+                      int32_t* n_ball_out_dev, const void* grid_ws_dev, size_t grid_ws_bytes, void* stream);
+int nesti_quadric_fit_at(const nesti_config_t* cfg, const float* cloud_dev, int N, const float* query_xyz_dev, int M,
+                         const double* r_abs, int query_row0, float* normals_out_dev, float* curv_out_dev, float* plane_out_dev,
+                         int32_t* n_ball_out_dev, const void* grid_ws_dev, size_t grid_ws_bytes, void* stream);
+/* Host only: steps 5 and 7 on the CPU, the arithmetic of the two entries above (csrc/quadric_solve.h), in the scaled units of the fit
+ * (k is not divided by r).  m[21] as in step 4; a[6] the coefficients; k[2] = (k_max, k_min); *ok = 1 if the fit succeeded, else 0
+ * with a = 0 and k = 0 (m[0] < 6, or a pivot failed: rank-deficient or NaN moments).  Returns 1 for a null pointer. */
+int nesti_quadric_solve(const double m[21], double a[6], double k[2], int* ok);
+
 /* ---- depth images in, normal images out (depth.hip; DESIGN.md 2 "Depth images") --------------------------------------------------
  * The two ends of the reference's Kinect route: MATLAB/ScanNet_depth2xyz.m (depth + intrinsics + pose -> cloud) before
  * test_n_est_w_experts.py, and MATLAB/ScanNet_world2cam_normals.m / MATLAB/export_visualizations_nyu.m:146-153 (per-point results

@@ -9,7 +9,9 @@ The trained-model directory holds either ``model.nstw`` (variables + hyper-param
 :mod:`.weights`) or the reference's own ``parameters.p`` / ``gmm.p`` / ``model.ckpt.*`` (read by
 :mod:`.tf_ckpt` without TensorFlow); ``--synthetic_weights`` substitutes seeded random weights (no
 checkpoint ships with the reference).  ``--estimator pca`` needs none of them: the plane-fit normals of :mod:`.pca`, written as
-``<shape>.normals`` (one scale), ``<shape>.pca_eig`` and ``<shape>.pca_count`` (every scale)."""
+``<shape>.normals`` (one scale), ``<shape>.pca_eig`` and ``<shape>.pca_count`` (every scale); nor does ``--estimator quadric``: the
+quadric-fit normals and principal curvatures of :mod:`.quadric`, written as ``<shape>.normals`` and ``<shape>.curv`` (one scale),
+``<shape>.quadric_curv`` and ``<shape>.quadric_count`` (every scale)."""
 import argparse
 import ctypes
 import os
@@ -97,17 +99,26 @@ def build_parser():
     p.add_argument("--orient_k", type=int, default=8, help="--orient mst: neighbours per point, 1 .. 16 [default: 8]")
     p.add_argument("--viewpoint", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"),
                    help="--orient viewpoint (required) / --orient mst (optional): the sensor position in the cloud's coordinates")
-    p.add_argument("--estimator", default="net", choices=["net", "pca"],
+    p.add_argument("--estimator", default="net", choices=["net", "pca", "quadric"],
                    help="net (default): Nesti-Net, from the trained model in --results_path.  pca: the classical plane fit at every patch "
                         "radius of --model's configuration (DESIGN.md 2 'Plane-fit normals'); no model.nstw and no --synthetic_weights "
                         "are needed or read.  Writes <shape>.normals (the scale --pca_scale), <shape>.pca_eig (M rows of 3 S "
                         "eigenvalues in units of r^2, ascending per scale; surface variation = the first over the sum of the three) and "
                         "<shape>.pca_count (M rows of S ball sizes); a scale whose ball holds fewer than 3 points is written as 0 0 0.  "
                         "Honours --sparse_patches, --query_positions, --orient, --orient_k and --viewpoint (the orientation radius is "
-                        "that of --pca_scale); --depth_images 1, --reproducible 1 and --subsample reference* belong to net")
+                        "that of --pca_scale); --depth_images 1, --reproducible 1 and --subsample reference* belong to net.  "
+                        "quadric: a degree-2 height function fitted to the same balls in the plane fit's frame (DESIGN.md 2 'Quadric "
+                        "fit'), under the same conditions.  Writes <shape>.normals (the fitted surface's normal at the scale "
+                        "--quadric_scale), <shape>.curv (M rows k_max k_min at that scale, in 1 / length: the two columns the "
+                        "reference's dataset reads; positive where the surface bends toward the written normal), <shape>.quadric_curv "
+                        "(M rows of 2 S values, unoriented) and <shape>.quadric_count (M rows of S ball sizes); a fit that fails (fewer "
+                        "than 6 points in the ball, or a singular system) is written as 0 0 0 and 0 0")
     p.add_argument("--pca_scale", type=int, default=-1,
                    help="--estimator pca: the scale whose normals go to <shape>.normals, an index into the patch radii; negative "
                         "counts from the end [default: -1, the largest]")
+    p.add_argument("--quadric_scale", type=int, default=-1,
+                   help="--estimator quadric: the scale whose normals and curvatures go to <shape>.normals and <shape>.curv, an index "
+                        "into the patch radii; negative counts from the end [default: -1, the largest]")
     p.add_argument("--synthetic_weights", action="store_true", help="use seeded synthetic weights if model.nstw is absent")
     return p
 
@@ -202,9 +213,47 @@ def run_pca(FLAGS, cfg, scale, pc_path, output_dir, printout):
     return 0
 
 
+def run_quadric(FLAGS, cfg, scale, pc_path, output_dir, printout):
+    """``--estimator quadric``: per shape the quadric fit at every scale, the optional orientation of the rows of scale ``scale`` (>= 0)
+    with the flip of their curvatures, and the four files.  No model is loaded."""
+    from . import quadric as _quadric
+    dataset = PointcloudPatchDataset(pc_path, FLAGS.testset, cfg, seed=3627473, sparse_patches=FLAGS.sparse_patches,
+                                     device="cuda:%d" % FLAGS.gpu, query_positions=bool(FLAGS.query_positions))
+    for ind, name in enumerate(dataset.shape_names):
+        cloud = dataset.get_shape(ind)
+        res = _quadric.quadric_cloud(cloud, scale, None if FLAGS.orient == "0" else FLAGS.orient, FLAGS.viewpoint, FLAGS.orient_k)
+        failed = int((res["normals_all"][:, scale] == 0).all(axis=1).sum())
+        printout("quadric fit of %s: %d rows, radius %.6g (scale %d of %d); %d rows without a fit in that ball (fewer than 6 points or a "
+                 "singular system: written as 0 0 0 and 0 0)" % (name, cloud.patch_count, cloud.r_abs[scale], scale, cfg.n_scales, failed))
+        if res["orient"] is not None:
+            ost = res["orient"]
+            printout("orientation of %s (%s): %d of %d rows oriented, %d flipped, %d connected piece%s, %d edges"
+                     % (name, FLAGS.orient, ost["n_eligible"], cloud.patch_count, ost["n_flipped"], ost["n_components"],
+                        "" if ost["n_components"] == 1 else "s", ost["n_edges"]))
+        textio.write_f32(os.path.join(output_dir, name + ".normals"), res["normals"])
+        textio.write_f32(os.path.join(output_dir, name + ".curv"), res["curv"])
+        textio.write_f32(os.path.join(output_dir, name + ".quadric_curv"), res["curv_all"].reshape(len(res["curv_all"]), -1))
+        textio.write_i32_rows(os.path.join(output_dir, name + ".quadric_count"), res["n_ball"])
+        printout("saved normals, curvatures and ball sizes for " + name)
+    return 0
+
+
 def main(argv=None):
     parser = build_parser()
     FLAGS = parser.parse_args(argv)
+    if FLAGS.pca_scale != -1 and FLAGS.estimator != "pca":
+        parser.error("--pca_scale belongs to --estimator pca")
+    if FLAGS.quadric_scale != -1 and FLAGS.estimator != "quadric":
+        parser.error("--quadric_scale belongs to --estimator quadric")
+    if FLAGS.estimator == "quadric":
+        if FLAGS.depth_images:
+            parser.error("--estimator quadric does not take --depth_images 1: depth frames belong to the network path (--estimator net)")
+        if FLAGS.reproducible:
+            parser.error("--estimator quadric does not take --reproducible 1: it freezes the network's thresholds (--estimator net); "
+                         "the quadric fit has none")
+        if FLAGS.subsample != "hash":
+            parser.error("--estimator quadric does not take --subsample %s: the quadric fit uses the full ball and subsamples nothing"
+                         % FLAGS.subsample)
     if FLAGS.estimator == "pca":
         if FLAGS.depth_images:
             parser.error("--estimator pca does not take --depth_images 1: depth frames belong to the network path (--estimator net)")
@@ -214,8 +263,6 @@ def main(argv=None):
         if FLAGS.subsample != "hash":
             parser.error("--estimator pca does not take --subsample %s: the plane fit uses the full ball and subsamples nothing"
                          % FLAGS.subsample)
-    elif FLAGS.pca_scale != -1:
-        parser.error("--pca_scale belongs to --estimator pca")
     if FLAGS.query_positions and FLAGS.sparse_patches:
         parser.error("--query_positions 1 and --sparse_patches 1 are mutually exclusive: the queries are positions or cloud points")
     if FLAGS.query_positions and FLAGS.subsample != "hash":
@@ -263,6 +310,16 @@ def main(argv=None):
         except ValueError as e:
             raise SystemExit("--pca_scale with --model %s: %s" % (FLAGS.model, e))
         rc = run_pca(FLAGS, cfg, scale, pc_path, output_dir, printout)
+        flog.close()
+        return rc
+    if FLAGS.estimator == "quadric":
+        from .pca import check_scale
+        cfg = NestiConfig.for_model(FLAGS.model)
+        try:
+            scale = check_scale(FLAGS.quadric_scale, cfg.n_scales)
+        except ValueError as e:
+            raise SystemExit("--quadric_scale with --model %s: %s" % (FLAGS.model, e))
+        rc = run_quadric(FLAGS, cfg, scale, pc_path, output_dir, printout)
         flog.close()
         return rc
 

@@ -35,15 +35,10 @@
 // device: the CPU restatement (tests/_pca_fixture.py) bounds each step
 #pragma clang fp contract(off)
 
-#include "pca_eig.h"
+#include "pca_dev.h"     // the fit itself, shared with pass 1 of quadric.hip
 
 namespace nesti {
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
-constexpr int kRowsPerBlock = kThreads / kWave;
-constexpr int kSums = 9;              // sum d (3), sum d d^T (6: xx xy xz yy yz zz)
 
 struct PcaParams {
   PatchParams p;                      // points_out / n_eff_out / nbr_out unused; n_ball_out optional
@@ -51,88 +46,22 @@ struct PcaParams {
   float* eig_out;                     // [M, S, 3] or NULL
 };
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v = v + __shfl_xor(v, off, kWave);
-  return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-
 template <int S>
 __global__ __launch_bounds__(kThreads) void pca_kernel(const PcaParams pp) {
   const PatchParams& p = pp.p;
   const int lane = threadIdx.x & (kWave - 1);
-  // the row is the same in every lane of a wave: say so, and the centre and its tests live in scalar registers
-  const int q = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6)));
+  const int q = wave_row();
   if (q >= p.M) return;                                       // whole waves leave: the shuffles below see full waves
   const float* centre = query_centre(p, q);
   const float cf0 = centre[0], cf1 = centre[1], cf2 = centre[2];
-  WaveSpans spans = {0, 0};                                   // lane t < 9: x-span t of the cell block (block_span, patches_dev.h)
-  if (!centre_lost(cf0, cf1, cf2) && lane < 9) {
-    const Span s = block_span(*p.header, p.start, p.N, cf0, cf1, cf2, lane);
-    spans.b = s.b;
-    spans.e = s.e;
-  }
-  const double cx = cf0, cy = cf1, cz = cf2;
-  double acc[S][kSums];
-  int cnt[S];
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    cnt[s] = 0;
-#pragma unroll
-    for (int k = 0; k < kSums; ++k) acc[s][k] = 0.0;
-  }
-  walk_block(p.sorted, spans, lane, kWave, cx, cy, cz, [&](const float4& c, double d2) {
-    // the differences ball_d2 was given, formed again: the same operations, so the same values
-    const double dx = (double)c.x - cx, dy = (double)c.y - cy, dz = (double)c.z - cz;
-    const double xx = __dmul_rn(dx, dx), yy = __dmul_rn(dy, dy), zz = __dmul_rn(dz, dz);
-    const double xy = dx * dy, xz = dx * dz, yz = dy * dz;
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      if (d2 <= p.r2[s]) {
-        ++cnt[s];
-        acc[s][0] += dx; acc[s][1] += dy; acc[s][2] += dz;
-        acc[s][3] += xx; acc[s][4] += xy; acc[s][5] += xz;
-        acc[s][6] += yy; acc[s][7] += yz; acc[s][8] += zz;
-      }
-    }
-  });
-  // every lane ends up with every total; lane s keeps those of scale s (lanes >= S: of the last scale, and write nothing)
-  double sum[kSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  int n = 0;
-  double r2 = 1.0;
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    const int ns = wave_sum(cnt[s]);
-    const bool mine = lane == s || (s == S - 1 && lane >= S);
-    if (mine) { n = ns; r2 = p.r2[s]; }
-#pragma unroll
-    for (int k = 0; k < kSums; ++k) {
-      const double t = wave_sum(acc[s][k]);
-      if (mine) sum[k] = t;
-    }
-  }
-  if (lane >= S) return;
-  float nrm[3] = {0.f, 0.f, 0.f}, ev[3] = {0.f, 0.f, 0.f};
-  if (n >= 3) {
-    const double dn = (double)n;
-    const double mx = sum[0] / dn, my = sum[1] / dn, mz = sum[2] / dn;
-    const double c[6] = {(sum[3] / dn - mx * mx) / r2, (sum[4] / dn - mx * my) / r2, (sum[5] / dn - mx * mz) / r2,
-                         (sum[6] / dn - my * my) / r2, (sum[7] / dn - my * mz) / r2, (sum[8] / dn - mz * mz) / r2};
-    double w[3], vec[3][3];
-    sym3_eig(c, w, vec);
-    const double len = sqrt((vec[0][0] * vec[0][0] + vec[0][1] * vec[0][1]) + vec[0][2] * vec[0][2]);
-    float fx = (float)(vec[0][0] / len), fy = (float)(vec[0][1] / len), fz = (float)(vec[0][2] / len);
-    const float lead = fz != 0.f ? fz : (fy != 0.f ? fy : fx);
-    if (lead < 0.f) { fx = -fx; fy = -fy; fz = -fz; }
-    nrm[0] = fx + 0.f; nrm[1] = fy + 0.f; nrm[2] = fz + 0.f;   // -0 + +0 = +0: no negative zero leaves
-#pragma unroll
-    for (int k = 0; k < 3; ++k) ev[k] = (float)fmax(0.0, w[k]);
-  }
+  const WaveSpans spans = wave_spans(p, lane, cf0, cf1, cf2);
+  double sum[kSums];
+  int n;
+  double r2;
+  plane_sums<S>(p, spans, lane, (double)cf0, (double)cf1, (double)cf2, sum, n, r2);
+  if (lane >= S) return;                                      // lane s solves scale s
+  float nrm[3], ev[3];
+  plane_solve(sum, n, r2, nrm, ev);
   const size_t o = (size_t)q * S + lane;
   if (pp.normals_out) { pp.normals_out[o * 3] = nrm[0]; pp.normals_out[o * 3 + 1] = nrm[1]; pp.normals_out[o * 3 + 2] = nrm[2]; }
   if (pp.eig_out) { pp.eig_out[o * 3] = ev[0]; pp.eig_out[o * 3 + 1] = ev[1]; pp.eig_out[o * 3 + 2] = ev[2]; }

@@ -1,0 +1,116 @@
+// The plane fit of one query by one wave (DESIGN.md 2 "Plane-fit normals"), shared by pca_kernel (pca.hip) and by pass 1 of
+// quadric_kernel (quadric.hip): the query's spans, the nine fp64 sums and the count of every scale, their wave reductions, and the
+// solve with its rounding and sign rule.  One definition, so the plane normal of the quadric fit IS nesti_pca_normals' normal, bit for bit.
+//
+// For the including unit: include patches_dev.h first, under the compiler's default contraction (ball_d2, see there), then
+// `#pragma clang fp contract(off)`, then this header -- every product and sum below is rounded on its own.
+#pragma once
+#include "patches_dev.h"
+#include "pca_eig.h"
+
+namespace nesti {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWave = 64;
+constexpr int kRowsPerBlock = kThreads / kWave;
+constexpr int kSums = 9;              // sum d (3), sum d d^T (6: xx xy xz yy yz zz)
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) v = v + __shfl_xor(v, off, kWave);
+  return v;
+}
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+  return v;
+}
+
+// the row of this wave (the same in every lane: said so, and the centre and its tests live in scalar registers); a wave beyond the
+// last row gets M or more and leaves whole, so the shuffles of the others see full waves
+__device__ __forceinline__ int wave_row() {
+  return __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6)));
+}
+
+// lane t < 9: x-span t of the cell block round the centre (block_span, patches_dev.h); empty for a centre that is not finite
+__device__ __forceinline__ WaveSpans wave_spans(const PatchParams& p, int lane, float cf0, float cf1, float cf2) {
+  WaveSpans spans = {0, 0};
+  if (!centre_lost(cf0, cf1, cf2) && lane < 9) {
+    const Span s = block_span(*p.header, p.start, p.N, cf0, cf1, cf2, lane);
+    spans.b = s.b;
+    spans.e = s.e;
+  }
+  return spans;
+}
+
+// The sums of d and d d^T and the count of every scale's ball.  A candidate is tested once for all scales: the six products of d are
+// formed once and added to the sums of every scale whose ball holds it.  Every lane ends up with every total; lane s keeps those of
+// scale s (lanes >= S: of the last scale).
+template <int S>
+__device__ __forceinline__ void plane_sums(const PatchParams& p, const WaveSpans& spans, int lane, double cx, double cy, double cz,
+                                           double (&sum)[kSums], int& n, double& r2) {
+  double acc[S][kSums];
+  int cnt[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    cnt[s] = 0;
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) acc[s][k] = 0.0;
+  }
+  walk_block(p.sorted, spans, lane, kWave, cx, cy, cz, [&](const float4& c, double d2) {
+    // the differences ball_d2 was given, formed again: the same operations, so the same values
+    const double dx = (double)c.x - cx, dy = (double)c.y - cy, dz = (double)c.z - cz;
+    const double xx = __dmul_rn(dx, dx), yy = __dmul_rn(dy, dy), zz = __dmul_rn(dz, dz);
+    const double xy = dx * dy, xz = dx * dz, yz = dy * dz;
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      if (d2 <= p.r2[s]) {
+        ++cnt[s];
+        acc[s][0] += dx; acc[s][1] += dy; acc[s][2] += dz;
+        acc[s][3] += xx; acc[s][4] += xy; acc[s][5] += xz;
+        acc[s][6] += yy; acc[s][7] += yz; acc[s][8] += zz;
+      }
+    }
+  });
+#pragma unroll
+  for (int k = 0; k < kSums; ++k) sum[k] = 0.0;
+  n = 0;
+  r2 = 1.0;
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    const int ns = wave_sum(cnt[s]);
+    const bool mine = lane == s || (s == S - 1 && lane >= S);
+    if (mine) { n = ns; r2 = p.r2[s]; }
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) {
+      const double t = wave_sum(acc[s][k]);
+      if (mine) sum[k] = t;
+    }
+  }
+}
+
+// covariance in units of r^2 -> Jacobi -> the normal (normalised in fp64, rounded to f32 once, signed on the f32 values so that the
+// first non-zero of (n_z, n_y, n_x) is positive, zeros +0) and the clamped eigenvalues; n < 3: all 0
+__device__ __forceinline__ void plane_solve(const double (&sum)[kSums], int n, double r2, float (&nrm)[3], float (&ev)[3]) {
+  nrm[0] = 0.f; nrm[1] = 0.f; nrm[2] = 0.f;
+  ev[0] = 0.f; ev[1] = 0.f; ev[2] = 0.f;
+  if (n >= 3) {
+    const double dn = (double)n;
+    const double mx = sum[0] / dn, my = sum[1] / dn, mz = sum[2] / dn;
+    const double c[6] = {(sum[3] / dn - mx * mx) / r2, (sum[4] / dn - mx * my) / r2, (sum[5] / dn - mx * mz) / r2,
+                         (sum[6] / dn - my * my) / r2, (sum[7] / dn - my * mz) / r2, (sum[8] / dn - mz * mz) / r2};
+    double w[3], vec[3][3];
+    sym3_eig(c, w, vec);
+    const double len = sqrt((vec[0][0] * vec[0][0] + vec[0][1] * vec[0][1]) + vec[0][2] * vec[0][2]);
+    float fx = (float)(vec[0][0] / len), fy = (float)(vec[0][1] / len), fz = (float)(vec[0][2] / len);
+    const float lead = fz != 0.f ? fz : (fy != 0.f ? fy : fx);
+    if (lead < 0.f) { fx = -fx; fy = -fy; fz = -fz; }
+    nrm[0] = fx + 0.f; nrm[1] = fy + 0.f; nrm[2] = fz + 0.f;   // -0 + +0 = +0: no negative zero leaves
+#pragma unroll
+    for (int k = 0; k < 3; ++k) ev[k] = (float)fmax(0.0, w[k]);
+  }
+}
+
+}  // namespace
+}  // namespace nesti

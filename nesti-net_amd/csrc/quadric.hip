@@ -1,0 +1,257 @@
+// Quadric-fit normals and principal curvatures at every patch scale (DESIGN.md 2 "Quadric fit"): the osculating-jet estimator of
+// Cazals and Pouget at degree 2, the second row of the paper's comparison tables, and the source of the per-point principal curvatures
+// the reference's data layer reads from <shape>.curv (utils/pcpnet_dataset.py:260-263, 349-352, 410-413).  No model, no weights.
+//
+// Per query centre c and scale s (radius r), over the FULL ball of nesti_pca_normals (fp64 ball_d2 <= r^2, not capped, not subsampled),
+// with d = (double)p - (double)c and n the ball size:
+//   1  n0 = the plane-fit normal of that ball exactly as nesti_pca_normals returns it (pca_dev.h: rounded to f32, signed), taken back
+//      to fp64 and not renormalised; it is an output too (plane_out)
+//   2  frame from n0 alone: j = the index of the smallest |n0_j| (ties: x, y, z), t1 = (n0 x e_j) / |n0 x e_j|, t2 = n0 x t1
+//   3  (u, v, h) = ((t . d) / r) for t = t1, t2, n0, the dot product bracketed (tx dx + ty dy) + tz dz; phi = (1, u, v, u^2, u v, v^2)
+//   4  the moments m[0..14] = sum u^p v^q (p + q <= 4), m[15..20] = sum h phi_i, m[0] = n.  The monomials are formed as
+//      u2 = u u, uv = u v, v2 = v v, u3 = u2 u, u2v = u2 v, uv2 = u v2, v3 = v2 v, u4 = u2 u2, u3v = u3 v, u2v2 = u2 v2, uv3 = u v3,
+//      v4 = v2 v2, and h u, h v, h u2, h uv, h v2
+//   5  N a = b by Cholesky with a pivot threshold (quadric_solve.h); the fit FAILS if n < 6, if n0 is the zero row, if a pivot fails
+//      or if a coefficient is not finite
+//   6  nu = (n0 - a1 t1) - a2 t2, normalised in fp64, rounded to f32 once, zeros +0.  nu . n0 > 0; no second sign rule
+//   7  curvatures from the shape operator in an orthonormal tangent basis (quadric_solve.h), divided by r: absolute units, k_max >= k_min,
+//      positive where the surface bends toward nu
+//   8  a failed fit writes nu = 0 0 0 and k = 0 0 (so does one whose nu or k would not be finite, which takes an overflow);
+//      plane_out and n_ball are written as nesti_pca_normals writes them
+//
+// One wave per query, four queries per workgroup, like pca_kernel.  Pass 1 is pca_kernel's (pca_dev.h).  Lane s then holds n0 of scale
+// s; it is read from there into scalar registers and every lane builds the same frame.  Pass 2 walks the same spans again and adds the
+// 20 fp64 sums of every scale whose ball holds the candidate; the totals come from the fixed xor-butterfly and lane s solves scale s.
+//
+// DETERMINISM, as in pca.hip: no floating-point atomics, no LDS; candidate i of a span goes to lane (i - span begin) mod 64 and the
+// lanes meet in a fixed tree, so for ONE prepared grid a row's bits do not depend on batching, streams or partition.
+#include <string.h>
+
+#include <cmath>
+#include <string>
+
+#include "kernels.h"
+// before the pragma below, like pca.hip: the ball is the plane fit's ball (ball_d2, patches_dev.h)
+#include "patches_dev.h"
+
+// every product and sum below -- the plane fit of pca_dev.h and the solve of quadric_solve.h included -- is rounded on its own, on the
+// host (nesti_quadric_solve) as on the device: the CPU restatement (tests/_quadric_fixture.py) bounds each step
+#pragma clang fp contract(off)
+
+#include "pca_dev.h"
+#include "quadric_solve.h"
+
+namespace nesti {
+namespace {
+
+constexpr int kQSums = kQuadricMoments - 1;   // m[1..20]: m[0] = n is known from pass 1
+
+struct QuadricParams {
+  PatchParams p;                      // points_out / n_eff_out / nbr_out unused; n_ball_out optional
+  double r[NESTI_MAX_SCALES];         // the radii themselves: (t . d) / r
+  float* normals_out;                 // [M, S, 3] or NULL
+  float* curv_out;                    // [M, S, 2] or NULL
+  float* plane_out;                   // [M, S, 3] or NULL
+};
+
+// a value that is the same in every lane, into scalar registers
+__device__ __forceinline__ double wave_uniform(double v) {
+  return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+
+// step 2: the frame (t1, t2, n0) of a plane normal, f[0..2] = t1, f[3..5] = t2, f[6..8] = n0
+__device__ __forceinline__ void quadric_frame(double nx, double ny, double nz, double (&f)[9]) {
+  const double ax = fabs(nx), ay = fabs(ny), az = fabs(nz);
+  double cx, cy, cz;                                          // n0 x e_j
+  if (ax <= ay && ax <= az) { cx = 0.0; cy = nz; cz = -ny; }
+  else if (ay <= az) { cx = -nz; cy = 0.0; cz = nx; }
+  else { cx = ny; cy = -nx; cz = 0.0; }
+  const double len = sqrt((cx * cx + cy * cy) + cz * cz);
+  f[0] = cx / len; f[1] = cy / len; f[2] = cz / len;
+  f[3] = ny * f[2] - nz * f[1];
+  f[4] = nz * f[0] - nx * f[2];
+  f[5] = nx * f[1] - ny * f[0];
+  f[6] = nx; f[7] = ny; f[8] = nz;
+}
+
+template <int S>
+__global__ __launch_bounds__(kThreads) void quadric_kernel(const QuadricParams qp) {
+  const PatchParams& p = qp.p;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int q = wave_row();
+  if (q >= p.M) return;                                       // whole waves leave: the shuffles below see full waves
+  const float* centre = query_centre(p, q);
+  const float cf0 = centre[0], cf1 = centre[1], cf2 = centre[2];
+  const WaveSpans spans = wave_spans(p, lane, cf0, cf1, cf2);
+  const double cx = cf0, cy = cf1, cz = cf2;
+  // ---- pass 1: the plane fit; lane s solves scale s ---------------------------------------------------------------------------------
+  int n;
+  float nrm[3], ev[3];
+  {
+    double sum[kSums], r2;
+    plane_sums<S>(p, spans, lane, cx, cy, cz, sum, n, r2);
+    plane_solve(sum, lane < S ? n : 0, r2, nrm, ev);
+  }
+  // ---- the frame of every scale, the same in every lane.  A scale that cannot be fitted (n < 6, or no plane normal) gets a ball
+  // nothing is inside of, so pass 2 adds nothing for it
+  double fr[S][9], r2live[S], rad[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    const float bx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(nrm[0]), s));
+    const float by = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(nrm[1]), s));
+    const float bz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(nrm[2]), s));
+    const int ns = __builtin_amdgcn_readlane(n, s);
+    const bool live = ns >= kQuadricMinPoints && (bx != 0.f || by != 0.f || bz != 0.f);
+    double f[9];
+    quadric_frame((double)bx, (double)by, (double)bz, f);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) fr[s][k] = wave_uniform(live ? f[k] : 0.0);
+    r2live[s] = live ? p.r2[s] : -1.0;
+    rad[s] = qp.r[s];
+  }
+  // ---- pass 2: the moments ------------------------------------------------------------------------------------------------------------
+  double acc[S][kQSums];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+#pragma unroll
+    for (int k = 0; k < kQSums; ++k) acc[s][k] = 0.0;
+  }
+  walk_block(p.sorted, spans, lane, kWave, cx, cy, cz, [&](const float4& c, double d2) {
+    const double dx = (double)c.x - cx, dy = (double)c.y - cy, dz = (double)c.z - cz;
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      if (d2 <= r2live[s]) {
+        const double* f = fr[s];
+        const double u = ((f[0] * dx + f[1] * dy) + f[2] * dz) / rad[s];
+        const double v = ((f[3] * dx + f[4] * dy) + f[5] * dz) / rad[s];
+        const double h = ((f[6] * dx + f[7] * dy) + f[8] * dz) / rad[s];
+        const double u2 = u * u, uv = u * v, v2 = v * v;
+        const double u3 = u2 * u, u2v = u2 * v, uv2 = u * v2, v3 = v2 * v;
+        double* a = acc[s];
+        a[0] += u; a[1] += v;
+        a[2] += u2; a[3] += uv; a[4] += v2;
+        a[5] += u3; a[6] += u2v; a[7] += uv2; a[8] += v3;
+        a[9] += u2 * u2; a[10] += u3 * v; a[11] += u2 * v2; a[12] += u * v3; a[13] += v2 * v2;
+        a[14] += h; a[15] += h * u; a[16] += h * v; a[17] += h * u2; a[18] += h * uv; a[19] += h * v2;
+      }
+    }
+  });
+  // every lane ends up with every total; lane s keeps those, the frame and the radius of scale s
+  double m[kQuadricMoments], f[9], r = 1.0;
+#pragma unroll
+  for (int k = 0; k < kQuadricMoments; ++k) m[k] = 0.0;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) f[k] = 0.0;
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    const bool mine = lane == s;
+    if (mine) {
+      r = rad[s];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) f[k] = fr[s][k];
+    }
+#pragma unroll
+    for (int k = 0; k < kQSums; ++k) {
+      const double t = wave_sum(acc[s][k]);
+      if (mine) m[k + 1] = t;
+    }
+  }
+  if (lane >= S) return;
+  m[0] = (double)n;
+  // ---- lane s: solve, normal, curvatures ------------------------------------------------------------------------------------------------
+  float nu[3] = {0.f, 0.f, 0.f}, kf[2] = {0.f, 0.f};
+  double a[kQuadricCoeffs];
+  const bool fitted = n >= kQuadricMinPoints && (nrm[0] != 0.f || nrm[1] != 0.f || nrm[2] != 0.f);
+  if (quadric_solve(m, a) && fitted) {
+    const double vx = (f[6] - a[1] * f[0]) - a[2] * f[3], vy = (f[7] - a[1] * f[1]) - a[2] * f[4], vz = (f[8] - a[1] * f[2]) - a[2] * f[5];
+    const double len = sqrt((vx * vx + vy * vy) + vz * vz);
+    double k[2];
+    quadric_curvatures(a, k);
+    const float fx = (float)(vx / len), fy = (float)(vy / len), fz = (float)(vz / len);
+    const float k0 = (float)(k[0] / r), k1 = (float)(k[1] / r);
+    if (finite_bits(fx) && finite_bits(fy) && finite_bits(fz) && finite_bits(k0) && finite_bits(k1)) {
+      nu[0] = fx + 0.f; nu[1] = fy + 0.f; nu[2] = fz + 0.f;    // -0 + +0 = +0: no negative zero leaves
+      kf[0] = k0; kf[1] = k1;
+    }
+  }
+  const size_t o = (size_t)q * S + lane;
+  if (qp.normals_out) { qp.normals_out[o * 3] = nu[0]; qp.normals_out[o * 3 + 1] = nu[1]; qp.normals_out[o * 3 + 2] = nu[2]; }
+  if (qp.curv_out) { qp.curv_out[o * 2] = kf[0]; qp.curv_out[o * 2 + 1] = kf[1]; }
+  if (qp.plane_out) { qp.plane_out[o * 3] = nrm[0]; qp.plane_out[o * 3 + 1] = nrm[1]; qp.plane_out[o * 3 + 2] = nrm[2]; }
+  if (p.n_ball_out) p.n_ball_out[o] = n;
+}
+
+// nesti_quadric_fit (centres = cloud points, by index or row) and nesti_quadric_fit_at (centres = positions): one body
+int quadric_impl(const char* who, bool at, const nesti_config_t* cfg, const float* cloud_dev, int N, const int32_t* query_idx_dev,
+                 const float* query_xyz_dev, int M, const double* r_abs, int query_row0, float* normals_out_dev, float* curv_out_dev,
+                 float* plane_out_dev, int32_t* n_ball_out_dev, const void* grid_ws_dev, size_t grid_ws_bytes, void* stream) {
+  const std::string w(who);
+  if (refuse_grid_cloud(w, cfg, cloud_dev, N, r_abs, grid_ws_dev, grid_ws_bytes)) return 1;
+  if (M < 0) NESTI_FAIL(w + ": M must be >= 0");
+  if (refuse_query_rows(w, N, !at && !query_idx_dev, M, query_row0)) return 1;
+  if (M == 0) return 0;
+  if (at && !query_xyz_dev) NESTI_FAIL(w + ": null query_xyz_dev");
+  QuadricParams qp;
+  patch_params_fill(&qp.p, cfg, cloud_dev, N, query_idx_dev, M, r_abs, 0, query_row0, grid_ws_dev);
+  qp.p.query_xyz = at ? query_xyz_dev : nullptr;
+  qp.p.n_ball_out = n_ball_out_dev;
+  for (int s = 0; s < NESTI_MAX_SCALES; ++s) qp.r[s] = s < cfg->n_scales ? r_abs[s] : 1.0;
+  qp.normals_out = normals_out_dev;
+  qp.curv_out = curv_out_dev;
+  qp.plane_out = plane_out_dev;
+  const dim3 grid((unsigned)((M + kRowsPerBlock - 1) / kRowsPerBlock)), block(kThreads);
+  hipStream_t st = (hipStream_t)stream;
+  const int tok = prof_begin(NESTI_PROF_PATCHES, st);
+  switch (cfg->n_scales) {
+    case 1: hipLaunchKernelGGL(quadric_kernel<1>, grid, block, 0, st, qp); break;
+    case 2: hipLaunchKernelGGL(quadric_kernel<2>, grid, block, 0, st, qp); break;
+    case 3: hipLaunchKernelGGL(quadric_kernel<3>, grid, block, 0, st, qp); break;
+    default: hipLaunchKernelGGL(quadric_kernel<4>, grid, block, 0, st, qp); break;
+  }
+  prof_end(NESTI_PROF_PATCHES, tok, st);
+  NESTI_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+}  // namespace nesti
+
+using namespace nesti;
+
+extern "C" {
+
+int nesti_quadric_fit(const nesti_config_t* cfg, const float* cloud_dev, int N, const int32_t* query_idx_dev, int M,
+                      const double* r_abs, int query_row0, float* normals_out_dev, float* curv_out_dev, float* plane_out_dev,
+                      int32_t* n_ball_out_dev, const void* grid_ws_dev, size_t grid_ws_bytes, void* stream) {
+  return quadric_impl("nesti_quadric_fit", false, cfg, cloud_dev, N, query_idx_dev, nullptr, M, r_abs, query_row0, normals_out_dev,
+                      curv_out_dev, plane_out_dev, n_ball_out_dev, grid_ws_dev, grid_ws_bytes, stream);
+}
+
+int nesti_quadric_fit_at(const nesti_config_t* cfg, const float* cloud_dev, int N, const float* query_xyz_dev, int M,
+                         const double* r_abs, int query_row0, float* normals_out_dev, float* curv_out_dev, float* plane_out_dev,
+                         int32_t* n_ball_out_dev, const void* grid_ws_dev, size_t grid_ws_bytes, void* stream) {
+  return quadric_impl("nesti_quadric_fit_at", true, cfg, cloud_dev, N, nullptr, query_xyz_dev, M, r_abs, query_row0, normals_out_dev,
+                      curv_out_dev, plane_out_dev, n_ball_out_dev, grid_ws_dev, grid_ws_bytes, stream);
+}
+
+int nesti_quadric_solve(const double m[21], double a[6], double k[2], int* ok) {
+  if (!m || !a || !k || !ok) NESTI_FAIL("nesti_quadric_solve: null argument");
+  double mm[kQuadricMoments], aa[kQuadricCoeffs], kk[2] = {0.0, 0.0};
+  for (int i = 0; i < kQuadricMoments; ++i) mm[i] = m[i];
+  bool fitted = quadric_solve(mm, aa);
+  if (fitted) {
+    quadric_curvatures(aa, kk);
+    if (!std::isfinite(kk[0]) || !std::isfinite(kk[1])) {     // an overflow: a failed fit like any other
+      fitted = false;
+      kk[0] = kk[1] = 0.0;
+      for (int i = 0; i < kQuadricCoeffs; ++i) aa[i] = 0.0;
+    }
+  }
+  for (int i = 0; i < kQuadricCoeffs; ++i) a[i] = aa[i];
+  k[0] = kk[0];
+  k[1] = kk[1];
+  *ok = fitted ? 1 : 0;
+  return 0;
+}
+
+}  // extern "C"

@@ -215,6 +215,39 @@ class CloudPatches:
                 ctypes.c_void_p(st.cuda_stream)), entry)
         return normals, eig, n_ball
 
+    def quadric(self, first, count, out=None, stream=None):
+        """Quadric-fit normals and principal curvatures of patch rows [first, first + count) at every scale (``nesti_quadric_fit`` /
+        ``nesti_quadric_fit_at``; DESIGN.md 2 "Quadric fit"): device tensors ``(normals [count,S,3] f32, curv [count,S,2] f32 (k_max,
+        k_min; absolute units), plane [count,S,3] f32 (the bits of ``pca``'s normals), n_ball [count,S] int32)``, or the four of ``out``.
+        Serves all points, ``pidx`` and ``queries``; asynchronous on ``stream``.  A failed fit (fewer than 6 points in the ball, no plane
+        normal, a singular system) has normal 0 0 0 and curvatures 0 0.  For this grid a row's bits do not depend on the batching."""
+        S = self.cfg.n_scales
+        if first < 0 or count < 0 or first + count > self.patch_count:
+            raise ValueError("patch rows [%d, %d) outside [0, %d)" % (first, first + count, self.patch_count))
+        shapes = (((count, S, 3), torch.float32), ((count, S, 2), torch.float32), ((count, S, 3), torch.float32), ((count, S), torch.int32))
+        if out is None:
+            out = tuple(torch.empty(shape, dtype=dt, device=self.device) for shape, dt in shapes)
+        else:
+            out = tuple(out)
+            if len(out) != 4 or any(tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device
+                                    for t, (shape, dt) in zip(out, shapes)):
+                raise ValueError("out: contiguous (normals [count,S,3] f32, curv [count,S,2] f32, plane [count,S,3] f32, n_ball [count,S] "
+                                 "int32) on %s" % self.device)
+        normals, curv, plane, n_ball = out
+        at = self.queries is not None
+        if at:
+            q = self.queries[first:first + count]
+        else:
+            q = self.pidx[first:first + count].contiguous() if self.pidx is not None else None
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        entry = "nesti_quadric_fit_at" if at else "nesti_quadric_fit"
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(self.lib, entry)(
+                ctypes.byref(self._c), _lib.ptr(self.cloud), self.n_points, _lib.ptr(q), count, self._r, ctypes.c_int(first),
+                _lib.ptr(normals), _lib.ptr(curv), _lib.ptr(plane), _lib.ptr(n_ball), _lib.ptr(self._ws), self._ws.numel(),
+                ctypes.c_void_p(st.cuda_stream)), entry)
+        return normals, curv, plane, n_ball
+
     def build_reference_order(self, first, count, picks, pick_offsets, want_idx=False, out=None, stream=None):
         """Patch tensors of rows [first, first + count) exactly as the reference's ``PointcloudPatchDataset.__getitem__`` builds
         them (``nesti_patches_query_ref``): balls in cKDTree's visiting order, over-full balls thinned by ``picks`` (uint16 device

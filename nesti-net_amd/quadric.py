@@ -1,0 +1,72 @@
+"""Quadric-fit normals and principal curvatures at every patch scale on the GPU (``csrc/quadric.hip``; DESIGN.md 2 "Quadric fit"): the
+osculating-jet estimator of Cazals and Pouget at degree 2 -- the second row of the paper's comparison tables, and the source of the
+per-point principal curvatures the reference's data layer reads from ``<shape>.curv`` (``utils/pcpnet_dataset.py:260-263``).  It needs no
+model and no weights: per query and patch radius, a height function ``h = a . (1, u, v, u^2, u v, v^2)`` fitted to the full ball in the
+frame of the plane fit; the normal is the fitted surface's at the query and the curvatures are the eigenvalues of its shape operator.
+There is no CPU fallback."""
+import numpy as np
+
+from .config import NestiConfig
+from .pca import ORIENT_MODES, check_scale, orient_rows
+
+
+def mean_gauss(curv):
+    """(H, K) = ((k_max + k_min) / 2, k_max k_min) of curvatures [..., 2] (float32 in, float32 out)."""
+    curv = np.asarray(curv, np.float32)
+    return (curv[..., 0] + curv[..., 1]) * np.float32(0.5), curv[..., 0] * curv[..., 1]
+
+
+def quadric_cloud(cloud, scale=-1, orient=None, viewpoint=None, orient_k=8):
+    """``quadric_fit`` for a prepared ``provider.CloudPatches`` (all of its patch rows); synchronises."""
+    import torch
+    from . import orient as _orient
+    s = check_scale(scale, cloud.cfg.n_scales)
+    if orient not in ORIENT_MODES:
+        raise ValueError("orient must be None, 'mst' or 'viewpoint'")
+    with torch.cuda.device(cloud.device):
+        normals_all, curv_all, plane_all, n_ball = cloud.quadric(0, cloud.patch_count)
+        normals = normals_all[:, s, :].contiguous()
+        curv = curv_all[:, s, :].contiguous()
+        stats = None
+        if orient is not None and cloud.patch_count:
+            before = normals.clone()
+            stats = orient_rows(cloud, normals, s, orient, viewpoint, orient_k)
+            # the flip rule: the pass changes sign bits only, and a row whose normal it turned has curvatures (-k_min, -k_max)
+            flipped = (before.view(torch.int32) != normals.view(torch.int32)).any(dim=1, keepdim=True)
+            curv = torch.where(flipped, -curv.flip(1), curv)
+        torch.cuda.current_stream(cloud.device).synchronize()
+    return {"normals": normals.cpu().numpy(), "curv": curv.cpu().numpy(), "normals_all": normals_all.cpu().numpy(),
+            "curv_all": curv_all.cpu().numpy(), "plane_all": plane_all.cpu().numpy(), "n_ball": n_ball.cpu().numpy(),
+            "orient": None if orient is None else (_orient.stats_dict(stats) if stats is not None else dict.fromkeys(_orient.STAT_NAMES, 0))}
+
+
+def quadric_fit(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, viewpoint=None, orient_k=8, device="cuda:0"):
+    """Quadric-fit normals and principal curvatures of a cloud: numpy in, a dict of numpy arrays out (synchronises).  Queries are all
+    points, the points ``pidx`` or the positions ``queries`` [M,3] (mutually exclusive), as for ``pca.pca_normals``; the radii are
+    ``cfg.patch_radius`` times the cloud's bounding-box diagonal.
+
+      normals      [M,3]    the fitted surface's normal at ``scale`` (default -1: the largest), after the optional orientation
+      curv         [M,2]    (k_max, k_min) at ``scale``, in absolute units (1 / length: a PCPNet ``.curv`` row), positive where the
+                            surface bends toward ``normals``; after the optional orientation
+      normals_all  [M,S,3]  every scale, unoriented: on the side of the plane-fit normal
+      curv_all     [M,S,2]  every scale, signs referring to ``normals_all``
+      plane_all    [M,S,3]  the plane-fit normals the frames were built from: ``pca_normals``' ``normals_all``
+      n_ball       [M,S]    points in the ball (the full ball: not capped at ``cfg.num_point``, not subsampled)
+      orient       the stats dict of ``orient.orient_normals``, or None
+
+    A failed fit -- fewer than 6 points in the ball, no plane normal, or a singular system (collinear points, say) -- has normal 0 0 0
+    and curvatures 0 0; the orientation leaves such rows alone.  ``orient='mst' | 'viewpoint'`` orients the rows of ``scale`` with
+    radius ``r_abs[scale]``; where it turns a normal the row's curvatures become ``(-k_min, -k_max)``.
+    Raises ``ValueError`` for a ``scale`` outside [-S, S) and for ``pidx`` together with ``queries``."""
+    cfg = cfg or NestiConfig()
+    check_scale(scale, cfg.n_scales)
+    if orient not in ORIENT_MODES:
+        raise ValueError("orient must be None, 'mst' or 'viewpoint'")
+    if pidx is not None and queries is not None:
+        raise ValueError("pidx and queries are mutually exclusive: a query is a cloud point (pidx) or a position (queries)")
+    if orient is not None:
+        from .orient import _check_args
+        _check_args(1.0, orient_k, viewpoint, orient)
+    from .provider import CloudPatches
+    cloud = CloudPatches(np.asarray(pts, dtype=np.float32), cfg, device=device, pidx=pidx, queries=queries)
+    return quadric_cloud(cloud, scale, orient, viewpoint, orient_k)

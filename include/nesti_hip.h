@@ -33,6 +33,7 @@ extern "C" {
 #endif
 
 #define NESTI_MAX_SCALES 4
+#define NESTI_KNN_MAX_K 256   /* the largest K of nesti_knn and of a neighbour list (nesti_*_nbr) */
 #define NESTI_MAX_EXPERTS 8
 #define NESTI_MUPS_CH 20 /* channels per scale: utils/tf_util.py:711-720 */
 
@@ -545,6 +546,72 @@ int nesti_quadric_fit_at(const nesti_config_t* cfg, const float* cloud_dev, int 
  * (k is not divided by r).  m[21] as in step 4; a[6] the coefficients; k[2] = (k_max, k_min); *ok = 1 if the fit succeeded, else 0
  * with a = 0 and k = 0 (m[0] < 6, or a pivot failed: rank-deficient or NaN moments).  Returns 1 for a null pointer. */
 int nesti_quadric_solve(const double m[21], double a[6], double k[2], int* ok);
+
+/* ---- k-nearest-neighbour neighbourhoods (knn.hip; DESIGN.md 2 "k-nearest neighbourhoods") -----------------------------------------
+ * An exact k-NN search on the uniform grid of nesti_patches_grid, and the plane fit and the quadric fit over neighbour lists instead of
+ * balls: a neighbourhood that adapts to the density where a fixed radius starves the sparse part of a cloud.  No model, no weights.
+ *
+ * SEARCH.  For a centre c -- cloud point query_idx_dev[i], or cloud row query_row0 + i where query_idx_dev is NULL (an index is clamped
+ * into the cloud), or the position query_xyz_dev[i] -- over ALL N cloud points j, in fp64:
+ *     d = (double)p_j - (double)c,   d2_j = (dx dx + dy dy) + dz dz, each of the five operations rounded on its own
+ * (not the fused d2 of the ball test: a restatement in plain IEEE arithmetic predicts every bit).  The result is the K smallest pairs
+ * (d2_j, j) in lexicographic order, ascending:
+ *     nbr_out_dev   [M, K] int32   j
+ *     d2_out_dev    [M, K] fp64    d2_j                (may be NULL)
+ *     count_out_dev [M]    int32   min(K, N)           (may be NULL)
+ * Slots beyond the count hold -1 and +inf.  A centre with a non-finite coordinate (tested on the bits) has count 0.  A cloud point
+ * queried by index is its own neighbour (d2 = 0), as a ball contains its centre; duplicates tie on d2 and are ordered by index.  There
+ * is no radius bound: a query far from everything still gets its K nearest.  1 <= K <= NESTI_KNN_MAX_K.
+ * A cloud point with a NaN coordinate has a NaN d2 and is never a neighbour: the count of a query then falls below min(K, N) where
+ * fewer than K other points exist.  Under nesti_profile_enable the search and the list fits are booked in the patches category, like
+ * nesti_pca_normals and nesti_quadric_fit.
+ * GRID.  grid_ws_dev is any workspace prepared by nesti_patches_grid over this cloud (any config, any radii); the result does not
+ * depend on which one, nor on the order the build left inside a cell -- only the time does (aim at the order of K points in a
+ * 3 x 3 x 3 cell block).  The search starts at the centre's (clamped) cell and grows the visited block shell by shell until it holds K
+ * candidates and the K-th d2 is STRICTLY below the square of the distance from the centre to the nearest face of the block that still
+ * has grid beyond it (less a margin of 2^-50 of the magnitudes involved, which covers the rounding of the cell assignment:
+ * csrc/knn.hip), or the block covers the grid.  A position outside the bounding box starts from the clamped border cell.
+ * One wave per query; candidates are compacted by ballot into an LDS buffer that is cut back to the K smallest pairs whenever it
+ * fills: no floating-point atomics, no dependence on which workgroup runs first, and no limit on the points of one cell.
+ * Argument errors (null cloud / workspace / nbr_out_dev, N <= 0, K outside 1 .. NESTI_KNN_MAX_K, M < 0, a short workspace, rows
+ * beyond the cloud, null positions) are reported before any device call; M = 0 is a no-op.  The calls enqueue one kernel on `stream`,
+ * neither synchronise nor read anything back, and can be captured into a graph. */
+int nesti_knn(const float* cloud_dev, int N, const int32_t* query_idx_dev, int M, int query_row0, int K, int32_t* nbr_out_dev,
+              double* d2_out_dev, int32_t* count_out_dev, const void* grid_ws_dev, size_t grid_ws_bytes, void* stream);
+int nesti_knn_at(const float* cloud_dev, int N, const float* query_xyz_dev, int M, int K, int32_t* nbr_out_dev, double* d2_out_dev,
+                 int32_t* count_out_dev, const void* grid_ws_dev, size_t grid_ws_bytes, void* stream);
+/* FITS OVER NEIGHBOUR LISTS.  Centres as for nesti_knn; nbr_dev [M, K] int32 (device) is the list of every row, 1 <= K <=
+ * NESTI_KNN_MAX_K; ks [S] (HOST) are the neighbour counts of the scales, 1 <= S <= NESTI_MAX_SCALES, 1 <= ks[0] <= ... <= ks[S-1]
+ * <= K.  No grid is needed.  The list is untrusted: the valid prefix of a row ends at its first entry outside [0, N) (the -1 padding
+ * of nesti_knn, a bad index), so a bad entry never causes an out-of-bounds read; a centre with a non-finite coordinate has an empty
+ * prefix.  Lists need not be sorted and need not come from nesti_knn.  Per row and scale s: n_s = min(ks[s], valid prefix), the points
+ * are the first n_s entries, d and d2 as for nesti_knn, and r2_s = the largest d2 among them (the last one of a sorted list).
+ *   plane fit    nesti_pca_normals' estimator with the prefix in place of the ball and r2_s in place of r^2: the same nine sums by
+ *                the same operations (slot i is added in lane i mod 64, a lane's slots in ascending order, the lanes meet in the same
+ *                xor-butterfly), the same solve, rounding and sign rule.  Eigenvalues are in units of the neighbourhood's own radius
+ *                squared.  n_s < 3 or r2_s == 0: normal 0 0 0, eigenvalues 0 0 0.
+ *   quadric fit  steps 1 - 8 of nesti_quadric_fit with the prefix in place of the ball, r = sqrt(r2_s) (fp64) in place of the radius,
+ *                pass 1 = the plane fit above bit for bit (plane_out_dev).  The failure rule is that entry's, plus r2_s == 0.
+ *   outputs      (device; any may be NULL) normals / eig / curv / plane as for the ball entries, [M,S,..];
+ *                radius_out_dev [M,S] f32 = (float)sqrt(r2_s); count_out_dev [M,S] int32 = n_s.
+ * DETERMINISM: no floating-point atomics, and the summation order is fixed by the list.  With the list of nesti_knn a row's output
+ * bits are a pure function of (cloud, centre, ks): independent of batching, of streams, of the grid and of the grid BUILD -- more
+ * than the ball entries promise, whose sums follow the order inside a cell.  Scale s of ks equals the single scale of a run with
+ * ks = {ks[s]}.
+ * Argument errors (null cloud / list / ks, N <= 0, K outside 1 .. NESTI_KNN_MAX_K, S outside 1 .. NESTI_MAX_SCALES, ks not ascending
+ * or outside 1 .. K, M < 0, rows beyond the cloud, null positions) are reported before any device call; M = 0 is a no-op. */
+int nesti_pca_normals_nbr(const float* cloud_dev, int N, const int32_t* query_idx_dev, int M, int query_row0, const int32_t* nbr_dev,
+                          int K, const int32_t* ks, int S, float* normals_out_dev, float* eig_out_dev, float* radius_out_dev,
+                          int32_t* count_out_dev, void* stream);
+int nesti_pca_normals_nbr_at(const float* cloud_dev, int N, const float* query_xyz_dev, int M, const int32_t* nbr_dev, int K,
+                             const int32_t* ks, int S, float* normals_out_dev, float* eig_out_dev, float* radius_out_dev,
+                             int32_t* count_out_dev, void* stream);
+int nesti_quadric_fit_nbr(const float* cloud_dev, int N, const int32_t* query_idx_dev, int M, int query_row0, const int32_t* nbr_dev,
+                          int K, const int32_t* ks, int S, float* normals_out_dev, float* curv_out_dev, float* plane_out_dev,
+                          float* radius_out_dev, int32_t* count_out_dev, void* stream);
+int nesti_quadric_fit_nbr_at(const float* cloud_dev, int N, const float* query_xyz_dev, int M, const int32_t* nbr_dev, int K,
+                             const int32_t* ks, int S, float* normals_out_dev, float* curv_out_dev, float* plane_out_dev,
+                             float* radius_out_dev, int32_t* count_out_dev, void* stream);
 
 /* ---- depth images in, normal images out (depth.hip; DESIGN.md 2 "Depth images") --------------------------------------------------
  * The two ends of the reference's Kinect route: MATLAB/ScanNet_depth2xyz.m (depth + intrinsics + pose -> cloud) before

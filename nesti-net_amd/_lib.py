@@ -101,6 +101,7 @@ GATE_WIDEN_PASSES = 3  # NESTI_GATE_WIDEN_PASSES
 ORIENT_MST, ORIENT_VIEWPOINT = 0, 1   # NESTI_ORIENT_*
 DEPTH_U16, DEPTH_F32 = 0, 1           # NESTI_DEPTH_*
 DEPTH_MAX_PIXELS = 1 << 26
+KNN_MAX_K = 256                       # NESTI_KNN_MAX_K
 
 
 class NestiError(RuntimeError):
@@ -173,6 +174,12 @@ SIGNATURES = {
     "nesti_quadric_fit_at": (_i, [_cfgp, _vp, _i, _vp, _i, ctypes.POINTER(ctypes.c_double), _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "nesti_quadric_solve": (_i, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                  ctypes.POINTER(_i)]),
+    "nesti_knn": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "nesti_knn_at": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "nesti_pca_normals_nbr": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, ctypes.POINTER(ctypes.c_int32), _i, _vp, _vp, _vp, _vp, _vp]),
+    "nesti_pca_normals_nbr_at": (_i, [_vp, _i, _vp, _i, _vp, _i, ctypes.POINTER(ctypes.c_int32), _i, _vp, _vp, _vp, _vp, _vp]),
+    "nesti_quadric_fit_nbr": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, ctypes.POINTER(ctypes.c_int32), _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "nesti_quadric_fit_nbr_at": (_i, [_vp, _i, _vp, _i, _vp, _i, ctypes.POINTER(ctypes.c_int32), _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nesti_depth_workspace_bytes": (_sz, [_i, _i]),
     "nesti_depth_to_cloud": (_i, [_vp, _i, _i, _i, ctypes.POINTER(CCamera), _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "nesti_image_scatter": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),

@@ -11,7 +11,8 @@ The trained-model directory holds either ``model.nstw`` (variables + hyper-param
 checkpoint ships with the reference).  ``--estimator pca`` needs none of them: the plane-fit normals of :mod:`.pca`, written as
 ``<shape>.normals`` (one scale), ``<shape>.pca_eig`` and ``<shape>.pca_count`` (every scale); nor does ``--estimator quadric``: the
 quadric-fit normals and principal curvatures of :mod:`.quadric`, written as ``<shape>.normals`` and ``<shape>.curv`` (one scale),
-``<shape>.quadric_curv`` and ``<shape>.quadric_count`` (every scale)."""
+``<shape>.quadric_curv`` and ``<shape>.quadric_count`` (every scale).  ``--knn K[,K...]`` fits either of the two over the K nearest
+neighbours instead of balls and adds ``<shape>.knn_radius``."""
 import argparse
 import ctypes
 import os
@@ -119,6 +120,12 @@ def build_parser():
     p.add_argument("--quadric_scale", type=int, default=-1,
                    help="--estimator quadric: the scale whose normals and curvatures go to <shape>.normals and <shape>.curv, an index "
                         "into the patch radii; negative counts from the end [default: -1, the largest]")
+    p.add_argument("--knn", default=None, metavar="K[,K...]",
+                   help="--estimator pca / quadric: fit over the K nearest neighbours of every query instead of balls (DESIGN.md 2 "
+                        "'k-nearest neighbourhoods'): one neighbour count per scale, at most 4, ascending, each in 1 .. 256.  The files "
+                        "are those of the estimator -- <shape>.pca_count / <shape>.quadric_count then hold the neighbour counts, "
+                        "--pca_scale / --quadric_scale index the counts -- plus <shape>.knn_radius (M rows of S distances to the "
+                        "farthest neighbour).  --orient mst then uses the largest patch radius of --model's configuration")
     p.add_argument("--synthetic_weights", action="store_true", help="use seeded synthetic weights if model.nstw is absent")
     return p
 
@@ -189,7 +196,7 @@ def run_depth_frame(est, frames, name, FLAGS, output_dir, printout, on_cloud, wr
     printout("saved experts for " + name)
 
 
-def run_pca(FLAGS, cfg, scale, pc_path, output_dir, printout):
+def run_pca(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None):
     """``--estimator pca``: per shape the plane fit at every scale, the optional orientation of the rows of scale ``scale`` (>= 0), and
     the three files.  No model is loaded."""
     from . import pca as _pca
@@ -197,10 +204,15 @@ def run_pca(FLAGS, cfg, scale, pc_path, output_dir, printout):
                                      device="cuda:%d" % FLAGS.gpu, query_positions=bool(FLAGS.query_positions))
     for ind, name in enumerate(dataset.shape_names):
         cloud = dataset.get_shape(ind)
-        res = _pca.pca_cloud(cloud, scale, None if FLAGS.orient == "0" else FLAGS.orient, FLAGS.viewpoint, FLAGS.orient_k)
-        short = int((res["n_ball"][:, scale] < 3).sum())
-        printout("plane fit of %s: %d rows, radius %.6g (scale %d of %d); %d rows with fewer than 3 points in that ball (written as 0 0 0)"
-                 % (name, cloud.patch_count, cloud.r_abs[scale], scale, cfg.n_scales, short))
+        res = _pca.pca_cloud(cloud, scale, None if FLAGS.orient == "0" else FLAGS.orient, FLAGS.viewpoint, FLAGS.orient_k, knn=ks)
+        if ks is None:
+            short = int((res["n_ball"][:, scale] < 3).sum())
+            printout("plane fit of %s: %d rows, radius %.6g (scale %d of %d); %d rows with fewer than 3 points in that ball (written as 0 0 0)"
+                     % (name, cloud.patch_count, cloud.r_abs[scale], scale, cfg.n_scales, short))
+        else:
+            printout("plane fit of %s: %d rows, %d nearest neighbours (scale %d of %d); %d rows without a fit (written as 0 0 0)"
+                     % (name, cloud.patch_count, ks[scale], scale, len(ks), int((res["normals"] == 0).all(axis=1).sum())))
+            textio.write_f32(os.path.join(output_dir, name + ".knn_radius"), res["radius"])
         if res["orient"] is not None:
             ost = res["orient"]
             printout("orientation of %s (%s): %d of %d rows oriented, %d flipped, %d connected piece%s, %d edges"
@@ -213,7 +225,7 @@ def run_pca(FLAGS, cfg, scale, pc_path, output_dir, printout):
     return 0
 
 
-def run_quadric(FLAGS, cfg, scale, pc_path, output_dir, printout):
+def run_quadric(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None):
     """``--estimator quadric``: per shape the quadric fit at every scale, the optional orientation of the rows of scale ``scale`` (>= 0)
     with the flip of their curvatures, and the four files.  No model is loaded."""
     from . import quadric as _quadric
@@ -221,10 +233,15 @@ def run_quadric(FLAGS, cfg, scale, pc_path, output_dir, printout):
                                      device="cuda:%d" % FLAGS.gpu, query_positions=bool(FLAGS.query_positions))
     for ind, name in enumerate(dataset.shape_names):
         cloud = dataset.get_shape(ind)
-        res = _quadric.quadric_cloud(cloud, scale, None if FLAGS.orient == "0" else FLAGS.orient, FLAGS.viewpoint, FLAGS.orient_k)
+        res = _quadric.quadric_cloud(cloud, scale, None if FLAGS.orient == "0" else FLAGS.orient, FLAGS.viewpoint, FLAGS.orient_k, knn=ks)
         failed = int((res["normals_all"][:, scale] == 0).all(axis=1).sum())
-        printout("quadric fit of %s: %d rows, radius %.6g (scale %d of %d); %d rows without a fit in that ball (fewer than 6 points or a "
-                 "singular system: written as 0 0 0 and 0 0)" % (name, cloud.patch_count, cloud.r_abs[scale], scale, cfg.n_scales, failed))
+        if ks is None:
+            printout("quadric fit of %s: %d rows, radius %.6g (scale %d of %d); %d rows without a fit in that ball (fewer than 6 points or a "
+                     "singular system: written as 0 0 0 and 0 0)" % (name, cloud.patch_count, cloud.r_abs[scale], scale, cfg.n_scales, failed))
+        else:
+            printout("quadric fit of %s: %d rows, %d nearest neighbours (scale %d of %d); %d rows without a fit (fewer than 6 points or a "
+                     "singular system: written as 0 0 0 and 0 0)" % (name, cloud.patch_count, ks[scale], scale, len(ks), failed))
+            textio.write_f32(os.path.join(output_dir, name + ".knn_radius"), res["radius"])
         if res["orient"] is not None:
             ost = res["orient"]
             printout("orientation of %s (%s): %d of %d rows oriented, %d flipped, %d connected piece%s, %d edges"
@@ -245,6 +262,15 @@ def main(argv=None):
         parser.error("--pca_scale belongs to --estimator pca")
     if FLAGS.quadric_scale != -1 and FLAGS.estimator != "quadric":
         parser.error("--quadric_scale belongs to --estimator quadric")
+    ks = None
+    if FLAGS.knn is not None:
+        if FLAGS.estimator == "net":
+            parser.error("--knn belongs to --estimator pca / --estimator quadric")
+        from .knn import check_ks
+        try:
+            ks = check_ks([int(v) for v in FLAGS.knn.split(",")])
+        except ValueError as e:
+            parser.error("--knn %s: %s" % (FLAGS.knn, e))
     if FLAGS.estimator == "quadric":
         if FLAGS.depth_images:
             parser.error("--estimator quadric does not take --depth_images 1: depth frames belong to the network path (--estimator net)")
@@ -306,20 +332,20 @@ def main(argv=None):
         from .pca import check_scale
         cfg = NestiConfig.for_model(FLAGS.model)
         try:
-            scale = check_scale(FLAGS.pca_scale, cfg.n_scales)
+            scale = check_scale(FLAGS.pca_scale, cfg.n_scales if ks is None else len(ks))
         except ValueError as e:
             raise SystemExit("--pca_scale with --model %s: %s" % (FLAGS.model, e))
-        rc = run_pca(FLAGS, cfg, scale, pc_path, output_dir, printout)
+        rc = run_pca(FLAGS, cfg, scale, pc_path, output_dir, printout, ks)
         flog.close()
         return rc
     if FLAGS.estimator == "quadric":
         from .pca import check_scale
         cfg = NestiConfig.for_model(FLAGS.model)
         try:
-            scale = check_scale(FLAGS.quadric_scale, cfg.n_scales)
+            scale = check_scale(FLAGS.quadric_scale, cfg.n_scales if ks is None else len(ks))
         except ValueError as e:
             raise SystemExit("--quadric_scale with --model %s: %s" % (FLAGS.model, e))
-        rc = run_quadric(FLAGS, cfg, scale, pc_path, output_dir, printout)
+        rc = run_quadric(FLAGS, cfg, scale, pc_path, output_dir, printout, ks)
         flog.close()
         return rc
 

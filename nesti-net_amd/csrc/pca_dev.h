@@ -1,6 +1,7 @@
-// The plane fit of one query by one wave (DESIGN.md 2 "Plane-fit normals"), shared by pca_kernel (pca.hip) and by pass 1 of
-// quadric_kernel (quadric.hip): the query's spans, the nine fp64 sums and the count of every scale, their wave reductions, and the
-// solve with its rounding and sign rule.  One definition, so the plane normal of the quadric fit IS nesti_pca_normals' normal, bit for bit.
+// The plane fit of one query by one wave (DESIGN.md 2 "Plane-fit normals"), shared by pca_kernel (pca.hip), by pass 1 of
+// quadric_kernel (quadric.hip) and by the neighbour-list kernels of knn.hip: the query's spans, the nine fp64 sums and the count of
+// every scale, their wave reductions, and the solve with its rounding and sign rule.  One definition, so the plane normal of the
+// quadric fit IS nesti_pca_normals' normal, bit for bit.
 //
 // For the including unit: include patches_dev.h first, under the compiler's default contraction (ball_d2, see there), then
 // `#pragma clang fp contract(off)`, then this header -- every product and sum below is rounded on its own.
@@ -26,6 +27,16 @@ __device__ __forceinline__ int wave_sum(int v) {
   for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
   return v;
 }
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, kWave));
+  return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, kWave));
+  return v;
+}
 
 // the row of this wave (the same in every lane: said so, and the centre and its tests live in scalar registers); a wave beyond the
 // last row gets M or more and leaves whole, so the shuffles of the others see full waves
@@ -44,6 +55,43 @@ __device__ __forceinline__ WaveSpans wave_spans(const PatchParams& p, int lane, 
   return spans;
 }
 
+// The per-candidate body of the plane fit, shared by the ball walk below and the neighbour-list walk (knn.hip: walk_list): the nine terms of a
+// difference d -- d itself and the six products of d d^T, formed once per candidate -- and their addition to one scale's sums.
+struct PlaneTerms {
+  double v[kSums];
+};
+__device__ __forceinline__ PlaneTerms plane_terms(double dx, double dy, double dz) {
+  const double xx = __dmul_rn(dx, dx), yy = __dmul_rn(dy, dy), zz = __dmul_rn(dz, dz);
+  const double xy = dx * dy, xz = dx * dz, yz = dy * dz;
+  return {{dx, dy, dz, xx, xy, xz, yy, yz, zz}};
+}
+__device__ __forceinline__ void plane_add(double (&acc)[kSums], const PlaneTerms& t) {
+#pragma unroll
+  for (int k = 0; k < kSums; ++k) acc[k] += t.v[k];
+}
+
+// The totals of the per-lane sums and counts of every scale: one fixed xor-butterfly each.  Every lane ends up with every total; lane
+// s keeps those of scale s, with its r^2 (lanes >= S: of the last scale).
+template <int S>
+__device__ __forceinline__ void plane_totals(const double (&acc)[S][kSums], const int (&cnt)[S], const double* r2s, int lane,
+                                             double (&sum)[kSums], int& n, double& r2) {
+#pragma unroll
+  for (int k = 0; k < kSums; ++k) sum[k] = 0.0;
+  n = 0;
+  r2 = 1.0;
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    const int ns = wave_sum(cnt[s]);
+    const bool mine = lane == s || (s == S - 1 && lane >= S);
+    if (mine) { n = ns; r2 = r2s[s]; }
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) {
+      const double t = wave_sum(acc[s][k]);
+      if (mine) sum[k] = t;
+    }
+  }
+}
+
 // The sums of d and d d^T and the count of every scale's ball.  A candidate is tested once for all scales: the six products of d are
 // formed once and added to the sums of every scale whose ball holds it.  Every lane ends up with every total; lane s keeps those of
 // scale s (lanes >= S: of the last scale).
@@ -60,34 +108,16 @@ __device__ __forceinline__ void plane_sums(const PatchParams& p, const WaveSpans
   }
   walk_block(p.sorted, spans, lane, kWave, cx, cy, cz, [&](const float4& c, double d2) {
     // the differences ball_d2 was given, formed again: the same operations, so the same values
-    const double dx = (double)c.x - cx, dy = (double)c.y - cy, dz = (double)c.z - cz;
-    const double xx = __dmul_rn(dx, dx), yy = __dmul_rn(dy, dy), zz = __dmul_rn(dz, dz);
-    const double xy = dx * dy, xz = dx * dz, yz = dy * dz;
+    const PlaneTerms t = plane_terms((double)c.x - cx, (double)c.y - cy, (double)c.z - cz);
 #pragma unroll
     for (int s = 0; s < S; ++s) {
       if (d2 <= p.r2[s]) {
         ++cnt[s];
-        acc[s][0] += dx; acc[s][1] += dy; acc[s][2] += dz;
-        acc[s][3] += xx; acc[s][4] += xy; acc[s][5] += xz;
-        acc[s][6] += yy; acc[s][7] += yz; acc[s][8] += zz;
+        plane_add(acc[s], t);
       }
     }
   });
-#pragma unroll
-  for (int k = 0; k < kSums; ++k) sum[k] = 0.0;
-  n = 0;
-  r2 = 1.0;
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    const int ns = wave_sum(cnt[s]);
-    const bool mine = lane == s || (s == S - 1 && lane >= S);
-    if (mine) { n = ns; r2 = p.r2[s]; }
-#pragma unroll
-    for (int k = 0; k < kSums; ++k) {
-      const double t = wave_sum(acc[s][k]);
-      if (mine) sum[k] = t;
-    }
-  }
+  plane_totals<S>(acc, cnt, p.r2, lane, sum, n, r2);
 }
 
 // covariance in units of r^2 -> Jacobi -> the normal (normalised in fp64, rounded to f32 once, signed on the f32 values so that the

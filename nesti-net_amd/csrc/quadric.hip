@@ -39,12 +39,10 @@
 #pragma clang fp contract(off)
 
 #include "pca_dev.h"
-#include "quadric_solve.h"
+#include "quadric_dev.h"  // the frames, the per-candidate body, the totals and the solve, shared with the neighbour-list kernel of knn.hip
 
 namespace nesti {
 namespace {
-
-constexpr int kQSums = kQuadricMoments - 1;   // m[1..20]: m[0] = n is known from pass 1
 
 struct QuadricParams {
   PatchParams p;                      // points_out / n_eff_out / nbr_out unused; n_ball_out optional
@@ -53,26 +51,6 @@ struct QuadricParams {
   float* curv_out;                    // [M, S, 2] or NULL
   float* plane_out;                   // [M, S, 3] or NULL
 };
-
-// a value that is the same in every lane, into scalar registers
-__device__ __forceinline__ double wave_uniform(double v) {
-  return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
-}
-
-// step 2: the frame (t1, t2, n0) of a plane normal, f[0..2] = t1, f[3..5] = t2, f[6..8] = n0
-__device__ __forceinline__ void quadric_frame(double nx, double ny, double nz, double (&f)[9]) {
-  const double ax = fabs(nx), ay = fabs(ny), az = fabs(nz);
-  double cx, cy, cz;                                          // n0 x e_j
-  if (ax <= ay && ax <= az) { cx = 0.0; cy = nz; cz = -ny; }
-  else if (ay <= az) { cx = -nz; cy = 0.0; cz = nx; }
-  else { cx = ny; cy = -nx; cz = 0.0; }
-  const double len = sqrt((cx * cx + cy * cy) + cz * cz);
-  f[0] = cx / len; f[1] = cy / len; f[2] = cz / len;
-  f[3] = ny * f[2] - nz * f[1];
-  f[4] = nz * f[0] - nx * f[2];
-  f[5] = nx * f[1] - ny * f[0];
-  f[6] = nx; f[7] = ny; f[8] = nz;
-}
 
 template <int S>
 __global__ __launch_bounds__(kThreads) void quadric_kernel(const QuadricParams qp) {
@@ -95,18 +73,11 @@ __global__ __launch_bounds__(kThreads) void quadric_kernel(const QuadricParams q
   // ---- the frame of every scale, the same in every lane.  A scale that cannot be fitted (n < 6, or no plane normal) gets a ball
   // nothing is inside of, so pass 2 adds nothing for it
   double fr[S][9], r2live[S], rad[S];
+  bool live[S];
+  quadric_frames<S>(nrm, n, fr, live);
 #pragma unroll
   for (int s = 0; s < S; ++s) {
-    const float bx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(nrm[0]), s));
-    const float by = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(nrm[1]), s));
-    const float bz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(nrm[2]), s));
-    const int ns = __builtin_amdgcn_readlane(n, s);
-    const bool live = ns >= kQuadricMinPoints && (bx != 0.f || by != 0.f || bz != 0.f);
-    double f[9];
-    quadric_frame((double)bx, (double)by, (double)bz, f);
-#pragma unroll
-    for (int k = 0; k < 9; ++k) fr[s][k] = wave_uniform(live ? f[k] : 0.0);
-    r2live[s] = live ? p.r2[s] : -1.0;
+    r2live[s] = live[s] ? p.r2[s] : -1.0;
     rad[s] = qp.r[s];
   }
   // ---- pass 2: the moments ------------------------------------------------------------------------------------------------------------
@@ -120,20 +91,7 @@ __global__ __launch_bounds__(kThreads) void quadric_kernel(const QuadricParams q
     const double dx = (double)c.x - cx, dy = (double)c.y - cy, dz = (double)c.z - cz;
 #pragma unroll
     for (int s = 0; s < S; ++s) {
-      if (d2 <= r2live[s]) {
-        const double* f = fr[s];
-        const double u = ((f[0] * dx + f[1] * dy) + f[2] * dz) / rad[s];
-        const double v = ((f[3] * dx + f[4] * dy) + f[5] * dz) / rad[s];
-        const double h = ((f[6] * dx + f[7] * dy) + f[8] * dz) / rad[s];
-        const double u2 = u * u, uv = u * v, v2 = v * v;
-        const double u3 = u2 * u, u2v = u2 * v, uv2 = u * v2, v3 = v2 * v;
-        double* a = acc[s];
-        a[0] += u; a[1] += v;
-        a[2] += u2; a[3] += uv; a[4] += v2;
-        a[5] += u3; a[6] += u2v; a[7] += uv2; a[8] += v3;
-        a[9] += u2 * u2; a[10] += u3 * v; a[11] += u2 * v2; a[12] += u * v3; a[13] += v2 * v2;
-        a[14] += h; a[15] += h * u; a[16] += h * v; a[17] += h * u2; a[18] += h * uv; a[19] += h * v2;
-      }
+      if (d2 <= r2live[s]) quadric_add(acc[s], fr[s], rad[s], dx, dy, dz);
     }
   });
   // every lane ends up with every total; lane s keeps those, the frame and the radius of scale s
@@ -143,42 +101,10 @@ __global__ __launch_bounds__(kThreads) void quadric_kernel(const QuadricParams q
 #pragma unroll
   for (int k = 0; k < 9; ++k) f[k] = 0.0;
 #pragma unroll
-  for (int s = 0; s < S; ++s) {
-    const bool mine = lane == s;
-    if (mine) {
-      r = rad[s];
-#pragma unroll
-      for (int k = 0; k < 9; ++k) f[k] = fr[s][k];
-    }
-#pragma unroll
-    for (int k = 0; k < kQSums; ++k) {
-      const double t = wave_sum(acc[s][k]);
-      if (mine) m[k + 1] = t;
-    }
-  }
+  for (int s = 0; s < S; ++s) quadric_totals(acc[s], fr[s], rad[s], lane == s, m, f, r);
   if (lane >= S) return;
-  m[0] = (double)n;
   // ---- lane s: solve, normal, curvatures ------------------------------------------------------------------------------------------------
-  float nu[3] = {0.f, 0.f, 0.f}, kf[2] = {0.f, 0.f};
-  double a[kQuadricCoeffs];
-  const bool fitted = n >= kQuadricMinPoints && (nrm[0] != 0.f || nrm[1] != 0.f || nrm[2] != 0.f);
-  if (quadric_solve(m, a) && fitted) {
-    const double vx = (f[6] - a[1] * f[0]) - a[2] * f[3], vy = (f[7] - a[1] * f[1]) - a[2] * f[4], vz = (f[8] - a[1] * f[2]) - a[2] * f[5];
-    const double len = sqrt((vx * vx + vy * vy) + vz * vz);
-    double k[2];
-    quadric_curvatures(a, k);
-    const float fx = (float)(vx / len), fy = (float)(vy / len), fz = (float)(vz / len);
-    const float k0 = (float)(k[0] / r), k1 = (float)(k[1] / r);
-    if (finite_bits(fx) && finite_bits(fy) && finite_bits(fz) && finite_bits(k0) && finite_bits(k1)) {
-      nu[0] = fx + 0.f; nu[1] = fy + 0.f; nu[2] = fz + 0.f;    // -0 + +0 = +0: no negative zero leaves
-      kf[0] = k0; kf[1] = k1;
-    }
-  }
-  const size_t o = (size_t)q * S + lane;
-  if (qp.normals_out) { qp.normals_out[o * 3] = nu[0]; qp.normals_out[o * 3 + 1] = nu[1]; qp.normals_out[o * 3 + 2] = nu[2]; }
-  if (qp.curv_out) { qp.curv_out[o * 2] = kf[0]; qp.curv_out[o * 2 + 1] = kf[1]; }
-  if (qp.plane_out) { qp.plane_out[o * 3] = nrm[0]; qp.plane_out[o * 3 + 1] = nrm[1]; qp.plane_out[o * 3 + 2] = nrm[2]; }
-  if (p.n_ball_out) p.n_ball_out[o] = n;
+  quadric_solve_write(m, f, r, n, nrm, (size_t)q * S + lane, QuadricOut{qp.normals_out, qp.curv_out, qp.plane_out, p.n_ball_out});
 }
 
 // nesti_quadric_fit (centres = cloud points, by index or row) and nesti_quadric_fit_at (centres = positions): one body

@@ -25,10 +25,11 @@ def variation(eig):
     return np.divide(eig[..., 0], total, out=np.zeros_like(total), where=total != 0)
 
 
-def orient_rows(cloud, normals, scale, mode, viewpoint=None, k=8):
+def orient_rows(cloud, normals, scale, mode, viewpoint=None, k=8, radius=None):
     """Orient the rows ``normals`` [patch_count, 3] (contiguous, on the cloud's device) of a prepared cloud IN PLACE with
     ``orient.orient_device``, the way ``NormalEstimator.orient`` does: positions are the cloud, ``cloud[pidx]`` or the (harmless) query
-    positions; the radius is ``r_abs[scale]``.  Only sign bits change, sentinel rows stay 0 0 0.  Returns the int32[4] stats tensor."""
+    positions; the radius is ``r_abs[scale]``, or ``radius`` where given (the k-NN fits, whose scales are no radii).  Only sign bits
+    change, sentinel rows stay 0 0 0.  Returns the int32[4] stats tensor."""
     import torch
     from . import orient as _orient
     if cloud.queries is not None:
@@ -37,30 +38,56 @@ def orient_rows(cloud, normals, scale, mode, viewpoint=None, k=8):
         pos = cloud.cloud[cloud.pidx.long()].contiguous()
     else:
         pos = cloud.cloud
-    return _orient.orient_device(pos, normals, float(cloud.r_abs[scale]), k, viewpoint, mode, torch.cuda.current_stream(cloud.device))
+    r = float(cloud.r_abs[scale]) if radius is None else float(radius)
+    return _orient.orient_device(pos, normals, r, k, viewpoint, mode, torch.cuda.current_stream(cloud.device))
 
 
-def pca_cloud(cloud, scale=-1, orient=None, viewpoint=None, orient_k=8):
-    """``pca_normals`` for a prepared ``provider.CloudPatches`` (all of its patch rows); synchronises."""
+def pca_cloud(cloud, scale=-1, orient=None, viewpoint=None, orient_k=8, knn=None):
+    """``pca_normals`` for a prepared ``provider.CloudPatches`` (all of its patch rows); synchronises.  ``knn``: neighbour counts
+    instead of the cloud's radii (``scale`` then indexes them, and the dict gains ``radius``)."""
     import torch
     from . import orient as _orient
-    s = check_scale(scale, cloud.cfg.n_scales)
+    ks = None
+    if knn is not None:
+        from .knn import check_ks
+        ks = check_ks(knn)
+    s = check_scale(scale, cloud.cfg.n_scales if ks is None else len(ks))
     if orient not in ORIENT_MODES:
         raise ValueError("orient must be None, 'mst' or 'viewpoint'")
     with torch.cuda.device(cloud.device):
-        normals_all, eig, n_ball = cloud.pca(0, cloud.patch_count)
+        radius = None
+        if ks is None:
+            normals_all, eig, n_ball = cloud.pca(0, cloud.patch_count)
+        else:
+            normals_all, eig, radius, n_ball = cloud.pca_knn(0, cloud.patch_count, ks)
         normals = normals_all[:, s, :].contiguous()
         stats = None
         if orient is not None and cloud.patch_count:
-            stats = orient_rows(cloud, normals, s, orient, viewpoint, orient_k)
+            stats = orient_rows(cloud, normals, s, orient, viewpoint, orient_k, radius=None if ks is None else max(cloud.r_abs))
         torch.cuda.current_stream(cloud.device).synchronize()
     eig_h = eig.cpu().numpy()
-    return {"normals": normals.cpu().numpy(), "normals_all": normals_all.cpu().numpy(), "eig": eig_h, "variation": variation(eig_h),
-            "n_ball": n_ball.cpu().numpy(),
-            "orient": None if orient is None else (_orient.stats_dict(stats) if stats is not None else dict.fromkeys(_orient.STAT_NAMES, 0))}
+    res = {"normals": normals.cpu().numpy(), "normals_all": normals_all.cpu().numpy(), "eig": eig_h, "variation": variation(eig_h),
+           "n_ball": n_ball.cpu().numpy(),
+           "orient": None if orient is None else (_orient.stats_dict(stats) if stats is not None else dict.fromkeys(_orient.STAT_NAMES, 0))}
+    if radius is not None:
+        res["radius"] = radius.cpu().numpy()
+    return res
 
 
-def pca_normals(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, viewpoint=None, orient_k=8, device="cuda:0"):
+def check_knn_args(knn, cfg):
+    """``knn=`` of ``pca_normals`` / ``quadric.quadric_fit`` -> (ks or None, the configuration to prepare the cloud with).  ``ValueError``
+    for a bad ``knn`` and for ``knn`` together with a ``cfg``: the scales of a k-NN fit are neighbour counts, a configuration's radii
+    would mean nothing."""
+    if knn is None:
+        return None, cfg or NestiConfig()
+    from .knn import check_ks
+    ks = check_ks(knn)
+    if cfg is not None:
+        raise ValueError("knn and cfg are mutually exclusive: the scales of a k-NN fit are the neighbour counts, not cfg.patch_radius")
+    return ks, NestiConfig()
+
+
+def pca_normals(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, viewpoint=None, orient_k=8, device="cuda:0", knn=None):
     """Plane-fit normals of a cloud: numpy in, a dict of numpy arrays out (synchronises).  Queries are all points, the points
     ``pidx`` or the positions ``queries`` [M,3] (mutually exclusive), as for ``NormalEstimator.estimate``; the radii are
     ``cfg.patch_radius`` times the cloud's bounding-box diagonal.
@@ -74,9 +101,19 @@ def pca_normals(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, v
 
     A scale whose ball holds fewer than 3 points has normal 0 0 0 and eigenvalues 0 0 0; the orientation leaves such rows alone.
     ``orient='mst' | 'viewpoint'`` orients the rows of ``scale`` with radius ``r_abs[scale]`` (only sign bits change).
-    Raises ``ValueError`` for a ``scale`` outside [-S, S) and for ``pidx`` together with ``queries``."""
-    cfg = cfg or NestiConfig()
-    check_scale(scale, cfg.n_scales)
+
+    ``knn`` -- an int or an ascending sequence of at most 4 ints in 1 .. 256 -- replaces the balls by the nearest neighbours
+    (DESIGN.md 2 "k-nearest neighbourhoods"): scale s is the ``knn[s]`` nearest cloud points of the query, itself included where it is
+    a cloud point; ``scale`` indexes ``knn``; ``n_ball`` holds the counts (``min(knn[s], N)``); the dict gains ``radius`` [M,S] float32,
+    the distance to the farthest neighbour, and ``eig`` is in units of that radius squared.  No row is a sentinel for want of
+    neighbours unless the cloud has fewer than 3 points (or the neighbours all coincide with the query).  A row's bits do not depend
+    on batching or on the search grid.  With ``orient='mst'`` the orientation graph's radius is the default configuration's largest
+    patch radius, as on the network path: the k-NN radii vary per row and are not a safe grid cell; ``'viewpoint'`` needs no radius.
+
+    Raises ``ValueError`` for a ``scale`` outside [-S, S), for ``pidx`` together with ``queries``, for a bad ``knn`` and for ``knn``
+    together with ``cfg`` (whose radii would mean nothing)."""
+    ks, cfg = check_knn_args(knn, cfg)
+    check_scale(scale, cfg.n_scales if ks is None else len(ks))
     if orient not in ORIENT_MODES:
         raise ValueError("orient must be None, 'mst' or 'viewpoint'")
     if pidx is not None and queries is not None:
@@ -85,5 +122,6 @@ def pca_normals(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, v
         from .orient import _check_args
         _check_args(1.0, orient_k, viewpoint, orient)
     from .provider import CloudPatches
-    cloud = CloudPatches(np.asarray(pts, dtype=np.float32), cfg, device=device, pidx=pidx, queries=queries)
-    return pca_cloud(cloud, scale, orient, viewpoint, orient_k)
+    # the k-NN fits never read the radius grid (the orientation pass builds its own): a cloud without extent is served too
+    cloud = CloudPatches(np.asarray(pts, dtype=np.float32), cfg, device=device, pidx=pidx, queries=queries, radius_grid=ks is None)
+    return pca_cloud(cloud, scale, orient, viewpoint, orient_k, knn=ks)

@@ -68,9 +68,11 @@ class CloudPatches:
     ``queries`` ([M,3], converted to float32; mutually exclusive with ``pidx``): the patch centres are these POSITIONS instead
     of cloud points -- a downsampled copy, mesh vertices, voxel centres, another sweep -- while the neighbourhoods come from
     this cloud and ``r_abs`` from ITS bounding box.  Patch row i is ``queries[i]``; a position whose balls are all empty gets
-    the sentinel outputs."""
+    the sentinel outputs.
 
-    def __init__(self, pts, cfg: NestiConfig, device="cuda:0", seed=3627473, pidx=None, queries=None):
+    ``radius_grid=False`` skips the radius grid: only :meth:`knn`, :meth:`pca_knn` and :meth:`quadric_knn` may then be called."""
+
+    def __init__(self, pts, cfg: NestiConfig, device="cuda:0", seed=3627473, pidx=None, queries=None, radius_grid=True):
         if pidx is not None and queries is not None:
             raise ValueError("pidx and queries are mutually exclusive: a query is a cloud point (pidx) or a position (queries)")
         if queries is not None:
@@ -103,7 +105,13 @@ class CloudPatches:
         self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self._c = cfg.to_c()
         self._r = (ctypes.c_double * len(self.r_abs))(*self.r_abs)
-        self.build_grid()
+        # radius_grid=False: a cloud prepared for the k-NN entries alone (knn.knn), which build their own search grid and serve a cloud
+        # without extent -- a single point, say -- whose radii are 0 and whose radius grid cannot be built
+        self._has_radius_grid = bool(radius_grid)
+        self._extent = pts.max(0).astype(np.float64) - pts.min(0) if len(pts) else np.zeros(3)
+        self._knn_grids = {}                  # search-only grids of the k-NN entries: key -> (workspace, build event); knn_grid
+        if radius_grid:
+            self.build_grid()
 
     def build_grid(self, stream=None):
         """(Re)build the uniform search grid on the device -- the cKDTree construction of the
@@ -247,6 +255,122 @@ class CloudPatches:
                 _lib.ptr(normals), _lib.ptr(curv), _lib.ptr(plane), _lib.ptr(n_ball), _lib.ptr(self._ws), self._ws.numel(),
                 ctypes.c_void_p(st.cuda_stream)), entry)
         return normals, curv, plane, n_ball
+
+    # ---- k-nearest neighbourhoods (csrc/knn.hip; DESIGN.md 2 "k-nearest neighbourhoods") ----------------------------------------
+    KNN_GRIDS_KEPT = 4                        # search-only grids kept per cloud, each the size of the radius grid's workspace
+
+    def knn_grid(self, grid, k, stream):
+        """The grid workspace of a k-NN search: ``grid`` None -> the search-only grid of ``knn.default_radius(N, k, extent)``, built
+        with the one-scale ``nesti_patches_grid`` on first use; ``"radius"`` -> the patch grid of this cloud (left untouched); a
+        positive float -> a grid of that pseudo-radius.  Built grids are kept by pseudo-radius, the ``KNN_GRIDS_KEPT`` most recently
+        used; an older one is dropped (its memory is held until the work queued on ``stream`` so far is done; a caller that
+        searches one cloud from several streams over more grids than that orders them itself).  A grid is built on ``stream``; a later call on another stream waits for that build.  The choice moves the time of a
+        search, never its result."""
+        if isinstance(grid, str):
+            if grid != "radius":
+                raise ValueError("grid must be None, 'radius' or a positive pseudo-radius: got %r" % (grid,))
+            if not self._has_radius_grid:
+                raise ValueError("grid='radius': this cloud was prepared without its radius grid")
+            return self._ws
+        from . import knn as _knn
+        if grid is None:
+            radius = _knn.default_radius(self.n_points, _knn.check_k(k), self._extent)
+        else:
+            radius = float(grid)
+            if not (radius > 0.0 and np.isfinite(radius)):
+                raise ValueError("grid must be None, 'radius' or a positive pseudo-radius: got %r" % (grid,))
+        if radius in self._knn_grids:
+            ws, built = self._knn_grids.pop(radius)
+        else:
+            while len(self._knn_grids) >= self.KNN_GRIDS_KEPT:
+                old_ws, _ = self._knn_grids.pop(next(iter(self._knn_grids)))      # the least recently used
+                old_ws.record_stream(stream)
+            ws = torch.empty(self._ws.numel(), dtype=torch.uint8, device=self.device)
+            one = NestiConfig.for_model("ss_norm_est").to_c()      # a one-scale config: the grid reads n_scales and the radius
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.nesti_patches_grid(ctypes.byref(one), _lib.ptr(self.cloud), self.n_points, (ctypes.c_double * 1)(radius),
+                                                       _lib.ptr(ws), ws.numel(), ctypes.c_void_p(stream.cuda_stream)), "nesti_patches_grid")
+            built = torch.cuda.Event()
+            built.record(stream)
+        self._knn_grids[radius] = (ws, built)                                     # most recently used last
+        stream.wait_event(built)
+        return ws
+
+    def _knn_queries(self, first, count):
+        """(at, queries) of patch rows [first, first + count), validated: ``at`` -- the queries are positions; ``queries`` -- their
+        [count,3] positions, the [count] indices of ``pidx``, or None (row i is cloud point first + i)."""
+        if first < 0 or count < 0 or first + count > self.patch_count:
+            raise ValueError("patch rows [%d, %d) outside [0, %d)" % (first, first + count, self.patch_count))
+        if self.queries is not None:
+            return True, self.queries[first:first + count]
+        return False, (self.pidx[first:first + count].contiguous() if self.pidx is not None else None)
+
+    def knn(self, first, count, k, grid=None, stream=None):
+        """The ``k`` nearest cloud points of patch rows [first, first + count) (``nesti_knn`` / ``nesti_knn_at``): device tensors
+        ``(idx [count,k] int32, d2 [count,k] float64, n [count] int32)``; -1 / +inf beyond ``n = min(k, N)``.  Exact and independent of
+        ``grid`` (:meth:`knn_grid`).  Serves all points, ``pidx`` and ``queries``; asynchronous on ``stream``."""
+        from . import knn as _knn
+        k = _knn.check_k(k)
+        at, q = self._knn_queries(first, count)
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        ws = self.knn_grid(grid, k, st)
+        idx = torch.empty((count, k), dtype=torch.int32, device=self.device)
+        d2 = torch.empty((count, k), dtype=torch.float64, device=self.device)
+        n = torch.empty((count,), dtype=torch.int32, device=self.device)
+        if count == 0:                    # a no-op; an empty tensor has no address to pass
+            return idx, d2, n
+        tail = (k, _lib.ptr(idx), _lib.ptr(d2), _lib.ptr(n), _lib.ptr(ws), ws.numel(), ctypes.c_void_p(st.cuda_stream))
+        with torch.cuda.device(self.device):
+            if at:
+                _lib.check(self.lib.nesti_knn_at(_lib.ptr(self.cloud), self.n_points, _lib.ptr(q), count, *tail), "nesti_knn_at")
+            else:
+                _lib.check(self.lib.nesti_knn(_lib.ptr(self.cloud), self.n_points, _lib.ptr(q), count, ctypes.c_int(first), *tail), "nesti_knn")
+        return idx, d2, n
+
+    def _fit_nbr(self, entry, first, count, ks, nbr, shapes, stream):
+        """One list-fit entry (``entry`` / ``entry + "_at"``) over ``nbr`` [count, K]: the outputs of ``shapes`` + radius + count."""
+        at, q = self._knn_queries(first, count)
+        S = len(ks)
+        if nbr.dtype != torch.int32 or nbr.dim() != 2 or nbr.shape[0] != count or not nbr.is_contiguous() or nbr.device != self.device:
+            raise ValueError("nbr: a contiguous int32 [count, K] tensor on %s" % self.device)
+        out = tuple(torch.empty((count, S, w), dtype=torch.float32, device=self.device) for w in shapes)
+        radius = torch.empty((count, S), dtype=torch.float32, device=self.device)
+        n = torch.empty((count, S), dtype=torch.int32, device=self.device)
+        if count == 0:                    # a no-op; an empty list has no address to pass
+            return out + (radius, n)
+        tail = (_lib.ptr(nbr), int(nbr.shape[1]), (ctypes.c_int32 * S)(*ks), S) + tuple(_lib.ptr(t) for t in out) + \
+               (_lib.ptr(radius), _lib.ptr(n), ctypes.c_void_p(stream.cuda_stream))
+        with torch.cuda.device(self.device):
+            if at:
+                _lib.check(getattr(self.lib, entry + "_at")(_lib.ptr(self.cloud), self.n_points, _lib.ptr(q), count, *tail), entry + "_at")
+            else:
+                _lib.check(getattr(self.lib, entry)(_lib.ptr(self.cloud), self.n_points, _lib.ptr(q), count, ctypes.c_int(first), *tail), entry)
+        return out + (radius, n)
+
+    def pca_knn(self, first, count, ks, grid=None, nbr=None, stream=None):
+        """Plane-fit normals of patch rows [first, first + count) over their nearest neighbours: scale s is the first ``ks[s]``
+        entries of ONE sorted list (one search at K = max(ks), then ``nesti_pca_normals_nbr``).  Device tensors ``(normals [count,S,3]
+        f32, eig [count,S,3] f32 in units of the neighbourhood's own radius squared, radius [count,S] f32, n [count,S] int32)``.
+        ``nbr`` [count,K] int32: the caller's own lists instead of a search (untrusted: a row ends at its first entry outside the
+        cloud).  A row's bits are a pure function of (cloud, centre, ks): independent of batching, streams, ``grid`` and grid build.
+        Serves all points, ``pidx`` and ``queries``; asynchronous on ``stream``."""
+        from . import knn as _knn
+        ks = _knn.check_ks(ks)
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if nbr is None:
+            nbr = self.knn(first, count, ks[-1], grid=grid, stream=st)[0]
+        return self._fit_nbr("nesti_pca_normals_nbr", first, count, ks, nbr, (3, 3), st)
+
+    def quadric_knn(self, first, count, ks, grid=None, nbr=None, stream=None):
+        """Quadric-fit normals and principal curvatures of patch rows [first, first + count) over their nearest neighbours, as
+        :meth:`pca_knn`: device tensors ``(normals [count,S,3] f32, curv [count,S,2] f32 (k_max, k_min; absolute units), plane
+        [count,S,3] f32 (the bits of ``pca_knn``'s normals), radius [count,S] f32, n [count,S] int32)``."""
+        from . import knn as _knn
+        ks = _knn.check_ks(ks)
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if nbr is None:
+            nbr = self.knn(first, count, ks[-1], grid=grid, stream=st)[0]
+        return self._fit_nbr("nesti_quadric_fit_nbr", first, count, ks, nbr, (3, 2, 3), st)
 
     def build_reference_order(self, first, count, picks, pick_offsets, want_idx=False, out=None, stream=None):
         """Patch tensors of rows [first, first + count) exactly as the reference's ``PointcloudPatchDataset.__getitem__`` builds

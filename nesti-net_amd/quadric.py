@@ -7,7 +7,7 @@ There is no CPU fallback."""
 import numpy as np
 
 from .config import NestiConfig
-from .pca import ORIENT_MODES, check_scale, orient_rows
+from .pca import ORIENT_MODES, check_knn_args, check_scale, orient_rows
 
 
 def mean_gauss(curv):
@@ -16,31 +16,43 @@ def mean_gauss(curv):
     return (curv[..., 0] + curv[..., 1]) * np.float32(0.5), curv[..., 0] * curv[..., 1]
 
 
-def quadric_cloud(cloud, scale=-1, orient=None, viewpoint=None, orient_k=8):
-    """``quadric_fit`` for a prepared ``provider.CloudPatches`` (all of its patch rows); synchronises."""
+def quadric_cloud(cloud, scale=-1, orient=None, viewpoint=None, orient_k=8, knn=None):
+    """``quadric_fit`` for a prepared ``provider.CloudPatches`` (all of its patch rows); synchronises.  ``knn``: neighbour counts
+    instead of the cloud's radii (``scale`` then indexes them, and the dict gains ``radius``)."""
     import torch
     from . import orient as _orient
-    s = check_scale(scale, cloud.cfg.n_scales)
+    ks = None
+    if knn is not None:
+        from .knn import check_ks
+        ks = check_ks(knn)
+    s = check_scale(scale, cloud.cfg.n_scales if ks is None else len(ks))
     if orient not in ORIENT_MODES:
         raise ValueError("orient must be None, 'mst' or 'viewpoint'")
     with torch.cuda.device(cloud.device):
-        normals_all, curv_all, plane_all, n_ball = cloud.quadric(0, cloud.patch_count)
+        radius = None
+        if ks is None:
+            normals_all, curv_all, plane_all, n_ball = cloud.quadric(0, cloud.patch_count)
+        else:
+            normals_all, curv_all, plane_all, radius, n_ball = cloud.quadric_knn(0, cloud.patch_count, ks)
         normals = normals_all[:, s, :].contiguous()
         curv = curv_all[:, s, :].contiguous()
         stats = None
         if orient is not None and cloud.patch_count:
             before = normals.clone()
-            stats = orient_rows(cloud, normals, s, orient, viewpoint, orient_k)
+            stats = orient_rows(cloud, normals, s, orient, viewpoint, orient_k, radius=None if ks is None else max(cloud.r_abs))
             # the flip rule: the pass changes sign bits only, and a row whose normal it turned has curvatures (-k_min, -k_max)
             flipped = (before.view(torch.int32) != normals.view(torch.int32)).any(dim=1, keepdim=True)
             curv = torch.where(flipped, -curv.flip(1), curv)
         torch.cuda.current_stream(cloud.device).synchronize()
-    return {"normals": normals.cpu().numpy(), "curv": curv.cpu().numpy(), "normals_all": normals_all.cpu().numpy(),
-            "curv_all": curv_all.cpu().numpy(), "plane_all": plane_all.cpu().numpy(), "n_ball": n_ball.cpu().numpy(),
-            "orient": None if orient is None else (_orient.stats_dict(stats) if stats is not None else dict.fromkeys(_orient.STAT_NAMES, 0))}
+    res = {"normals": normals.cpu().numpy(), "curv": curv.cpu().numpy(), "normals_all": normals_all.cpu().numpy(),
+           "curv_all": curv_all.cpu().numpy(), "plane_all": plane_all.cpu().numpy(), "n_ball": n_ball.cpu().numpy(),
+           "orient": None if orient is None else (_orient.stats_dict(stats) if stats is not None else dict.fromkeys(_orient.STAT_NAMES, 0))}
+    if radius is not None:
+        res["radius"] = radius.cpu().numpy()
+    return res
 
 
-def quadric_fit(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, viewpoint=None, orient_k=8, device="cuda:0"):
+def quadric_fit(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, viewpoint=None, orient_k=8, device="cuda:0", knn=None):
     """Quadric-fit normals and principal curvatures of a cloud: numpy in, a dict of numpy arrays out (synchronises).  Queries are all
     points, the points ``pidx`` or the positions ``queries`` [M,3] (mutually exclusive), as for ``pca.pca_normals``; the radii are
     ``cfg.patch_radius`` times the cloud's bounding-box diagonal.
@@ -57,9 +69,18 @@ def quadric_fit(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, v
     A failed fit -- fewer than 6 points in the ball, no plane normal, or a singular system (collinear points, say) -- has normal 0 0 0
     and curvatures 0 0; the orientation leaves such rows alone.  ``orient='mst' | 'viewpoint'`` orients the rows of ``scale`` with
     radius ``r_abs[scale]``; where it turns a normal the row's curvatures become ``(-k_min, -k_max)``.
-    Raises ``ValueError`` for a ``scale`` outside [-S, S) and for ``pidx`` together with ``queries``."""
-    cfg = cfg or NestiConfig()
-    check_scale(scale, cfg.n_scales)
+
+    ``knn`` -- an int or an ascending sequence of at most 4 ints in 1 .. 256 -- replaces the balls by the nearest neighbours, as for
+    ``pca.pca_normals``: scale s is fitted to the ``knn[s]`` nearest cloud points, scaled by the distance to the farthest of them;
+    ``scale`` indexes ``knn``; ``n_ball`` holds the counts and the dict gains ``radius`` [M,S] float32.  ``plane_all`` is
+    ``pca_normals(..., knn=knn)``'s ``normals_all``, bit for bit.  With ``orient='mst'`` the orientation graph's radius is the default
+    configuration's largest patch radius (the k-NN radii vary per row and are not a safe grid cell); ``'viewpoint'`` needs no radius;
+    the curvature flip is the same.
+
+    Raises ``ValueError`` for a ``scale`` outside [-S, S), for ``pidx`` together with ``queries``, for a bad ``knn`` and for ``knn``
+    together with ``cfg`` (whose radii would mean nothing)."""
+    ks, cfg = check_knn_args(knn, cfg)
+    check_scale(scale, cfg.n_scales if ks is None else len(ks))
     if orient not in ORIENT_MODES:
         raise ValueError("orient must be None, 'mst' or 'viewpoint'")
     if pidx is not None and queries is not None:
@@ -68,5 +89,6 @@ def quadric_fit(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, v
         from .orient import _check_args
         _check_args(1.0, orient_k, viewpoint, orient)
     from .provider import CloudPatches
-    cloud = CloudPatches(np.asarray(pts, dtype=np.float32), cfg, device=device, pidx=pidx, queries=queries)
-    return quadric_cloud(cloud, scale, orient, viewpoint, orient_k)
+    # the k-NN fits never read the radius grid (the orientation pass builds its own): a cloud without extent is served too
+    cloud = CloudPatches(np.asarray(pts, dtype=np.float32), cfg, device=device, pidx=pidx, queries=queries, radius_grid=ks is None)
+    return quadric_cloud(cloud, scale, orient, viewpoint, orient_k, knn=ks)

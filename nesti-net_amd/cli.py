@@ -20,6 +20,8 @@ import sys
 
 import torch
 
+from . import pca as _pca
+from . import quadric as _quadric
 from . import textio
 from . import weights as wts
 from .config import ARCH_EXPERTS, ARCH_MULTI, ARCH_SINGLE, ARCH_SWITCH, NestiConfig
@@ -196,72 +198,72 @@ def run_depth_frame(est, frames, name, FLAGS, output_dir, printout, on_cloud, wr
     printout("saved experts for " + name)
 
 
-def run_pca(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None):
-    """``--estimator pca``: per shape the plane fit at every scale, the optional orientation of the rows of scale ``scale`` (>= 0), and
-    the three files.  No model is loaded."""
-    from . import pca as _pca
+# --estimator pca / quadric: what differs between the two model-free fits.  ``missing(res, scale, ks)`` counts the rows without a fit at
+# the written scale, ``no_fit`` says what they are for balls and for neighbour counts; ``files`` = (extension, writer, key of the result)
+FITS = {
+    "pca": {
+        "fit": _pca.pca_cloud, "noun": "plane fit", "scale_flag": "pca_scale",
+        "missing": lambda res, scale, ks: (res["n_ball"][:, scale] < 3).sum() if ks is None else (res["normals"] == 0).all(axis=1).sum(),
+        "no_fit": ("with fewer than 3 points in that ball (written as 0 0 0)", "without a fit (written as 0 0 0)"),
+        "files": ((".normals", textio.write_f32, "normals"), (".pca_eig", textio.write_f32, "eig"),
+                  (".pca_count", textio.write_i32_rows, "n_ball")),
+        "saved": "saved normals, eigenvalues and ball sizes for "},
+    "quadric": {
+        "fit": _quadric.quadric_cloud, "noun": "quadric fit", "scale_flag": "quadric_scale",
+        "missing": lambda res, scale, ks: (res["normals_all"][:, scale] == 0).all(axis=1).sum(),
+        "no_fit": ("without a fit in that ball (fewer than 6 points or a singular system: written as 0 0 0 and 0 0)",
+                   "without a fit (fewer than 6 points or a singular system: written as 0 0 0 and 0 0)"),
+        "files": ((".normals", textio.write_f32, "normals"), (".curv", textio.write_f32, "curv"),
+                  (".quadric_curv", textio.write_f32, "curv_all"), (".quadric_count", textio.write_i32_rows, "n_ball")),
+        "saved": "saved normals, curvatures and ball sizes for "},
+}
+
+
+def orient_line(name, mode, stats, rows):
+    """The log line of an orientation pass over the ``rows`` rows of shape ``name``; ``stats``: ``orient.stats_dict``."""
+    return ("orientation of %s (%s): %d of %d rows oriented, %d flipped, %d connected piece%s, %d edges"
+            % (name, mode, stats["n_eligible"], rows, stats["n_flipped"], stats["n_components"],
+               "" if stats["n_components"] == 1 else "s", stats["n_edges"]))
+
+
+def fit_line(estimator, name, rows, scale, n_scales, missing, radius=None, k=None):
+    """The log line of ``--estimator pca / quadric`` for shape ``name``: the written scale is the ball of ``radius`` or, with ``--knn``,
+    the ``k`` nearest neighbours; ``missing`` of the ``rows`` rows have no fit there."""
+    fit = FITS[estimator]
+    return ("%s of %s: %d rows, %s (scale %d of %d); %d rows %s"
+            % (fit["noun"], name, rows, "radius %.6g" % radius if k is None else "%d nearest neighbours" % k, scale, n_scales, missing,
+               fit["no_fit"][k is not None]))
+
+
+def run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None):
+    """``--estimator pca / quadric`` (``FITS``): per shape the fit at every scale, the optional orientation of the rows of scale ``scale``
+    (>= 0; the quadric fit flips their curvatures with them), and the estimator's files.  No model is loaded."""
+    fit = FITS[FLAGS.estimator]
     dataset = PointcloudPatchDataset(pc_path, FLAGS.testset, cfg, seed=3627473, sparse_patches=FLAGS.sparse_patches,
                                      device="cuda:%d" % FLAGS.gpu, query_positions=bool(FLAGS.query_positions))
     for ind, name in enumerate(dataset.shape_names):
         cloud = dataset.get_shape(ind)
-        res = _pca.pca_cloud(cloud, scale, None if FLAGS.orient == "0" else FLAGS.orient, FLAGS.viewpoint, FLAGS.orient_k, knn=ks)
+        res = fit["fit"](cloud, scale, None if FLAGS.orient == "0" else FLAGS.orient, FLAGS.viewpoint, FLAGS.orient_k, knn=ks)
+        missing = int(fit["missing"](res, scale, ks))
         if ks is None:
-            short = int((res["n_ball"][:, scale] < 3).sum())
-            printout("plane fit of %s: %d rows, radius %.6g (scale %d of %d); %d rows with fewer than 3 points in that ball (written as 0 0 0)"
-                     % (name, cloud.patch_count, cloud.r_abs[scale], scale, cfg.n_scales, short))
+            printout(fit_line(FLAGS.estimator, name, cloud.patch_count, scale, cfg.n_scales, missing, radius=cloud.r_abs[scale]))
         else:
-            printout("plane fit of %s: %d rows, %d nearest neighbours (scale %d of %d); %d rows without a fit (written as 0 0 0)"
-                     % (name, cloud.patch_count, ks[scale], scale, len(ks), int((res["normals"] == 0).all(axis=1).sum())))
+            printout(fit_line(FLAGS.estimator, name, cloud.patch_count, scale, len(ks), missing, k=ks[scale]))
             textio.write_f32(os.path.join(output_dir, name + ".knn_radius"), res["radius"])
         if res["orient"] is not None:
-            ost = res["orient"]
-            printout("orientation of %s (%s): %d of %d rows oriented, %d flipped, %d connected piece%s, %d edges"
-                     % (name, FLAGS.orient, ost["n_eligible"], cloud.patch_count, ost["n_flipped"], ost["n_components"],
-                        "" if ost["n_components"] == 1 else "s", ost["n_edges"]))
-        textio.write_f32(os.path.join(output_dir, name + ".normals"), res["normals"])
-        textio.write_f32(os.path.join(output_dir, name + ".pca_eig"), res["eig"].reshape(len(res["eig"]), -1))
-        textio.write_i32_rows(os.path.join(output_dir, name + ".pca_count"), res["n_ball"])
-        printout("saved normals, eigenvalues and ball sizes for " + name)
-    return 0
-
-
-def run_quadric(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None):
-    """``--estimator quadric``: per shape the quadric fit at every scale, the optional orientation of the rows of scale ``scale`` (>= 0)
-    with the flip of their curvatures, and the four files.  No model is loaded."""
-    from . import quadric as _quadric
-    dataset = PointcloudPatchDataset(pc_path, FLAGS.testset, cfg, seed=3627473, sparse_patches=FLAGS.sparse_patches,
-                                     device="cuda:%d" % FLAGS.gpu, query_positions=bool(FLAGS.query_positions))
-    for ind, name in enumerate(dataset.shape_names):
-        cloud = dataset.get_shape(ind)
-        res = _quadric.quadric_cloud(cloud, scale, None if FLAGS.orient == "0" else FLAGS.orient, FLAGS.viewpoint, FLAGS.orient_k, knn=ks)
-        failed = int((res["normals_all"][:, scale] == 0).all(axis=1).sum())
-        if ks is None:
-            printout("quadric fit of %s: %d rows, radius %.6g (scale %d of %d); %d rows without a fit in that ball (fewer than 6 points or a "
-                     "singular system: written as 0 0 0 and 0 0)" % (name, cloud.patch_count, cloud.r_abs[scale], scale, cfg.n_scales, failed))
-        else:
-            printout("quadric fit of %s: %d rows, %d nearest neighbours (scale %d of %d); %d rows without a fit (fewer than 6 points or a "
-                     "singular system: written as 0 0 0 and 0 0)" % (name, cloud.patch_count, ks[scale], scale, len(ks), failed))
-            textio.write_f32(os.path.join(output_dir, name + ".knn_radius"), res["radius"])
-        if res["orient"] is not None:
-            ost = res["orient"]
-            printout("orientation of %s (%s): %d of %d rows oriented, %d flipped, %d connected piece%s, %d edges"
-                     % (name, FLAGS.orient, ost["n_eligible"], cloud.patch_count, ost["n_flipped"], ost["n_components"],
-                        "" if ost["n_components"] == 1 else "s", ost["n_edges"]))
-        textio.write_f32(os.path.join(output_dir, name + ".normals"), res["normals"])
-        textio.write_f32(os.path.join(output_dir, name + ".curv"), res["curv"])
-        textio.write_f32(os.path.join(output_dir, name + ".quadric_curv"), res["curv_all"].reshape(len(res["curv_all"]), -1))
-        textio.write_i32_rows(os.path.join(output_dir, name + ".quadric_count"), res["n_ball"])
-        printout("saved normals, curvatures and ball sizes for " + name)
+            printout(orient_line(name, FLAGS.orient, res["orient"], cloud.patch_count))
+        for ext, write, key in fit["files"]:
+            write(os.path.join(output_dir, name + ext), res[key].reshape(len(res[key]), -1))
+        printout(fit["saved"] + name)
     return 0
 
 
 def main(argv=None):
     parser = build_parser()
     FLAGS = parser.parse_args(argv)
-    if FLAGS.pca_scale != -1 and FLAGS.estimator != "pca":
-        parser.error("--pca_scale belongs to --estimator pca")
-    if FLAGS.quadric_scale != -1 and FLAGS.estimator != "quadric":
-        parser.error("--quadric_scale belongs to --estimator quadric")
+    for est, fit in FITS.items():
+        if getattr(FLAGS, fit["scale_flag"]) != -1 and FLAGS.estimator != est:
+            parser.error("--%s belongs to --estimator %s" % (fit["scale_flag"], est))
     ks = None
     if FLAGS.knn is not None:
         if FLAGS.estimator == "net":
@@ -271,24 +273,15 @@ def main(argv=None):
             ks = check_ks([int(v) for v in FLAGS.knn.split(",")])
         except ValueError as e:
             parser.error("--knn %s: %s" % (FLAGS.knn, e))
-    if FLAGS.estimator == "quadric":
-        if FLAGS.depth_images:
-            parser.error("--estimator quadric does not take --depth_images 1: depth frames belong to the network path (--estimator net)")
-        if FLAGS.reproducible:
-            parser.error("--estimator quadric does not take --reproducible 1: it freezes the network's thresholds (--estimator net); "
-                         "the quadric fit has none")
-        if FLAGS.subsample != "hash":
-            parser.error("--estimator quadric does not take --subsample %s: the quadric fit uses the full ball and subsamples nothing"
-                         % FLAGS.subsample)
-    if FLAGS.estimator == "pca":
-        if FLAGS.depth_images:
-            parser.error("--estimator pca does not take --depth_images 1: depth frames belong to the network path (--estimator net)")
-        if FLAGS.reproducible:
-            parser.error("--estimator pca does not take --reproducible 1: it freezes the network's thresholds (--estimator net); the "
-                         "plane fit has none")
-        if FLAGS.subsample != "hash":
-            parser.error("--estimator pca does not take --subsample %s: the plane fit uses the full ball and subsamples nothing"
-                         % FLAGS.subsample)
+    fit = FITS.get(FLAGS.estimator)
+    if fit:
+        for given, flag, why in ((FLAGS.depth_images, "--depth_images 1", "depth frames belong to the network path (--estimator net)"),
+                                 (FLAGS.reproducible, "--reproducible 1",
+                                  "it freezes the network's thresholds (--estimator net); the %s has none" % fit["noun"]),
+                                 (FLAGS.subsample != "hash", "--subsample %s" % FLAGS.subsample,
+                                  "the %s uses the full ball and subsamples nothing" % fit["noun"])):
+            if given:
+                parser.error("--estimator %s does not take %s: %s" % (FLAGS.estimator, flag, why))
     if FLAGS.query_positions and FLAGS.sparse_patches:
         parser.error("--query_positions 1 and --sparse_patches 1 are mutually exclusive: the queries are positions or cloud points")
     if FLAGS.query_positions and FLAGS.subsample != "hash":
@@ -328,24 +321,13 @@ def main(argv=None):
         flog.write(data + "\n")
         sys.stdout.flush()
 
-    if FLAGS.estimator == "pca":
-        from .pca import check_scale
+    if fit:
         cfg = NestiConfig.for_model(FLAGS.model)
         try:
-            scale = check_scale(FLAGS.pca_scale, cfg.n_scales if ks is None else len(ks))
+            scale = _pca.check_scale(getattr(FLAGS, fit["scale_flag"]), cfg.n_scales if ks is None else len(ks))
         except ValueError as e:
-            raise SystemExit("--pca_scale with --model %s: %s" % (FLAGS.model, e))
-        rc = run_pca(FLAGS, cfg, scale, pc_path, output_dir, printout, ks)
-        flog.close()
-        return rc
-    if FLAGS.estimator == "quadric":
-        from .pca import check_scale
-        cfg = NestiConfig.for_model(FLAGS.model)
-        try:
-            scale = check_scale(FLAGS.quadric_scale, cfg.n_scales if ks is None else len(ks))
-        except ValueError as e:
-            raise SystemExit("--quadric_scale with --model %s: %s" % (FLAGS.model, e))
-        rc = run_quadric(FLAGS, cfg, scale, pc_path, output_dir, printout, ks)
+            raise SystemExit("--%s with --model %s: %s" % (fit["scale_flag"], FLAGS.model, e))
+        rc = run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks)
         flog.close()
         return rc
 
@@ -442,9 +424,7 @@ def main(argv=None):
             # after the whole shape is estimated (in the reproducible mode: after its last verified pass); only signs change
             from .orient import stats_dict
             ost = stats_dict(est.orient(cloud, normals, FLAGS.orient, FLAGS.viewpoint, FLAGS.orient_k))
-            printout("orientation of %s (%s): %d of %d rows oriented, %d flipped, %d connected piece%s, %d edges"
-                     % (name, FLAGS.orient, ost["n_eligible"], cloud.patch_count, ost["n_flipped"], ost["n_components"],
-                        "" if ost["n_components"] == 1 else "s", ost["n_edges"]))
+            printout(orient_line(name, FLAGS.orient, ost, cloud.patch_count))
         torch.cuda.synchronize()
         if FLAGS.query_positions:
             # the sentinel (pool.hip: mask_empty_queries_kernel): expert -1; the single-tower models have only the (0, 0, 0) normal

@@ -425,12 +425,8 @@ int knn_impl(const char* who, bool at, const float* cloud_dev, int N, const int3
   if (at && !query_xyz_dev) NESTI_FAIL(w + ": null query_xyz_dev");
   KnnParams kp;
   memset(&kp, 0, sizeof(kp));
-  const WsLayout L = patch_ws_layout(N);
-  const unsigned char* ws = (const unsigned char*)grid_ws_dev;
+  patch_params_grid(&kp.p, N, grid_ws_dev);
   kp.p.cloud = cloud_dev;
-  kp.p.sorted = (const float4*)(ws + L.sorted);
-  kp.p.start = (const int*)(ws + L.start);
-  kp.p.header = (const GridHeader*)(ws + L.header);
   kp.p.query_idx = query_idx_dev;
   kp.p.query_xyz = at ? query_xyz_dev : nullptr;
   kp.p.M = M; kp.p.N = N; kp.p.row0 = query_row0;
@@ -438,13 +434,7 @@ int knn_impl(const char* who, bool at, const float* cloud_dev, int N, const int3
   kp.nbr_out = nbr_out_dev;
   kp.d2_out = d2_out_dev;
   kp.count_out = count_out_dev;
-  const dim3 grid((unsigned)((M + kRowsPerBlock - 1) / kRowsPerBlock)), block(kThreads);
-  hipStream_t st = (hipStream_t)stream;
-  const int tok = prof_begin(NESTI_PROF_PATCHES, st);   // the profiler's neighbourhood slot, like pca.hip and quadric.hip
-  hipLaunchKernelGGL(knn_kernel, grid, block, 0, st, kp);
-  prof_end(NESTI_PROF_PATCHES, tok, st);
-  NESTI_CHECK_HIP(hipGetLastError());
-  return 0;
+  return launch_wave_rows(knn_kernel, kp, M, stream);
 }
 
 // what the two list fits refuse, under the entry's name, and their parameter block
@@ -484,18 +474,7 @@ int pca_nbr_impl(const char* who, bool at, const float* cloud_dev, int N, const 
   if (M == 0) return 0;
   pp.normals_out = normals_out_dev;
   pp.eig_out = eig_out_dev;
-  const dim3 grid((unsigned)((M + kRowsPerBlock - 1) / kRowsPerBlock)), block(kThreads);
-  hipStream_t st = (hipStream_t)stream;
-  const int tok = prof_begin(NESTI_PROF_PATCHES, st);
-  switch (S) {
-    case 1: hipLaunchKernelGGL(pca_nbr_kernel<1>, grid, block, 0, st, pp); break;
-    case 2: hipLaunchKernelGGL(pca_nbr_kernel<2>, grid, block, 0, st, pp); break;
-    case 3: hipLaunchKernelGGL(pca_nbr_kernel<3>, grid, block, 0, st, pp); break;
-    default: hipLaunchKernelGGL(pca_nbr_kernel<4>, grid, block, 0, st, pp); break;
-  }
-  prof_end(NESTI_PROF_PATCHES, tok, st);
-  NESTI_CHECK_HIP(hipGetLastError());
-  return 0;
+  return with_scales(S, [&](auto s) { return launch_wave_rows(pca_nbr_kernel<decltype(s)::value>, pp, M, stream); });
 }
 
 // nesti_quadric_fit_nbr and nesti_quadric_fit_nbr_at: one body
@@ -508,18 +487,7 @@ int quadric_nbr_impl(const char* who, bool at, const float* cloud_dev, int N, co
     return 1;
   if (M == 0) return 0;
   qp.out = QuadricOut{normals_out_dev, curv_out_dev, plane_out_dev, nullptr};
-  const dim3 grid((unsigned)((M + kRowsPerBlock - 1) / kRowsPerBlock)), block(kThreads);
-  hipStream_t st = (hipStream_t)stream;
-  const int tok = prof_begin(NESTI_PROF_PATCHES, st);
-  switch (S) {
-    case 1: hipLaunchKernelGGL(quadric_nbr_kernel<1>, grid, block, 0, st, qp); break;
-    case 2: hipLaunchKernelGGL(quadric_nbr_kernel<2>, grid, block, 0, st, qp); break;
-    case 3: hipLaunchKernelGGL(quadric_nbr_kernel<3>, grid, block, 0, st, qp); break;
-    default: hipLaunchKernelGGL(quadric_nbr_kernel<4>, grid, block, 0, st, qp); break;
-  }
-  prof_end(NESTI_PROF_PATCHES, tok, st);
-  NESTI_CHECK_HIP(hipGetLastError());
-  return 0;
+  return with_scales(S, [&](auto s) { return launch_wave_rows(quadric_nbr_kernel<decltype(s)::value>, qp, M, stream); });
 }
 
 }  // namespace

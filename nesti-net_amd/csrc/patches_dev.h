@@ -273,17 +273,22 @@ __device__ __forceinline__ float patch_coord(const PatchParams& p, int idx, int 
   return __fdiv_rn(__fsub_rn(p.cloud[(size_t)idx * 3 + axis], c), rad);
 }
 
+// host side: the view of the search grid inside its workspace (sorted, start, header); every entry that walks the grid fills it here
+inline void patch_params_grid(PatchParams* p, int N, const void* grid_ws_dev) {
+  const WsLayout L = patch_ws_layout(N);
+  const unsigned char* ws = (const unsigned char*)grid_ws_dev;
+  p->sorted = (const float4*)(ws + L.sorted);
+  p->start = (const int*)(ws + L.start);
+  p->header = (const GridHeader*)(ws + L.header);
+}
+
 // host side: fill the kernel parameter block from the C-ABI arguments (validated by the caller)
 inline void patch_params_fill(PatchParams* p, const nesti_config_t* cfg, const float* cloud_dev, int N,
                               const int32_t* query_idx_dev, int M, const double* r_abs, uint64_t seed, int query_row0,
                               const void* grid_ws_dev) {
-  const WsLayout L = patch_ws_layout(N);
-  const unsigned char* ws = (const unsigned char*)grid_ws_dev;
   memset(p, 0, sizeof(*p));
+  patch_params_grid(p, N, grid_ws_dev);
   p->cloud = cloud_dev;
-  p->sorted = (const float4*)(ws + L.sorted);
-  p->start = (const int*)(ws + L.start);
-  p->header = (const GridHeader*)(ws + L.header);
   p->query_idx = query_idx_dev;
   p->M = M; p->N = N; p->S = cfg->n_scales; p->P = cfg->points_per_scale; p->seed = seed; p->row0 = query_row0;
   for (int s = 0; s < cfg->n_scales; ++s) {

@@ -84,18 +84,7 @@ int pca_impl(const char* who, bool at, const nesti_config_t* cfg, const float* c
   pp.p.n_ball_out = n_ball_out_dev;
   pp.normals_out = normals_out_dev;
   pp.eig_out = eig_out_dev;
-  const dim3 grid((unsigned)((M + kRowsPerBlock - 1) / kRowsPerBlock)), block(kThreads);
-  hipStream_t st = (hipStream_t)stream;
-  const int tok = prof_begin(NESTI_PROF_PATCHES, st);
-  switch (cfg->n_scales) {
-    case 1: hipLaunchKernelGGL(pca_kernel<1>, grid, block, 0, st, pp); break;
-    case 2: hipLaunchKernelGGL(pca_kernel<2>, grid, block, 0, st, pp); break;
-    case 3: hipLaunchKernelGGL(pca_kernel<3>, grid, block, 0, st, pp); break;
-    default: hipLaunchKernelGGL(pca_kernel<4>, grid, block, 0, st, pp); break;
-  }
-  prof_end(NESTI_PROF_PATCHES, tok, st);
-  NESTI_CHECK_HIP(hipGetLastError());
-  return 0;
+  return with_scales(cfg->n_scales, [&](auto s) { return launch_wave_rows(pca_kernel<decltype(s)::value>, pp, M, stream); });
 }
 
 }  // namespace

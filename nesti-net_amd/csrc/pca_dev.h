@@ -44,6 +44,30 @@ __device__ __forceinline__ int wave_row() {
   return __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6)));
 }
 
+// host side: f(std::integral_constant<int, S>) for the number of scales S in 1 .. NESTI_MAX_SCALES (checked by the caller) a launch
+// is instantiated for, like with_elem_type (kernels.h)
+static_assert(NESTI_MAX_SCALES == 4, "with_scales names every S");
+template <class F>
+int with_scales(int S, F&& f) {
+  switch (S) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    default: return f(std::integral_constant<int, 4>{});
+  }
+}
+// host side: one launch of a one-wave-per-row kernel (wave_row) over M > 0 rows on `stream`, timed in the profiler's neighbourhood slot
+template <class Params>
+int launch_wave_rows(void (*kernel)(Params), const Params& params, int M, void* stream) {
+  const dim3 grid((unsigned)((M + kRowsPerBlock - 1) / kRowsPerBlock)), block(kThreads);
+  hipStream_t st = (hipStream_t)stream;
+  const int tok = prof_begin(NESTI_PROF_PATCHES, st);
+  hipLaunchKernelGGL(kernel, grid, block, 0, st, params);
+  prof_end(NESTI_PROF_PATCHES, tok, st);
+  NESTI_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 // lane t < 9: x-span t of the cell block round the centre (block_span, patches_dev.h); empty for a centre that is not finite
 __device__ __forceinline__ WaveSpans wave_spans(const PatchParams& p, int lane, float cf0, float cf1, float cf2) {
   WaveSpans spans = {0, 0};

@@ -125,18 +125,7 @@ int quadric_impl(const char* who, bool at, const nesti_config_t* cfg, const floa
   qp.normals_out = normals_out_dev;
   qp.curv_out = curv_out_dev;
   qp.plane_out = plane_out_dev;
-  const dim3 grid((unsigned)((M + kRowsPerBlock - 1) / kRowsPerBlock)), block(kThreads);
-  hipStream_t st = (hipStream_t)stream;
-  const int tok = prof_begin(NESTI_PROF_PATCHES, st);
-  switch (cfg->n_scales) {
-    case 1: hipLaunchKernelGGL(quadric_kernel<1>, grid, block, 0, st, qp); break;
-    case 2: hipLaunchKernelGGL(quadric_kernel<2>, grid, block, 0, st, qp); break;
-    case 3: hipLaunchKernelGGL(quadric_kernel<3>, grid, block, 0, st, qp); break;
-    default: hipLaunchKernelGGL(quadric_kernel<4>, grid, block, 0, st, qp); break;
-  }
-  prof_end(NESTI_PROF_PATCHES, tok, st);
-  NESTI_CHECK_HIP(hipGetLastError());
-  return 0;
+  return with_scales(cfg->n_scales, [&](auto s) { return launch_wave_rows(quadric_kernel<decltype(s)::value>, qp, M, stream); });
 }
 
 }  // namespace

@@ -28,49 +28,51 @@ def variation(eig):
 def orient_rows(cloud, normals, scale, mode, viewpoint=None, k=8, radius=None):
     """Orient the rows ``normals`` [patch_count, 3] (contiguous, on the cloud's device) of a prepared cloud IN PLACE with
     ``orient.orient_device``, the way ``NormalEstimator.orient`` does: positions are the cloud, ``cloud[pidx]`` or the (harmless) query
-    positions; the radius is ``r_abs[scale]``, or ``radius`` where given (the k-NN fits, whose scales are no radii).  Only sign bits
-    change, sentinel rows stay 0 0 0.  Returns the int32[4] stats tensor."""
+    positions (``CloudPatches.centre_positions``); the radius is ``r_abs[scale]``, or ``radius`` where given (the k-NN fits, whose
+    scales are no radii).  Only sign bits change, sentinel rows stay 0 0 0.  Returns the int32[4] stats tensor."""
     import torch
     from . import orient as _orient
-    if cloud.queries is not None:
-        pos = _orient.harmless_positions(cloud.queries)
-    elif cloud.pidx is not None:
-        pos = cloud.cloud[cloud.pidx.long()].contiguous()
-    else:
-        pos = cloud.cloud
     r = float(cloud.r_abs[scale]) if radius is None else float(radius)
-    return _orient.orient_device(pos, normals, r, k, viewpoint, mode, torch.cuda.current_stream(cloud.device))
+    return _orient.orient_device(cloud.centre_positions(), normals, r, k, viewpoint, mode, torch.cuda.current_stream(cloud.device))
 
 
-def pca_cloud(cloud, scale=-1, orient=None, viewpoint=None, orient_k=8, knn=None):
-    """``pca_normals`` for a prepared ``provider.CloudPatches`` (all of its patch rows); synchronises.  ``knn``: neighbour counts
-    instead of the cloud's radii (``scale`` then indexes them, and the dict gains ``radius``)."""
+def fit_cloud(cloud, ball, nbr, names, scale, orient, viewpoint, orient_k, knn, after=None):
+    """What ``pca_cloud`` and ``quadric.quadric_cloud`` share: fit all patch rows of a prepared cloud with the method ``ball`` -- over
+    the neighbour counts ``knn`` with the method ``nbr`` --, take the normals of ``scale``, orient them, synchronise.  ``names``: the
+    dict keys of the ball method's outputs, normals first and counts last (a k-NN method returns ``radius`` before the counts).
+    ``after(out, s, before)`` runs behind the orientation step on the dict of device tensors, ``out["normals"]`` among them, with the
+    scale's index and the normals from before the pass (None where none ran), and may add tensors.  Returns the dict as numpy arrays,
+    with ``orient``."""
     import torch
     from . import orient as _orient
     ks = None
     if knn is not None:
         from .knn import check_ks
         ks = check_ks(knn)
+        names = names[:-1] + ("radius",) + names[-1:]
     s = check_scale(scale, cloud.cfg.n_scales if ks is None else len(ks))
     if orient not in ORIENT_MODES:
         raise ValueError("orient must be None, 'mst' or 'viewpoint'")
     with torch.cuda.device(cloud.device):
-        radius = None
-        if ks is None:
-            normals_all, eig, n_ball = cloud.pca(0, cloud.patch_count)
-        else:
-            normals_all, eig, radius, n_ball = cloud.pca_knn(0, cloud.patch_count, ks)
-        normals = normals_all[:, s, :].contiguous()
-        stats = None
+        out = dict(zip(names, ball(0, cloud.patch_count) if ks is None else nbr(0, cloud.patch_count, ks)))
+        normals = out["normals"] = out[names[0]][:, s, :].contiguous()
+        before = stats = None
         if orient is not None and cloud.patch_count:
+            before = normals.clone() if after else None
             stats = orient_rows(cloud, normals, s, orient, viewpoint, orient_k, radius=None if ks is None else max(cloud.r_abs))
+        if after:
+            after(out, s, before)
         torch.cuda.current_stream(cloud.device).synchronize()
-    eig_h = eig.cpu().numpy()
-    res = {"normals": normals.cpu().numpy(), "normals_all": normals_all.cpu().numpy(), "eig": eig_h, "variation": variation(eig_h),
-           "n_ball": n_ball.cpu().numpy(),
-           "orient": None if orient is None else (_orient.stats_dict(stats) if stats is not None else dict.fromkeys(_orient.STAT_NAMES, 0))}
-    if radius is not None:
-        res["radius"] = radius.cpu().numpy()
+    res = {key: t.cpu().numpy() for key, t in out.items()}
+    res["orient"] = None if orient is None else (_orient.stats_dict(stats) if stats is not None else dict.fromkeys(_orient.STAT_NAMES, 0))
+    return res
+
+
+def pca_cloud(cloud, scale=-1, orient=None, viewpoint=None, orient_k=8, knn=None):
+    """``pca_normals`` for a prepared ``provider.CloudPatches`` (all of its patch rows); synchronises.  ``knn``: neighbour counts
+    instead of the cloud's radii (``scale`` then indexes them, and the dict gains ``radius``)."""
+    res = fit_cloud(cloud, cloud.pca, cloud.pca_knn, ("normals_all", "eig", "n_ball"), scale, orient, viewpoint, orient_k, knn)
+    res["variation"] = variation(res["eig"])
     return res
 
 
@@ -85,6 +87,24 @@ def check_knn_args(knn, cfg):
     if cfg is not None:
         raise ValueError("knn and cfg are mutually exclusive: the scales of a k-NN fit are the neighbour counts, not cfg.patch_radius")
     return ks, NestiConfig()
+
+
+def prepare_cloud(pts, cfg, pidx, queries, scale, orient, viewpoint, orient_k, device, knn):
+    """The "numpy in" front of ``pca_normals`` and ``quadric.quadric_fit``: every argument check, then the ``CloudPatches``.  Returns the
+    arguments of ``pca_cloud`` / ``quadric.quadric_cloud``."""
+    ks, cfg = check_knn_args(knn, cfg)
+    check_scale(scale, cfg.n_scales if ks is None else len(ks))
+    if orient not in ORIENT_MODES:
+        raise ValueError("orient must be None, 'mst' or 'viewpoint'")
+    if pidx is not None and queries is not None:
+        raise ValueError("pidx and queries are mutually exclusive: a query is a cloud point (pidx) or a position (queries)")
+    if orient is not None:
+        from .orient import _check_args
+        _check_args(1.0, orient_k, viewpoint, orient)
+    from .provider import CloudPatches
+    # the k-NN fits never read the radius grid (the orientation pass builds its own): a cloud without extent is served too
+    cloud = CloudPatches(np.asarray(pts, dtype=np.float32), cfg, device=device, pidx=pidx, queries=queries, radius_grid=ks is None)
+    return cloud, scale, orient, viewpoint, orient_k, ks
 
 
 def pca_normals(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, viewpoint=None, orient_k=8, device="cuda:0", knn=None):
@@ -112,16 +132,4 @@ def pca_normals(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, v
 
     Raises ``ValueError`` for a ``scale`` outside [-S, S), for ``pidx`` together with ``queries``, for a bad ``knn`` and for ``knn``
     together with ``cfg`` (whose radii would mean nothing)."""
-    ks, cfg = check_knn_args(knn, cfg)
-    check_scale(scale, cfg.n_scales if ks is None else len(ks))
-    if orient not in ORIENT_MODES:
-        raise ValueError("orient must be None, 'mst' or 'viewpoint'")
-    if pidx is not None and queries is not None:
-        raise ValueError("pidx and queries are mutually exclusive: a query is a cloud point (pidx) or a position (queries)")
-    if orient is not None:
-        from .orient import _check_args
-        _check_args(1.0, orient_k, viewpoint, orient)
-    from .provider import CloudPatches
-    # the k-NN fits never read the radius grid (the orientation pass builds its own): a cloud without extent is served too
-    cloud = CloudPatches(np.asarray(pts, dtype=np.float32), cfg, device=device, pidx=pidx, queries=queries, radius_grid=ks is None)
-    return pca_cloud(cloud, scale, orient, viewpoint, orient_k, knn=ks)
+    return pca_cloud(*prepare_cloud(pts, cfg, pidx, queries, scale, orient, viewpoint, orient_k, device, knn))

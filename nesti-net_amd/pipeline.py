@@ -504,15 +504,9 @@ class NormalEstimator:
         from . import orient as _orient
         if normals.shape[0] != cloud.patch_count:
             raise ValueError("orientation needs the normals of all %d patch rows, got %d" % (cloud.patch_count, normals.shape[0]))
-        if cloud.queries is not None:
-            pos = _orient.harmless_positions(cloud.queries)      # a non-finite position has no neighbourhood: its row is the sentinel
-        elif cloud.pidx is not None:
-            pos = cloud.cloud[cloud.pidx.long()].contiguous()
-        else:
-            pos = cloud.cloud
         if not normals.is_contiguous():
             raise ValueError("orientation works in place on a contiguous [M, 3] tensor")
-        return _orient.orient_device(pos, normals, float(cloud.r_abs[-1]), k, viewpoint, mode,
+        return _orient.orient_device(cloud.centre_positions(), normals, float(cloud.r_abs[-1]), k, viewpoint, mode,
                                      torch.cuda.current_stream(self.device))
 
     def estimate(self, pts, pidx=None, queries=None, orient=None, viewpoint=None, orient_k=8):

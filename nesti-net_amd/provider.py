@@ -15,6 +15,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import knn as _knn
+from . import orient as _orient
 from .config import NestiConfig
 
 
@@ -59,6 +61,19 @@ def check_queries(queries):
     if len(bad):
         raise ValueError("queries row %d is not finite: %s" % (bad[0], q[bad[0]].tolist()))
     return q
+
+
+def check_out(out, specs, device, what=""):
+    """``out=`` of a method that writes a tuple of tensors: ``specs`` is that tuple as ``(shape, dtype)`` pairs.  None -> fresh tensors
+    on ``device``; otherwise the caller's own as a tuple, each contiguous, of its shape and dtype and on ``device`` -- ``ValueError``
+    naming ``what`` (the tuple in words) if not."""
+    if out is None:
+        return tuple(torch.empty(shape, dtype=dt, device=device) for shape, dt in specs)
+    out = tuple(out)
+    if len(out) != len(specs) or any(tuple(t.shape) != tuple(shape) or t.dtype != dt or not t.is_contiguous() or t.device != device
+                                     for t, (shape, dt) in zip(out, specs)):
+        raise ValueError("out: contiguous %s on %s" % (what, device))
+    return out
 
 
 class CloudPatches:
@@ -113,14 +128,59 @@ class CloudPatches:
         if radius_grid:
             self.build_grid()
 
+    def _stream(self, stream):
+        """``stream``, or the current stream of the cloud's device."""
+        return stream if stream is not None else torch.cuda.current_stream(self.device)
+
+    def _rows(self, first, count):
+        """(at, queries) of patch rows [first, first + count), validated: ``at`` -- the queries are positions; ``queries`` -- their
+        [count,3] positions, the [count] indices of ``pidx``, or None (row i is cloud point first + i)."""
+        if first < 0 or count < 0 or first + count > self.patch_count:
+            raise ValueError("patch rows [%d, %d) outside [0, %d)" % (first, first + count, self.patch_count))
+        if self.queries is not None:
+            return True, self.queries[first:first + count]
+        return False, (self.pidx[first:first + count].contiguous() if self.pidx is not None else None)
+
+    def _call(self, name, at, q, count, first, args, stream, ball=True, seed=()):
+        """One entry over patch rows: ``name``, or ``name + "_at"`` where the queries are positions, called on the cloud's device and
+        checked under that name.  The two argument layouts of include/nesti_hip.h: a ball entry (``ball``) takes the configuration,
+        the radii, ``query_row0`` in both forms (after ``seed`` where it has one) and, behind its own ``args``, the radius grid; a
+        k-NN or list-fit entry takes ``query_row0`` in the index form only.  The stream comes last."""
+        entry = name + "_at" if at else name
+        head = (_lib.ptr(self.cloud), self.n_points, _lib.ptr(q), count)
+        row0 = (ctypes.c_int(first),)
+        if ball:
+            head = (ctypes.byref(self._c),) + head + (self._r,) + seed + row0
+            args = tuple(args) + (_lib.ptr(self._ws), self._ws.numel())
+        elif not at:
+            head += row0
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(self.lib, entry)(*head, *args, ctypes.c_void_p(stream.cuda_stream)), entry)
+
+    def centre_positions(self):
+        """The [patch_count, 3] positions of the patch rows (device): the query positions made harmless for an orientation pass
+        (``orient.harmless_positions``: a non-finite position has no neighbourhood, its row is the sentinel), ``cloud[pidx]``, or the
+        cloud itself."""
+        if self.queries is not None:
+            return _orient.harmless_positions(self.queries)
+        if self.pidx is not None:
+            return self.cloud[self.pidx.long()].contiguous()
+        return self.cloud
+
     def build_grid(self, stream=None):
         """(Re)build the uniform search grid on the device -- the cKDTree construction of the
         reference (``utils/pcpnet_dataset.py:37``).  Asynchronous on ``stream``."""
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.nesti_patches_grid(ctypes.byref(self._c), _lib.ptr(self.cloud), self.n_points, self._r,
-                                                   _lib.ptr(self._ws), self._ws.numel(), ctypes.c_void_p(st.cuda_stream)),
+                                                   _lib.ptr(self._ws), self._ws.numel(), ctypes.c_void_p(self._stream(stream).cuda_stream)),
                        "nesti_patches_grid")
+
+    def _patch_out(self, count, out, want_idx):
+        """(points [count,S*P,3] f32, n_eff [count,S] int32) -- the two of ``out`` as they are, where given -- and nbr [count,S*P]
+        int32 or None."""
+        S, P = self.cfg.n_scales, self.cfg.num_point
+        points, n_eff = out if out is not None else check_out(None, (((count, S * P, 3), torch.float32), ((count, S), torch.int32)), self.device)
+        return points, n_eff, (torch.empty((count, S * P), dtype=torch.int32, device=self.device) if want_idx else None)
 
     def build(self, first, count, want_idx=False, out=None, stream=None):
         """Patches for local patch rows [first, first+count) (file order, or ``pidx`` order when
@@ -129,27 +189,11 @@ class CloudPatches:
         Returns points [count,S*P,3] f32, n_eff [count,S] int32 (+ nbr_idx [count,S*P], n_ball
         [count,S] when ``want_idx``).  The subsample key uses the global row ``first + i`` so
         results do not depend on batching."""
-        S, P = self.cfg.n_scales, self.cfg.num_point
-        if first < 0 or count < 0 or first + count > self.patch_count:
-            raise ValueError("patch rows [%d, %d) outside [0, %d)" % (first, first + count, self.patch_count))
-        # sparse: <shape>.pidx rows; full: NULL -> the kernel uses point index = patch row; positions: rows of queries
-        qidx = self.pidx[first:first + count].contiguous() if self.pidx is not None else None
-        if out is None:
-            points = torch.empty((count, S * P, 3), dtype=torch.float32, device=self.device)
-            n_eff = torch.empty((count, S), dtype=torch.int32, device=self.device)
-        else:
-            points, n_eff = out
-        nbr = torch.empty((count, S * P), dtype=torch.int32, device=self.device) if want_idx else None
-        n_ball = torch.empty((count, S), dtype=torch.int32, device=self.device) if want_idx else None
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        at = self.queries is not None
-        entry = "nesti_patches_query_at" if at else "nesti_patches_query"
-        with torch.cuda.device(self.device):
-            _lib.check(getattr(self.lib, entry)(
-                ctypes.byref(self._c), _lib.ptr(self.cloud), self.n_points, _lib.ptr(self.queries[first:first + count] if at else qidx),
-                count, self._r, ctypes.c_uint64(self.seed), ctypes.c_int(first), _lib.ptr(points), _lib.ptr(n_eff), _lib.ptr(nbr),
-                _lib.ptr(n_ball), _lib.ptr(self._ws), self._ws.numel(), ctypes.c_void_p(st.cuda_stream)),
-                entry)
+        at, q = self._rows(first, count)
+        points, n_eff, nbr = self._patch_out(count, out, want_idx)
+        n_ball = torch.empty((count, self.cfg.n_scales), dtype=torch.int32, device=self.device) if want_idx else None
+        self._call("nesti_patches_query", at, q, count, first, [_lib.ptr(t) for t in (points, n_eff, nbr, n_ball)], self._stream(stream),
+                   seed=(ctypes.c_uint64(self.seed),))
         if want_idx:
             return points, n_eff, nbr, n_ball
         return points, n_eff
@@ -179,17 +223,10 @@ class CloudPatches:
     def count_balls(self, first, count, stream=None):
         """Ball sizes [count, S] int32 (device) of patch rows [first, first + count): what the reference's random stream needs
         (``nesti_patches_count``)."""
-        S = self.cfg.n_scales
         self._index_queries_only("count_balls")
-        if first < 0 or count < 0 or first + count > self.patch_count:
-            raise ValueError("patch rows [%d, %d) outside [0, %d)" % (first, first + count, self.patch_count))
-        qidx = self.pidx[first:first + count].contiguous() if self.pidx is not None else None
-        n_ball = torch.empty((count, S), dtype=torch.int32, device=self.device)
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.nesti_patches_count(ctypes.byref(self._c), _lib.ptr(self.cloud), self.n_points, _lib.ptr(qidx), count,
-                                                    self._r, ctypes.c_int(first), _lib.ptr(n_ball), _lib.ptr(self._ws), self._ws.numel(),
-                                                    ctypes.c_void_p(st.cuda_stream)), "nesti_patches_count")
+        at, q = self._rows(first, count)
+        n_ball = torch.empty((count, self.cfg.n_scales), dtype=torch.int32, device=self.device)
+        self._call("nesti_patches_count", at, q, count, first, [_lib.ptr(n_ball)], self._stream(stream))
         return n_ball
 
     def pca(self, first, count, out=None, stream=None):
@@ -198,30 +235,11 @@ class CloudPatches:
         or the three of ``out``.  Serves all points, ``pidx`` and ``queries``; asynchronous on ``stream``.  A scale whose ball holds
         fewer than 3 points has normal 0 0 0 and eigenvalues 0 0 0.  For this grid a row's bits do not depend on the batching."""
         S = self.cfg.n_scales
-        if first < 0 or count < 0 or first + count > self.patch_count:
-            raise ValueError("patch rows [%d, %d) outside [0, %d)" % (first, first + count, self.patch_count))
-        if out is None:
-            normals = torch.empty((count, S, 3), dtype=torch.float32, device=self.device)
-            eig = torch.empty((count, S, 3), dtype=torch.float32, device=self.device)
-            n_ball = torch.empty((count, S), dtype=torch.int32, device=self.device)
-        else:
-            normals, eig, n_ball = out
-            for t, shape, dt in ((normals, (count, S, 3), torch.float32), (eig, (count, S, 3), torch.float32), (n_ball, (count, S), torch.int32)):
-                if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
-                    raise ValueError("out: contiguous (normals [count,S,3] f32, eig [count,S,3] f32, n_ball [count,S] int32) on %s" % self.device)
-        at = self.queries is not None
-        if at:
-            q = self.queries[first:first + count]
-        else:
-            q = self.pidx[first:first + count].contiguous() if self.pidx is not None else None
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        entry = "nesti_pca_normals_at" if at else "nesti_pca_normals"
-        with torch.cuda.device(self.device):
-            _lib.check(getattr(self.lib, entry)(
-                ctypes.byref(self._c), _lib.ptr(self.cloud), self.n_points, _lib.ptr(q), count, self._r, ctypes.c_int(first),
-                _lib.ptr(normals), _lib.ptr(eig), _lib.ptr(n_ball), _lib.ptr(self._ws), self._ws.numel(),
-                ctypes.c_void_p(st.cuda_stream)), entry)
-        return normals, eig, n_ball
+        at, q = self._rows(first, count)
+        out = check_out(out, (((count, S, 3), torch.float32), ((count, S, 3), torch.float32), ((count, S), torch.int32)), self.device,
+                        "(normals [count,S,3] f32, eig [count,S,3] f32, n_ball [count,S] int32)")
+        self._call("nesti_pca_normals", at, q, count, first, [_lib.ptr(t) for t in out], self._stream(stream))
+        return out
 
     def quadric(self, first, count, out=None, stream=None):
         """Quadric-fit normals and principal curvatures of patch rows [first, first + count) at every scale (``nesti_quadric_fit`` /
@@ -230,31 +248,12 @@ class CloudPatches:
         Serves all points, ``pidx`` and ``queries``; asynchronous on ``stream``.  A failed fit (fewer than 6 points in the ball, no plane
         normal, a singular system) has normal 0 0 0 and curvatures 0 0.  For this grid a row's bits do not depend on the batching."""
         S = self.cfg.n_scales
-        if first < 0 or count < 0 or first + count > self.patch_count:
-            raise ValueError("patch rows [%d, %d) outside [0, %d)" % (first, first + count, self.patch_count))
-        shapes = (((count, S, 3), torch.float32), ((count, S, 2), torch.float32), ((count, S, 3), torch.float32), ((count, S), torch.int32))
-        if out is None:
-            out = tuple(torch.empty(shape, dtype=dt, device=self.device) for shape, dt in shapes)
-        else:
-            out = tuple(out)
-            if len(out) != 4 or any(tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device
-                                    for t, (shape, dt) in zip(out, shapes)):
-                raise ValueError("out: contiguous (normals [count,S,3] f32, curv [count,S,2] f32, plane [count,S,3] f32, n_ball [count,S] "
-                                 "int32) on %s" % self.device)
-        normals, curv, plane, n_ball = out
-        at = self.queries is not None
-        if at:
-            q = self.queries[first:first + count]
-        else:
-            q = self.pidx[first:first + count].contiguous() if self.pidx is not None else None
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        entry = "nesti_quadric_fit_at" if at else "nesti_quadric_fit"
-        with torch.cuda.device(self.device):
-            _lib.check(getattr(self.lib, entry)(
-                ctypes.byref(self._c), _lib.ptr(self.cloud), self.n_points, _lib.ptr(q), count, self._r, ctypes.c_int(first),
-                _lib.ptr(normals), _lib.ptr(curv), _lib.ptr(plane), _lib.ptr(n_ball), _lib.ptr(self._ws), self._ws.numel(),
-                ctypes.c_void_p(st.cuda_stream)), entry)
-        return normals, curv, plane, n_ball
+        at, q = self._rows(first, count)
+        out = check_out(out, (((count, S, 3), torch.float32), ((count, S, 2), torch.float32), ((count, S, 3), torch.float32),
+                              ((count, S), torch.int32)), self.device,
+                        "(normals [count,S,3] f32, curv [count,S,2] f32, plane [count,S,3] f32, n_ball [count,S] int32)")
+        self._call("nesti_quadric_fit", at, q, count, first, [_lib.ptr(t) for t in out], self._stream(stream))
+        return out
 
     # ---- k-nearest neighbourhoods (csrc/knn.hip; DESIGN.md 2 "k-nearest neighbourhoods") ----------------------------------------
     KNN_GRIDS_KEPT = 4                        # search-only grids kept per cloud, each the size of the radius grid's workspace
@@ -272,7 +271,6 @@ class CloudPatches:
             if not self._has_radius_grid:
                 raise ValueError("grid='radius': this cloud was prepared without its radius grid")
             return self._ws
-        from . import knn as _knn
         if grid is None:
             radius = _knn.default_radius(self.n_points, _knn.check_k(k), self._extent)
         else:
@@ -296,56 +294,36 @@ class CloudPatches:
         stream.wait_event(built)
         return ws
 
-    def _knn_queries(self, first, count):
-        """(at, queries) of patch rows [first, first + count), validated: ``at`` -- the queries are positions; ``queries`` -- their
-        [count,3] positions, the [count] indices of ``pidx``, or None (row i is cloud point first + i)."""
-        if first < 0 or count < 0 or first + count > self.patch_count:
-            raise ValueError("patch rows [%d, %d) outside [0, %d)" % (first, first + count, self.patch_count))
-        if self.queries is not None:
-            return True, self.queries[first:first + count]
-        return False, (self.pidx[first:first + count].contiguous() if self.pidx is not None else None)
-
     def knn(self, first, count, k, grid=None, stream=None):
         """The ``k`` nearest cloud points of patch rows [first, first + count) (``nesti_knn`` / ``nesti_knn_at``): device tensors
         ``(idx [count,k] int32, d2 [count,k] float64, n [count] int32)``; -1 / +inf beyond ``n = min(k, N)``.  Exact and independent of
         ``grid`` (:meth:`knn_grid`).  Serves all points, ``pidx`` and ``queries``; asynchronous on ``stream``."""
-        from . import knn as _knn
         k = _knn.check_k(k)
-        at, q = self._knn_queries(first, count)
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        at, q = self._rows(first, count)
+        st = self._stream(stream)
         ws = self.knn_grid(grid, k, st)
-        idx = torch.empty((count, k), dtype=torch.int32, device=self.device)
-        d2 = torch.empty((count, k), dtype=torch.float64, device=self.device)
-        n = torch.empty((count,), dtype=torch.int32, device=self.device)
-        if count == 0:                    # a no-op; an empty tensor has no address to pass
-            return idx, d2, n
-        tail = (k, _lib.ptr(idx), _lib.ptr(d2), _lib.ptr(n), _lib.ptr(ws), ws.numel(), ctypes.c_void_p(st.cuda_stream))
-        with torch.cuda.device(self.device):
-            if at:
-                _lib.check(self.lib.nesti_knn_at(_lib.ptr(self.cloud), self.n_points, _lib.ptr(q), count, *tail), "nesti_knn_at")
-            else:
-                _lib.check(self.lib.nesti_knn(_lib.ptr(self.cloud), self.n_points, _lib.ptr(q), count, ctypes.c_int(first), *tail), "nesti_knn")
-        return idx, d2, n
+        out = check_out(None, (((count, k), torch.int32), ((count, k), torch.float64), ((count,), torch.int32)), self.device)
+        if count:                         # 0 rows: a no-op; an empty tensor has no address to pass
+            self._call("nesti_knn", at, q, count, first, [k] + [_lib.ptr(t) for t in out] + [_lib.ptr(ws), ws.numel()], st, ball=False)
+        return out
 
-    def _fit_nbr(self, entry, first, count, ks, nbr, shapes, stream):
-        """One list-fit entry (``entry`` / ``entry + "_at"``) over ``nbr`` [count, K]: the outputs of ``shapes`` + radius + count."""
-        at, q = self._knn_queries(first, count)
+    def _fit_nbr(self, name, first, count, ks, grid, nbr, widths, stream):
+        """One list-fit entry over the rows' sorted neighbour lists -- ``nbr`` [count, K], or one search at K = max(ks): outputs of
+        ``widths`` + radius + count."""
+        ks = _knn.check_ks(ks)
+        st = self._stream(stream)
+        if nbr is None:
+            nbr = self.knn(first, count, ks[-1], grid=grid, stream=st)[0]
+        at, q = self._rows(first, count)
         S = len(ks)
         if nbr.dtype != torch.int32 or nbr.dim() != 2 or nbr.shape[0] != count or not nbr.is_contiguous() or nbr.device != self.device:
             raise ValueError("nbr: a contiguous int32 [count, K] tensor on %s" % self.device)
-        out = tuple(torch.empty((count, S, w), dtype=torch.float32, device=self.device) for w in shapes)
-        radius = torch.empty((count, S), dtype=torch.float32, device=self.device)
-        n = torch.empty((count, S), dtype=torch.int32, device=self.device)
-        if count == 0:                    # a no-op; an empty list has no address to pass
-            return out + (radius, n)
-        tail = (_lib.ptr(nbr), int(nbr.shape[1]), (ctypes.c_int32 * S)(*ks), S) + tuple(_lib.ptr(t) for t in out) + \
-               (_lib.ptr(radius), _lib.ptr(n), ctypes.c_void_p(stream.cuda_stream))
-        with torch.cuda.device(self.device):
-            if at:
-                _lib.check(getattr(self.lib, entry + "_at")(_lib.ptr(self.cloud), self.n_points, _lib.ptr(q), count, *tail), entry + "_at")
-            else:
-                _lib.check(getattr(self.lib, entry)(_lib.ptr(self.cloud), self.n_points, _lib.ptr(q), count, ctypes.c_int(first), *tail), entry)
-        return out + (radius, n)
+        out = check_out(None, tuple(((count, S, w), torch.float32) for w in widths) + (((count, S), torch.float32), ((count, S), torch.int32)),
+                        self.device)
+        if count:                         # 0 rows: a no-op; an empty list has no address to pass
+            self._call(name, at, q, count, first, [_lib.ptr(nbr), int(nbr.shape[1]), (ctypes.c_int32 * S)(*ks), S] + [_lib.ptr(t) for t in out],
+                       st, ball=False)
+        return out
 
     def pca_knn(self, first, count, ks, grid=None, nbr=None, stream=None):
         """Plane-fit normals of patch rows [first, first + count) over their nearest neighbours: scale s is the first ``ks[s]``
@@ -354,50 +332,28 @@ class CloudPatches:
         ``nbr`` [count,K] int32: the caller's own lists instead of a search (untrusted: a row ends at its first entry outside the
         cloud).  A row's bits are a pure function of (cloud, centre, ks): independent of batching, streams, ``grid`` and grid build.
         Serves all points, ``pidx`` and ``queries``; asynchronous on ``stream``."""
-        from . import knn as _knn
-        ks = _knn.check_ks(ks)
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        if nbr is None:
-            nbr = self.knn(first, count, ks[-1], grid=grid, stream=st)[0]
-        return self._fit_nbr("nesti_pca_normals_nbr", first, count, ks, nbr, (3, 3), st)
+        return self._fit_nbr("nesti_pca_normals_nbr", first, count, ks, grid, nbr, (3, 3), stream)
 
     def quadric_knn(self, first, count, ks, grid=None, nbr=None, stream=None):
         """Quadric-fit normals and principal curvatures of patch rows [first, first + count) over their nearest neighbours, as
         :meth:`pca_knn`: device tensors ``(normals [count,S,3] f32, curv [count,S,2] f32 (k_max, k_min; absolute units), plane
         [count,S,3] f32 (the bits of ``pca_knn``'s normals), radius [count,S] f32, n [count,S] int32)``."""
-        from . import knn as _knn
-        ks = _knn.check_ks(ks)
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        if nbr is None:
-            nbr = self.knn(first, count, ks[-1], grid=grid, stream=st)[0]
-        return self._fit_nbr("nesti_quadric_fit_nbr", first, count, ks, nbr, (3, 2, 3), st)
+        return self._fit_nbr("nesti_quadric_fit_nbr", first, count, ks, grid, nbr, (3, 2, 3), stream)
 
     def build_reference_order(self, first, count, picks, pick_offsets, want_idx=False, out=None, stream=None):
         """Patch tensors of rows [first, first + count) exactly as the reference's ``PointcloudPatchDataset.__getitem__`` builds
         them (``nesti_patches_query_ref``): balls in cKDTree's visiting order, over-full balls thinned by ``picks`` (uint16 device
         tensor, any 2-byte dtype) at ``pick_offsets`` [count * S] int64 (device; -1 = the ball holds <= P points) -- the table
         ``refsample.RefStream.picks`` replays from the ball sizes of :meth:`count_balls`."""
-        S, P = self.cfg.n_scales, self.cfg.num_point
         self._index_queries_only("build_reference_order")
-        if first < 0 or count < 0 or first + count > self.patch_count:
-            raise ValueError("patch rows [%d, %d) outside [0, %d)" % (first, first + count, self.patch_count))
+        at, q = self._rows(first, count)
         rank, order = self.ensure_tree_order()
-        qidx = self.pidx[first:first + count].contiguous() if self.pidx is not None else None
-        if out is None:
-            points = torch.empty((count, S * P, 3), dtype=torch.float32, device=self.device)
-            n_eff = torch.empty((count, S), dtype=torch.int32, device=self.device)
-        else:
-            points, n_eff = out
-        nbr = torch.empty((count, S * P), dtype=torch.int32, device=self.device) if want_idx else None
-        if pick_offsets.dtype != torch.int64 or pick_offsets.numel() < count * S or picks.element_size() != 2:
+        points, n_eff, nbr = self._patch_out(count, out, want_idx)
+        if pick_offsets.dtype != torch.int64 or pick_offsets.numel() < count * self.cfg.n_scales or picks.element_size() != 2:
             raise ValueError("picks: 2-byte elements, pick_offsets: int64 [count * S]")
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.nesti_patches_query_ref(
-                ctypes.byref(self._c), _lib.ptr(self.cloud), self.n_points, _lib.ptr(qidx), count, self._r, ctypes.c_int(first),
-                _lib.ptr(rank), _lib.ptr(order), _lib.ptr(picks) if picks.numel() else None, _lib.ptr(pick_offsets), _lib.ptr(points),
-                _lib.ptr(n_eff), _lib.ptr(nbr), _lib.ptr(self._ws), self._ws.numel(), ctypes.c_void_p(st.cuda_stream)),
-                "nesti_patches_query_ref")
+        self._call("nesti_patches_query_ref", at, q, count, first,
+                   [_lib.ptr(rank), _lib.ptr(order), _lib.ptr(picks) if picks.numel() else None, _lib.ptr(pick_offsets), _lib.ptr(points),
+                    _lib.ptr(n_eff), _lib.ptr(nbr)], self._stream(stream))
         if want_idx:
             return points, n_eff, nbr
         return points, n_eff

@@ -6,8 +6,7 @@ frame of the plane fit; the normal is the fitted surface's at the query and the 
 There is no CPU fallback."""
 import numpy as np
 
-from .config import NestiConfig
-from .pca import ORIENT_MODES, check_knn_args, check_scale, orient_rows
+from .pca import fit_cloud, prepare_cloud
 
 
 def mean_gauss(curv):
@@ -20,36 +19,16 @@ def quadric_cloud(cloud, scale=-1, orient=None, viewpoint=None, orient_k=8, knn=
     """``quadric_fit`` for a prepared ``provider.CloudPatches`` (all of its patch rows); synchronises.  ``knn``: neighbour counts
     instead of the cloud's radii (``scale`` then indexes them, and the dict gains ``radius``)."""
     import torch
-    from . import orient as _orient
-    ks = None
-    if knn is not None:
-        from .knn import check_ks
-        ks = check_ks(knn)
-    s = check_scale(scale, cloud.cfg.n_scales if ks is None else len(ks))
-    if orient not in ORIENT_MODES:
-        raise ValueError("orient must be None, 'mst' or 'viewpoint'")
-    with torch.cuda.device(cloud.device):
-        radius = None
-        if ks is None:
-            normals_all, curv_all, plane_all, n_ball = cloud.quadric(0, cloud.patch_count)
-        else:
-            normals_all, curv_all, plane_all, radius, n_ball = cloud.quadric_knn(0, cloud.patch_count, ks)
-        normals = normals_all[:, s, :].contiguous()
-        curv = curv_all[:, s, :].contiguous()
-        stats = None
-        if orient is not None and cloud.patch_count:
-            before = normals.clone()
-            stats = orient_rows(cloud, normals, s, orient, viewpoint, orient_k, radius=None if ks is None else max(cloud.r_abs))
+
+    def curvatures(out, s, before):
+        out["curv"] = out["curv_all"][:, s, :].contiguous()
+        if before is not None:
             # the flip rule: the pass changes sign bits only, and a row whose normal it turned has curvatures (-k_min, -k_max)
-            flipped = (before.view(torch.int32) != normals.view(torch.int32)).any(dim=1, keepdim=True)
-            curv = torch.where(flipped, -curv.flip(1), curv)
-        torch.cuda.current_stream(cloud.device).synchronize()
-    res = {"normals": normals.cpu().numpy(), "curv": curv.cpu().numpy(), "normals_all": normals_all.cpu().numpy(),
-           "curv_all": curv_all.cpu().numpy(), "plane_all": plane_all.cpu().numpy(), "n_ball": n_ball.cpu().numpy(),
-           "orient": None if orient is None else (_orient.stats_dict(stats) if stats is not None else dict.fromkeys(_orient.STAT_NAMES, 0))}
-    if radius is not None:
-        res["radius"] = radius.cpu().numpy()
-    return res
+            flipped = (before.view(torch.int32) != out["normals"].view(torch.int32)).any(dim=1, keepdim=True)
+            out["curv"] = torch.where(flipped, -out["curv"].flip(1), out["curv"])
+
+    return fit_cloud(cloud, cloud.quadric, cloud.quadric_knn, ("normals_all", "curv_all", "plane_all", "n_ball"), scale, orient, viewpoint,
+                     orient_k, knn, after=curvatures)
 
 
 def quadric_fit(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, viewpoint=None, orient_k=8, device="cuda:0", knn=None):
@@ -79,16 +58,4 @@ def quadric_fit(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, v
 
     Raises ``ValueError`` for a ``scale`` outside [-S, S), for ``pidx`` together with ``queries``, for a bad ``knn`` and for ``knn``
     together with ``cfg`` (whose radii would mean nothing)."""
-    ks, cfg = check_knn_args(knn, cfg)
-    check_scale(scale, cfg.n_scales if ks is None else len(ks))
-    if orient not in ORIENT_MODES:
-        raise ValueError("orient must be None, 'mst' or 'viewpoint'")
-    if pidx is not None and queries is not None:
-        raise ValueError("pidx and queries are mutually exclusive: a query is a cloud point (pidx) or a position (queries)")
-    if orient is not None:
-        from .orient import _check_args
-        _check_args(1.0, orient_k, viewpoint, orient)
-    from .provider import CloudPatches
-    # the k-NN fits never read the radius grid (the orientation pass builds its own): a cloud without extent is served too
-    cloud = CloudPatches(np.asarray(pts, dtype=np.float32), cfg, device=device, pidx=pidx, queries=queries, radius_grid=ks is None)
-    return quadric_cloud(cloud, scale, orient, viewpoint, orient_k, knn=ks)
+    return quadric_cloud(*prepare_cloud(pts, cfg, pidx, queries, scale, orient, viewpoint, orient_k, device, knn))

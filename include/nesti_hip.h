@@ -235,7 +235,9 @@ void nesti_model_destroy(nesti_model_t* m);
  *   changed        rechecked rows whose arg-max differs between the two gates,
  *   max_margin_err largest |(l_a - l_k)_f16 - (l_a - l_k)_f16x3| over the rechecked rows and all experts k, a = the f16
  *                  arg-max: the f16 gate's error on exactly the quantity tau guards,
- *   sum_sq_pair_err / pairs: the same errors squared and summed over all (rechecked row, k != a) pairs, and their count:
+ *   sum_sq_pair_err / pairs: the same errors squared and summed over all (rechecked row, k != a) pairs, and their count --
+ *                  exactly the pairs summed: a pair with a non-finite logit on either side measures nothing and enters neither
+ *                  max_margin_err nor the sum nor the count (a row with such a logit is always rechecked) --:
  *                  sqrt(sum / pairs) is the standard deviation sigma of the f16 pass's error on one logit difference (the
  *                  errors are rounding noise: zero-mean, independent of the margin); tau is chosen as a multiple of it,
  *   widened        rows re-decided by a widening pass, widen_events: widening passes that were not empty,
@@ -798,6 +800,54 @@ int nesti_debug_tower_ops(const nesti_config_t* cfg, int dtype, int tower, int b
 int nesti_debug_tower_step(const nesti_model_t* m, int tower, const nesti_debug_pass_t* pass, int op, const void* mups_dev, int batch,
                            const int32_t* point_index_dev, const int32_t* npoints_dev, int walk, void* ws_dev, size_t ws_bytes,
                            void* stream);
+
+/* ---- test hook: one launcher of the deciding kernels alone (tests/test_gpu_decisions.py; no reference counterpart) ------
+ * The two-stage gate, the conditioning guard, the gate's softmax and the routing helpers (csrc/kernels.h, csrc/pool.hip), each
+ * run on CALLER buffers: no model, the counter blocks (cstat, gstat, rstat: 8 x uint64 each) and the 512-byte fcounts block
+ * are the caller's too.  op names the launcher; the struct carries its arguments under the launcher's own names, the few
+ * launchers whose names differ say so below.  Forwards and nothing else; before any device call it refuses an unknown op, a
+ * null pointer the launcher dereferences, E outside 1 .. NESTI_MAX_EXPERTS and n_rounds above the 24 the fcounts block holds. */
+enum { NESTI_DECISION_GATE_FINISH = 0,     /* logits lstride B E probs? expert? counts? lists (with counts)                      */
+       NESTI_DECISION_GATE_FLAG = 1,       /* logits lstride B E tau widen probs? expert keep fcounts flag_list cap n_rounds cstat rstat? */
+       NESTI_DECISION_GATE_WIDEN = 2,      /* keep B E widen fcounts flag_list cap n_rounds cstat                                 */
+       NESTI_DECISION_GATE_RECHECK = 3,    /* logits (compact rows) lstride flag_list count_ptr cap E keep probs? expert cstat
+                                            * widen rstat? fcounts (with rstat)                                                   */
+       NESTI_DECISION_ROUND_COUNTS = 4,    /* counts n_lists cap n_rounds round_out                                               */
+       NESTI_DECISION_SWITCH_FINISH = 5,   /* logits lstride B thr (the threshold) probs? expert? counts? lists (with counts)     */
+       NESTI_DECISION_X8_GUARD_BEGIN = 6,  /* pass thr scale B gstat slot rstat?                                                  */
+       NESTI_DECISION_X8_GUARD_FLAG = 7,   /* lists (ONE list) count_ptr B (count_cap) normals slot glist gcount cap gstat        */
+       NESTI_DECISION_X8_GUARD_FIX = 8,    /* src sstride glist gcount cap normals gstat thr scale rstat?                         */
+       NESTI_DECISION_ROUTE = 9,           /* expert B E counts lists                                                             */
+       NESTI_DECISION_SCATTER3 = 10,       /* src sstride index? count_ptr? cap (count_cap) normals (the destination)             */
+       NESTI_DECISION_STAT_MAX_EXPORT = 11,/* word dst                                                                            */
+       NESTI_DECISION_STAT_MAX_IMPORT = 12,/* word src B (the number of floats)                                                   */
+       NESTI_DECISION_OPS = 13 };
+typedef struct {
+  const float* logits;
+  int lstride, B, E, n_lists, cap, n_rounds, pass, sstride;
+  float tau, widen, thr, scale;
+  float* probs;
+  int32_t* expert;
+  float* keep;
+  int32_t* fcounts;
+  int32_t* flag_list;
+  const int32_t* count_ptr;
+  int32_t* counts;
+  int32_t* lists;
+  int32_t* round_out;
+  uint64_t* cstat;
+  uint64_t* gstat;
+  uint64_t* rstat;
+  uint64_t* word;
+  float* slot;
+  float* normals;
+  const float* src;
+  const int32_t* index;
+  int32_t* glist;
+  int32_t* gcount;
+  float* dst;
+} nesti_debug_decision_t;
+int nesti_debug_decision_step(int op, const nesti_debug_decision_t* a, void* stream);
 
 /* The weight packer without a device (tests/test_pack.py): builds the graph and packs ONE layer (index `layer` of the model, as
  * nesti_debug_op_t::layer) on the host, with the very code nesti_model_create uploads from.  form: the packing of a launch form --

@@ -95,6 +95,20 @@ class CDebugPack(ctypes.Structure):
                 ("w_bytes", ctypes.c_int64), ("n_bias", ctypes.c_int64), ("tap", ctypes.c_int8 * 4 * 125)]
 
 
+class CDebugDecision(ctypes.Structure):
+    """Mirror of ``nesti_debug_decision_t``."""
+    _fields_ = [("logits", ctypes.c_void_p)] + \
+               [(n, ctypes.c_int) for n in ("lstride", "B", "E", "n_lists", "cap", "n_rounds", "pass_", "sstride")] + \
+               [(n, ctypes.c_float) for n in ("tau", "widen", "thr", "scale")] + \
+               [(n, ctypes.c_void_p) for n in ("probs", "expert", "keep", "fcounts", "flag_list", "count_ptr", "counts", "lists",
+                                               "round_out", "cstat", "gstat", "rstat", "word", "slot", "normals", "src", "index",
+                                               "glist", "gcount", "dst")]
+
+
+# NESTI_DECISION_*: op of nesti_debug_decision_step
+DECISION_OPS = ("gate_finish", "gate_flag", "gate_widen", "gate_recheck", "round_counts", "switch_finish", "x8_guard_begin",
+                "x8_guard_flag", "x8_guard_fix", "route", "scatter3", "stat_max_export", "stat_max_import")
+
 X8_GUARD_BAR, X8_GUARD_WIDEN, X8_GUARD_DEFAULT = 2.5e-6, 1.5, 0.25   # NESTI_X8_GUARD_* (include/nesti_hip.h)
 GATE_WIDEN = 1.5      # NESTI_GATE_WIDEN (include/nesti_hip.h)
 GATE_WIDEN_PASSES = 3  # NESTI_GATE_WIDEN_PASSES
@@ -191,6 +205,7 @@ SIGNATURES = {
                                    ctypes.POINTER(CDebugOp), _i, ctypes.POINTER(_i), _vp, _i, ctypes.POINTER(_i),
                                    ctypes.POINTER(_sz)]),
     "nesti_debug_tower_step": (_i, [_vp, _i, ctypes.POINTER(CDebugPass), _i, _vp, _i, _vp, _vp, _i, _vp, _sz, _vp]),
+    "nesti_debug_decision_step": (_i, [_i, ctypes.POINTER(CDebugDecision), _vp]),
     "nesti_debug_pack_layer": (_i, [_cfgp, ctypes.POINTER(CTensor), _i, _i, _i, _i, ctypes.POINTER(CDebugPack), _vp, _sz, _vp, _sz]),
     "nesti_write_text_f32": (_i, [ctypes.c_char_p, _vp, ctypes.c_int64, _i]),
     "nesti_write_text_i32": (_i, [ctypes.c_char_p, _vp, ctypes.c_int64]),

@@ -1005,4 +1005,65 @@ int nesti_debug_tower_step(const nesti_model_t* m, int tower, const nesti_debug_
   return run_op(rc, T, T.ops[op], ptr);
 }
 
+// ---- test hook: one launcher of the deciding kernels alone, on caller buffers (include/nesti_hip.h) --------------------------------
+int nesti_debug_decision_step(int op, const nesti_debug_decision_t* a, void* stream) {
+  const std::string who = "nesti_debug_decision_step: ";
+  if (!a) NESTI_FAIL(who + "null argument");
+  if (op < 0 || op >= NESTI_DECISION_OPS) NESTI_FAIL(who + "unknown op");
+  const hipStream_t st = (hipStream_t)stream;
+  auto u64 = [](uint64_t* p) { return reinterpret_cast<unsigned long long*>(p); };
+  const bool uses_E = op == NESTI_DECISION_GATE_FINISH || op == NESTI_DECISION_GATE_FLAG || op == NESTI_DECISION_GATE_WIDEN ||
+                      op == NESTI_DECISION_GATE_RECHECK || op == NESTI_DECISION_ROUTE;
+  if (uses_E && (a->E < 1 || a->E > NESTI_MAX_EXPERTS)) NESTI_FAIL(who + "E outside 1 .. NESTI_MAX_EXPERTS");
+  if (a->n_rounds > kMaxCascadeRounds) NESTI_FAIL(who + "n_rounds above kMaxCascadeRounds");
+#define NESTI_NEED(cond, what) if (!(cond)) NESTI_FAIL(who + "null pointer: " what)
+  switch (op) {
+    case NESTI_DECISION_GATE_FINISH:
+      NESTI_NEED(a->logits && (!a->counts || a->lists), "logits, lists");
+      return launch_gate_finish(a->logits, a->lstride, a->B, a->E, a->probs, a->expert, a->counts, a->lists, st);
+    case NESTI_DECISION_GATE_FLAG:
+      NESTI_NEED(a->logits && a->expert && a->keep && a->fcounts && a->flag_list && a->cstat, "logits, expert, keep, fcounts, flag_list, cstat");
+      return launch_gate_flag(a->logits, a->lstride, a->B, a->E, a->tau, a->widen, a->probs, a->expert, a->keep, a->fcounts, a->flag_list,
+                              a->cap, a->n_rounds, u64(a->cstat), u64(a->rstat), st);
+    case NESTI_DECISION_GATE_WIDEN:
+      NESTI_NEED(a->keep && a->fcounts && a->flag_list && a->cstat, "keep, fcounts, flag_list, cstat");
+      return launch_gate_widen(a->keep, a->B, a->E, a->widen, a->fcounts, a->flag_list, a->cap, a->n_rounds, u64(a->cstat), st);
+    case NESTI_DECISION_GATE_RECHECK:
+      NESTI_NEED(a->logits && a->flag_list && a->count_ptr && a->keep && a->expert && a->cstat && (!a->rstat || a->fcounts),
+                 "logits, flag_list, count_ptr, keep, expert, cstat, fcounts");
+      return launch_gate_recheck(a->logits, a->lstride, a->flag_list, a->count_ptr, a->cap, a->E, a->keep, a->probs, a->expert,
+                                 u64(a->cstat), a->fcounts, a->widen, u64(a->rstat), st);
+    case NESTI_DECISION_ROUND_COUNTS:
+      NESTI_NEED(a->counts && a->round_out, "counts, round_out");
+      return launch_round_counts(a->counts, a->n_lists, a->cap, a->n_rounds, a->round_out, st);
+    case NESTI_DECISION_SWITCH_FINISH:
+      NESTI_NEED(a->logits && (!a->counts || a->lists), "logits, lists");
+      return launch_switch_finish(a->logits, a->lstride, a->B, a->thr, a->probs, a->expert, a->counts, a->lists, st);
+    case NESTI_DECISION_X8_GUARD_BEGIN:
+      NESTI_NEED(a->gstat && a->slot, "gstat, slot");
+      return launch_x8_guard_begin(a->pass, a->thr, a->scale, a->B, u64(a->gstat), a->slot, u64(a->rstat), st);
+    case NESTI_DECISION_X8_GUARD_FLAG:
+      NESTI_NEED(a->lists && a->count_ptr && a->normals && a->slot && a->glist && a->gcount && a->gstat,
+                 "lists, count_ptr, normals, slot, glist, gcount, gstat");
+      return launch_x8_guard_flag(a->lists, a->count_ptr, a->B, a->normals, a->slot, a->glist, a->gcount, a->cap, u64(a->gstat), st);
+    case NESTI_DECISION_X8_GUARD_FIX:
+      NESTI_NEED(a->src && a->glist && a->gcount && a->normals && a->gstat, "src, glist, gcount, normals, gstat");
+      return launch_x8_guard_fix(a->src, a->sstride, a->glist, a->gcount, a->cap, a->normals, u64(a->gstat), a->thr, a->scale,
+                                 u64(a->rstat), st);
+    case NESTI_DECISION_ROUTE:
+      NESTI_NEED(a->expert && a->counts && a->lists, "expert, counts, lists");
+      return launch_route(a->expert, a->B, a->E, a->counts, a->lists, st);
+    case NESTI_DECISION_SCATTER3:
+      NESTI_NEED(a->src && a->normals, "src, normals");
+      return launch_scatter3(a->src, a->sstride, a->index, a->count_ptr, a->cap, a->normals, st);
+    case NESTI_DECISION_STAT_MAX_EXPORT:
+      NESTI_NEED(a->word && a->dst, "word, dst");
+      return launch_stat_max_export(u64(a->word), a->dst, st);
+    default:   // NESTI_DECISION_STAT_MAX_IMPORT
+      NESTI_NEED(a->word && a->src, "word, src");
+      return launch_stat_max_import(u64(a->word), a->src, a->B, st);
+  }
+#undef NESTI_NEED
+}
+
 }  // extern "C"

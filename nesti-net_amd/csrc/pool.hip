@@ -192,20 +192,21 @@ __global__ void gate_begin_kernel(int32_t* __restrict__ fcounts, const unsigned 
   reinterpret_cast<float*>(fcounts)[kTauEffOff] = rstat ? tau : fmaxf(tau, widen * m);
 }
 
-__device__ __forceinline__ float top2_margin(const float* l, int E, bool* has_nan) {
+__device__ __forceinline__ float top2_margin(const float* l, int E, bool* nonfinite) {
   float mx = -INFINITY, second = -INFINITY;
-  bool nan = false;
+  bool bad = false;
   for (int e = 0; e < E; ++e) {
-    nan |= !(l[e] == l[e]);
+    bad |= !(fabsf(l[e]) < INFINITY);     // NaN, +inf, -inf
     if (l[e] > mx) { second = mx; mx = l[e]; } else second = fmaxf(second, l[e]);
   }
-  *has_nan = nan;
+  *nonfinite = bad;
   return mx - second;
 }
 
 // Stage 1 (on the plain-f16 gate's logits): softmax + first-index arg-max like gate_finish_kernel; the logits are kept for
-// stage 2's error measurement and every row whose top-2 logit margin is below tau_eff -- or that holds a NaN logit (fmaxf and
-// the > comparisons above skip NaNs, so such a row could otherwise keep a large finite margin) -- is appended to flag_list.
+// stage 2's error measurement and every row whose top-2 logit margin is below tau_eff -- or that holds a logit that is not finite:
+// fmaxf and the > comparisons above skip NaNs, so a NaN row could otherwise keep a large finite margin; a +inf logit gives the
+// margin inf (never below tau_eff) and NaN probabilities, a -inf one hides an expert -- is appended to flag_list.
 __global__ void gate_flag_kernel(const float* __restrict__ logits, int lstride, int B, int E,
                                  float* __restrict__ probs, int32_t* __restrict__ expert, float* __restrict__ keep,
                                  int32_t* __restrict__ fcounts, int32_t* __restrict__ flag_list,
@@ -219,9 +220,9 @@ __global__ void gate_flag_kernel(const float* __restrict__ logits, int lstride, 
     keep[(size_t)b * NESTI_MAX_EXPERTS + e] = l[e];
     mx = fmaxf(mx, l[e]);
   }
-  bool has_nan;
-  const float margin = top2_margin(l, E, &has_nan);
-  const bool flag = has_nan || !(margin >= tau);   // a NaN margin (inf - inf) is rechecked too
+  bool nonfinite;
+  const float margin = top2_margin(l, E, &nonfinite);
+  const bool flag = nonfinite || !(margin >= tau);
   float sum = 0.f;
   for (int e = 0; e < E; ++e) { l[e] = expf(l[e] - mx); sum += l[e]; }
   int best = 0;
@@ -262,9 +263,9 @@ __global__ void gate_widen_kernel(const float* __restrict__ keep, int B, int E, 
   if (!(upper > lower)) return;
   float l[NESTI_MAX_EXPERTS];
   for (int e = 0; e < E; ++e) l[e] = keep[(size_t)b * NESTI_MAX_EXPERTS + e];
-  bool has_nan;
-  const float margin = top2_margin(l, E, &has_nan);
-  if (has_nan || !(margin >= lower && margin < upper)) return;    // NaN rows went through the first list
+  bool nonfinite;
+  const float margin = top2_margin(l, E, &nonfinite);
+  if (nonfinite || !(margin >= lower && margin < upper)) return;    // rows with a non-finite logit went through the first list
   const int pos = atomicAdd(&fcounts[kWidenCountOff], 1);
   flag_list[pos] = b;
   atomicAdd(&cstat[1], 1ull);
@@ -313,11 +314,14 @@ __global__ void gate_recheck_kernel(const float* __restrict__ logits, int lstrid
   for (int e = 0; e < E; ++e) { l[e] = logits[(size_t)j * lstride + e]; mx = fmaxf(mx, l[e]); }
   const int a = expert[b];                       // the f16 gate's arg-max
   float err = 0.f, sq = 0.f;
+  int pairs = 0;
   for (int e = 0; e < E; ++e) {
     const float d16 = keep[(size_t)b * NESTI_MAX_EXPERTS + a] - keep[(size_t)b * NESTI_MAX_EXPERTS + e];
     const float pe = fabsf(d16 - (l[a] - l[e]));      // the f16 pass's error on the logit difference (a, e); 0 for e == a
+    if (!(pe < INFINITY)) continue;                   // a non-finite logit on either side: the pair measures nothing
     err = fmaxf(err, pe);
     sq += pe * pe;
+    pairs += e != a;
   }
   float sum = 0.f;
   for (int e = 0; e < E; ++e) { l[e] = expf(l[e] - mx); sum += l[e]; }
@@ -330,13 +334,11 @@ __global__ void gate_recheck_kernel(const float* __restrict__ logits, int lstrid
   }
   expert[b] = best;
   if (best != a) atomicAdd(&cstat[2], 1ull);
-  if (err == err) {
-    atomicMax(&cstat[3], (unsigned long long)__float_as_uint(err));
-    atomicAdd(reinterpret_cast<double*>(&cstat[4]), (double)sq);
-    atomicAdd(&cstat[5], (unsigned long long)(E - 1));
-    // reproducible mode: the error that would have widened the call's margin is counted, not acted on
-    if (rstat && widen * err > reinterpret_cast<const float*>(fcounts)[kTauEffOff]) atomicAdd(&rstat[0], 1ull);
-  }
+  atomicMax(&cstat[3], (unsigned long long)__float_as_uint(err));
+  atomicAdd(reinterpret_cast<double*>(&cstat[4]), (double)sq);
+  atomicAdd(&cstat[5], (unsigned long long)pairs);
+  // reproducible mode: the error that would have widened the call's margin is counted, not acted on
+  if (rstat && widen * err > reinterpret_cast<const float*>(fcounts)[kTauEffOff]) atomicAdd(&rstat[0], 1ull);
 }
 
 // tf.where(noise_est < 0.015, n_est_small, n_est_large) as a routing decision (models/ms_sw_n_est.py:80-82)

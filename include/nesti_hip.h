@@ -124,7 +124,19 @@ int nesti_gmm_grid(int n, double variance, float* w, float* mu, float* sigma);
  * Rows whose n_eff is 0 (the zero-padded tail of the reference's last batch,
  * test_n_est_w_experts.py:134-140) are written as zeros instead of NaN.
  * out_dtype NESTI_BF16X3 / NESTI_F16X3: out_cstride is a multiple of 128 16-bit elements and channel c is stored as the planes
- * hi at 128*(c/64) + c%64 and lo 64 elements further (value = hi + lo). */
+ * hi at 128*(c/64) + c%64 and lo 64 elements further (value = hi + lo).
+ * INPUT DOMAIN.  Rows 0 .. min(n_eff, P-1) of a scale are read and must hold finite coordinates; rows beyond n_eff are never
+ * read and may hold anything (NaN and infinities included).  The posterior is evaluated per axis, q_i = e_i / sum_i e_i with
+ * e_i = expf(-((x - mu_i) / sigma)^2 / 2), so one axis of one point stays defined while at least one e_i is non-zero: the
+ * float32 expf is 0 below about -103.97 (-87.34 where subnormal results are flushed), i.e. once the NEAREST centre is further
+ * than sigma sqrt(2 x 87.34) = 13.2 sigma away.  With the outermost centre at 1 - 1/n that is
+ *     8^3 grid, variance 0.0156 (sigma 0.125):  |x| > 0.875 + 13.2 x 0.125 = 2.52   (2.68 with subnormals)
+ *     3^3 grid, variance 0.111  (sigma 0.333):  |x| > 0.667 + 13.2 x 0.333 = 5.07   (5.47 with subnormals)
+ * The outputs are finite, and within the bound tests/_mups_fixture.py derives, for every coordinate in [-2, 2] on both grids
+ * (the `outside` case of tests/test_gpu_mups_cases.py); the transcription of the reference's three-axis form in float32
+ * (oracle/mups_ref.mups_literal) already gives NaN at the corners of that cube on the 8^3 grid.  The product path stays far inside:
+ * the ball query keeps a patch coordinate (p - c) / r at norm <= 1 (up to its float32 rounding).  Beyond the figures above an
+ * axis is 0 / 0 and the channels of that (row, scale) are not finite (this file is built without NaN semantics: unspecified). */
 int nesti_mups_forward(const nesti_config_t* cfg, const float* points_dev,
                        const int32_t* n_eff_dev, int B, void* out_dev, int out_dtype,
                        int out_cstride, void* stream);
@@ -358,7 +370,10 @@ int nesti_model_mups_rows(const nesti_model_t* m);    /* rows per point of the i
                                                        * or 64 (3^3 grid: row 16i+4j+k of a 4^3 index space, rows with
                                                        * a coordinate of 3 are zero) */
 /* MuPS (utils/tf_util.py:655-753 + models/experts_n_est.py:66-76) of a batch in the layout and dtype
- * nesti_gate_forward / nesti_experts_forward read: mups_out_dev is [B, nesti_model_mups_rows, nesti_model_mups_cstride]. */
+ * nesti_gate_forward / nesti_experts_forward read: mups_out_dev is [B, nesti_model_mups_rows, nesti_model_mups_cstride].
+ * Every element of it is written (pad channels and, on the 3^3 grid, the dead rows as zeros).  Input domain: as
+ * nesti_mups_forward -- finite coordinates in the rows up to n_eff, |x| <= 2 tested, 0 / 0 on an axis from |x| > 2.52 (8^3)
+ * or 5.07 (3^3); nesti_forward and the call of a model take caller-supplied points under the same domain. */
 int nesti_model_mups(const nesti_model_t* m, const float* points_dev, const int32_t* n_eff_dev, int B,
                      void* mups_out_dev, void* stream);
 

@@ -139,16 +139,17 @@ __device__ __forceinline__ void zero_pad_row(void* out, size_t row_off, int pad0
 }
 
 // Turn raw statistics into the 20 channels of one Gaussian, before L2 normalisation.
-// Channel order: utils/tf_util.py:710-719,744-747.
+// Channel order: utils/tf_util.py:710-719,744-747.  centred: s.sq holds sum (Q - w) over the nrows rows (mups3_kernel), not
+// sum Q (the 8^3 kernels), so nrows w is not subtracted again.
 __device__ __forceinline__ void finish(const Stats1& s, int nrows, bool has_masked, float m_f,
-                                       float w, float (&v)[20]) {
+                                       float w, bool centred, float (&v)[20]) {
   const float rsw = 1.0f / sqrtf(w);           // 1/sqrt(w)        :709,714
   const float rs2w = 1.0f / sqrtf(2.0f * w);   // 1/sqrt(2w)       :718
   // Masked rows (index > n_eff) contribute exactly 0 to every max/min/sum (:697,:702).
   float pmax = (s.mq - w);
   if (has_masked) pmax = fmaxf(pmax, 0.f);
   v[0] = pmax * rsw;
-  v[1] = (s.sq - (float)nrows * w) * rsw;
+  v[1] = (centred ? s.sq : s.sq - (float)nrows * w) * rsw;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     float a = s.mu_max[c], b = s.mu_min[c], d = s.sg_max[c], e = s.sg_min[c];
@@ -257,8 +258,8 @@ __device__ __forceinline__ void mups_one_scale(MupsShared& sh, Coord coord, int 
 
   float v0[20], v1[20];
   const float m_f = (float)m;                    // utils/tf_util.py:722
-  finish(pick(acc, 0), nrows, has_masked, m_f, w, v0);
-  finish(pick(acc, 1), nrows, has_masked, m_f, w, v1);
+  finish(pick(acc, 0), nrows, has_masked, m_f, w, /*centred=*/false, v0);
+  finish(pick(acc, 1), nrows, has_masked, m_f, w, /*centred=*/false, v1);
 
   // L2 normalisation over the 512 Gaussians, per channel (utils/tf_util.py:738-740)
   float part[20];
@@ -403,7 +404,9 @@ __global__ __launch_bounds__(64) void mups3_kernel(const float* __restrict__ poi
           const float4 X = stage[nl][gi], Y = stage[nl][3 + gj], Z = stage[nl][6 + gk];
           const float Q = X.x * (Y.x * Z.x);
           const float d[3] = {X.y, Y.y, Z.y}, e[3] = {X.z, Y.z, Z.z};
-          st.sq += Q;
+          // sum (Q - w), as utils/tf_util.py:709-711 forms it: on this grid Q is O(1/27) to O(1), and sum Q - nrows w cancels
+          // (a point set spread evenly over the cube has sum Q ~ nrows w) with the error of a sum of magnitude nrows / 27
+          st.sq += Q - w;
           st.mq = fmaxf(st.mq, Q);
 #pragma unroll
           for (int c = 0; c < 3; ++c) {
@@ -414,7 +417,7 @@ __global__ __launch_bounds__(64) void mups3_kernel(const float* __restrict__ poi
         }
       }
     }
-    if (own) finish(st, nrows, has_masked, (float)m, w, v);
+    if (own) finish(st, nrows, has_masked, (float)m, w, /*centred=*/true, v);
     else {
 #pragma unroll
       for (int c = 0; c < 20; ++c) v[c] = 0.f;

@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from .config import ARCH_MULTI, ARCH_SINGLE, CASCADE_DTYPES, DTYPES, NestiConfig
+from .provider import check_out
 
 _TORCH_DT = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16,
              "bf16x3": torch.bfloat16, "f16x3": torch.float16,   # pair modes: 16-bit elements, two planes [hi | lo] per 64-channel group
@@ -36,12 +37,13 @@ def get_3d_grid_gmm(subdivisions=(8, 8, 8), variance=0.0156):
     return w, mu, sg
 
 
-def mups_forward(cfg: NestiConfig, points, n_eff, out_dtype="f32", out_cstride=None, stream=None):
+def mups_forward(cfg: NestiConfig, points, n_eff, out_dtype="f32", out_cstride=None, stream=None, out=None):
     """``get_3dmfv_n_est`` per scale + MuPS assembly (``utils/tf_util.py:655-753``,
     ``models/experts_n_est.py:66-76``).
 
     points [B, S*P, 3] float32 cuda, n_eff [B, S] (any integer/float dtype, like the
-    uint16 placeholder ``models/experts_n_est.py:35``) -> [B, R, R, R, cstride]."""
+    uint16 placeholder ``models/experts_n_est.py:35``) -> [B, R, R, R, cstride].  ``out``: the caller's own tensor of that shape
+    (contiguous, of ``out_dtype``'s element type, on the points' device) instead of a fresh one; every element of it is written."""
     lib = _lib.load()
     if not points.is_cuda:
         raise _lib.NestiError("mups_forward needs CUDA/HIP tensors; there is no CPU path")
@@ -54,7 +56,7 @@ def mups_forward(cfg: NestiConfig, points, n_eff, out_dtype="f32", out_cstride=N
     if tuple(n_eff_i.shape) != (B, S):
         raise ValueError("n_eff must be [B, %d]" % S)
     cs = out_cstride or 20 * S
-    out = torch.empty((B, R, R, R, cs), dtype=_TORCH_DT[out_dtype], device=points.device)
+    out, = check_out(None if out is None else (out,), (((B, R, R, R, cs), _TORCH_DT[out_dtype]),), points.device, "[B, R, R, R, cstride] MuPS tensor")
     c = cfg.to_c()
     st = stream if stream is not None else torch.cuda.current_stream(points.device)
     with torch.cuda.device(points.device):
@@ -234,9 +236,10 @@ class NestiNet:
         return ctypes.c_void_p(s.cuda_stream)
 
     # -- pieces (tests and the reference-shaped API) ---------------------------------------
-    def mups(self, points, n_eff, stream=None):
+    def mups(self, points, n_eff, stream=None, out=None):
         """MuPS in the layout / dtype the towers read (``nesti_model_mups``): [B, Ri, Ri, Ri, cstride] with
-        Ri = 8, or Ri = 4 for the 3^3 grid (the 27 voxels sit at [:, :3, :3, :3], the rest is zero)."""
+        Ri = 8, or Ri = 4 for the 3^3 grid (the 27 voxels sit at [:, :3, :3, :3], the rest is zero).  ``out``: the caller's own
+        tensor of that shape (contiguous, the model's element type, on its device); every element of it is written."""
         B = points.shape[0]
         S, P = self.cfg.n_scales, self.cfg.num_point
         if tuple(points.shape) != (B, S * P, 3):
@@ -244,7 +247,8 @@ class NestiNet:
         points = points.contiguous().float()
         n_eff_i = n_eff.to(device=points.device, dtype=torch.int32).contiguous().view(B, S)
         Ri = round(self.lib.nesti_model_mups_rows(self._handle) ** (1.0 / 3.0))
-        out = torch.empty((B, Ri, Ri, Ri, self.mups_cstride), dtype=_TORCH_DT[self.dtype], device=self.device)
+        out, = check_out(None if out is None else (out,), (((B, Ri, Ri, Ri, self.mups_cstride), _TORCH_DT[self.dtype]),), self.device,
+                         "[B, Ri, Ri, Ri, cstride] MuPS tensor")
         with torch.cuda.device(self.device):
             _lib.check(self.lib.nesti_model_mups(self._handle, _lib.ptr(points), _lib.ptr(n_eff_i), B, _lib.ptr(out),
                                                  self._stream(stream)), "nesti_model_mups")

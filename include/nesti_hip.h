@@ -34,6 +34,9 @@ extern "C" {
 
 #define NESTI_MAX_SCALES 4
 #define NESTI_KNN_MAX_K 256   /* the largest K of nesti_knn and of a neighbour list (nesti_*_nbr) */
+#define NESTI_HOUGH_MAX_T 4096   /* nesti_hough_normals_nbr: the most triplets per row and scale, */
+#define NESTI_HOUGH_MAX_BINS 16  /* ... bins per axis of the accumulator */
+#define NESTI_HOUGH_MAX_ROT 8    /* ... and rotations of it */
 #define NESTI_MAX_EXPERTS 8
 #define NESTI_MUPS_CH 20 /* channels per scale: utils/tf_util.py:711-720 */
 
@@ -629,6 +632,59 @@ int nesti_quadric_fit_nbr(const float* cloud_dev, int N, const int32_t* query_id
 int nesti_quadric_fit_nbr_at(const float* cloud_dev, int N, const float* query_xyz_dev, int M, const int32_t* nbr_dev, int K,
                              const int32_t* ks, int S, float* normals_out_dev, float* curv_out_dev, float* plane_out_dev,
                              float* radius_out_dev, int32_t* count_out_dev, void* stream);
+
+/* ---- Hough-transform normals over neighbour lists (hough.hip; DESIGN.md 2 "Hough-transform normals") ------------------------------
+ * The sharp-feature estimator after Boulch and Marlet (SGP 2012): planes through hashed triplets of a neighbourhood vote for their
+ * normal in an accumulator over the hemisphere; the fullest bin names the normal.  Where the plane fit and the quadric fit average
+ * across a crease, the vote picks one of its faces.  The conventions are the library's own (no parity with the authors' code): fp64
+ * throughout, every operation rounded on its own, only + - x / sqrt, comparisons and integer arithmetic -- a restatement in plain IEEE
+ * arithmetic predicts every output bit.  No model, no weights, and no ball variant: the estimator exists over lists only.
+ *
+ * Centres, nbr_dev [M, K], ks [S], the valid prefix, n_s = min(ks[s], valid prefix), d = (double)p - (double)c and r2_s are exactly as
+ * for nesti_pca_normals_nbr: the list is untrusted, the prefix ends at the first entry outside [0, N), and a non-finite centre has an
+ * empty prefix.  T triplets, 1 .. NESTI_HOUGH_MAX_T; B bins per axis, 2 .. NESTI_HOUGH_MAX_BINS; R rotations, 1 ..
+ * NESTI_HOUGH_MAX_ROT; rot [R, 9] fp64 row-major on the HOST; seed; query_row0 (both entries: the key row of row i is query_row0 + i).
+ * Per row i with key row q = query_row0 + i, per scale s with n = n_s and slots d_0 .. d_{n-1}:
+ *  1 TRIPLET t = 0 .. T-1.  h_c = the subsample hash (splitmix64 finaliser) of (seed, q, 0, 3 t + c) for c = 0, 1, 2 -- the
+ *    scale argument is 0 on purpose: scale s of ks equals the single scale of a run with ks = {ks[s]}.  Indices from 64-bit products:
+ *      i0 = (h0 n) >> 32;   j = (h1 (n - 1)) >> 32, i1 = j + (j >= i0);   lo, hi = min, max(i0, i1);
+ *      j = (h2 (n - 2)) >> 32, j += (j >= lo), i2 = j + (j >= hi).          The three are distinct for n >= 3.
+ *  2 PLANE.  e1 = d_i1 - d_i0, e2 = d_i2 - d_i0; v = e1 x e2, each component two products and one difference;
+ *    l1 = (e1x^2 + e1y^2) + e1z^2, l2 and qq (the same sum for v) likewise.  The triplet is VALID iff qq > 2^-20 (l1 l2): false for NaN,
+ *    for coincident points and for near-collinear ones (sine below 2^-10).  u = v / sqrt(qq), three divisions.
+ *  3 VOTE, for each rotation rho.  w_k = (rot[rho][3k] u_x + rot[rho][3k+1] u_y) + rot[rho][3k+2] u_z; sigma = -1 if the first non-zero
+ *    of (w_z, w_y, w_x) is negative, else +1; w <- sigma w; m = (|w_x| + |w_y|) + w_z, a = w_x / m, b = w_y / m (the hemi-octahedral
+ *    map of the upper hemisphere onto a square); bi = clamp((int)floor(((a + b) + 1) (B / 2.0)), 0, B - 1), bj the same with a - b;
+ *    bin = bi B + bj; count[rho][bin] += 1, an integer.
+ *  4 WINNER.  Per rho the bin with the largest count, among equals the smaller bin; rho* = the rotation whose winner has the largest
+ *    count, among equals the smaller rho.  win = that count; valid = the number of valid triplets.
+ *  5 NORMAL.  Over the valid triplets whose bin under rho* is the winner, the sum of sigma_t u_t (sigma_t: the sign of step 3 under
+ *    rho*; u_t: the unrotated vector).  Lane l of a 64-lane wave adds its triplets t = l, l + 64, ... in ascending order into three fp64
+ *    partial sums; the lanes meet in an xor-butterfly (offsets 32, 16, ..., 1).  nn = (X^2 + Y^2) + Z^2; if nn > 0 and finite the
+ *    normal is (X, Y, Z) / sqrt(nn), rounded to f32 once, then signed on the f32 values so that the first non-zero of (n_z, n_y, n_x)
+ *    is positive; zeros are +0.
+ *  6 OUTPUTS (device; any may be NULL):
+ *      normals_out_dev [M,S,3] f32    the normal of step 5
+ *      conf_out_dev    [M,S]   f32    (float)((double)win / (double)valid)
+ *      votes_out_dev   [M,S,2] int32  (win, valid)
+ *      radius_out_dev  [M,S]   f32    (float)sqrt(r2_s), as the other list entries write it
+ *      count_out_dev   [M,S]   int32  n_s, likewise
+ *  7 SENTINEL.  n < 3, valid == 0 or a failed step 5 gives normal 0 0 0, confidence 0 and votes (0, valid); radius and count are still
+ *    written.  No output is NaN or infinite for finite input.
+ * DETERMINISM: no floating-point atomics (the votes are integer additions).  A row's bits are a pure function of (cloud, centre, list
+ * prefix, T, B, R, rot, seed, key row): independent of batching, of streams and of the grid.
+ * Argument errors -- those of nesti_pca_normals_nbr; T, B or R out of range; null rot; a rotation with a non-finite entry or with
+ * max |rot rot^T - I| > 1e-6; query_row0 < 0 (both entries) -- are reported before any device call; M = 0 is a no-op.  Each call
+ * enqueues one kernel on `stream`, neither synchronises nor reads anything back, and can be captured into a graph.  Under
+ * nesti_profile_enable the launch is booked in the patches category, like the other list fits. */
+int nesti_hough_normals_nbr(const float* cloud_dev, int N, const int32_t* query_idx_dev, int M, int query_row0, const int32_t* nbr_dev,
+                            int K, const int32_t* ks, int S, int T, int B, int R, const double* rot, uint64_t seed,
+                            float* normals_out_dev, float* conf_out_dev, int32_t* votes_out_dev, float* radius_out_dev,
+                            int32_t* count_out_dev, void* stream);
+int nesti_hough_normals_nbr_at(const float* cloud_dev, int N, const float* query_xyz_dev, int M, int query_row0, const int32_t* nbr_dev,
+                               int K, const int32_t* ks, int S, int T, int B, int R, const double* rot, uint64_t seed,
+                               float* normals_out_dev, float* conf_out_dev, int32_t* votes_out_dev, float* radius_out_dev,
+                               int32_t* count_out_dev, void* stream);
 
 /* ---- depth images in, normal images out (depth.hip; DESIGN.md 2 "Depth images") --------------------------------------------------
  * The two ends of the reference's Kinect route: MATLAB/ScanNet_depth2xyz.m (depth + intrinsics + pose -> cloud) before

@@ -116,6 +116,7 @@ ORIENT_MST, ORIENT_VIEWPOINT = 0, 1   # NESTI_ORIENT_*
 DEPTH_U16, DEPTH_F32 = 0, 1           # NESTI_DEPTH_*
 DEPTH_MAX_PIXELS = 1 << 26
 KNN_MAX_K = 256                       # NESTI_KNN_MAX_K
+HOUGH_MAX_T, HOUGH_MAX_BINS, HOUGH_MAX_ROT = 4096, 16, 8   # NESTI_HOUGH_MAX_*
 
 
 class NestiError(RuntimeError):
@@ -194,6 +195,10 @@ SIGNATURES = {
     "nesti_pca_normals_nbr_at": (_i, [_vp, _i, _vp, _i, _vp, _i, ctypes.POINTER(ctypes.c_int32), _i, _vp, _vp, _vp, _vp, _vp]),
     "nesti_quadric_fit_nbr": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, ctypes.POINTER(ctypes.c_int32), _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nesti_quadric_fit_nbr_at": (_i, [_vp, _i, _vp, _i, _vp, _i, ctypes.POINTER(ctypes.c_int32), _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "nesti_hough_normals_nbr": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, ctypes.POINTER(ctypes.c_int32), _i, _i, _i, _i,
+                                     ctypes.POINTER(ctypes.c_double), _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "nesti_hough_normals_nbr_at": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, ctypes.POINTER(ctypes.c_int32), _i, _i, _i, _i,
+                                        ctypes.POINTER(ctypes.c_double), _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nesti_depth_workspace_bytes": (_sz, [_i, _i]),
     "nesti_depth_to_cloud": (_i, [_vp, _i, _i, _i, ctypes.POINTER(CCamera), _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "nesti_image_scatter": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),

@@ -12,7 +12,9 @@ checkpoint ships with the reference).  ``--estimator pca`` needs none of them: t
 ``<shape>.normals`` (one scale), ``<shape>.pca_eig`` and ``<shape>.pca_count`` (every scale); nor does ``--estimator quadric``: the
 quadric-fit normals and principal curvatures of :mod:`.quadric`, written as ``<shape>.normals`` and ``<shape>.curv`` (one scale),
 ``<shape>.quadric_curv`` and ``<shape>.quadric_count`` (every scale).  ``--knn K[,K...]`` fits either of the two over the K nearest
-neighbours instead of balls and adds ``<shape>.knn_radius``."""
+neighbours instead of balls and adds ``<shape>.knn_radius``.  ``--estimator hough --knn K[,K...]`` is the Hough-transform estimator of
+:mod:`.hough`, which exists over neighbour lists only: ``<shape>.normals`` (one scale), ``<shape>.hough_conf``, ``<shape>.hough_votes`` and
+``<shape>.hough_count`` (every scale) and ``<shape>.knn_radius``."""
 import argparse
 import ctypes
 import os
@@ -21,6 +23,7 @@ import sys
 import torch
 
 from . import pca as _pca
+from . import hough as _hough
 from . import quadric as _quadric
 from . import textio
 from . import weights as wts
@@ -102,7 +105,7 @@ def build_parser():
     p.add_argument("--orient_k", type=int, default=8, help="--orient mst: neighbours per point, 1 .. 16 [default: 8]")
     p.add_argument("--viewpoint", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"),
                    help="--orient viewpoint (required) / --orient mst (optional): the sensor position in the cloud's coordinates")
-    p.add_argument("--estimator", default="net", choices=["net", "pca", "quadric"],
+    p.add_argument("--estimator", default="net", choices=["net", "pca", "quadric", "hough"],
                    help="net (default): Nesti-Net, from the trained model in --results_path.  pca: the classical plane fit at every patch "
                         "radius of --model's configuration (DESIGN.md 2 'Plane-fit normals'); no model.nstw and no --synthetic_weights "
                         "are needed or read.  Writes <shape>.normals (the scale --pca_scale), <shape>.pca_eig (M rows of 3 S "
@@ -115,13 +118,29 @@ def build_parser():
                         "--quadric_scale), <shape>.curv (M rows k_max k_min at that scale, in 1 / length: the two columns the "
                         "reference's dataset reads; positive where the surface bends toward the written normal), <shape>.quadric_curv "
                         "(M rows of 2 S values, unoriented) and <shape>.quadric_count (M rows of S ball sizes); a fit that fails (fewer "
-                        "than 6 points in the ball, or a singular system) is written as 0 0 0 and 0 0")
+                        "than 6 points in the ball, or a singular system) is written as 0 0 0 and 0 0.  "
+                        "hough: the sharp-feature estimator after Boulch and Marlet (DESIGN.md 2 'Hough-transform normals'), under the "
+                        "same conditions; it exists over neighbour lists only and requires --knn.  Writes <shape>.normals (the scale "
+                        "--hough_scale), <shape>.hough_conf (M rows of S confidences: the winning bin's share of the valid triplets), "
+                        "<shape>.hough_votes (M rows of 2 S integers: winning votes and valid triplets per scale), <shape>.hough_count "
+                        "(M rows of S neighbour counts) and <shape>.knn_radius; a row with fewer than 3 neighbours or only degenerate "
+                        "triplets is written as 0 0 0 with confidence 0")
     p.add_argument("--pca_scale", type=int, default=-1,
                    help="--estimator pca: the scale whose normals go to <shape>.normals, an index into the patch radii; negative "
                         "counts from the end [default: -1, the largest]")
     p.add_argument("--quadric_scale", type=int, default=-1,
                    help="--estimator quadric: the scale whose normals and curvatures go to <shape>.normals and <shape>.curv, an index "
                         "into the patch radii; negative counts from the end [default: -1, the largest]")
+    p.add_argument("--hough_scale", type=int, default=-1,
+                   help="--estimator hough: the scale whose normals go to <shape>.normals, an index into --knn; negative counts from "
+                        "the end [default: -1, the largest]")
+    p.add_argument("--hough_triplets", type=int, default=_hough.DEFAULT_TRIPLETS,
+                   help="--estimator hough: planes drawn per row and scale, 1 .. 4096 [default: %d]" % _hough.DEFAULT_TRIPLETS)
+    p.add_argument("--hough_bins", type=int, default=_hough.DEFAULT_BINS,
+                   help="--estimator hough: bins per axis of the accumulator, 2 .. 16 [default: %d]" % _hough.DEFAULT_BINS)
+    p.add_argument("--hough_rotations", type=int, default=_hough.DEFAULT_ROTATIONS,
+                   help="--estimator hough: rotated copies of the accumulator, 1 .. 8 [default: %d]" % _hough.DEFAULT_ROTATIONS)
+    p.add_argument("--hough_seed", type=int, default=0, help="--estimator hough: the seed of the triplet hash [default: 0]")
     p.add_argument("--knn", default=None, metavar="K[,K...]",
                    help="--estimator pca / quadric: fit over the K nearest neighbours of every query instead of balls (DESIGN.md 2 "
                         "'k-nearest neighbourhoods'): one neighbour count per scale, at most 4, ascending, each in 1 .. 256.  The files "
@@ -216,6 +235,16 @@ FITS = {
         "files": ((".normals", textio.write_f32, "normals"), (".curv", textio.write_f32, "curv"),
                   (".quadric_curv", textio.write_f32, "curv_all"), (".quadric_count", textio.write_i32_rows, "n_ball")),
         "saved": "saved normals, curvatures and ball sizes for "},
+    # over neighbour lists only (--knn is required): ``params`` = (keyword of the fit, flag) pairs passed on from the command line
+    "hough": {
+        "fit": _hough.hough_cloud, "noun": "Hough transform", "scale_flag": "hough_scale",
+        "params": (("triplets", "hough_triplets"), ("bins", "hough_bins"), ("rotations", "hough_rotations"), ("seed", "hough_seed")),
+        "missing": lambda res, scale, ks: (res["normals_all"][:, scale] == 0).all(axis=1).sum(),
+        "no_fit": (None, "without a fit (fewer than 3 neighbours or only degenerate triplets: written as 0 0 0)"),
+        "subsamples": "the Hough transform draws its triplets by hash over the whole neighbourhood and subsamples no patch",
+        "files": ((".normals", textio.write_f32, "normals"), (".hough_conf", textio.write_f32, "conf"),
+                  (".hough_votes", textio.write_i32_rows, "votes"), (".hough_count", textio.write_i32_rows, "n_ball")),
+        "saved": "saved normals, confidences, votes and neighbour counts for "},
 }
 
 
@@ -243,7 +272,9 @@ def run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None):
                                      device="cuda:%d" % FLAGS.gpu, query_positions=bool(FLAGS.query_positions))
     for ind, name in enumerate(dataset.shape_names):
         cloud = dataset.get_shape(ind)
-        res = fit["fit"](cloud, scale, None if FLAGS.orient == "0" else FLAGS.orient, FLAGS.viewpoint, FLAGS.orient_k, knn=ks)
+        params = {kw: getattr(FLAGS, flag) for kw, flag in fit.get("params", ())}
+        res = fit["fit"](cloud, scale=scale, orient=None if FLAGS.orient == "0" else FLAGS.orient, viewpoint=FLAGS.viewpoint,
+                         orient_k=FLAGS.orient_k, knn=ks, **params)
         missing = int(fit["missing"](res, scale, ks))
         if ks is None:
             printout(fit_line(FLAGS.estimator, name, cloud.patch_count, scale, cfg.n_scales, missing, radius=cloud.r_abs[scale]))
@@ -264,6 +295,9 @@ def main(argv=None):
     for est, fit in FITS.items():
         if getattr(FLAGS, fit["scale_flag"]) != -1 and FLAGS.estimator != est:
             parser.error("--%s belongs to --estimator %s" % (fit["scale_flag"], est))
+        for _, flag in fit.get("params", ()):
+            if getattr(FLAGS, flag) != parser.get_default(flag) and FLAGS.estimator != est:
+                parser.error("--%s belongs to --estimator %s" % (flag, est))
     ks = None
     if FLAGS.knn is not None:
         if FLAGS.estimator == "net":
@@ -274,12 +308,19 @@ def main(argv=None):
         except ValueError as e:
             parser.error("--knn %s: %s" % (FLAGS.knn, e))
     fit = FITS.get(FLAGS.estimator)
+    if FLAGS.estimator == "hough":
+        if ks is None:
+            parser.error("--estimator hough needs --knn K[,K...]: the Hough transform exists over neighbour lists only")
+        try:
+            _hough.check_params(FLAGS.hough_triplets, FLAGS.hough_bins, FLAGS.hough_rotations, FLAGS.hough_seed)
+        except ValueError as e:
+            parser.error("--estimator hough: %s" % e)
     if fit:
         for given, flag, why in ((FLAGS.depth_images, "--depth_images 1", "depth frames belong to the network path (--estimator net)"),
                                  (FLAGS.reproducible, "--reproducible 1",
                                   "it freezes the network's thresholds (--estimator net); the %s has none" % fit["noun"]),
                                  (FLAGS.subsample != "hash", "--subsample %s" % FLAGS.subsample,
-                                  "the %s uses the full ball and subsamples nothing" % fit["noun"])):
+                                  fit.get("subsamples", "the %s uses the full ball and subsamples nothing" % fit["noun"]))):
             if given:
                 parser.error("--estimator %s does not take %s: %s" % (FLAGS.estimator, flag, why))
     if FLAGS.query_positions and FLAGS.sparse_patches:

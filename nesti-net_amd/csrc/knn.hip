@@ -54,29 +54,14 @@
 #pragma clang fp contract(off)
 
 #include "pca_dev.h"
+#include "nbr_dev.h"       // the list's parameter block, prefix and walk (shared with hough.hip); knn_d2, wave_lds_fence
 #include "quadric_dev.h"
 
 namespace nesti {
 namespace {
 
 constexpr int kKnnCap = 1024;                               // pairs per wave
-constexpr int kNbrTrips = NESTI_KNN_MAX_K / kWave;          // slots per lane of a neighbour list
-static_assert(NESTI_KNN_MAX_K % kWave == 0 && NESTI_KNN_MAX_K + kWave <= kKnnCap, "a cut leaves room for the next trip");
-
-// (dx dx + dy dy) + dz dz in fp64, each operation rounded on its own (contraction is off in this file)
-__device__ __forceinline__ double knn_d2(double dx, double dy, double dz) {
-  const double s = dx * dx + dy * dy;
-  return s + dz * dz;
-}
-
-// the lanes of one wave see each other's LDS writes after this; waves of a workgroup run different queries and never meet
-__device__ __forceinline__ void wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+static_assert(NESTI_KNN_MAX_K + kWave <= kKnnCap, "a cut leaves room for the next trip");
 
 struct KnnParams {
   PatchParams p;                      // cloud, sorted, start, header, query_idx / query_xyz, M, N, row0
@@ -240,49 +225,7 @@ __global__ __launch_bounds__(kThreads) void knn_kernel(const KnnParams kp) {
 
 // ---- the fits over neighbour lists --------------------------------------------------------------------------------------------------
 
-struct NbrParams {
-  PatchParams p;                      // cloud, query_idx / query_xyz, M, N, row0 (no grid)
-  const int32_t* nbr;                 // [M, K]
-  int K;
-  int ks[NESTI_MAX_SCALES];           // ascending, 1 <= ks[s] <= K
-  float* radius_out;                  // [M, S] or NULL
-  int32_t* count_out;                 // [M, S] or NULL
-};
-
-// The list of row q: slot lane + 64 t into j[t] (0 where the slot is not used), and n[s] = min(ks[s], valid prefix) in every lane.
-template <int S>
-__device__ __forceinline__ void nbr_row(const NbrParams& np, int q, int lane, bool lost, int (&j)[kNbrTrips], int (&n)[S]) {
-  const int kmax = np.ks[S - 1];
-  int bad = lost ? 0 : kmax;                                  // the first slot whose entry lies outside [0, N)
-#pragma unroll
-  for (int t = 0; t < kNbrTrips; ++t) {
-    const int i = lane + t * kWave;
-    j[t] = 0;
-    if (i < kmax) {
-      const int v = np.nbr[(size_t)q * np.K + i];
-      if ((unsigned)v >= (unsigned)np.p.N) bad = min(bad, i);
-      else j[t] = v;
-    }
-  }
-  bad = wave_min(bad);
-#pragma unroll
-  for (int s = 0; s < S; ++s) n[s] = min(np.ks[s], bad);
-}
-
-// body(slot, dx, dy, dz, d2) for the slots lane, lane + 64, ... below n of the list: the walk of the list kernels
-template <class Body>
-__device__ __forceinline__ void walk_list(const float* cloud, const int (&j)[kNbrTrips], int n, int lane, double cx, double cy, double cz,
-                                          Body&& body) {
-#pragma unroll
-  for (int t = 0; t < kNbrTrips; ++t) {
-    const int i = lane + t * kWave;
-    if (i < n) {
-      const float* pt = cloud + (size_t)j[t] * 3;
-      const double dx = (double)pt[0] - cx, dy = (double)pt[1] - cy, dz = (double)pt[2] - cz;
-      body(i, dx, dy, dz, knn_d2(dx, dy, dz));
-    }
-  }
-}
+// NbrParams, nbr_row and walk_list: nbr_dev.h
 
 // The plane fit of every scale over the list: plane_sums of pca_dev.h with a prefix in place of a ball.  Lane s ends up with the sums,
 // the count n_s and r2_s of scale s; the solve sees n = 0 where r2_s == 0.  Writes the radius and the count of the lane's scale.
@@ -405,10 +348,7 @@ __global__ __launch_bounds__(kThreads) void quadric_nbr_kernel(const QuadricNbrP
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
 
-int refuse_knn_k(const std::string& w, int K) {
-  if (K < 1 || K > NESTI_KNN_MAX_K) NESTI_FAIL(w + ": K must be in 1 .. " + std::to_string(NESTI_KNN_MAX_K));
-  return 0;
-}
+// refuse_knn_k and nbr_params_fill (what the list fits refuse, and their parameter block): nbr_dev.h
 
 // nesti_knn (centres = cloud points, by index or row) and nesti_knn_at (centres = positions): one body
 int knn_impl(const char* who, bool at, const float* cloud_dev, int N, const int32_t* query_idx_dev, const float* query_xyz_dev, int M,
@@ -435,32 +375,6 @@ int knn_impl(const char* who, bool at, const float* cloud_dev, int N, const int3
   kp.d2_out = d2_out_dev;
   kp.count_out = count_out_dev;
   return launch_wave_rows(knn_kernel, kp, M, stream);
-}
-
-// what the two list fits refuse, under the entry's name, and their parameter block
-int nbr_params_fill(const std::string& w, bool at, NbrParams* np, const float* cloud_dev, int N, const int32_t* query_idx_dev,
-                    const float* query_xyz_dev, int M, int query_row0, const int32_t* nbr_dev, int K, const int32_t* ks, int S,
-                    float* radius_out_dev, int32_t* count_out_dev) {
-  if (!cloud_dev || !nbr_dev || !ks) NESTI_FAIL(w + ": null argument");
-  if (N <= 0) NESTI_FAIL(w + ": empty cloud");
-  if (refuse_knn_k(w, K)) return 1;
-  if (S < 1 || S > NESTI_MAX_SCALES) NESTI_FAIL(w + ": bad n_scales");
-  for (int s = 0; s < S; ++s)
-    if (ks[s] < 1 || ks[s] > K || (s && ks[s] < ks[s - 1])) NESTI_FAIL(w + ": ks must be ascending and in 1 .. K");
-  if (M < 0) NESTI_FAIL(w + ": M must be >= 0");
-  if (refuse_query_rows(w, N, !at && !query_idx_dev, M, query_row0)) return 1;
-  if (M > 0 && at && !query_xyz_dev) NESTI_FAIL(w + ": null query_xyz_dev");
-  memset(np, 0, sizeof(*np));
-  np->p.cloud = cloud_dev;
-  np->p.query_idx = query_idx_dev;
-  np->p.query_xyz = at ? query_xyz_dev : nullptr;
-  np->p.M = M; np->p.N = N; np->p.S = S; np->p.row0 = query_row0;
-  np->nbr = nbr_dev;
-  np->K = K;
-  for (int s = 0; s < NESTI_MAX_SCALES; ++s) np->ks[s] = ks[s < S ? s : S - 1];
-  np->radius_out = radius_out_dev;
-  np->count_out = count_out_dev;
-  return 0;
 }
 
 // nesti_pca_normals_nbr and nesti_pca_normals_nbr_at: one body

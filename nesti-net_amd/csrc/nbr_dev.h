@@ -1,0 +1,109 @@
+// The walk of an untrusted neighbour list by one wave (DESIGN.md 2 "k-nearest neighbourhoods"), shared by the list kernels of knn.hip
+// (plane fit, quadric fit) and by hough.hip: the parameter block, the valid prefix of a row, the per-slot differences and what every
+// list entry refuses on the host.  One definition, so the prefix, d, d2 and r2_s of every list entry are the same values.
+//
+// For the including unit: include patches_dev.h first, then `#pragma clang fp contract(off)`, then pca_dev.h and this header -- every
+// product and sum below is rounded on its own.
+#pragma once
+#include "pca_dev.h"
+
+namespace nesti {
+namespace {
+
+constexpr int kNbrTrips = NESTI_KNN_MAX_K / kWave;          // slots per lane of a neighbour list
+static_assert(NESTI_KNN_MAX_K % kWave == 0, "a list is whole trips of the wave");
+
+// (dx dx + dy dy) + dz dz in fp64, each operation rounded on its own (contraction is off in the including file)
+__device__ __forceinline__ double knn_d2(double dx, double dy, double dz) {
+  const double s = dx * dx + dy * dy;
+  return s + dz * dz;
+}
+
+// the lanes of one wave see each other's LDS writes after this; waves of a workgroup run different queries and never meet
+__device__ __forceinline__ void wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+struct NbrParams {
+  PatchParams p;                      // cloud, query_idx / query_xyz, M, N, row0 (no grid)
+  const int32_t* nbr;                 // [M, K]
+  int K;
+  int ks[NESTI_MAX_SCALES];           // ascending, 1 <= ks[s] <= K
+  float* radius_out;                  // [M, S] or NULL
+  int32_t* count_out;                 // [M, S] or NULL
+};
+
+// The list of row q: slot lane + 64 t into j[t] (0 where the slot is not used), and n[s] = min(ks[s], valid prefix) in every lane.
+template <int S>
+__device__ __forceinline__ void nbr_row(const NbrParams& np, int q, int lane, bool lost, int (&j)[kNbrTrips], int (&n)[S]) {
+  const int kmax = np.ks[S - 1];
+  int bad = lost ? 0 : kmax;                                  // the first slot whose entry lies outside [0, N)
+#pragma unroll
+  for (int t = 0; t < kNbrTrips; ++t) {
+    const int i = lane + t * kWave;
+    j[t] = 0;
+    if (i < kmax) {
+      const int v = np.nbr[(size_t)q * np.K + i];
+      if ((unsigned)v >= (unsigned)np.p.N) bad = min(bad, i);
+      else j[t] = v;
+    }
+  }
+  bad = wave_min(bad);
+#pragma unroll
+  for (int s = 0; s < S; ++s) n[s] = min(np.ks[s], bad);
+}
+
+// body(slot, dx, dy, dz, d2) for the slots lane, lane + 64, ... below n of the list: the walk of the list kernels
+template <class Body>
+__device__ __forceinline__ void walk_list(const float* cloud, const int (&j)[kNbrTrips], int n, int lane, double cx, double cy, double cz,
+                                          Body&& body) {
+#pragma unroll
+  for (int t = 0; t < kNbrTrips; ++t) {
+    const int i = lane + t * kWave;
+    if (i < n) {
+      const float* pt = cloud + (size_t)j[t] * 3;
+      const double dx = (double)pt[0] - cx, dy = (double)pt[1] - cy, dz = (double)pt[2] - cz;
+      body(i, dx, dy, dz, knn_d2(dx, dy, dz));
+    }
+  }
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------------
+
+inline int refuse_knn_k(const std::string& w, int K) {
+  if (K < 1 || K > NESTI_KNN_MAX_K) NESTI_FAIL(w + ": K must be in 1 .. " + std::to_string(NESTI_KNN_MAX_K));
+  return 0;
+}
+
+// what the list entries refuse, under the entry's name, and their parameter block
+inline int nbr_params_fill(const std::string& w, bool at, NbrParams* np, const float* cloud_dev, int N, const int32_t* query_idx_dev,
+                           const float* query_xyz_dev, int M, int query_row0, const int32_t* nbr_dev, int K, const int32_t* ks, int S,
+                           float* radius_out_dev, int32_t* count_out_dev) {
+  if (!cloud_dev || !nbr_dev || !ks) NESTI_FAIL(w + ": null argument");
+  if (N <= 0) NESTI_FAIL(w + ": empty cloud");
+  if (refuse_knn_k(w, K)) return 1;
+  if (S < 1 || S > NESTI_MAX_SCALES) NESTI_FAIL(w + ": bad n_scales");
+  for (int s = 0; s < S; ++s)
+    if (ks[s] < 1 || ks[s] > K || (s && ks[s] < ks[s - 1])) NESTI_FAIL(w + ": ks must be ascending and in 1 .. K");
+  if (M < 0) NESTI_FAIL(w + ": M must be >= 0");
+  if (refuse_query_rows(w, N, !at && !query_idx_dev, M, query_row0)) return 1;
+  if (M > 0 && at && !query_xyz_dev) NESTI_FAIL(w + ": null query_xyz_dev");
+  memset(np, 0, sizeof(*np));
+  np->p.cloud = cloud_dev;
+  np->p.query_idx = query_idx_dev;
+  np->p.query_xyz = at ? query_xyz_dev : nullptr;
+  np->p.M = M; np->p.N = N; np->p.S = S; np->p.row0 = query_row0;
+  np->nbr = nbr_dev;
+  np->K = K;
+  for (int s = 0; s < NESTI_MAX_SCALES; ++s) np->ks[s] = ks[s < S ? s : S - 1];
+  np->radius_out = radius_out_dev;
+  np->count_out = count_out_dev;
+  return 0;
+}
+
+}  // namespace
+}  // namespace nesti

@@ -79,7 +79,7 @@ __device__ __forceinline__ WaveSpans wave_spans(const PatchParams& p, int lane, 
   return spans;
 }
 
-// The per-candidate body of the plane fit, shared by the ball walk below and the neighbour-list walk (knn.hip: walk_list): the nine terms of a
+// The per-candidate body of the plane fit, shared by the ball walk below and the neighbour-list walk (nbr_dev.h: walk_list): the nine terms of a
 // difference d -- d itself and the six products of d d^T, formed once per candidate -- and their addition to one scale's sums.
 struct PlaneTerms {
   double v[kSums];

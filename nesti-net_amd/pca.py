@@ -41,10 +41,13 @@ def fit_cloud(cloud, ball, nbr, names, scale, orient, viewpoint, orient_k, knn, 
     the neighbour counts ``knn`` with the method ``nbr`` --, take the normals of ``scale``, orient them, synchronise.  ``names``: the
     dict keys of the ball method's outputs, normals first and counts last (a k-NN method returns ``radius`` before the counts).
     ``after(out, s, before)`` runs behind the orientation step on the dict of device tensors, ``out["normals"]`` among them, with the
-    scale's index and the normals from before the pass (None where none ran), and may add tensors.  Returns the dict as numpy arrays,
-    with ``orient``."""
+    scale's index and the normals from before the pass (None where none ran), and may add tensors.  ``ball=None``: an estimator that
+    exists over neighbour lists only (``hough.hough_cloud``), for which ``knn`` must be given.  Returns the dict as numpy arrays, with
+    ``orient``."""
     import torch
     from . import orient as _orient
+    if ball is None and knn is None:
+        raise ValueError("this estimator exists over neighbour lists only: knn must be given")
     ks = None
     if knn is not None:
         from .knn import check_ks

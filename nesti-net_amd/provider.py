@@ -85,7 +85,8 @@ class CloudPatches:
     this cloud and ``r_abs`` from ITS bounding box.  Patch row i is ``queries[i]``; a position whose balls are all empty gets
     the sentinel outputs.
 
-    ``radius_grid=False`` skips the radius grid: only :meth:`knn`, :meth:`pca_knn` and :meth:`quadric_knn` may then be called."""
+    ``radius_grid=False`` skips the radius grid: only :meth:`knn`, :meth:`pca_knn`, :meth:`quadric_knn` and :meth:`hough_knn` may
+    then be called."""
 
     def __init__(self, pts, cfg: NestiConfig, device="cuda:0", seed=3627473, pidx=None, queries=None, radius_grid=True):
         if pidx is not None and queries is not None:
@@ -141,18 +142,19 @@ class CloudPatches:
             return True, self.queries[first:first + count]
         return False, (self.pidx[first:first + count].contiguous() if self.pidx is not None else None)
 
-    def _call(self, name, at, q, count, first, args, stream, ball=True, seed=()):
+    def _call(self, name, at, q, count, first, args, stream, ball=True, seed=(), keyed=False):
         """One entry over patch rows: ``name``, or ``name + "_at"`` where the queries are positions, called on the cloud's device and
         checked under that name.  The two argument layouts of include/nesti_hip.h: a ball entry (``ball``) takes the configuration,
         the radii, ``query_row0`` in both forms (after ``seed`` where it has one) and, behind its own ``args``, the radius grid; a
-        k-NN or list-fit entry takes ``query_row0`` in the index form only.  The stream comes last."""
+        k-NN or list-fit entry takes ``query_row0`` in the index form only -- in both forms where its hash is keyed by the row
+        (``keyed``: the Hough entries).  The stream comes last."""
         entry = name + "_at" if at else name
         head = (_lib.ptr(self.cloud), self.n_points, _lib.ptr(q), count)
         row0 = (ctypes.c_int(first),)
         if ball:
             head = (ctypes.byref(self._c),) + head + (self._r,) + seed + row0
             args = tuple(args) + (_lib.ptr(self._ws), self._ws.numel())
-        elif not at:
+        elif not at or keyed:
             head += row0
         with torch.cuda.device(self.device):
             _lib.check(getattr(self.lib, entry)(*head, *args, ctypes.c_void_p(stream.cuda_stream)), entry)
@@ -307,9 +309,10 @@ class CloudPatches:
             self._call("nesti_knn", at, q, count, first, [k] + [_lib.ptr(t) for t in out] + [_lib.ptr(ws), ws.numel()], st, ball=False)
         return out
 
-    def _fit_nbr(self, name, first, count, ks, grid, nbr, widths, stream):
+    def _fit_nbr(self, name, first, count, ks, grid, nbr, widths, stream, params=(), keyed=False):
         """One list-fit entry over the rows' sorted neighbour lists -- ``nbr`` [count, K], or one search at K = max(ks): outputs of
-        ``widths`` + radius + count."""
+        ``widths`` (a width w: f32 [count,S,w]; a pair (tail, dtype): [count,S] + tail) + radius + count.  ``params``: the entry's own
+        arguments between the scales and the outputs; ``keyed``: see :meth:`_call`."""
         ks = _knn.check_ks(ks)
         st = self._stream(stream)
         if nbr is None:
@@ -318,11 +321,12 @@ class CloudPatches:
         S = len(ks)
         if nbr.dtype != torch.int32 or nbr.dim() != 2 or nbr.shape[0] != count or not nbr.is_contiguous() or nbr.device != self.device:
             raise ValueError("nbr: a contiguous int32 [count, K] tensor on %s" % self.device)
-        out = check_out(None, tuple(((count, S, w), torch.float32) for w in widths) + (((count, S), torch.float32), ((count, S), torch.int32)),
-                        self.device)
+        specs = tuple(((count, S) + tuple(w[0]), w[1]) if isinstance(w, tuple) else ((count, S, w), torch.float32) for w in widths)
+        out = check_out(None, specs + (((count, S), torch.float32), ((count, S), torch.int32)), self.device)
         if count:                         # 0 rows: a no-op; an empty list has no address to pass
-            self._call(name, at, q, count, first, [_lib.ptr(nbr), int(nbr.shape[1]), (ctypes.c_int32 * S)(*ks), S] + [_lib.ptr(t) for t in out],
-                       st, ball=False)
+            self._call(name, at, q, count, first,
+                       [_lib.ptr(nbr), int(nbr.shape[1]), (ctypes.c_int32 * S)(*ks), S] + list(params) + [_lib.ptr(t) for t in out],
+                       st, ball=False, keyed=keyed)
         return out
 
     def pca_knn(self, first, count, ks, grid=None, nbr=None, stream=None):
@@ -339,6 +343,20 @@ class CloudPatches:
         :meth:`pca_knn`: device tensors ``(normals [count,S,3] f32, curv [count,S,2] f32 (k_max, k_min; absolute units), plane
         [count,S,3] f32 (the bits of ``pca_knn``'s normals), radius [count,S] f32, n [count,S] int32)``."""
         return self._fit_nbr("nesti_quadric_fit_nbr", first, count, ks, grid, nbr, (3, 2, 3), stream)
+
+    def hough_knn(self, first, count, ks, triplets, bins, rotations, seed, grid=None, nbr=None, stream=None):
+        """Hough-transform normals of patch rows [first, first + count) over their nearest neighbours (``nesti_hough_normals_nbr`` /
+        ``_at``; DESIGN.md 2 "Hough-transform normals"), as :meth:`pca_knn`: one search at K = max(ks), then ``triplets`` hashed
+        planes per row and scale voting in ``rotations`` rotated ``bins`` x ``bins`` accumulators (``hough.ROTATIONS``).  Device
+        tensors ``(normals [count,S,3] f32, conf [count,S] f32, votes [count,S,2] int32 (winning bin, valid triplets), radius
+        [count,S] f32, n [count,S] int32)``.  The hash is keyed by the patch row ``first + i``, so a row's bits do not depend on the
+        batching."""
+        from . import hough as _hough
+        T, B, R, seed = _hough.check_params(triplets, bins, rotations, seed)
+        rot = _hough.rotation_table(R)
+        params = [T, B, R, rot.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.c_uint64(seed)]
+        return self._fit_nbr("nesti_hough_normals_nbr", first, count, ks, grid, nbr, (3, ((), torch.float32), ((2,), torch.int32)),
+                             stream, params=params, keyed=True)
 
     def build_reference_order(self, first, count, picks, pick_offsets, want_idx=False, out=None, stream=None):
         """Patch tensors of rows [first, first + count) exactly as the reference's ``PointcloudPatchDataset.__getitem__`` builds

@@ -686,6 +686,53 @@ int nesti_hough_normals_nbr_at(const float* cloud_dev, int N, const float* query
                                float* normals_out_dev, float* conf_out_dev, int32_t* votes_out_dev, float* radius_out_dev,
                                int32_t* count_out_dev, void* stream);
 
+/* ---- feature-preserving normal smoothing over neighbour lists (smooth.hip; DESIGN.md 2 "Normal smoothing") ------------------------
+ * One pass of a bilateral filter of normals (Jones et al. 2004, Sun et al. 2007, the anisotropic normal smoothing of Huang et al.
+ * 2013): a row's normal becomes the weighted mean of its neighbours' normals, the weight falling to zero where a neighbour's normal
+ * leaves a cone round the row's own -- rows agree along a face, not across a crease.  It runs after any estimator; positions never
+ * move.  The conventions are the library's own: fp64 throughout, every operation rounded on its own, only + - x / sqrt, comparisons
+ * and integer arithmetic -- a restatement in plain IEEE arithmetic predicts every output bit.
+ *
+ * Centres (query_idx_dev / query_row0, M rows), nbr_dev [M, K] with row stride K (1 <= K <= NESTI_KNN_MAX_K) and the valid prefix are
+ * exactly as for nesti_pca_normals_nbr: the list is untrusted, the prefix ends at the first entry outside [0, N), and a non-finite
+ * centre position has an empty prefix.  normals_in_dev [N, 3] f32 holds a normal for every cloud point and is indexed like the cloud.
+ * k in 1 .. K: the number of leading entries used.  cos_t and falloff: fp64 on the host.  There is no _at entry: a position has no
+ * normal of its own to compare with.
+ *  1 ELIGIBILITY.  A normal is eligible iff its three components are finite and one is non-zero, tested on the bits (the rule of
+ *    nesti_orient_normals).  c = the centre's cloud index, n_c = normals_in[c], q_c = (x x + y y) + z z of n_c in fp64.  A row whose
+ *    n_c is not eligible, or whose prefix is empty, gets the three floats of normals_in[c] copied bit for bit, support 0 and count 0.
+ *  2 PREFIX.  n = min(k, valid prefix); d = (double)p - (double)c and d2 = (dx dx + dy dy) + dz dz per slot; r2 = the largest d2 of
+ *    the prefix.
+ *  3 SLOT i < n with neighbour j, n_j = normals_in[j] eligible (an ineligible neighbour adds nothing), q_j like q_c:
+ *      d = (n_c.x n_j.x + n_c.y n_j.y) + n_c.z n_j.z;   ca = |d| / sqrt(q_c q_j);   t = (ca - cos_t) / (1 - cos_t);
+ *      if not t > 0 the slot adds nothing (this also catches NaN);   t = min(t, 1);
+ *      u = 1 - (falloff d2) / r2 if r2 > 0, else u = 1;   W = (u u) (t t);
+ *      g = W / sqrt(q_j), negated if d < 0 -- the unoriented alignment: a neighbour counts on the centre's side;
+ *      X += g n_j.x, Y += g n_j.y, Z += g n_j.z;   Wsum += W;   cnt += 1, an integer.
+ *  4 ORDER.  Lane l of a 64-lane wave adds its slots l, l + 64, ... in ascending order into partial sums that start at +0.0; the lanes
+ *    meet in an xor-butterfly (offsets 32, 16, ..., 1): the order of the other list fits.
+ *  5 RESULT.  nn = (X X + Y Y) + Z Z; if nn > 0 and finite the output is (X, Y, Z) / sqrt(nn), rounded to f32 once, zeros written as
+ *    +0; otherwise the input row is copied bit for bit (support and count are still those of step 3).  No sign rule is applied:
+ *    every term lies in the centre's closed half-space, so an oriented field stays oriented and an unoriented one keeps each row's
+ *    side.
+ *  6 OUTPUTS (device; any may be NULL):
+ *      normals_out_dev [M,3] f32
+ *      support_out_dev [M]   f32    (float)Wsum
+ *      count_out_dev   [M]   int32  cnt
+ * DETERMINISM: no atomics.  A row's bits are a pure function of (cloud, centre, list prefix, the normals it reads, k, cos_t, falloff).
+ * Argument errors -- those of nesti_pca_normals_nbr; a null normals_in_dev; k outside 1 .. K; cos_t not finite or outside
+ * [0, 0.999999]; falloff not finite or outside [0, 1]; normals_out_dev == normals_in_dev (the pass is a Jacobi step: rows read their
+ * neighbours' input) -- are reported before any device call; M = 0 is a no-op.  Each call enqueues one kernel on `stream`, neither
+ * synchronises nor reads anything back, and can be captured into a graph.  Under nesti_profile_enable the launch is booked in the
+ * patches category, like the other list fits. */
+int nesti_smooth_normals_nbr(const float* cloud_dev, int N, const float* normals_in_dev, const int32_t* query_idx_dev, int M,
+                             int query_row0, const int32_t* nbr_dev, int K, int k, double cos_t, double falloff, float* normals_out_dev,
+                             float* support_out_dev, int32_t* count_out_dev, void* stream);
+/* Measurement and tests only: the lane group that serves a row of nesti_smooth_normals_nbr in this process.  0 (the default): the
+ * smallest of 16, 32 and 64 lanes that holds k; 16, 32 or 64: at least that many (a group smaller than k is widened to hold it), so 64
+ * forces the one-wave-per-row form.  The choice moves the time of a pass, never a byte of its result.  Any other value is refused. */
+int nesti_debug_smooth_lanes(int lanes);
+
 /* ---- depth images in, normal images out (depth.hip; DESIGN.md 2 "Depth images") --------------------------------------------------
  * The two ends of the reference's Kinect route: MATLAB/ScanNet_depth2xyz.m (depth + intrinsics + pose -> cloud) before
  * test_n_est_w_experts.py, and MATLAB/ScanNet_world2cam_normals.m / MATLAB/export_visualizations_nyu.m:146-153 (per-point results

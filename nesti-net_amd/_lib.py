@@ -199,6 +199,8 @@ SIGNATURES = {
                                      ctypes.POINTER(ctypes.c_double), _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nesti_hough_normals_nbr_at": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, ctypes.POINTER(ctypes.c_int32), _i, _i, _i, _i,
                                         ctypes.POINTER(ctypes.c_double), _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "nesti_smooth_normals_nbr": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp]),
+    "nesti_debug_smooth_lanes": (_i, [_i]),
     "nesti_depth_workspace_bytes": (_sz, [_i, _i]),
     "nesti_depth_to_cloud": (_i, [_vp, _i, _i, _i, ctypes.POINTER(CCamera), _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "nesti_image_scatter": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),

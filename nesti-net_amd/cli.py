@@ -14,7 +14,8 @@ quadric-fit normals and principal curvatures of :mod:`.quadric`, written as ``<s
 ``<shape>.quadric_curv`` and ``<shape>.quadric_count`` (every scale).  ``--knn K[,K...]`` fits either of the two over the K nearest
 neighbours instead of balls and adds ``<shape>.knn_radius``.  ``--estimator hough --knn K[,K...]`` is the Hough-transform estimator of
 :mod:`.hough`, which exists over neighbour lists only: ``<shape>.normals`` (one scale), ``<shape>.hough_conf``, ``<shape>.hough_votes`` and
-``<shape>.hough_count`` (every scale) and ``<shape>.knn_radius``."""
+``<shape>.hough_count`` (every scale) and ``<shape>.knn_radius``.  ``--smooth ITERS`` smooths the written normals of any estimator with
+the feature-preserving filter of :mod:`.smooth` before the orientation and adds ``<shape>.smooth_support``."""
 import argparse
 import ctypes
 import os
@@ -24,6 +25,7 @@ import torch
 
 from . import pca as _pca
 from . import hough as _hough
+from . import smooth as _smooth
 from . import quadric as _quadric
 from . import textio
 from . import weights as wts
@@ -147,8 +149,36 @@ def build_parser():
                         "are those of the estimator -- <shape>.pca_count / <shape>.quadric_count then hold the neighbour counts, "
                         "--pca_scale / --quadric_scale index the counts -- plus <shape>.knn_radius (M rows of S distances to the "
                         "farthest neighbour).  --orient mst then uses the largest patch radius of --model's configuration")
+    p.add_argument("--smooth", type=int, default=0, metavar="ITERS",
+                   help="smooth the written normals with ITERS passes (1 .. 64) of the feature-preserving filter of DESIGN.md 2 'Normal "
+                        "smoothing', for every --estimator, before --orient: a row's normal becomes the weighted mean of its nearest "
+                        "neighbours' normals, a neighbour beyond --smooth_angle of the row's own normal having no weight, so creases are "
+                        "kept.  Only <shape>.normals changes (.experts and .experts_probs stay byte-identical); writes "
+                        "<shape>.smooth_support (M rows: the weight sum and the number of weighted neighbours of the last pass).  Needs a "
+                        "normal at every point: refused with --sparse_patches 1, --query_positions 1 and --depth_images 1 [default: 0 = off]")
+    p.add_argument("--smooth_k", type=int, default=_smooth.DEFAULT_K,
+                   help="--smooth: nearest neighbours per row, 1 .. 256 [default: %d]" % _smooth.DEFAULT_K)
+    p.add_argument("--smooth_angle", type=float, default=_smooth.DEFAULT_ANGLE,
+                   help="--smooth: the angle in degrees, in (0, 90], at which a neighbour's weight reaches 0 [default: %g]" % _smooth.DEFAULT_ANGLE)
+    p.add_argument("--smooth_falloff", type=float, default=_smooth.DEFAULT_FALLOFF,
+                   help="--smooth: the distance falloff in [0, 1]; the farthest neighbour weighs (1 - falloff)^2 [default: %g]"
+                        % _smooth.DEFAULT_FALLOFF)
     p.add_argument("--synthetic_weights", action="store_true", help="use seeded synthetic weights if model.nstw is absent")
     return p
+
+
+def smooth_line(name, rows, params, count):
+    """The log line of ``--smooth`` for shape ``name``: the rows, the passes and the rows whose count is 1 (nothing but the row's own
+    normal had a weight in the last pass); ``count``: the int32 counts of the last pass."""
+    return ("smoothing of %s: %d rows, %d pass%s over %d nearest neighbours (%g degrees, falloff %g); %d rows with count 1"
+            % (name, rows, params.iters, "" if params.iters == 1 else "es", params.k, params.angle, params.falloff, int((count == 1).sum())))
+
+
+def write_smooth_support(path, support, count):
+    """``<shape>.smooth_support``: M rows of ``support count``."""
+    with open(path, "w") as f:
+        for s, c in zip(support.tolist(), count.tolist()):
+            f.write("%.9g %d\n" % (s, c))
 
 
 def fit_batch(cfg, dtype, batch, device, lanes=2, reserve=2 << 30):
@@ -264,7 +294,7 @@ def fit_line(estimator, name, rows, scale, n_scales, missing, radius=None, k=Non
                fit["no_fit"][k is not None]))
 
 
-def run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None):
+def run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None, smooth=None):
     """``--estimator pca / quadric`` (``FITS``): per shape the fit at every scale, the optional orientation of the rows of scale ``scale``
     (>= 0; the quadric fit flips their curvatures with them), and the estimator's files.  No model is loaded."""
     fit = FITS[FLAGS.estimator]
@@ -274,13 +304,16 @@ def run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None):
         cloud = dataset.get_shape(ind)
         params = {kw: getattr(FLAGS, flag) for kw, flag in fit.get("params", ())}
         res = fit["fit"](cloud, scale=scale, orient=None if FLAGS.orient == "0" else FLAGS.orient, viewpoint=FLAGS.viewpoint,
-                         orient_k=FLAGS.orient_k, knn=ks, **params)
+                         orient_k=FLAGS.orient_k, knn=ks, smooth=smooth, **params)
         missing = int(fit["missing"](res, scale, ks))
         if ks is None:
             printout(fit_line(FLAGS.estimator, name, cloud.patch_count, scale, cfg.n_scales, missing, radius=cloud.r_abs[scale]))
         else:
             printout(fit_line(FLAGS.estimator, name, cloud.patch_count, scale, len(ks), missing, k=ks[scale]))
             textio.write_f32(os.path.join(output_dir, name + ".knn_radius"), res["radius"])
+        if smooth is not None:
+            printout(smooth_line(name, cloud.patch_count, smooth, res["smooth_count"]))
+            write_smooth_support(os.path.join(output_dir, name + ".smooth_support"), res["smooth_support"], res["smooth_count"])
         if res["orient"] is not None:
             printout(orient_line(name, FLAGS.orient, res["orient"], cloud.patch_count))
         for ext, write, key in fit["files"]:
@@ -323,6 +356,21 @@ def main(argv=None):
                                   fit.get("subsamples", "the %s uses the full ball and subsamples nothing" % fit["noun"]))):
             if given:
                 parser.error("--estimator %s does not take %s: %s" % (FLAGS.estimator, flag, why))
+    smooth = None
+    if FLAGS.smooth:
+        for given, flag, why in ((FLAGS.sparse_patches, "--sparse_patches 1", "not all rows have normals"),
+                                 (FLAGS.query_positions, "--query_positions 1", "not all rows have normals"),
+                                 (FLAGS.depth_images, "--depth_images 1", "smoothing of depth frames is left for later")):
+            if given:
+                parser.error("--smooth does not go with %s: %s" % (flag, why))
+        try:
+            smooth = _smooth.check_params(FLAGS.smooth_k, FLAGS.smooth, FLAGS.smooth_angle, FLAGS.smooth_falloff)
+        except ValueError as e:
+            parser.error("--smooth: %s" % e)
+    else:
+        for flag in ("smooth_k", "smooth_angle", "smooth_falloff"):
+            if getattr(FLAGS, flag) != parser.get_default(flag):
+                parser.error("--%s belongs to --smooth ITERS" % flag)
     if FLAGS.query_positions and FLAGS.sparse_patches:
         parser.error("--query_positions 1 and --sparse_patches 1 are mutually exclusive: the queries are positions or cloud points")
     if FLAGS.query_positions and FLAGS.subsample != "hash":
@@ -368,7 +416,7 @@ def main(argv=None):
             scale = _pca.check_scale(getattr(FLAGS, fit["scale_flag"]), cfg.n_scales if ks is None else len(ks))
         except ValueError as e:
             raise SystemExit("--%s with --model %s: %s" % (fit["scale_flag"], FLAGS.model, e))
-        rc = run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks)
+        rc = run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks, smooth)
         flog.close()
         return rc
 
@@ -461,6 +509,12 @@ def main(argv=None):
                         rs["gate_violations"] + rs["guard_violations"] == 0, lv["max_margin_err"], lv["max_dn"]))
         else:
             normals, expert, probs = est.run(cloud)
+        support = None
+        if smooth is not None:
+            # after the whole shape is estimated and before the orientation; a pure function of the estimated normals, so a
+            # reproducible run stays one
+            normals, support, count = _smooth.smooth_cloud(cloud, normals.contiguous(), smooth)
+            printout(smooth_line(name, cloud.patch_count, smooth, count.cpu().numpy()))
         if FLAGS.orient != "0":
             # after the whole shape is estimated (in the reproducible mode: after its last verified pass); only signs change
             from .orient import stats_dict
@@ -474,6 +528,8 @@ def main(argv=None):
                      % (name, cloud.patch_count, int(alone.sum().item())))
         # byte-identical to the reference's np.savetxt calls (test_n_est_w_experts.py:182-188), ~6x faster
         textio.write_f32(os.path.join(output_dir, name + ".normals"), normals.cpu().numpy())
+        if support is not None:
+            write_smooth_support(os.path.join(output_dir, name + ".smooth_support"), support.cpu().numpy(), count.cpu().numpy())
         printout("saved normals for " + name)
         if expert is None or arch == ARCH_SWITCH:   # the ablation drivers write .normals only (test_n_est.py:118,
             continue                                 # test_n_est_w_switching.py:158)

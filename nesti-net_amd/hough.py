@@ -64,19 +64,20 @@ def _need_knn(knn):
 
 
 def hough_cloud(cloud, knn=DEFAULT_KNN, scale=-1, triplets=DEFAULT_TRIPLETS, bins=DEFAULT_BINS, rotations=DEFAULT_ROTATIONS, seed=0,
-                orient=None, viewpoint=None, orient_k=8):
-    """``hough_normals`` for a prepared ``provider.CloudPatches`` (all of its patch rows); synchronises."""
+                orient=None, viewpoint=None, orient_k=8, smooth=None):
+    """``hough_normals`` for a prepared ``provider.CloudPatches`` (all of its patch rows); synchronises.  ``smooth``: see
+    ``pca.fit_cloud``."""
     _need_knn(knn)
     T, B, R, seed = check_params(triplets, bins, rotations, seed)
 
-    def nbr(first, count, ks):
-        return cloud.hough_knn(first, count, ks, T, B, R, seed)
+    def nbr(first, count, ks, nbr=None):
+        return cloud.hough_knn(first, count, ks, T, B, R, seed, nbr=nbr)
 
-    return fit_cloud(cloud, None, nbr, ("normals_all", "conf", "votes", "n_ball"), scale, orient, viewpoint, orient_k, knn)
+    return fit_cloud(cloud, None, nbr, ("normals_all", "conf", "votes", "n_ball"), scale, orient, viewpoint, orient_k, knn, smooth=smooth)
 
 
 def hough_normals(pts, knn=DEFAULT_KNN, pidx=None, queries=None, scale=-1, triplets=DEFAULT_TRIPLETS, bins=DEFAULT_BINS,
-                  rotations=DEFAULT_ROTATIONS, seed=0, orient=None, viewpoint=None, orient_k=8, device="cuda:0", cfg=None):
+                  rotations=DEFAULT_ROTATIONS, seed=0, orient=None, viewpoint=None, orient_k=8, device="cuda:0", cfg=None, smooth=None):
     """Hough-transform normals of a cloud: numpy in, a dict of numpy arrays out (synchronises).  Queries are all points, the points
     ``pidx`` or the positions ``queries`` [M,3] (mutually exclusive), as for ``pca.pca_normals``.  ``knn`` -- an int or an ascending
     sequence of at most 4 ints in 1 .. 256 -- names the neighbourhoods: scale s is the ``knn[s]`` nearest cloud points of the query
@@ -96,10 +97,15 @@ def hough_normals(pts, knn=DEFAULT_KNN, pidx=None, queries=None, scale=-1, tripl
     (coincident or collinear neighbours), has normal 0 0 0, ``conf`` 0 and votes (0, valid); the orientation leaves such rows alone.
     ``orient`` is as for ``pca.pca_normals(..., knn=...)``.
 
+    ``smooth`` -- as for ``pca.pca_normals`` -- smooths ``normals`` over all points before the orientation, over the lists of the
+    estimator's own search where ``max(knn)`` reaches the smoothing's ``k``: the vote keeps a crease, the smoothing takes the bins'
+    noise off the faces.  The dict gains ``smooth_support`` and ``smooth_count``.
+
     Raises ``ValueError`` for ``knn=None`` (there is no ball variant), for a ``cfg`` (the scales are neighbour counts: a
-    configuration's radii would mean nothing), for parameters outside their ranges, for a ``scale`` outside [-S, S) and for ``pidx``
-    together with ``queries``."""
+    configuration's radii would mean nothing), for parameters outside their ranges, for a ``scale`` outside [-S, S), for ``pidx``
+    together with ``queries``, for a bad ``smooth`` and for ``smooth`` with ``pidx`` or ``queries``."""
     _need_knn(knn)
     check_params(triplets, bins, rotations, seed)
-    cloud, scale, orient, viewpoint, orient_k, ks = prepare_cloud(pts, cfg, pidx, queries, scale, orient, viewpoint, orient_k, device, knn)
-    return hough_cloud(cloud, ks, scale, triplets, bins, rotations, seed, orient, viewpoint, orient_k)
+    cloud, scale, orient, viewpoint, orient_k, ks = prepare_cloud(pts, cfg, pidx, queries, scale, orient, viewpoint, orient_k, device, knn,
+                                                                  smooth)
+    return hough_cloud(cloud, ks, scale, triplets, bins, rotations, seed, orient, viewpoint, orient_k, smooth=smooth)

@@ -36,14 +36,17 @@ def orient_rows(cloud, normals, scale, mode, viewpoint=None, k=8, radius=None):
     return _orient.orient_device(cloud.centre_positions(), normals, r, k, viewpoint, mode, torch.cuda.current_stream(cloud.device))
 
 
-def fit_cloud(cloud, ball, nbr, names, scale, orient, viewpoint, orient_k, knn, after=None):
+def fit_cloud(cloud, ball, nbr, names, scale, orient, viewpoint, orient_k, knn, after=None, smooth=None):
     """What ``pca_cloud`` and ``quadric.quadric_cloud`` share: fit all patch rows of a prepared cloud with the method ``ball`` -- over
     the neighbour counts ``knn`` with the method ``nbr`` --, take the normals of ``scale``, orient them, synchronise.  ``names``: the
     dict keys of the ball method's outputs, normals first and counts last (a k-NN method returns ``radius`` before the counts).
     ``after(out, s, before)`` runs behind the orientation step on the dict of device tensors, ``out["normals"]`` among them, with the
     scale's index and the normals from before the pass (None where none ran), and may add tensors.  ``ball=None``: an estimator that
-    exists over neighbour lists only (``hough.hough_cloud``), for which ``knn`` must be given.  Returns the dict as numpy arrays, with
-    ``orient``."""
+    exists over neighbour lists only (``hough.hough_cloud``), for which ``knn`` must be given.  ``smooth`` (``smooth.as_params``: None,
+    a number of passes or a dict) smooths the scale's normals over all points between those two steps -- ``normals_all`` stays as
+    fitted -- and adds ``smooth_support`` and ``smooth_count``; a k-NN fit whose lists hold at least ``k`` entries is given the lists
+    of ONE search (``nbr`` then takes them as its ``nbr=`` keyword) which the passes reuse, a prefix of a sorted list being the k-NN
+    list; otherwise the passes search once for themselves.  Returns the dict as numpy arrays, with ``orient``."""
     import torch
     from . import orient as _orient
     if ball is None and knn is None:
@@ -56,9 +59,23 @@ def fit_cloud(cloud, ball, nbr, names, scale, orient, viewpoint, orient_k, knn, 
     s = check_scale(scale, cloud.cfg.n_scales if ks is None else len(ks))
     if orient not in ORIENT_MODES:
         raise ValueError("orient must be None, 'mst' or 'viewpoint'")
+    from . import smooth as _smooth
+    sm = _smooth.as_params(smooth)
+    if sm is not None:
+        _smooth.refuse_subset(cloud.pidx, cloud.queries)
     with torch.cuda.device(cloud.device):
-        out = dict(zip(names, ball(0, cloud.patch_count) if ks is None else nbr(0, cloud.patch_count, ks)))
+        lists = None
+        if ks is None:
+            out = dict(zip(names, ball(0, cloud.patch_count)))
+        elif sm is not None and ks[-1] >= sm.k:
+            lists = cloud.knn(0, cloud.patch_count, ks[-1])[0]
+            out = dict(zip(names, nbr(0, cloud.patch_count, ks, nbr=lists)))
+        else:
+            out = dict(zip(names, nbr(0, cloud.patch_count, ks)))
         normals = out["normals"] = out[names[0]][:, s, :].contiguous()
+        if sm is not None:
+            normals, out["smooth_support"], out["smooth_count"] = _smooth.smooth_cloud(cloud, normals, sm, nbr=lists)
+            out["normals"] = normals
         before = stats = None
         if orient is not None and cloud.patch_count:
             before = normals.clone() if after else None
@@ -71,10 +88,11 @@ def fit_cloud(cloud, ball, nbr, names, scale, orient, viewpoint, orient_k, knn, 
     return res
 
 
-def pca_cloud(cloud, scale=-1, orient=None, viewpoint=None, orient_k=8, knn=None):
+def pca_cloud(cloud, scale=-1, orient=None, viewpoint=None, orient_k=8, knn=None, smooth=None):
     """``pca_normals`` for a prepared ``provider.CloudPatches`` (all of its patch rows); synchronises.  ``knn``: neighbour counts
-    instead of the cloud's radii (``scale`` then indexes them, and the dict gains ``radius``)."""
-    res = fit_cloud(cloud, cloud.pca, cloud.pca_knn, ("normals_all", "eig", "n_ball"), scale, orient, viewpoint, orient_k, knn)
+    instead of the cloud's radii (``scale`` then indexes them, and the dict gains ``radius``).  ``smooth``: see ``fit_cloud``."""
+    res = fit_cloud(cloud, cloud.pca, cloud.pca_knn, ("normals_all", "eig", "n_ball"), scale, orient, viewpoint, orient_k, knn,
+                    smooth=smooth)
     res["variation"] = variation(res["eig"])
     return res
 
@@ -92,10 +110,14 @@ def check_knn_args(knn, cfg):
     return ks, NestiConfig()
 
 
-def prepare_cloud(pts, cfg, pidx, queries, scale, orient, viewpoint, orient_k, device, knn):
+def prepare_cloud(pts, cfg, pidx, queries, scale, orient, viewpoint, orient_k, device, knn, smooth=None):
     """The "numpy in" front of ``pca_normals`` and ``quadric.quadric_fit``: every argument check, then the ``CloudPatches``.  Returns the
-    arguments of ``pca_cloud`` / ``quadric.quadric_cloud``."""
+    arguments of ``pca_cloud`` / ``quadric.quadric_cloud`` (``smooth``, checked here, is not among them)."""
     ks, cfg = check_knn_args(knn, cfg)
+    if smooth is not None:
+        from . import smooth as _smooth
+        _smooth.as_params(smooth)
+        _smooth.refuse_subset(pidx, queries)
     check_scale(scale, cfg.n_scales if ks is None else len(ks))
     if orient not in ORIENT_MODES:
         raise ValueError("orient must be None, 'mst' or 'viewpoint'")
@@ -110,7 +132,8 @@ def prepare_cloud(pts, cfg, pidx, queries, scale, orient, viewpoint, orient_k, d
     return cloud, scale, orient, viewpoint, orient_k, ks
 
 
-def pca_normals(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, viewpoint=None, orient_k=8, device="cuda:0", knn=None):
+def pca_normals(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, viewpoint=None, orient_k=8, device="cuda:0", knn=None,
+                smooth=None):
     """Plane-fit normals of a cloud: numpy in, a dict of numpy arrays out (synchronises).  Queries are all points, the points
     ``pidx`` or the positions ``queries`` [M,3] (mutually exclusive), as for ``NormalEstimator.estimate``; the radii are
     ``cfg.patch_radius`` times the cloud's bounding-box diagonal.
@@ -133,6 +156,11 @@ def pca_normals(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, v
     on batching or on the search grid.  With ``orient='mst'`` the orientation graph's radius is the default configuration's largest
     patch radius, as on the network path: the k-NN radii vary per row and are not a safe grid cell; ``'viewpoint'`` needs no radius.
 
-    Raises ``ValueError`` for a ``scale`` outside [-S, S), for ``pidx`` together with ``queries``, for a bad ``knn`` and for ``knn``
-    together with ``cfg`` (whose radii would mean nothing)."""
-    return pca_cloud(*prepare_cloud(pts, cfg, pidx, queries, scale, orient, viewpoint, orient_k, device, knn))
+    ``smooth`` -- None, a number of passes or a dict of ``k``, ``iters``, ``angle``, ``falloff`` (``smooth.smooth_normals``) -- smooths
+    ``normals`` over all points before the orientation (DESIGN.md 2 "Normal smoothing"); ``normals_all`` stays as fitted and the dict
+    gains ``smooth_support`` [M] float32 and ``smooth_count`` [M] int32 of the last pass.  It needs all points.
+
+    Raises ``ValueError`` for a ``scale`` outside [-S, S), for ``pidx`` together with ``queries``, for a bad ``knn``, for ``knn``
+    together with ``cfg`` (whose radii would mean nothing), for a bad ``smooth`` and for ``smooth`` with ``pidx`` or ``queries`` (the
+    rows' neighbours would have no normal)."""
+    return pca_cloud(*prepare_cloud(pts, cfg, pidx, queries, scale, orient, viewpoint, orient_k, device, knn, smooth), smooth=smooth)

@@ -509,19 +509,31 @@ class NormalEstimator:
         return _orient.orient_device(cloud.centre_positions(), normals, float(cloud.r_abs[-1]), k, viewpoint, mode,
                                      torch.cuda.current_stream(self.device))
 
-    def estimate(self, pts, pidx=None, queries=None, orient=None, viewpoint=None, orient_k=8):
+    def estimate(self, pts, pidx=None, queries=None, orient=None, viewpoint=None, orient_k=8, smooth=None):
         """Convenience: numpy cloud in, numpy results out (synchronises).  ``queries`` [M,3]: positions instead of cloud points;
         a position without a neighbourhood comes back as normal (0, 0, 0), expert -1, probabilities 0.  ``orient`` = ``'mst'`` /
         ``'viewpoint'`` (default None: signs as the experts produced them): :meth:`orient` runs over the estimated rows, only signs
-        change, and ``self.last_orient`` holds the stats dict."""
+        change, and ``self.last_orient`` holds the stats dict.  ``smooth`` -- None, a number of passes or a dict of ``k``, ``iters``,
+        ``angle``, ``falloff`` (``smooth.smooth_normals``) -- smooths the normals over all points before the orientation; it needs
+        all points (``ValueError`` with ``pidx`` or ``queries``: the rows' neighbours would have no normal), leaves experts and
+        probabilities alone, and ``self.last_smooth`` holds ``smooth_support`` and ``smooth_count`` of the last pass."""
         if orient not in (None, "mst", "viewpoint"):
             raise ValueError("orient must be None, 'mst' or 'viewpoint'")
+        from . import smooth as _smooth
+        sm = _smooth.as_params(smooth)
+        if sm is not None:
+            _smooth.refuse_subset(pidx, queries)
         cloud = self.prepare(np.asarray(pts, dtype=np.float32), pidx, queries)
         normals, expert, probs = self.run(cloud)
+        if sm is not None:
+            with torch.cuda.device(self.device):
+                normals, support, count = _smooth.smooth_cloud(cloud, normals.contiguous(), sm)
         if orient is not None:
             from .orient import stats_dict
             self.last_orient = stats_dict(self.orient(cloud, normals, orient, viewpoint, orient_k))
         torch.cuda.synchronize(self.device)
+        if sm is not None:
+            self.last_smooth = {"smooth_support": support.cpu().numpy(), "smooth_count": count.cpu().numpy()}
         if expert is None:
             return normals.cpu().numpy(), None, None
         return normals.cpu().numpy(), expert.cpu().numpy(), probs.cpu().numpy()

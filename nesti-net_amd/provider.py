@@ -358,6 +358,37 @@ class CloudPatches:
         return self._fit_nbr("nesti_hough_normals_nbr", first, count, ks, grid, nbr, (3, ((), torch.float32), ((2,), torch.int32)),
                              stream, params=params, keyed=True)
 
+    def smooth_knn(self, normals, first, count, k, cos_t, falloff, nbr=None, grid=None, stream=None):
+        """One pass of feature-preserving normal smoothing over patch rows [first, first + count) (``nesti_smooth_normals_nbr``;
+        DESIGN.md 2 "Normal smoothing"): ``normals`` [n_points,3] f32 on the device holds a normal for every cloud point; a row's
+        normal becomes the weighted mean of the normals of its ``k`` nearest cloud points, the weight 0 where the (unoriented) angle
+        to the row's own normal reaches acos(``cos_t``) and falling with the distance by ``falloff``.  Device tensors ``(normals
+        [count,3] f32, support [count] f32 (the sum of the weights), count [count] int32 (the neighbours that had one))``.  ``nbr``
+        [count,K >= k] int32: the caller's own lists instead of a search at K = k (untrusted, as for :meth:`pca_knn`).  The pass is a
+        Jacobi step: the returned normals are a fresh tensor, never ``normals``.  Serves all points and ``pidx``; a cloud built with
+        ``queries=`` raises ``ValueError`` (a position has no normal of its own).  Asynchronous on ``stream``."""
+        from . import smooth as _smooth
+        if self.queries is not None:
+            raise ValueError("smooth_knn: a cloud with position queries cannot be smoothed: a position has no normal of its own")
+        k, cos_t, falloff = _smooth.check_pass(k, cos_t, falloff)
+        if (not isinstance(normals, torch.Tensor) or normals.dtype != torch.float32 or tuple(normals.shape) != (self.n_points, 3)
+                or not normals.is_contiguous() or normals.device != self.device):
+            raise ValueError("normals: a contiguous float32 [n_points, 3] tensor on %s" % self.device)
+        st = self._stream(stream)
+        if nbr is None:
+            nbr = self.knn(first, count, k, grid=grid, stream=st)[0]
+        at, q = self._rows(first, count)
+        if (nbr.dtype != torch.int32 or nbr.dim() != 2 or nbr.shape[0] != count or nbr.shape[1] < k or not nbr.is_contiguous()
+                or nbr.device != self.device):
+            raise ValueError("nbr: a contiguous int32 [count, K >= k] tensor on %s" % self.device)
+        out = check_out(None, (((count, 3), torch.float32), ((count,), torch.float32), ((count,), torch.int32)), self.device)
+        if count:                         # 0 rows: a no-op; an empty list has no address to pass
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.nesti_smooth_normals_nbr(
+                    _lib.ptr(self.cloud), self.n_points, _lib.ptr(normals), _lib.ptr(q), count, first, _lib.ptr(nbr), int(nbr.shape[1]), k,
+                    cos_t, falloff, *[_lib.ptr(t) for t in out], ctypes.c_void_p(st.cuda_stream)), "nesti_smooth_normals_nbr")
+        return out
+
     def build_reference_order(self, first, count, picks, pick_offsets, want_idx=False, out=None, stream=None):
         """Patch tensors of rows [first, first + count) exactly as the reference's ``PointcloudPatchDataset.__getitem__`` builds
         them (``nesti_patches_query_ref``): balls in cKDTree's visiting order, over-full balls thinned by ``picks`` (uint16 device

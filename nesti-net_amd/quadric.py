@@ -15,9 +15,10 @@ def mean_gauss(curv):
     return (curv[..., 0] + curv[..., 1]) * np.float32(0.5), curv[..., 0] * curv[..., 1]
 
 
-def quadric_cloud(cloud, scale=-1, orient=None, viewpoint=None, orient_k=8, knn=None):
+def quadric_cloud(cloud, scale=-1, orient=None, viewpoint=None, orient_k=8, knn=None, smooth=None):
     """``quadric_fit`` for a prepared ``provider.CloudPatches`` (all of its patch rows); synchronises.  ``knn``: neighbour counts
-    instead of the cloud's radii (``scale`` then indexes them, and the dict gains ``radius``)."""
+    instead of the cloud's radii (``scale`` then indexes them, and the dict gains ``radius``).  ``smooth``: see ``pca.fit_cloud``; the
+    curvatures are untouched by the smoothing and still flip with the orientation."""
     import torch
 
     def curvatures(out, s, before):
@@ -28,10 +29,11 @@ def quadric_cloud(cloud, scale=-1, orient=None, viewpoint=None, orient_k=8, knn=
             out["curv"] = torch.where(flipped, -out["curv"].flip(1), out["curv"])
 
     return fit_cloud(cloud, cloud.quadric, cloud.quadric_knn, ("normals_all", "curv_all", "plane_all", "n_ball"), scale, orient, viewpoint,
-                     orient_k, knn, after=curvatures)
+                     orient_k, knn, after=curvatures, smooth=smooth)
 
 
-def quadric_fit(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, viewpoint=None, orient_k=8, device="cuda:0", knn=None):
+def quadric_fit(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, viewpoint=None, orient_k=8, device="cuda:0", knn=None,
+                smooth=None):
     """Quadric-fit normals and principal curvatures of a cloud: numpy in, a dict of numpy arrays out (synchronises).  Queries are all
     points, the points ``pidx`` or the positions ``queries`` [M,3] (mutually exclusive), as for ``pca.pca_normals``; the radii are
     ``cfg.patch_radius`` times the cloud's bounding-box diagonal.
@@ -56,6 +58,9 @@ def quadric_fit(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, v
     configuration's largest patch radius (the k-NN radii vary per row and are not a safe grid cell); ``'viewpoint'`` needs no radius;
     the curvature flip is the same.
 
-    Raises ``ValueError`` for a ``scale`` outside [-S, S), for ``pidx`` together with ``queries``, for a bad ``knn`` and for ``knn``
-    together with ``cfg`` (whose radii would mean nothing)."""
-    return quadric_cloud(*prepare_cloud(pts, cfg, pidx, queries, scale, orient, viewpoint, orient_k, device, knn))
+    ``smooth`` -- as for ``pca.pca_normals`` -- smooths ``normals`` over all points before the orientation; ``curv`` is untouched by
+    it (the curvatures are the fit's) and still flips with the orientation; the dict gains ``smooth_support`` and ``smooth_count``.
+
+    Raises ``ValueError`` for a ``scale`` outside [-S, S), for ``pidx`` together with ``queries``, for a bad ``knn``, for ``knn``
+    together with ``cfg`` (whose radii would mean nothing), for a bad ``smooth`` and for ``smooth`` with ``pidx`` or ``queries``."""
+    return quadric_cloud(*prepare_cloud(pts, cfg, pidx, queries, scale, orient, viewpoint, orient_k, device, knn, smooth), smooth=smooth)

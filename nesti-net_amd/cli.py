@@ -12,7 +12,8 @@ checkpoint ships with the reference).  ``--estimator pca`` needs none of them: t
 ``<shape>.normals`` (one scale), ``<shape>.pca_eig`` and ``<shape>.pca_count`` (every scale); nor does ``--estimator quadric``: the
 quadric-fit normals and principal curvatures of :mod:`.quadric`, written as ``<shape>.normals`` and ``<shape>.curv`` (one scale),
 ``<shape>.quadric_curv`` and ``<shape>.quadric_count`` (every scale).  ``--knn K[,K...]`` fits either of the two over the K nearest
-neighbours instead of balls and adds ``<shape>.knn_radius``.  ``--estimator hough --knn K[,K...]`` is the Hough-transform estimator of
+neighbours instead of balls and adds ``<shape>.knn_radius``; ``--patch_radius R [R ...]`` gives the balls one to four radii of the
+caller's in place of the model configuration's.  ``--estimator hough --knn K[,K...]`` is the Hough-transform estimator of
 :mod:`.hough`, which exists over neighbour lists only: ``<shape>.normals`` (one scale), ``<shape>.hough_conf``, ``<shape>.hough_votes`` and
 ``<shape>.hough_count`` (every scale) and ``<shape>.knn_radius``.  ``--smooth ITERS`` smooths the written normals of any estimator with
 the feature-preserving filter of :mod:`.smooth` before the orientation and adds ``<shape>.smooth_support``."""
@@ -29,7 +30,7 @@ from . import smooth as _smooth
 from . import quadric as _quadric
 from . import textio
 from . import weights as wts
-from .config import ARCH_EXPERTS, ARCH_MULTI, ARCH_SINGLE, ARCH_SWITCH, NestiConfig
+from .config import ARCH_EXPERTS, ARCH_MULTI, ARCH_SINGLE, ARCH_SWITCH, MAX_SCALES, NestiConfig
 from .pipeline import NormalEstimator
 from .provider import PointcloudPatchDataset
 
@@ -133,6 +134,10 @@ def build_parser():
     p.add_argument("--quadric_scale", type=int, default=-1,
                    help="--estimator quadric: the scale whose normals and curvatures go to <shape>.normals and <shape>.curv, an index "
                         "into the patch radii; negative counts from the end [default: -1, the largest]")
+    p.add_argument("--patch_radius", type=float, nargs="+", default=None, metavar="R",
+                   help="--estimator pca / quadric without --knn: the patch radii as fractions of the bounding-box diagonal, 1 to 4 "
+                        "positive numbers in any order, in place of those of --model's configuration; --pca_scale / --quadric_scale "
+                        "index them and the files have as many scales [default: the radii of --model's configuration]")
     p.add_argument("--hough_scale", type=int, default=-1,
                    help="--estimator hough: the scale whose normals go to <shape>.normals, an index into --knn; negative counts from "
                         "the end [default: -1, the largest]")
@@ -341,6 +346,12 @@ def main(argv=None):
         except ValueError as e:
             parser.error("--knn %s: %s" % (FLAGS.knn, e))
     fit = FITS.get(FLAGS.estimator)
+    if FLAGS.patch_radius is not None:
+        if FLAGS.estimator not in ("pca", "quadric") or ks is not None:
+            parser.error("--patch_radius belongs to --estimator pca / --estimator quadric without --knn: the network's radii are its "
+                         "model's, and the scales of a k-NN fit are neighbour counts")
+        if len(FLAGS.patch_radius) > MAX_SCALES or not all(0.0 < r < float("inf") for r in FLAGS.patch_radius):
+            parser.error("--patch_radius takes 1 to %d positive finite numbers" % MAX_SCALES)
     if FLAGS.estimator == "hough":
         if ks is None:
             parser.error("--estimator hough needs --knn K[,K...]: the Hough transform exists over neighbour lists only")
@@ -412,6 +423,8 @@ def main(argv=None):
 
     if fit:
         cfg = NestiConfig.for_model(FLAGS.model)
+        if FLAGS.patch_radius is not None:
+            cfg.patch_radius = list(FLAGS.patch_radius)       # the fits read the radii and their number, nothing else of cfg
         try:
             scale = _pca.check_scale(getattr(FLAGS, fit["scale_flag"]), cfg.n_scales if ks is None else len(ks))
         except ValueError as e:

@@ -7,7 +7,11 @@ tests/test_gpu_quadric.py (restated in ``_quadric_check`` because the radius is 
     B = 16 n eps kappa_2(N) (||a||_2 + 1);  a pair with n >= 6 is ILL-CONDITIONED iff not B <= 1e-6;  every other pair is live and has
     | |nu| - 1 | <= 2^-22,  sin(angle(nu, nu_ref)) <= 2^-22 + 2 B,  r |k - k_ref| <= 2^-23 r |k_ref| + 8 (1 + ||a||_2) B,  nu . n0 > 0.
 The ill-conditioned share of a scale may not exceed 1 %, as in the radius test (computed on the CPU from the restatement: it is 0 at
-every k on both clouds; the largest kappa is 1.3e6, at k = 8 on the clean torus)."""
+every k on both clouds; the largest kappa is 1.3e6, at k = 8 on the clean torus).
+
+The fits are held to the restatement at three counts (``pca_nbr_kernel<3>``, ``quadric_nbr_kernel<3>``); one count runs through the
+prefix property (test 7), the Python layer (test 11) and the sphere (test 9), two counts only on sentinel rows (test 2) and on the
+command line (test 11), four never.  S = 1, 2 and 4 of both kernels against the restatement: tests/test_gpu_fit_scales.py."""
 import os
 
 import numpy as np

@@ -10,7 +10,9 @@ Notation: n the ball size, w the restatement's float64 eigenvalues in r^2 units,
                | |nu| - 1 | <= 2^-22.  rho is the Rayleigh quotient nu^T C nu / nu^T nu: the bound is a statement about the direction
                (an angle delta costs at most delta^2 w2), and the length of the f32 vector, which alone would move nu^T C nu by
                2^-23 w0, is held by the second inequality
-  eigenvalues  |w_k(gpu) - w_k| <= 2^-23 w_k + 8 n eps, ascending"""
+  eigenvalues  |w_k(gpu) - w_k| <= 2^-23 w_k + 8 n eps, ascending
+
+Every cloud here has three radii: this module runs ``pca_kernel<3>``.  S = 1, 2 and 4: tests/test_gpu_fit_scales.py."""
 import os
 
 import numpy as np

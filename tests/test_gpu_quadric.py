@@ -16,7 +16,9 @@ An ill-conditioned pair may be a failed fit or any finite values.  Every output 
 
 Measured on the CPU when the estimator was defined, on these clouds, rows and radii: reordering a ball at random moved a by at most
 1.9e-3 B and an 80-bit evaluation by 1.3e-3 B, the curvatures by 2.4e-4 of their bound -- a margin of ~500 over what a summation order
-should give.  The ill-conditioned share was 0 everywhere except box at the middle scale (1 of 464 pairs)."""
+should give.  The ill-conditioned share was 0 everywhere except box at the middle scale (1 of 464 pairs).
+
+Every cloud here has three radii: this module runs ``quadric_kernel<3>``.  S = 1, 2 and 4: tests/test_gpu_fit_scales.py."""
 import os
 
 import numpy as np

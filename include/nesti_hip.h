@@ -920,7 +920,7 @@ int nesti_debug_tower_step(const nesti_model_t* m, int tower, const nesti_debug_
                            void* stream);
 
 /* ---- test hook: one launcher of the deciding kernels alone (tests/test_gpu_decisions.py; no reference counterpart) ------
- * The two-stage gate, the conditioning guard, the gate's softmax and the routing helpers (csrc/kernels.h, csrc/pool.hip), each
+ * The two-stage gate, the conditioning guard, the gate's softmax and the routing helpers (csrc/decide.h, csrc/decide.hip), each
  * run on CALLER buffers: no model, the counter blocks (cstat, gstat, rstat: 8 x uint64 each) and the 512-byte fcounts block
  * are the caller's too.  op names the launcher; the struct carries its arguments under the launcher's own names, the few
  * launchers whose names differ say so below.  Forwards and nothing else; before any device call it refuses an unknown op, a

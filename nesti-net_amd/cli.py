@@ -535,7 +535,7 @@ def main(argv=None):
             printout(orient_line(name, FLAGS.orient, ost, cloud.patch_count))
         torch.cuda.synchronize()
         if FLAGS.query_positions:
-            # the sentinel (pool.hip: mask_empty_queries_kernel): expert -1; the single-tower models have only the (0, 0, 0) normal
+            # the sentinel (decide.hip: mask_empty_queries_kernel): expert -1; the single-tower models have only the (0, 0, 0) normal
             alone = (expert == -1) if expert is not None else (normals == 0).all(dim=1)
             printout("query positions of %s: %d, of which %d had no neighbourhood (no cloud point inside any ball: written as 0 0 0 / -1 / 0)"
                      % (name, cloud.patch_count, int(alone.sum().item())))

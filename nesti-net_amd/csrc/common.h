@@ -202,10 +202,12 @@ template <> struct Elem<NESTI_BF16X3> : Elem<NESTI_BF16> {};
 template <> struct Elem<NESTI_F16X3> : Elem<NESTI_F16> {};
 template <int DT> constexpr bool is_x3 = (DT == NESTI_BF16X3 || DT == NESTI_F16X3);
 
-// ---- optional kernel timing (model.hip) -----------------------------------------
+// ---- optional kernel timing (prof.hip) ------------------------------------------
 void prof_phase(int phase);                                 // NESTI_PHASE_*: what the following launches are booked under
 int prof_begin(int category, hipStream_t st);              // returns a token for prof_end (-1: nothing recorded)
 void prof_end(int category, int token, hipStream_t st);
+// whether `st` is being captured into a hipGraph: such a call records no timing spans and keeps every launch on `st` itself
+bool stream_capturing(hipStream_t st);
 
 // ---- launchers implemented in the .hip files -------------------------------
 // embed4: 3^3 grid only -- write rows in a 4^3 index space (64 rows per point, dead rows zero) for the conv towers

@@ -1,7 +1,9 @@
 // What the host-only units of libnesti_hip.so (graph.cpp, pack.cpp, plan.cpp) share with the HIP files: the error slot, the dtype
-// predicates, the layout constants the weight packer and the planner share with the kernels, and the kernels' parameter blocks
-// (ConvParams, PoolParams).  No HIP header: common.h includes this file, so host and device code see the same definitions.
+// predicates, the layout constants the weight packer and the planner share with the kernels, the counter and workspace words of the
+// deciding kernels, and the kernels' parameter blocks (ConvParams, PoolParams).  No HIP header: common.h includes this file, so host
+// and device code see the same definitions.
 #pragma once
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <string>
@@ -31,11 +33,53 @@ static inline int kernel_dtype(int dt) { return dt == NESTI_BF16X3 ? NESTI_BF16 
 constexpr int kPairPlanes = 2;    // hi, lo
 static inline int act_planes(int dt) { return (dt == NESTI_BF16X3 || dt == NESTI_F16X3) ? kPairPlanes : 1; }
 constexpr int kSplitGroup = 64;
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+constexpr size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 constexpr int kRowBytes = 128;    // bytes of one K-chunk row in LDS (64 x 16-bit or 32 x f32)
 constexpr int kTileM = 512;       // GEMM rows (voxels x points) per workgroup
 constexpr int kMaxTaps = 125;     // 5^3
+
+// ---- the words the deciding kernels (decide.hip) share with their host readers (model.hip) and the planner (plan.cpp) ------------
+#ifdef __HIP__
+#define NESTI_HD __host__ __device__
+#else
+#define NESTI_HD
+#endif
+// A model's counter blocks: 64 bytes = eight 64-bit words each (include/nesti_hip.h: nesti_cascade_stats_t, nesti_x8_guard_stats_t,
+// nesti_reproducible_stats_t).  cstat, the two-stage gate: queries; rechecked (rows decided by the f16x3 gate, widening rounds
+// included); changed; the bits of max_margin_err; a double, the sum of the squared pair errors; the number of pairs in that sum; rows
+// rechecked by a widening round; forward calls whose widening round was not empty
+enum CStat { kCQueries, kCRechecked, kCChanged, kCMaxErrBits, kCSumSq, kCPairs, kCWidened, kCWidenEvents };
+// gstat, the conditioning guard: queries; rows re-evaluated; the bits of the largest |dn|; rows dropped because a list was full
+enum GStat { kGQueries, kGRechecked, kGMaxDnBits, kGDropped };
+// rstat, the reproducible mode: rows whose error would have widened the gate's margin / the guard's band
+enum RStat { kRGateViolations, kRGuardViolations };
+// a float >= 0 kept as its bits in a counter word (it orders like its bit pattern, so atomicMax keeps the largest)
+NESTI_HD inline float counter_float(unsigned long long word) {
+  const uint32_t bits = (uint32_t)word;
+  float f;
+  __builtin_memcpy(&f, &bits, 4);
+  return f;
+}
+// the threshold of a forward call of the two-stage gate (decide.hip: gate_begin_kernel; nesti_model_cascade_stats reports it)
+NESTI_HD inline float gate_tau_eff(float tau, float widen, float max_margin_err) { return fmaxf(tau, widen * max_margin_err); }
+// the conditioning guard's widen / theta, theta = sqrt(2 x bar): scale x |dn| is the |n| below which an output may tilt by more than the bar
+inline float x8_guard_scale() { return NESTI_X8_GUARD_WIDEN / sqrtf(2.f * NESTI_X8_GUARD_BAR); }
+
+// fcounts, a block of the call's workspace (plan.cpp: ws_layout), as int32 words:
+//   [0] rows flagged by the filter pass, [kRoundCountsOff + r] of them in recheck round r (cap rows per round),
+//   [kTauEffOff] the call's threshold tau_eff as a float (raised to the upper end of every band a widening pass has covered),
+//   [kWidenUpperOff] the upper end of the current widening pass's band (float, snapshotted when the pass starts),
+//   [kWidenCountOff] rows flagged by the current widening pass, [kWidenRoundsOff + r] of them in its tower round r
+constexpr int kFcountsBytes = 512;
+constexpr int kMaxCascadeRounds = 24;
+constexpr int kRoundCountsOff = 8, kTauEffOff = 40, kWidenUpperOff = 41, kWidenCountOff = 48, kWidenRoundsOff = 56;
+static_assert(kRoundCountsOff + kMaxCascadeRounds <= kTauEffOff && (kWidenRoundsOff + kMaxCascadeRounds) * 4 <= kFcountsBytes, "fcounts layout");
+// ecounts, the next block, as int32 words: [e * rounds + r] rows of expert e's round r from word 0 (plan.h: they end before the
+// guard's words), [kGuardCountOff + e] the length of the guard's list for expert e, [kGuardSlotOff], [+ 1] the |n| band (floats)
+constexpr int kEcountsBytes = 1024;
+constexpr int kGuardCountOff = 128, kGuardSlotOff = 140;
+static_assert(kGuardCountOff + NESTI_MAX_EXPERTS <= kGuardSlotOff && (kGuardSlotOff + 2) * 4 <= kEcountsBytes, "ecounts layout");
 
 // host-side conversions used by the weight repacker (pack.cpp)
 uint16_t host_f32_to_bf16(float f);

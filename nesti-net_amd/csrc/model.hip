@@ -1,7 +1,8 @@
-// Host side of libnesti_hip.so that touches the device: C-ABI entry points, the kernel profiler, the tower runner and the forward
-// paths.  What a launch is and where its buffers live is decided by the planner (plan.cpp); here a launch gets its device addresses
-// and goes out.  The graph (graph.cpp), batch-norm folding and weight repacking for the MFMA kernels (pack.cpp) and the planner are
-// host-only units of their own.
+// The model on the device and its forward paths: the model object with its packed layers and counter blocks, the tower runner, the
+// gate (one pass or the two-stage cascade), the routed experts with their conditioning guard, and the C-ABI entries that create,
+// configure, read and run a model.  What a launch is and where its buffers live is decided by the planner (plan.cpp); here a launch
+// gets its device addresses and goes out.  The deciding kernels (decide.hip), the kernel profiler (prof.hip), the graph (graph.cpp),
+// batch-norm folding and weight repacking (pack.cpp) and the planner are units of their own.
 #include <math.h>
 #include <string.h>
 
@@ -12,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "decide.h"
 #include "kernels.h"
 #include "plan.h"
 
@@ -38,69 +40,6 @@ static thread_local std::string g_error;
 // (nesti_model_set_expert_mix / _gate_mix); off by default, so product models neither pay the packing time nor hold the copies
 static bool g_experiment_mix = false;
 void set_error(const std::string& msg) { g_error = msg; }
-
-// ------------------------------------------------------------------------------------------
-// optional per-category kernel timing with hipEvents on the launch stream (bench.py roofline leg)
-// ------------------------------------------------------------------------------------------
-constexpr int kProfSlots = NESTI_PROF_PHASES * NESTI_PROF_CATEGORIES;   // slot = phase * NESTI_PROF_CATEGORIES + category
-struct ProfState {
-  bool on = false;
-  int phase = NESTI_PHASE_INPUT;     // set by the forward path (prof_phase); launches are booked under it
-  std::vector<hipEvent_t> pool;      // recycled events
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> spans[kProfSlots];
-  double ms[kProfSlots] = {0};
-  long long launches[kProfSlots] = {0};
-};
-static ProfState g_prof;
-static std::mutex g_prof_mu;   // forward calls may come from several host threads (one stream each)
-
-static hipEvent_t prof_event() {
-  if (!g_prof.pool.empty()) { hipEvent_t e = g_prof.pool.back(); g_prof.pool.pop_back(); return e; }
-  hipEvent_t e = nullptr;
-  (void)hipEventCreate(&e);
-  return e;
-}
-// A stream that is being captured into a hipGraph records nothing: events captured into a graph cannot be
-// synchronised on or timed afterwards.
-static bool prof_capturing(hipStream_t st) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return false; }
-  return cs != hipStreamCaptureStatusNone;
-}
-void prof_phase(int phase) { if (g_prof.on) g_prof.phase = phase; }
-// prof_begin returns a token for prof_end (-1: nothing recorded): slot * 2^20 + index of the span within the slot
-int prof_begin(int cat, hipStream_t st) {
-  if (!g_prof.on || prof_capturing(st)) return -1;
-  std::lock_guard<std::mutex> lk(g_prof_mu);
-  // the input kernels are launched between forward passes, whatever phase the last one ended in
-  const int phase = (cat == NESTI_PROF_MUPS || cat == NESTI_PROF_PATCHES) ? NESTI_PHASE_INPUT : g_prof.phase;
-  const int slot = phase * NESTI_PROF_CATEGORIES + cat;
-  if (g_prof.spans[slot].size() >= (1u << 20)) return -1;
-  hipEvent_t a = prof_event(), b = prof_event();
-  (void)hipEventRecord(a, st);
-  g_prof.spans[slot].push_back({a, b});
-  return (slot << 20) | ((int)g_prof.spans[slot].size() - 1);
-}
-void prof_end(int, int token, hipStream_t st) {
-  if (token < 0) return;
-  std::lock_guard<std::mutex> lk(g_prof_mu);
-  const int slot = token >> 20, idx = token & ((1 << 20) - 1);
-  if (slot < kProfSlots && idx < (int)g_prof.spans[slot].size()) (void)hipEventRecord(g_prof.spans[slot][idx].second, st);
-}
-static void prof_collect() {
-  std::lock_guard<std::mutex> lk(g_prof_mu);
-  for (int c = 0; c < kProfSlots; ++c) {
-    for (auto& sp : g_prof.spans[c]) {
-      (void)hipEventSynchronize(sp.second);
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, sp.first, sp.second) == hipSuccess) g_prof.ms[c] += ms;
-      g_prof.launches[c] += 1;
-      g_prof.pool.push_back(sp.first);
-      g_prof.pool.push_back(sp.second);
-    }
-    g_prof.spans[c].clear();
-  }
-}
 
 namespace {
 
@@ -170,7 +109,7 @@ struct nesti_model {
   // (include/nesti_hip.h: nesti_model_set_x8_layers), x8_fmt which of the two forms forward calls use (8 or 6; nesti_model_set_x8_format)
   int x8_mask = 0;
   int x8_fmt = 6;
-  // ... and their conditioning guard (pool.hip: x8_guard_*): outputs with |n| below max(x8_guard_thr, NESTI_X8_GUARD_WIDEN x largest
+  // ... and their conditioning guard (decide.hip: x8_guard_*): outputs with |n| below max(x8_guard_thr, NESTI_X8_GUARD_WIDEN x largest
   // measured |dn| / theta) are re-evaluated in f16x3 proper; gstat = the device counters (include/nesti_hip.h: nesti_x8_guard_stats_t)
   float x8_guard_thr = NESTI_X8_GUARD_DEFAULT;
   int x8_guard_walk = NESTI_GUARD_WALK_GRID;   // workgroups of the guard towers' walking launches (host.h: ConvParams::walk)
@@ -200,7 +139,7 @@ struct nesti_model {
   int gate_mix = 0;          // EXPERIMENT (nesti_model_set_gate_mix): the f16x3 gating passes run their tap layers single-product
   float tau = 0.25f;
   nesti::StatBlock cstat;
-  // nesti_model_set_reproducible: rstat = the mode's own 64-byte counter block ([0] gate_violations, [1] guard_violations), allocated
+  // nesti_model_set_reproducible: rstat = the mode's own 64-byte counter block (host.h: RStat), allocated
   // with cstat / gstat; forward calls hand it to the kernels only while the mode is on (frozen() below), and then no decision of
   // theirs reads cstat / gstat
   bool reproducible = false;
@@ -322,7 +261,7 @@ int gate_cascade(const nesti_model* m, const void* X0, int B, const Arena& A, fl
   if (!expert) expert = A.at<int32_t>(A.L.expert);   // the recheck needs the arg-max whether or not the caller wants it
   float* keep = A.at<float>(A.L.keep);
   int32_t* flag_list = A.at<int32_t>(A.L.flags);
-  int32_t* fcounts = A.at<int32_t>(A.L.fcounts);         // kernels.h: kRoundCountsOff, kTauEffOff, kWidenCountOff, kWidenRoundsOff
+  int32_t* fcounts = A.at<int32_t>(A.L.fcounts);         // host.h: kRoundCountsOff, kTauEffOff, kWidenCountOff, kWidenRoundsOff
   const int lstride = m->graph.gate.bufs[m->graph.gate.out_buf].C;
   float* logits = nullptr;
   const RunCtx fast = pass_ctx(m, -1, /*fast=*/true, 0, B, nullptr, nullptr, stream, 0);
@@ -369,50 +308,109 @@ int gate_impl(const nesti_model* m, const void* X0, int B, const Arena& A, float
   return launch_gate_finish(logits, lstride, B, m->graph.cfg.n_experts, probs, expert, counts, lists, stream);
 }
 
-// counts / lists = the routing (null: every expert on every point); ecounts = the arena's per-(expert, round) counter block; glist = the
-// conditioning guard's row list (x8 models, top-1 routing)
-constexpr int kGuardCountOff = 128, kGuardSlotOff = 140;      // int32 words of the ecounts block: [E] list lengths, the |n| band
-int experts_impl(const nesti_model* m, const void* X0, int B, const Arena& A, const int32_t* counts, const int32_t* lists, float* normals,
-                 hipStream_t stream) {
-  int32_t* ecounts = A.at<int32_t>(A.L.ecounts);
-  int32_t* glist = m->graph.x8 ? A.at<int32_t>(A.L.glist) : nullptr;
-  const int E = m->graph.cfg.n_experts;
-  const int cap = std::min(expert_cap(A.NB), B), rounds = (B + cap - 1) / cap;
-  prof_phase(NESTI_PHASE_EXPERTS);
-  if (counts && launch_round_counts(counts, E, cap, rounds, ecounts, stream)) return 1;
-  const size_t x0_row = mups_row_bytes(m->mode());
-  // the conditioning guard of the FP8 cross-term layers (pool.hip): once expert e's rows are written, those whose |n| falls inside the
-  // pass's band go through the SAME tower in f16x3 proper, which replaces them and measures |dn|; a second pass covers the band a
-  // larger measurement of THIS call may have opened (normally empty).  A guard tower sees a handful of rows, so it is latency-bound
-  // (~3 ms: one workgroup walks a layer's whole K loop): in the first pass expert e's guard runs on the model's auxiliary stream, in its
-  // own slice of the tower workspace, while the caller's stream goes on with expert e + 1
-  const bool guard = counts && glist && m->x8_mask && m->gstat && m->x8_guard_thr >= 0.f;
-  const int gcap = std::min(guard_cap(A.NB), B);
-  float* gslot = guard ? reinterpret_cast<float*>(ecounts + kGuardSlotOff) : nullptr;
-  int32_t* gcount = guard ? ecounts + kGuardCountOff : nullptr;                 // [E]
-  const float gscale = NESTI_X8_GUARD_WIDEN / sqrtf(2.f * NESTI_X8_GUARD_BAR);
-  unsigned long long* rstat = m->frozen();   // reproducible mode: the band is [0, thr) and pass 0 is the only pass
-  size_t main_bytes = 0, guard_bytes = 0;
-  for (int e = 0; e < E && guard; ++e) {
-    main_bytes = std::max(main_bytes, align_up(tower_bytes(m->graph.experts[e], cap, m->dtype), 256));
-    guard_bytes = std::max(guard_bytes, tower_bytes(m->graph.experts[e], gcap, m->dtype));
+// The conditioning guard of the FP8 cross-term layers (decide.hip) over one experts_impl call: once expert e's rows are written, those
+// whose |n| falls inside the pass's band go through the SAME tower in f16x3 proper, which replaces them and measures |dn|; a second
+// pass covers the band a larger measurement of THIS call may have opened (normally empty).  A guard tower sees a handful of rows, so it
+// is latency-bound (~3 ms: one workgroup walks a layer's whole K loop): in the first pass expert e's guard runs on the model's
+// auxiliary stream (nesti_model::GuardLane), in its own slice of the tower workspace, while the caller's stream goes on with expert e + 1
+struct Guard {
+  const nesti_model* m;
+  const void* X0;
+  const int B;
+  const Arena& A;
+  const int32_t *counts, *lists;   // the routing
+  float* normals;
+  hipStream_t stream;              // the caller's
+  bool on, side = false;           // side: the first pass runs on the lane's stream, in [main_bytes, ...) of the tower arena
+  nesti_model::GuardLane* lane = nullptr;
+  std::unique_lock<std::mutex> lock;   // the lane's auxiliary stream and events: one call enqueues on them at a time
+  size_t main_bytes = 0;
+  int32_t* glist;                  // [E][gcap] row lists
+  const int gcap;
+  float* gslot = nullptr;          // the |n| band and the [E] list lengths: words of the ecounts block (host.h)
+  int32_t* gcount = nullptr;
+  const float scale = x8_guard_scale();
+  unsigned long long* rstat;       // reproducible mode: the band is [0, thr) and pass 0 is the only pass
+
+  // cap: rows of a routed expert's round (the caller's stream keeps a tower workspace of that many rows)
+  Guard(const nesti_model* m, const void* X0, int B, const Arena& A, const int32_t* counts, const int32_t* lists, float* normals, int cap,
+        hipStream_t stream)
+      : m(m), X0(X0), B(B), A(A), counts(counts), lists(lists), normals(normals), stream(stream),
+        glist(m->graph.x8 ? A.at<int32_t>(A.L.glist) : nullptr), gcap(std::min(guard_cap(A.NB), B)), rstat(m->frozen()) {
+    on = counts && glist && m->x8_mask && m->gstat && m->x8_guard_thr >= 0.f;
+    if (!on) return;
+    gslot = A.at<float>(A.L.ecounts) + kGuardSlotOff;
+    gcount = A.at<int32_t>(A.L.ecounts) + kGuardCountOff;
+    size_t guard_bytes = 0;
+    for (const Tower& T : m->graph.experts) {
+      main_bytes = std::max(main_bytes, align_up(tower_bytes(T, cap, m->dtype), 256));
+      guard_bytes = std::max(guard_bytes, tower_bytes(T, gcap, m->dtype));
+    }
+    // (a stream that is being captured into a hipGraph keeps everything on itself: the guard then runs on the caller's stream, one
+    // tower after the other, like it does when the two workspace slices do not fit)
+    lane = m->guard_lane(stream);
+    side = lane->gstream && main_bytes + guard_bytes <= A.tower_size() && !stream_capturing(stream);
+    if (side) lock = std::unique_lock<std::mutex>(lane->gmu);
   }
-  // (a stream that is being captured into a hipGraph keeps everything on itself: the guard then runs on the caller's stream, one
-  // tower after the other, like it does when the two workspace slices do not fit)
-  nesti_model::GuardLane* lane = guard ? m->guard_lane(stream) : nullptr;
-  const bool side = guard && lane->gstream && main_bytes + guard_bytes <= A.tower_size() && !prof_capturing(stream);
-  std::unique_lock<std::mutex> glk;
-  if (side) glk = std::unique_lock<std::mutex>(lane->gmu);   // the lane's auxiliary stream and events: one call enqueues on them at a time
-  auto guard_expert = [&](int e, hipStream_t st, unsigned char* arena, size_t arena_bytes, int walk_grid) -> int {
+
+  // expert e's rows inside the current band: flag, re-evaluate, replace
+  int expert(int e, hipStream_t st, unsigned char* arena, size_t arena_bytes, int walk_grid) {
     const Tower& T = m->graph.experts[e];
     int32_t* gl = glist + (size_t)e * gcap;
     if (launch_x8_guard_flag(lists + (size_t)e * B, counts + e, B, normals, gslot, gl, gcount + e, gcap, m->gstat.dev, st)) return 1;
     float* out = nullptr;
     const RunCtx rc = pass_ctx(m, e, false, /*x8_mask=*/0, gcap, gcount + e, gl, st, walk_grid);   // a small walking grid (a few dozen rows)
     if (run_tower(rc, T, X0, arena, arena_bytes, &out)) return 1;
-    return launch_x8_guard_fix(out, T.bufs[T.out_buf].C, gl, gcount + e, gcap, normals, m->gstat.dev, m->x8_guard_thr, gscale, rstat, st);
-  };
-  if (guard && launch_x8_guard_begin(0, m->x8_guard_thr, gscale, B, m->gstat.dev, gslot, rstat, stream)) return 1;
+    return launch_x8_guard_fix(out, T.bufs[T.out_buf].C, gl, gcount + e, gcap, normals, m->gstat.dev, m->x8_guard_thr, scale, rstat, st);
+  }
+
+  // before the first expert: the band of the first pass
+  int begin() { return on && launch_x8_guard_begin(0, m->x8_guard_thr, scale, B, m->gstat.dev, gslot, rstat, stream); }
+
+  // after expert e's rounds are enqueued on the caller's stream: its first pass
+  int after_expert(int e) {
+    if (!on) return 0;
+    prof_phase(NESTI_PHASE_GUARD);
+    if (side) {
+      NESTI_CHECK_HIP(hipEventRecord(lane->gev_done[e], stream));
+      NESTI_CHECK_HIP(hipStreamWaitEvent(lane->gstream, lane->gev_done[e], 0));
+      if (expert(e, lane->gstream, A.tower() + main_bytes, A.tower_size() - main_bytes, m->x8_guard_walk)) return 1;
+    } else if (expert(e, stream, A.tower(), A.tower_size(), m->x8_guard_walk)) {
+      return 1;
+    }
+    prof_phase(NESTI_PHASE_EXPERTS);
+    return 0;
+  }
+
+  // after the last expert: the lane joins the caller's stream, then the widening passes on it
+  int finish() {
+    if (!on) return 0;
+    if (side) {
+      NESTI_CHECK_HIP(hipEventRecord(lane->gev_join, lane->gstream));
+      NESTI_CHECK_HIP(hipStreamWaitEvent(stream, lane->gev_join, 0));
+      lock.unlock();
+    }
+    prof_phase(NESTI_PHASE_GUARD);
+    for (int pass = 1; pass <= (rstat ? 0 : NESTI_X8_GUARD_WIDEN_PASSES); ++pass) {
+      if (launch_x8_guard_begin(pass, m->x8_guard_thr, scale, B, m->gstat.dev, gslot, nullptr, stream)) return 1;
+      for (int e = 0; e < (int)m->graph.experts.size(); ++e)
+        if (expert(e, stream, A.tower(), A.tower_size(), NESTI_GUARD_WIDEN_WALK_GRID)) return 1;
+    }
+    return 0;
+  }
+};
+
+// counts / lists = the routing (null: every expert on every point); ecounts = the arena's per-(expert, round) counter block
+int experts_impl(const nesti_model* m, const void* X0, int B, const Arena& A, const int32_t* counts, const int32_t* lists, float* normals,
+                 hipStream_t stream) {
+  int32_t* ecounts = A.at<int32_t>(A.L.ecounts);
+  const int E = m->graph.cfg.n_experts;
+  const int cap = std::min(expert_cap(A.NB), B), rounds = (B + cap - 1) / cap;
+  prof_phase(NESTI_PHASE_EXPERTS);
+  if (counts && launch_round_counts(counts, E, cap, rounds, ecounts, stream)) return 1;
+  const size_t x0_row = mups_row_bytes(m->mode());
+  Guard guard(m, X0, B, A, counts, lists, normals, cap, stream);
+  if (guard.begin()) return 1;
   for (int e = 0; e < E; ++e) {
     const Tower& T = m->graph.experts[e];
     const int ostride = T.bufs[T.out_buf].C;
@@ -432,32 +430,9 @@ int experts_impl(const nesti_model* m, const void* X0, int B, const Arena& A, co
         if (launch_scatter3(out, ostride, nullptr, nullptr, take, normals + ((size_t)e * B + (size_t)r * cap) * 3, stream)) return 1;
       }
     }
-    if (guard) {
-      prof_phase(NESTI_PHASE_GUARD);
-      if (side) {
-        NESTI_CHECK_HIP(hipEventRecord(lane->gev_done[e], stream));
-        NESTI_CHECK_HIP(hipStreamWaitEvent(lane->gstream, lane->gev_done[e], 0));
-        if (guard_expert(e, lane->gstream, A.tower() + main_bytes, A.tower_size() - main_bytes, m->x8_guard_walk)) return 1;
-      } else if (guard_expert(e, stream, A.tower(), A.tower_size(), m->x8_guard_walk)) {
-        return 1;
-      }
-      prof_phase(NESTI_PHASE_EXPERTS);
-    }
+    if (guard.after_expert(e)) return 1;
   }
-  if (guard) {
-    if (side) {
-      NESTI_CHECK_HIP(hipEventRecord(lane->gev_join, lane->gstream));
-      NESTI_CHECK_HIP(hipStreamWaitEvent(stream, lane->gev_join, 0));
-      glk.unlock();
-    }
-    prof_phase(NESTI_PHASE_GUARD);
-    for (int pass = 1; pass <= (rstat ? 0 : NESTI_X8_GUARD_WIDEN_PASSES); ++pass) {
-      if (launch_x8_guard_begin(pass, m->x8_guard_thr, gscale, B, m->gstat.dev, gslot, nullptr, stream)) return 1;
-      for (int e = 0; e < E; ++e)
-        if (guard_expert(e, stream, A.tower(), A.tower_size(), NESTI_GUARD_WIDEN_WALK_GRID)) return 1;
-    }
-  }
-  return 0;
+  return guard.finish();
 }
 
 }  // namespace
@@ -604,9 +579,8 @@ int nesti_model_x8_guard_stats(const nesti_model_t* m, nesti_x8_guard_stats_t* o
   unsigned long long h[8];
   NESTI_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
   if (m->gstat.read(h, reset)) return 1;
-  out->queries = h[0]; out->rechecked = h[1]; out->dropped = h[3];
-  const uint32_t bits = (uint32_t)h[2];
-  memcpy(&out->max_dn, &bits, 4);
+  out->queries = h[kGQueries]; out->rechecked = h[kGRechecked]; out->dropped = h[kGDropped];
+  out->max_dn = counter_float(h[kGMaxDnBits]);
   out->thr = m->x8_guard_thr;
   out->thr_eff = m->x8_guard_thr < 0.f || m->reproducible ? m->x8_guard_thr
                                        : std::max(m->x8_guard_thr, NESTI_X8_GUARD_WIDEN * out->max_dn / sqrtf(2.f * NESTI_X8_GUARD_BAR));
@@ -630,15 +604,14 @@ int nesti_model_cascade_stats(const nesti_model_t* m, nesti_cascade_stats_t* out
   unsigned long long h[8];
   NESTI_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
   if (m->cstat.read(h, reset)) return 1;
-  out->queries = h[0]; out->rechecked = h[1]; out->changed = h[2];
-  const uint32_t bits = (uint32_t)h[3];
-  memcpy(&out->max_margin_err, &bits, 4);
+  out->queries = h[kCQueries]; out->rechecked = h[kCRechecked]; out->changed = h[kCChanged];
+  out->max_margin_err = counter_float(h[kCMaxErrBits]);
   out->tau = m->tau;
-  memcpy(&out->sum_sq_pair_err, &h[4], 8);
-  out->pairs = h[5];
-  out->widened = h[6];
-  out->widen_events = h[7];
-  out->tau_eff = m->reproducible ? m->tau : std::max(m->tau, NESTI_GATE_WIDEN * out->max_margin_err);
+  memcpy(&out->sum_sq_pair_err, &h[kCSumSq], 8);
+  out->pairs = h[kCPairs];
+  out->widened = h[kCWidened];
+  out->widen_events = h[kCWidenEvents];
+  out->tau_eff = m->reproducible ? m->tau : gate_tau_eff(m->tau, NESTI_GATE_WIDEN, out->max_margin_err);
   return 0;
 }
 
@@ -655,10 +628,9 @@ int nesti_model_reproducible_stats(const nesti_model_t* m, nesti_reproducible_st
   if (m->rstat.read(r, reset) || m->cstat.read(c, reset) || m->gstat.read(g, reset)) return 1;
   memset(out, 0, sizeof(*out));
   out->on = m->reproducible ? 1 : 0;
-  out->gate_violations = r[0]; out->guard_violations = r[1]; out->guard_dropped = g[3];
-  const uint32_t eb = (uint32_t)c[3], db = (uint32_t)g[2];
-  memcpy(&out->max_margin_err, &eb, 4);
-  memcpy(&out->max_dn, &db, 4);
+  out->gate_violations = r[kRGateViolations]; out->guard_violations = r[kRGuardViolations]; out->guard_dropped = g[kGDropped];
+  out->max_margin_err = counter_float(c[kCMaxErrBits]);
+  out->max_dn = counter_float(g[kGMaxDnBits]);
   out->tau = m->cascade ? m->tau : 0.f;
   out->thr = m->gstat ? m->x8_guard_thr : -1.f;
   return 0;
@@ -666,22 +638,22 @@ int nesti_model_reproducible_stats(const nesti_model_t* m, nesti_reproducible_st
 
 int nesti_model_gate_error_export(const nesti_model_t* m, float* dst_dev, void* stream) {
   if (!m || !m->cascade || !dst_dev) NESTI_FAIL("nesti_model_gate_error_export: not a NESTI_F16X3C model / null argument");
-  return launch_stat_max_export(m->cstat.dev + 3, dst_dev, (hipStream_t)stream);
+  return launch_stat_max_export(m->cstat.dev + kCMaxErrBits, dst_dev, (hipStream_t)stream);
 }
 
 int nesti_model_gate_error_import(nesti_model_t* m, const float* src_dev, int n, void* stream) {
   if (!m || !m->cascade || (n > 0 && !src_dev)) NESTI_FAIL("nesti_model_gate_error_import: not a NESTI_F16X3C model / null argument");
-  return launch_stat_max_import(m->cstat.dev + 3, src_dev, n, (hipStream_t)stream);
+  return launch_stat_max_import(m->cstat.dev + kCMaxErrBits, src_dev, n, (hipStream_t)stream);
 }
 
 int nesti_model_guard_error_export(const nesti_model_t* m, float* dst_dev, void* stream) {
   if (!m || !m->gstat || !dst_dev) NESTI_FAIL("nesti_model_guard_error_export: not an NESTI_F16X8 / NESTI_F16X8C model / null argument");
-  return launch_stat_max_export(m->gstat.dev + 2, dst_dev, (hipStream_t)stream);
+  return launch_stat_max_export(m->gstat.dev + kGMaxDnBits, dst_dev, (hipStream_t)stream);
 }
 
 int nesti_model_guard_error_import(nesti_model_t* m, const float* src_dev, int n, void* stream) {
   if (!m || !m->gstat || (n > 0 && !src_dev)) NESTI_FAIL("nesti_model_guard_error_import: not an NESTI_F16X8 / NESTI_F16X8C model / null argument");
-  return launch_stat_max_import(m->gstat.dev + 2, src_dev, n, (hipStream_t)stream);
+  return launch_stat_max_import(m->gstat.dev + kGMaxDnBits, src_dev, n, (hipStream_t)stream);
 }
 
 size_t nesti_workspace_bytes(const nesti_model_t* m, int max_batch) {
@@ -908,15 +880,6 @@ int nesti_estimate_normals_at(const nesti_model_t* m, const float* cloud_dev, in
                        n_ball_out_dev, stream);
 }
 
-int nesti_mask_empty_queries(const int32_t* n_eff_dev, int M, int S, float* normals_dev, int32_t* expert_dev, float* probs_dev, int E,
-                             void* stream) {
-  if (M <= 0) return 0;   // no rows: nothing to do
-  if (!n_eff_dev || !normals_dev) NESTI_FAIL("nesti_mask_empty_queries: null argument");
-  if (S < 1 || S > NESTI_MAX_SCALES) NESTI_FAIL("nesti_mask_empty_queries: bad n_scales");
-  if (probs_dev && E < 1) NESTI_FAIL("nesti_mask_empty_queries: probs_dev needs E >= 1 columns");
-  return launch_mask_empty_queries(n_eff_dev, M, S, normals_dev, expert_dev, probs_dev, E, (hipStream_t)stream);
-}
-
 }  // extern "C"
 
 // nesti_estimate_normals_multi / _multi_at: one body over the item type (nesti_shape_queries_t, nesti_shape_positions_t; `at` for the latter)
@@ -962,23 +925,6 @@ int nesti_estimate_normals_multi_at(const nesti_model_t* m, const nesti_shape_po
                         expert_out_dev, probs_out_dev, stream);
 }
 
-int nesti_profile_enable(int on) {
-  prof_collect();
-  for (int c = 0; c < kProfSlots; ++c) { g_prof.ms[c] = 0; g_prof.launches[c] = 0; }
-  g_prof.on = on != 0;
-  g_prof.phase = NESTI_PHASE_INPUT;
-  return 0;
-}
-
-int nesti_profile_read(double* ms, long long* launches) {
-  prof_collect();   // synchronises on the recorded events
-  for (int c = 0; c < kProfSlots; ++c) {
-    if (ms) ms[c] = g_prof.ms[c];
-    if (launches) launches[c] = g_prof.launches[c];
-  }
-  return 0;
-}
-
 int nesti_model_macs(const nesti_model_t* m, int tower, int kind, double* nominal, double* useful, double* issued) {
   if (!m) NESTI_FAIL("nesti_model_macs: null model");
   if (kind < -1 || kind > NESTI_PROF_ONE_BY_ONE) NESTI_FAIL("nesti_model_macs: kind must be -1 or a conv category");
@@ -1003,67 +949,6 @@ int nesti_debug_tower_step(const nesti_model_t* m, int tower, const nesti_debug_
   std::vector<unsigned char*> ptr;
   if (tower_ptrs(rc, T, mups_dev, (unsigned char*)ws_dev, ws_bytes, &ptr)) return 1;
   return run_op(rc, T, T.ops[op], ptr);
-}
-
-// ---- test hook: one launcher of the deciding kernels alone, on caller buffers (include/nesti_hip.h) --------------------------------
-int nesti_debug_decision_step(int op, const nesti_debug_decision_t* a, void* stream) {
-  const std::string who = "nesti_debug_decision_step: ";
-  if (!a) NESTI_FAIL(who + "null argument");
-  if (op < 0 || op >= NESTI_DECISION_OPS) NESTI_FAIL(who + "unknown op");
-  const hipStream_t st = (hipStream_t)stream;
-  auto u64 = [](uint64_t* p) { return reinterpret_cast<unsigned long long*>(p); };
-  const bool uses_E = op == NESTI_DECISION_GATE_FINISH || op == NESTI_DECISION_GATE_FLAG || op == NESTI_DECISION_GATE_WIDEN ||
-                      op == NESTI_DECISION_GATE_RECHECK || op == NESTI_DECISION_ROUTE;
-  if (uses_E && (a->E < 1 || a->E > NESTI_MAX_EXPERTS)) NESTI_FAIL(who + "E outside 1 .. NESTI_MAX_EXPERTS");
-  if (a->n_rounds > kMaxCascadeRounds) NESTI_FAIL(who + "n_rounds above kMaxCascadeRounds");
-#define NESTI_NEED(cond, what) if (!(cond)) NESTI_FAIL(who + "null pointer: " what)
-  switch (op) {
-    case NESTI_DECISION_GATE_FINISH:
-      NESTI_NEED(a->logits && (!a->counts || a->lists), "logits, lists");
-      return launch_gate_finish(a->logits, a->lstride, a->B, a->E, a->probs, a->expert, a->counts, a->lists, st);
-    case NESTI_DECISION_GATE_FLAG:
-      NESTI_NEED(a->logits && a->expert && a->keep && a->fcounts && a->flag_list && a->cstat, "logits, expert, keep, fcounts, flag_list, cstat");
-      return launch_gate_flag(a->logits, a->lstride, a->B, a->E, a->tau, a->widen, a->probs, a->expert, a->keep, a->fcounts, a->flag_list,
-                              a->cap, a->n_rounds, u64(a->cstat), u64(a->rstat), st);
-    case NESTI_DECISION_GATE_WIDEN:
-      NESTI_NEED(a->keep && a->fcounts && a->flag_list && a->cstat, "keep, fcounts, flag_list, cstat");
-      return launch_gate_widen(a->keep, a->B, a->E, a->widen, a->fcounts, a->flag_list, a->cap, a->n_rounds, u64(a->cstat), st);
-    case NESTI_DECISION_GATE_RECHECK:
-      NESTI_NEED(a->logits && a->flag_list && a->count_ptr && a->keep && a->expert && a->cstat && (!a->rstat || a->fcounts),
-                 "logits, flag_list, count_ptr, keep, expert, cstat, fcounts");
-      return launch_gate_recheck(a->logits, a->lstride, a->flag_list, a->count_ptr, a->cap, a->E, a->keep, a->probs, a->expert,
-                                 u64(a->cstat), a->fcounts, a->widen, u64(a->rstat), st);
-    case NESTI_DECISION_ROUND_COUNTS:
-      NESTI_NEED(a->counts && a->round_out, "counts, round_out");
-      return launch_round_counts(a->counts, a->n_lists, a->cap, a->n_rounds, a->round_out, st);
-    case NESTI_DECISION_SWITCH_FINISH:
-      NESTI_NEED(a->logits && (!a->counts || a->lists), "logits, lists");
-      return launch_switch_finish(a->logits, a->lstride, a->B, a->thr, a->probs, a->expert, a->counts, a->lists, st);
-    case NESTI_DECISION_X8_GUARD_BEGIN:
-      NESTI_NEED(a->gstat && a->slot, "gstat, slot");
-      return launch_x8_guard_begin(a->pass, a->thr, a->scale, a->B, u64(a->gstat), a->slot, u64(a->rstat), st);
-    case NESTI_DECISION_X8_GUARD_FLAG:
-      NESTI_NEED(a->lists && a->count_ptr && a->normals && a->slot && a->glist && a->gcount && a->gstat,
-                 "lists, count_ptr, normals, slot, glist, gcount, gstat");
-      return launch_x8_guard_flag(a->lists, a->count_ptr, a->B, a->normals, a->slot, a->glist, a->gcount, a->cap, u64(a->gstat), st);
-    case NESTI_DECISION_X8_GUARD_FIX:
-      NESTI_NEED(a->src && a->glist && a->gcount && a->normals && a->gstat, "src, glist, gcount, normals, gstat");
-      return launch_x8_guard_fix(a->src, a->sstride, a->glist, a->gcount, a->cap, a->normals, u64(a->gstat), a->thr, a->scale,
-                                 u64(a->rstat), st);
-    case NESTI_DECISION_ROUTE:
-      NESTI_NEED(a->expert && a->counts && a->lists, "expert, counts, lists");
-      return launch_route(a->expert, a->B, a->E, a->counts, a->lists, st);
-    case NESTI_DECISION_SCATTER3:
-      NESTI_NEED(a->src && a->normals, "src, normals");
-      return launch_scatter3(a->src, a->sstride, a->index, a->count_ptr, a->cap, a->normals, st);
-    case NESTI_DECISION_STAT_MAX_EXPORT:
-      NESTI_NEED(a->word && a->dst, "word, dst");
-      return launch_stat_max_export(u64(a->word), a->dst, st);
-    default:   // NESTI_DECISION_STAT_MAX_IMPORT
-      NESTI_NEED(a->word && a->src, "word, src");
-      return launch_stat_max_import(u64(a->word), a->src, a->B, st);
-  }
-#undef NESTI_NEED
 }
 
 }  // extern "C"

@@ -108,14 +108,14 @@ WsLayout ws_layout(const Mode& m, int NB) {
   L.expert = o; o += align_up((size_t)NB * 4, 256);
   L.counts = o; o += 256;
   L.lists = o; o += align_up((size_t)NB * NESTI_MAX_EXPERTS * 4, 256);
-  L.ecounts = o; o += 1024;          // [E][rounds] rows of each expert round; words 128-135 / 140-141: the conditioning guard's list lengths and |n| band
+  L.ecounts = o; o += kEcountsBytes;  // host.h: [E][rounds] rows of each expert round, the conditioning guard's list lengths and |n| band
   L.glist = o;
   if (m.g.x8) o += align_up((size_t)NESTI_MAX_EXPERTS * guard_cap(NB) * 4, 256);   // the conditioning guard's row lists, one per expert
   L.keep = L.flags = L.fcounts = o;
   if (m.cascade) {   // the f16 gate's logits, the flag list, [flag count | per-round counts]
     L.keep = o; o += align_up((size_t)NB * NESTI_MAX_EXPERTS * 4, 256);
     L.flags = o; o += align_up((size_t)NB * 4, 256);
-    L.fcounts = o; o += 512;          // kernels.h: the two-stage gate's per-call counters
+    L.fcounts = o; o += kFcountsBytes;  // host.h: the two-stage gate's per-call counters
   }
   L.tower = o; o += max_tower_bytes(m, NB);
   L.total = o;

@@ -58,7 +58,10 @@ inline int cascade_cap(int NB) { return NB <= 4096 ? NB : (int)align_up((size_t)
 // A routed expert sees about 1 / E of a batch, so its tower is sized for a quarter of a large batch and run in up to four
 // rounds over its routing list (rounds beyond the list's length launch empty grids: ~0.2 % of a 100k batch); the workspace of a
 // batch is then set by the gating net alone and a whole 100k-point cloud is one library batch in every mode but f16x3 / f32.
-inline int expert_cap(int NB) { return NB <= 8192 ? NB : (int)align_up((size_t)(NB + 3) / 4, 256); }
+constexpr int kExpertRounds = 4;
+constexpr int expert_cap(int NB) { return NB <= 8192 ? NB : (int)align_up((size_t)(NB + kExpertRounds - 1) / kExpertRounds, 256); }
+// the [E][rounds] round counts at the start of the ecounts block (host.h) end before the conditioning guard's words
+static_assert(kExpertRounds * expert_cap(8193) >= 8193 && NESTI_MAX_EXPERTS * kExpertRounds <= kGuardCountOff, "ecounts layout");
 // rows of ONE expert the conditioning guard can re-evaluate per pass (a fraction of a per cent of a batch are flagged at all)
 inline int guard_cap(int NB) { return expert_cap(NB) < 2048 ? expert_cap(NB) : 2048; }
 

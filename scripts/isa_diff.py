@@ -7,10 +7,13 @@ then
     python scripts/isa_diff.py OLD/nesti-net_amd/csrc NEW/nesti-net_amd/csrc
 
 Every *-hip-amdgcn-amd-amdhsa-gfx950.s is split per kernel symbol; comments, .file / .ident lines and the function index in
-local labels (.LBB<n>_<m>: it changes when the kernels of a file are emitted in another order) are dropped.  Printed per source
-file: kernels, identical, differing; per differing kernel: whether the opcode sequence is equal, the index of the first
-differing instruction and of the last v_mfma*, instruction counts and the code-object metadata on both sides.
-Exit status: 0 = same kernel symbols (whether or not their code differs), 1 = the symbol sets differ, 2 = usage.
+local labels (.LBB<n>_<m>: it changes when the kernels of a file are emitted in another order) are dropped.  Kernels are matched
+by symbol over the whole library, so a kernel that moved to another source file is compared with itself.  Printed per source
+file of the second build: kernels, identical, differing, moved (defined in another file of the first build); per differing
+kernel: whether the opcode sequence is equal, the index of the first differing instruction and of the last v_mfma*, instruction
+counts and the code-object metadata on both sides.
+Exit status: 0 = same kernel symbols (whether or not their code differs), 1 = the symbol sets differ or a symbol is defined in
+two files of one build, 2 = usage.
 """
 import re
 import shutil
@@ -76,10 +79,14 @@ def parse(path):
 
 
 def load(root):
-    out = {}
+    """({kernel symbol: (source file, Kernel)}, [symbols defined in two files]) of every assembly file under root."""
+    out, twice = {}, []
     for f in sorted(Path(root).rglob("*" + SUFFIX)):
-        out.setdefault(f.name[:-len(SUFFIX)], {}).update(parse(f))
-    return out
+        for sym, k in parse(f).items():
+            if sym in out:
+                twice.append(f"{sym}: {out[sym][0]}.hip and {f.name[:-len(SUFFIX)]}.hip")
+            out[sym] = (f.name[:-len(SUFFIX)], k)
+    return out, twice
 
 
 def demangle(syms):
@@ -99,31 +106,30 @@ def main(argv):
     if len(argv) != 3:
         print(__doc__)
         return 2
-    old, new = load(argv[1]), load(argv[2])
+    (old, old_twice), (new, new_twice) = load(argv[1]), load(argv[2])
     if not old or not new:
         print(f"no *{SUFFIX} under one of the directories: build with EXTRA_CXXFLAGS=-save-temps=obj")
         return 2
-    status = 0
-    total = [0, 0, 0]
-    details = []
-    print(f"{'file':<14}{'kernels':>8}{'identical':>11}{'differing':>11}")
-    for src in sorted(set(old) | set(new)):
-        ko, kn = old.get(src, {}), new.get(src, {})
-        if set(ko) != set(kn):
-            status = 1
-            for s in sorted(set(ko) - set(kn)):
-                details.append(f"{src}: only in the first build: {s}")
-            for s in sorted(set(kn) - set(ko)):
-                details.append(f"{src}: only in the second build: {s}")
-        both = sorted(set(ko) & set(kn))
-        if not ko and not kn:
-            continue             # a file without kernels (model.hip: host code only)
-        diff = [s for s in both
+    status = 1 if old_twice or new_twice else 0
+    details = [f"defined twice in the {n} build: {t}" for n, ts in (("first", old_twice), ("second", new_twice)) for t in ts]
+    if set(old) != set(new):
+        status = 1
+        details += [f"{old[s][0]}.hip: only in the first build: {s}" for s in sorted(set(old) - set(new))]
+        details += [f"{new[s][0]}.hip: only in the second build: {s}" for s in sorted(set(new) - set(old))]
+    both = sorted(set(old) & set(new))
+    total = [0, 0, 0, 0]
+    print(f"{'file':<14}{'kernels':>8}{'identical':>11}{'differing':>11}{'moved':>7}")
+    for src in sorted({new[s][0] for s in both}):
+        here = [s for s in both if new[s][0] == src]
+        ko, kn = {s: old[s][1] for s in here}, {s: new[s][1] for s in here}
+        diff = [s for s in here
                 if ko[s].lines != kn[s].lines or any(ko[s].meta.get(m) != kn[s].meta.get(m) for m in META)]
-        print(f"{src + '.hip':<14}{len(both):>8}{len(both) - len(diff):>11}{len(diff):>11}")
-        total[0] += len(both)
-        total[1] += len(both) - len(diff)
-        total[2] += len(diff)
+        moved = [s for s in here if old[s][0] != src]
+        print(f"{src + '.hip':<14}{len(here):>8}{len(here) - len(diff):>11}{len(diff):>11}{len(moved):>7}")
+        for i, n in enumerate((len(here), len(here) - len(diff), len(diff), len(moved))):
+            total[i] += n
+        for frm in sorted({old[s][0] for s in moved}):
+            details.append(f"{src}.hip: {sum(1 for s in moved if old[s][0] == frm)} kernels moved here from {frm}.hip")
         pretty = demangle(diff)
         for s in diff:
             a, b = ko[s], kn[s]
@@ -136,7 +142,7 @@ def main(argv):
                            f"instructions {pair(len(oa), len(ob))}")
             details.append("    " + "  ".join(f"{c}* {pair(a.count(c), b.count(c))}" for c in COUNTED))
             details.append("    " + "  ".join(f"{m} {pair(a.meta.get(m), b.meta.get(m))}" for m in META))
-    print(f"{'total':<14}{total[0]:>8}{total[1]:>11}{total[2]:>11}")
+    print(f"{'total':<14}{total[0]:>8}{total[1]:>11}{total[2]:>11}{total[3]:>7}")
     if details:
         print()
         print("\n".join(details))

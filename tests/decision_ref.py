@@ -1,4 +1,4 @@
-"""numpy restatement of the kernels that DECIDE (csrc/pool.hip): the two-stage gate (gate_begin / gate_flag / gate_widen_* /
+"""numpy restatement of the kernels that DECIDE (csrc/decide.hip): the two-stage gate (gate_begin / gate_flag / gate_widen_* /
 gate_recheck / round_counts), the conditioning guard (x8_guard_begin / _flag / _fix), the gate's softmax (gate_finish,
 switch_finish) and the routing helpers (route, scatter3, stat_max_export / _import, mask_empty_queries), with the counter blocks
 as plain Python lists and numpy arrays.
@@ -18,7 +18,7 @@ the squared sum or to `pairs`."""
 import numpy as np
 
 F32 = np.float32
-MAX_EXPERTS, MAX_ROUNDS = 8, 24                       # NESTI_MAX_EXPERTS; csrc/kernels.h: kMaxCascadeRounds
+MAX_EXPERTS, MAX_ROUNDS = 8, 24                       # NESTI_MAX_EXPERTS; csrc/host.h: kMaxCascadeRounds
 FC_ROUND_COUNTS, FC_TAU_EFF, FC_WIDEN_UPPER, FC_WIDEN_COUNT, FC_WIDEN_ROUNDS = 8, 40, 41, 48, 56   # int32 words of fcounts
 PROB_REL, SUM_REL, DN_REL = 2.0 ** -20, 2.0 ** -20, 2.0 ** -21
 GRID = 2.0 ** -10                                     # crafted logits are pairwise equal or at least this far apart

@@ -1,4 +1,4 @@
-"""The kernels that DECIDE (csrc/pool.hip) against tests/decision_ref.py, the numpy restatement of each.
+"""The kernels that DECIDE (csrc/decide.hip) against tests/decision_ref.py, the numpy restatement of each.
 
 Part A: every launcher alone through nesti_debug_decision_step, on crafted caller buffers: B = 300 rows (two 256-thread blocks,
 the last wave with 44 live lanes), logits of stride 64 with garbage beyond column E, E in {1, 2, 7, 8}, entries pairwise equal or

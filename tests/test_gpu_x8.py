@@ -1,5 +1,5 @@
 """NESTI_F16X8 / NESTI_F16X8C (round 6): the expert towers' tap layers at 8^3 (default: all four; mask 0xA: the 5^3 ones) with their
-two cross terms through ONE FP8 MFMA (conv8n.hip X8) and the conditioning guard behind them (pool.hip: x8_guard_*) -- pinned to
+two cross terms through ONE FP8 MFMA (conv8n.hip X8) and the conditioning guard behind them (decide.hip: x8_guard_*) -- pinned to
 f16x3 on 10k queries of the bench's cloud shape with a calibrated gate:
   * arg-max IDENTICAL to f16x3's on every query (the gating net is untouched) and probabilities bit-identical,
   * normals within 1 - cos <= 2.5e-6 of f16x3's on every query (the emulation that preceded the kernel: profiles/r06_fp8_cross_step0.txt;
@@ -152,7 +152,7 @@ def test_x8_prescale_follows_the_batch_norm_and_saturates_gracefully(gpu_device)
 
 
 def test_x8_conditioning_guard(gpu_device):
-    """Outputs of small norm are re-evaluated in f16x3 proper (pool.hip: x8_guard_*): threshold infinity == f16x3 bit for bit and
+    """Outputs of small norm are re-evaluated in f16x3 proper (decide.hip: x8_guard_*): threshold infinity == f16x3 bit for bit and
     measures |dn|; threshold < 0 == the bare FP8 loop; in between exactly the rows below the threshold carry f16x3's bits, the others
     the FP8 loop's; the threshold follows the measured |dn| (thr_eff), calibrate_x8_guard sets it from a sample, and with the guard in
     place the largest 1 - cos against f16x3 among the un-re-evaluated rows respects the bound 2.5e-6 / 1.5^2."""

@@ -37,6 +37,7 @@ extern "C" {
 #define NESTI_HOUGH_MAX_T 4096   /* nesti_hough_normals_nbr: the most triplets per row and scale, */
 #define NESTI_HOUGH_MAX_BINS 16  /* ... bins per axis of the accumulator */
 #define NESTI_HOUGH_MAX_ROT 8    /* ... and rotations of it */
+#define NESTI_SELECT_MAX_L 32    /* nesti_pca_select_nbr: the most neighbour counts of a ladder */
 #define NESTI_MAX_EXPERTS 8
 #define NESTI_MUPS_CH 20 /* channels per scale: utils/tf_util.py:711-720 */
 
@@ -632,6 +633,56 @@ int nesti_quadric_fit_nbr(const float* cloud_dev, int N, const int32_t* query_id
 int nesti_quadric_fit_nbr_at(const float* cloud_dev, int N, const float* query_xyz_dev, int M, const int32_t* nbr_dev, int K,
                              const int32_t* ks, int S, float* normals_out_dev, float* curv_out_dev, float* plane_out_dev,
                              float* radius_out_dev, int32_t* count_out_dev, void* stream);
+
+/* ---- scale-selected plane fit over neighbour lists (select.hip; DESIGN.md 2 "Scale-selected plane fit") ----------------------------
+ * The plane fit of nesti_pca_normals_nbr at every neighbour count of a LADDER, and per row the choice of one of them: the candidate of
+ * smallest surface variation e0 / (e0 + e1 + e2) -- Pauly, Keiser and Gross's multi-scale surface variation (2003) read as a selector,
+ * standing in for the bias / variance trade of Mitra and Nguyen (2003).  The conventions are the library's own (no parity with any
+ * published selector is claimed): the score uses only + - x / and comparisons, on the f32 eigenvalues AS WRITTEN, so a caller can
+ * recompute every choice from the outputs.  No model, no weights, no grid.
+ *
+ * Centres, nbr_dev [M, K] (1 <= K <= NESTI_KNN_MAX_K), the valid prefix and the untrusted-list rule are exactly as for
+ * nesti_pca_normals_nbr: the prefix ends at the first entry outside [0, N), a non-finite centre has an empty prefix, lists need not be
+ * sorted.  ks [L] (HOST) is the ladder: 1 <= L <= NESTI_SELECT_MAX_L, 1 <= ks[0] < ks[1] < ... < ks[L-1] <= K (strictly ascending).
+ * slack: fp64 on the host, finite and >= 0.
+ *  1 CANDIDATE c = 0 .. L-1.  n_c = min(ks[c], valid prefix); d and d2 per slot as for nesti_knn; r2_c = the largest d2 among the
+ *    first n_c slots (a prefix maximum: the last slot only where the list is sorted).  A short prefix gives several candidates the
+ *    same n_c: they are the same fit.
+ *  2 FIT.  The plane fit of candidate c is the output of nesti_pca_normals_nbr with ks = {ks[c]}, bit for bit: slot i is added in lane
+ *    i mod 64, a lane adds its slots in ascending order from +0.0, each of the nine totals goes through the same xor-butterfly
+ *    (offsets 32, 16, ..., 1), the same solve, rounding and sign rule.  n_c < 3 or r2_c == 0: normal 0 0 0, eigenvalues 0 0 0.
+ *  3 SCORE, from the f32 eigenvalues e0 <= e1 <= e2 of step 2:  den = ((double)e0 + (double)e1) + (double)e2;  v_c = (double)e0 / den.
+ *    Candidate c is ELIGIBLE iff n_c >= 3, r2_c > 0 and den > 0.
+ *  4 SELECTION.  v_min = the smallest v_c over the eligible candidates;  thr = v_min + v_min slack (a product, then a sum, each
+ *    rounded; +inf where it overflows);  sel = the LARGEST eligible c with v_c <= thr.  slack = 0: the arg-min, ties to the larger
+ *    count.  No eligible candidate: sel = -1 and every selected output is 0.
+ *  5 OUTPUTS (device; any may be NULL).  Selected:
+ *      normals_out_dev [M,3] f32    the normal of candidate sel
+ *      eig_out_dev     [M,3] f32    its eigenvalues, in units of r2_sel
+ *      sel_out_dev     [M]   int32  sel
+ *      k_out_dev       [M]   int32  n_sel
+ *      radius_out_dev  [M]   f32    (float)sqrt(r2_sel)
+ *    Per candidate:
+ *      variation_all_out_dev [M,L]   f32    (float)v_c, 0 where the candidate is not eligible
+ *      normals_all_out_dev   [M,L,3] f32    as nesti_pca_normals_nbr writes them
+ *      eig_all_out_dev       [M,L,3] f32
+ *      radius_all_out_dev    [M,L]   f32    (float)sqrt(r2_c)
+ *      count_all_out_dev     [M,L]   int32  n_c
+ * DETERMINISM: no atomics.  A row's bits are a pure function of (cloud, centre, list prefix, ladder, slack): independent of batching,
+ * of streams and of the grid the list came from.
+ * Argument errors -- those of nesti_pca_normals_nbr (null cloud / list / ks, N <= 0, K outside 1 .. NESTI_KNN_MAX_K, M < 0, rows
+ * beyond the cloud, null positions); L outside 1 .. NESTI_SELECT_MAX_L; a ladder that is not strictly ascending or lies outside
+ * 1 .. K; slack not finite or negative -- are reported under the entry's name before any device call; M = 0 is a no-op.  Each call
+ * enqueues one kernel on `stream`, neither synchronises nor reads anything back, and can be captured into a graph.  Under
+ * nesti_profile_enable the launch is booked in the patches category, like the other list fits. */
+int nesti_pca_select_nbr(const float* cloud_dev, int N, const int32_t* query_idx_dev, int M, int query_row0, const int32_t* nbr_dev,
+                         int K, const int32_t* ks, int L, double slack, float* normals_out_dev, float* eig_out_dev, int32_t* sel_out_dev,
+                         int32_t* k_out_dev, float* radius_out_dev, float* variation_all_out_dev, float* normals_all_out_dev,
+                         float* eig_all_out_dev, float* radius_all_out_dev, int32_t* count_all_out_dev, void* stream);
+int nesti_pca_select_nbr_at(const float* cloud_dev, int N, const float* query_xyz_dev, int M, const int32_t* nbr_dev, int K,
+                            const int32_t* ks, int L, double slack, float* normals_out_dev, float* eig_out_dev, int32_t* sel_out_dev,
+                            int32_t* k_out_dev, float* radius_out_dev, float* variation_all_out_dev, float* normals_all_out_dev,
+                            float* eig_all_out_dev, float* radius_all_out_dev, int32_t* count_all_out_dev, void* stream);
 
 /* ---- Hough-transform normals over neighbour lists (hough.hip; DESIGN.md 2 "Hough-transform normals") ------------------------------
  * The sharp-feature estimator after Boulch and Marlet (SGP 2012): planes through hashed triplets of a neighbourhood vote for their

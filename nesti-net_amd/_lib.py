@@ -116,6 +116,7 @@ ORIENT_MST, ORIENT_VIEWPOINT = 0, 1   # NESTI_ORIENT_*
 DEPTH_U16, DEPTH_F32 = 0, 1           # NESTI_DEPTH_*
 DEPTH_MAX_PIXELS = 1 << 26
 KNN_MAX_K = 256                       # NESTI_KNN_MAX_K
+SELECT_MAX_L = 32                     # NESTI_SELECT_MAX_L
 HOUGH_MAX_T, HOUGH_MAX_BINS, HOUGH_MAX_ROT = 4096, 16, 8   # NESTI_HOUGH_MAX_*
 
 
@@ -193,6 +194,8 @@ SIGNATURES = {
     "nesti_knn_at": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "nesti_pca_normals_nbr": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, ctypes.POINTER(ctypes.c_int32), _i, _vp, _vp, _vp, _vp, _vp]),
     "nesti_pca_normals_nbr_at": (_i, [_vp, _i, _vp, _i, _vp, _i, ctypes.POINTER(ctypes.c_int32), _i, _vp, _vp, _vp, _vp, _vp]),
+    "nesti_pca_select_nbr": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, ctypes.POINTER(ctypes.c_int32), _i, ctypes.c_double] + [_vp] * 11),
+    "nesti_pca_select_nbr_at": (_i, [_vp, _i, _vp, _i, _vp, _i, ctypes.POINTER(ctypes.c_int32), _i, ctypes.c_double] + [_vp] * 11),
     "nesti_quadric_fit_nbr": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, ctypes.POINTER(ctypes.c_int32), _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nesti_quadric_fit_nbr_at": (_i, [_vp, _i, _vp, _i, _vp, _i, ctypes.POINTER(ctypes.c_int32), _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nesti_hough_normals_nbr": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, ctypes.POINTER(ctypes.c_int32), _i, _i, _i, _i,

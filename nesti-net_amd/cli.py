@@ -16,7 +16,9 @@ neighbours instead of balls and adds ``<shape>.knn_radius``; ``--patch_radius R 
 caller's in place of the model configuration's.  ``--estimator hough --knn K[,K...]`` is the Hough-transform estimator of
 :mod:`.hough`, which exists over neighbour lists only: ``<shape>.normals`` (one scale), ``<shape>.hough_conf``, ``<shape>.hough_votes`` and
 ``<shape>.hough_count`` (every scale) and ``<shape>.knn_radius``.  ``--smooth ITERS`` smooths the written normals of any estimator with
-the feature-preserving filter of :mod:`.smooth` before the orientation and adds ``<shape>.smooth_support``."""
+the feature-preserving filter of :mod:`.smooth` before the orientation and adds ``<shape>.smooth_support``.  ``--estimator pca
+--knn_ladder K[,K...]`` is the scale-selected plane fit of :mod:`.select`: every row chooses its own neighbour count from the ladder;
+``<shape>.normals``, ``<shape>.select_k``, ``<shape>.select_eig``, ``<shape>.select_variation`` and ``<shape>.knn_radius``."""
 import argparse
 import ctypes
 import os
@@ -28,6 +30,7 @@ from . import pca as _pca
 from . import hough as _hough
 from . import smooth as _smooth
 from . import quadric as _quadric
+from . import select as _select
 from . import textio
 from . import weights as wts
 from .config import ARCH_EXPERTS, ARCH_MULTI, ARCH_SINGLE, ARCH_SWITCH, MAX_SCALES, NestiConfig
@@ -154,6 +157,18 @@ def build_parser():
                         "are those of the estimator -- <shape>.pca_count / <shape>.quadric_count then hold the neighbour counts, "
                         "--pca_scale / --quadric_scale index the counts -- plus <shape>.knn_radius (M rows of S distances to the "
                         "farthest neighbour).  --orient mst then uses the largest patch radius of --model's configuration")
+    p.add_argument("--knn_ladder", default=None, metavar="K[,K...]",
+                   help="--estimator pca: the scale-selected plane fit (DESIGN.md 2 'Scale-selected plane fit'): the plane fit over the "
+                        "K nearest neighbours for every K of the ladder -- 1 to 32 strictly ascending counts in 1 .. 256, or the word "
+                        "auto for %s -- and per row the candidate of smallest surface variation.  Writes <shape>.normals (the "
+                        "selected candidate), <shape>.select_k (M rows: the neighbours it used; 0: no candidate could be fitted, the "
+                        "normal is 0 0 0), <shape>.select_eig (M rows of its 3 eigenvalues), <shape>.select_variation (M rows of L "
+                        "scores, one per candidate) and <shape>.knn_radius (M rows: its radius).  Mutually exclusive with --knn, "
+                        "--patch_radius and --pca_scale; honours --sparse_patches, --query_positions, --smooth and --orient"
+                        % ",".join(map(str, _select.DEFAULT_LADDER)))
+    p.add_argument("--select_slack", type=float, default=None, metavar="X",
+                   help="--knn_ladder: choose the largest candidate whose surface variation is within (1 + X) of the row's smallest, "
+                        "X >= 0; 0 is the arg-min with ties to the larger count [default: 0]")
     p.add_argument("--smooth", type=int, default=0, metavar="ITERS",
                    help="smooth the written normals with ITERS passes (1 .. 64) of the feature-preserving filter of DESIGN.md 2 'Normal "
                         "smoothing', for every --estimator, before --orient: a row's normal becomes the weighted mean of its nearest "
@@ -283,6 +298,39 @@ FITS = {
 }
 
 
+def select_line(name, rows, ladder, slack, sel):
+    """The log line of ``--knn_ladder`` for shape ``name``: how many of the ``rows`` rows chose each count of the ladder; ``sel``: the
+    int32 indices into the ladder, -1 for a row without a fit."""
+    import numpy as np
+    hist = np.bincount(np.asarray(sel, dtype=np.int64) + 1, minlength=len(ladder) + 1)
+    return ("scale-selected plane fit of %s: %d rows, slack %g; chosen neighbour counts: %s; %d rows without a fit (written as 0 0 0)"
+            % (name, rows, slack, ", ".join("%d: %d" % (k, n) for k, n in zip(ladder, hist[1:].tolist())), int(hist[0])))
+
+
+def run_select(FLAGS, cfg, ladder, slack, pc_path, output_dir, printout, smooth=None):
+    """``--estimator pca --knn_ladder``: per shape the selected fit, the optional smoothing and orientation of its normals, and its
+    files.  No model is loaded."""
+    dataset = PointcloudPatchDataset(pc_path, FLAGS.testset, cfg, seed=3627473, sparse_patches=FLAGS.sparse_patches,
+                                     device="cuda:%d" % FLAGS.gpu, query_positions=bool(FLAGS.query_positions))
+    for ind, name in enumerate(dataset.shape_names):
+        cloud = dataset.get_shape(ind)
+        res = _select.select_cloud(cloud, ladder, slack, orient=None if FLAGS.orient == "0" else FLAGS.orient, viewpoint=FLAGS.viewpoint,
+                                   orient_k=FLAGS.orient_k, smooth=smooth)
+        printout(select_line(name, cloud.patch_count, ladder, slack, res["sel"]))
+        if smooth is not None:
+            printout(smooth_line(name, cloud.patch_count, smooth, res["smooth_count"]))
+            write_smooth_support(os.path.join(output_dir, name + ".smooth_support"), res["smooth_support"], res["smooth_count"])
+        if res["orient"] is not None:
+            printout(orient_line(name, FLAGS.orient, res["orient"], cloud.patch_count))
+        textio.write_f32(os.path.join(output_dir, name + ".normals"), res["normals"])
+        textio.write_i32(os.path.join(output_dir, name + ".select_k"), res["k"])
+        textio.write_f32(os.path.join(output_dir, name + ".select_eig"), res["eig"])
+        textio.write_f32(os.path.join(output_dir, name + ".select_variation"), res["variation_all"])
+        textio.write_f32(os.path.join(output_dir, name + ".knn_radius"), res["radius"])
+        printout("saved normals, chosen neighbour counts, eigenvalues and surface variations for " + name)
+    return 0
+
+
 def orient_line(name, mode, stats, rows):
     """The log line of an orientation pass over the ``rows`` rows of shape ``name``; ``stats``: ``orient.stats_dict``."""
     return ("orientation of %s (%s): %d of %d rows oriented, %d flipped, %d connected piece%s, %d edges"
@@ -345,6 +393,26 @@ def main(argv=None):
             ks = check_ks([int(v) for v in FLAGS.knn.split(",")])
         except ValueError as e:
             parser.error("--knn %s: %s" % (FLAGS.knn, e))
+    ladder, slack = None, 0.0
+    if FLAGS.knn_ladder is not None:
+        if FLAGS.estimator != "pca":
+            parser.error("--knn_ladder belongs to --estimator pca")
+        for given, flag in ((FLAGS.knn is not None, "--knn"), (FLAGS.patch_radius is not None, "--patch_radius"),
+                            (FLAGS.pca_scale != -1, "--pca_scale")):
+            if given:
+                parser.error("--knn_ladder and %s are mutually exclusive: every row chooses its own neighbour count from the ladder" % flag)
+        try:
+            ladder = _select.check_ladder(_select.DEFAULT_LADDER if FLAGS.knn_ladder.strip() == "auto"
+                                          else [int(v) for v in FLAGS.knn_ladder.split(",")])
+        except ValueError as e:
+            parser.error("--knn_ladder %s: %s" % (FLAGS.knn_ladder, e))
+    if FLAGS.select_slack is not None:
+        if ladder is None:
+            parser.error("--select_slack belongs to --estimator pca --knn_ladder K[,K...]")
+        try:
+            slack = _select.check_slack(FLAGS.select_slack)
+        except ValueError as e:
+            parser.error("--select_slack: %s" % e)
     fit = FITS.get(FLAGS.estimator)
     if FLAGS.patch_radius is not None:
         if FLAGS.estimator not in ("pca", "quadric") or ks is not None:
@@ -423,6 +491,10 @@ def main(argv=None):
 
     if fit:
         cfg = NestiConfig.for_model(FLAGS.model)
+        if ladder is not None:
+            rc = run_select(FLAGS, cfg, ladder, slack, pc_path, output_dir, printout, smooth)
+            flog.close()
+            return rc
         if FLAGS.patch_radius is not None:
             cfg.patch_radius = list(FLAGS.patch_radius)       # the fits read the radii and their number, nothing else of cfg
         try:

@@ -57,6 +57,23 @@ __device__ __forceinline__ void nbr_row(const NbrParams& np, int q, int lane, bo
   for (int s = 0; s < S; ++s) n[s] = min(np.ks[s], bad);
 }
 
+// nbr_row for a count that is not a template argument (select.hip: the top of a ladder): the slots below kmax into j[t] by the same
+// reads and the same test; returns min(kmax, valid prefix) in every lane
+__device__ __forceinline__ int nbr_row_upto(const NbrParams& np, int q, int lane, bool lost, int kmax, int (&j)[kNbrTrips]) {
+  int bad = lost ? 0 : kmax;
+#pragma unroll
+  for (int t = 0; t < kNbrTrips; ++t) {
+    const int i = lane + t * kWave;
+    j[t] = 0;
+    if (i < kmax) {
+      const int v = np.nbr[(size_t)q * np.K + i];
+      if ((unsigned)v >= (unsigned)np.p.N) bad = min(bad, i);
+      else j[t] = v;
+    }
+  }
+  return wave_min(bad);
+}
+
 // body(slot, dx, dy, dz, d2) for the slots lane, lane + 64, ... below n of the list: the walk of the list kernels
 template <class Body>
 __device__ __forceinline__ void walk_list(const float* cloud, const int (&j)[kNbrTrips], int n, int lane, double cx, double cy, double cz,

@@ -85,8 +85,8 @@ class CloudPatches:
     this cloud and ``r_abs`` from ITS bounding box.  Patch row i is ``queries[i]``; a position whose balls are all empty gets
     the sentinel outputs.
 
-    ``radius_grid=False`` skips the radius grid: only :meth:`knn`, :meth:`pca_knn`, :meth:`quadric_knn` and :meth:`hough_knn` may
-    then be called."""
+    ``radius_grid=False`` skips the radius grid: only :meth:`knn`, :meth:`pca_knn`, :meth:`quadric_knn`, :meth:`hough_knn`,
+    :meth:`pca_select` and :meth:`smooth_knn` may then be called."""
 
     def __init__(self, pts, cfg: NestiConfig, device="cuda:0", seed=3627473, pidx=None, queries=None, radius_grid=True):
         if pidx is not None and queries is not None:
@@ -337,6 +337,36 @@ class CloudPatches:
         cloud).  A row's bits are a pure function of (cloud, centre, ks): independent of batching, streams, ``grid`` and grid build.
         Serves all points, ``pidx`` and ``queries``; asynchronous on ``stream``."""
         return self._fit_nbr("nesti_pca_normals_nbr", first, count, ks, grid, nbr, (3, 3), stream)
+
+    def pca_select(self, first, count, ladder, slack=0.0, nbr=None, grid=None, stream=None):
+        """The scale-selected plane fit of patch rows [first, first + count) (``nesti_pca_select_nbr`` / ``_at``; DESIGN.md 2
+        "Scale-selected plane fit"): the plane fit of :meth:`pca_knn` at every neighbour count of ``ladder`` (1 .. 32 strictly ascending
+        counts in 1 .. 256) over ONE sorted list (one search at K = ladder[-1]), and per row the candidate of smallest surface variation
+        -- the largest one within ``v_min (1 + slack)``.  Device tensors ``(normals [count,3] f32, eig [count,3] f32, sel [count] int32
+        (the index into the ladder, -1: no candidate could be fitted and the row is 0), k [count] int32 (the neighbours used), radius
+        [count] f32, variation_all [count,L] f32, normals_all [count,L,3] f32, eig_all [count,L,3] f32, radius_all [count,L] f32,
+        count_all [count,L] int32)``; candidate c of the ``*_all`` tensors holds the bits of ``pca_knn`` at ``ks=(ladder[c],)``.
+        ``nbr`` [count,K >= ladder[-1]] int32: the caller's own lists instead of the search (untrusted, as for :meth:`pca_knn`).
+        Serves all points, ``pidx`` and ``queries``; asynchronous on ``stream``."""
+        from . import select as _select
+        ladder, slack = _select.check_ladder(ladder), _select.check_slack(slack)
+        st = self._stream(stream)
+        if nbr is None:
+            nbr = self.knn(first, count, ladder[-1], grid=grid, stream=st)[0]
+        at, q = self._rows(first, count)
+        L = len(ladder)
+        if (nbr.dtype != torch.int32 or nbr.dim() != 2 or nbr.shape[0] != count or nbr.shape[1] < ladder[-1] or not nbr.is_contiguous()
+                or nbr.device != self.device):
+            raise ValueError("nbr: a contiguous int32 [count, K >= ladder[-1]] tensor on %s" % self.device)
+        f32, i32 = torch.float32, torch.int32
+        out = check_out(None, (((count, 3), f32), ((count, 3), f32), ((count,), i32), ((count,), i32), ((count,), f32),
+                               ((count, L), f32), ((count, L, 3), f32), ((count, L, 3), f32), ((count, L), f32), ((count, L), i32)),
+                        self.device)
+        if count:                         # 0 rows: a no-op; an empty list has no address to pass
+            self._call("nesti_pca_select_nbr", at, q, count, first,
+                       [_lib.ptr(nbr), int(nbr.shape[1]), (ctypes.c_int32 * L)(*ladder), L, ctypes.c_double(slack)]
+                       + [_lib.ptr(t) for t in out], st, ball=False)
+        return out
 
     def quadric_knn(self, first, count, ks, grid=None, nbr=None, stream=None):
         """Quadric-fit normals and principal curvatures of patch rows [first, first + count) over their nearest neighbours, as

@@ -38,6 +38,7 @@ extern "C" {
 #define NESTI_HOUGH_MAX_BINS 16  /* ... bins per axis of the accumulator */
 #define NESTI_HOUGH_MAX_ROT 8    /* ... and rotations of it */
 #define NESTI_SELECT_MAX_L 32    /* nesti_pca_select_nbr: the most neighbour counts of a ladder */
+#define NESTI_ROBUST_MAX_ITERS 64 /* nesti_robust_normals_nbr: the most re-weighting iterations of a call */
 #define NESTI_MAX_EXPERTS 8
 #define NESTI_MUPS_CH 20 /* channels per scale: utils/tf_util.py:711-720 */
 
@@ -736,6 +737,67 @@ int nesti_hough_normals_nbr_at(const float* cloud_dev, int N, const float* query
                                int K, const int32_t* ks, int S, int T, int B, int R, const double* rot, uint64_t seed,
                                float* normals_out_dev, float* conf_out_dev, int32_t* votes_out_dev, float* radius_out_dev,
                                int32_t* count_out_dev, void* stream);
+
+/* ---- robust plane-fit normals over neighbour lists (robust.hip; DESIGN.md 2 "Robust plane fit") ------------------------------------
+ * An M-estimator of the plane through a neighbourhood, solved by iteratively re-weighted least squares (IRLS) -- after Mederos et al.
+ * (2003), Fleishman et al. (2005) and the RIMLS of Oztireli et al. (2009): residuals to the current plane down-weight the points of the
+ * other face of a crease, so the fit leans to one face where the plane fit averages both, and the normal stays continuous (no bins, no
+ * triplets).  With a start normal the same entry REFINES any other estimator's normals against the points.  The conventions are the
+ * library's own (no parity with any published code is claimed): fp64 throughout, every operation rounded on its own, only + - x /
+ * sqrt, comparisons and integer arithmetic -- a restatement in plain IEEE arithmetic predicts every output bit.  No model, no weights,
+ * no grid, and no ball variant.
+ *
+ * Centres, nbr_dev [M, K], ks [S], the valid prefix, n_s = min(ks[s], valid prefix), d = (double)p - (double)c, d2 and r2_s are exactly
+ * as for nesti_pca_normals_nbr: the list is untrusted, the prefix ends at the first entry outside [0, N), and a non-finite centre has an
+ * empty prefix.  On the HOST: iters in 0 .. NESTI_ROBUST_MAX_ITERS; sigma finite, in (0, 1e6]; falloff in [0, 1]; floor in [1e-6, 1].
+ * init_normals_dev [M,S,3] f32 (device) or NULL: the start normals, indexed like the outputs.  Per row, per scale s with n = n_s:
+ *  0 START.  plane = the normal nesti_pca_normals_nbr writes for the scale, bit for bit; it is always computed.  g = the init row where
+ *    an init is given, else plane.  The row is SKIPPED -- normal 0 0 0, iters_done 0, support 0, inliers 0, moments 0 -- if n < 3, if
+ *    r2_s == 0, if a d2 among the first n slots is not finite, or if g is 0 0 0 or has a non-finite component.  Otherwise g is put under
+ *    the sign rule on its f32 values (negated if the first non-zero of (g_z, g_y, g_x) is negative, zeros +0): the caller's sign never
+ *    reaches a bit of the result.
+ *  ONE ITERATION, from the f32 normal g:
+ *  1 v = (double)g / sqrt((g_x g_x + g_y g_y) + g_z g_z), the products of the converted values.
+ *  2 h_i = (v_x dx_i + v_y dy_i) + v_z dz_i;  c = the element of 0-based rank n / 2 (integer division) of the h_i in ascending order --
+ *    an element, never an average;  res_i = h_i - c.
+ *  3 med = the element of rank n / 2 of the |res_i|;  sig = max(sigma med, floor sqrt(r2_s)).
+ *  4 x_i = res_i / sig;  t_i = 1 / (1 + x_i x_i);  u_i = 1 - falloff (d2_i / r2_s);  a_i = u_i t_i;  w_i = a_i a_i  (Geman-McClure on
+ *    the residual times the u^2 of nesti_smooth_normals_nbr on the distance).
+ *  5 TEN SUMS.  sw = sum w_i, then sum w_i T for the nine terms T of the plane fit in its order: dx dy dz, then the products xx xy xz
+ *    yy yz zz of d, each rounded BEFORE it meets w_i.  Slot i is added in lane i mod 64 of a 64-lane wave, a lane adds its slots in
+ *    ascending order from +0.0, each total goes through the xor-butterfly of the plane fit (offsets 32, 16, ..., 1).
+ *  6 m = (sum w d) / sw;  C = ((sum w d d^T) / sw - m m^T) / r2_s;  then the plane fit's eigen-solve (the arithmetic of
+ *    nesti_sym3_eig), normalisation in fp64, one rounding to f32 and the sign rule: its solve with sw in the place of the count.
+ *  7 The iteration FAILS if not sw > 0, if fewer than 3 slots have w_i > 0, or if the new normal is 0 0 0 or has a non-finite
+ *    component.  After a failure g stays as it was and the row stops.  Otherwise g = the new normal.
+ *  The state between iterations is the f32 normal alone: iters = T equals T chained calls of iters = 1 through init_normals_dev, bit for
+ *  bit.  The result is g after the last iteration -- after a failure in the first one therefore the start normal under the sign rule,
+ *  as given (not renormalised).  iters = 0: (float)v of step 1, put under the sign rule once more (a component may round to zero).
+ *  8 OUTPUTS (device; any may be NULL, which leaves the others unchanged):
+ *      normals_out_dev [M,S,3]  f32    the robust normal
+ *      plane_out_dev   [M,S,3]  f32    plane of step 0
+ *      support_out_dev [M,S]    f32    (float)sw of the last successful iteration, 0 if none
+ *      inliers_out_dev [M,S]    int32  the slots with |res_i| <= sig in that iteration
+ *      iters_out_dev   [M,S]    int32  the successful iterations
+ *      moments_out_dev [M,S,10] fp64   the ten sums of that iteration in the order of step 5; zeros if none
+ *      radius_out_dev  [M,S]    f32    (float)sqrt(r2_s), as the other list entries write it, skipped rows included
+ *      count_out_dev   [M,S]    int32  n_s, likewise
+ * DETERMINISM: no atomics.  A row's bits are a pure function of (cloud, centre, list prefix, ks, iters, sigma, falloff, floor, its
+ * init row): independent of batching, of streams and of the grid the list came from.
+ * Argument errors -- those of nesti_pca_normals_nbr; iters, sigma, falloff or floor outside the ranges above (NaN included) -- are
+ * reported under the entry's name before any device call; M = 0 is a no-op.  Each call enqueues one kernel on `stream`, neither
+ * synchronises nor reads anything back, and can be captured into a graph.  Under nesti_profile_enable the launch is booked in the
+ * patches category, like the other list fits. */
+int nesti_robust_normals_nbr(const float* cloud_dev, int N, const int32_t* query_idx_dev, int M, int query_row0, const int32_t* nbr_dev,
+                             int K, const int32_t* ks, int S, int iters, double sigma, double falloff, double floor,
+                             const float* init_normals_dev, float* normals_out_dev, float* plane_out_dev, float* support_out_dev,
+                             int32_t* inliers_out_dev, int32_t* iters_out_dev, double* moments_out_dev, float* radius_out_dev,
+                             int32_t* count_out_dev, void* stream);
+int nesti_robust_normals_nbr_at(const float* cloud_dev, int N, const float* query_xyz_dev, int M, const int32_t* nbr_dev, int K,
+                                const int32_t* ks, int S, int iters, double sigma, double falloff, double floor,
+                                const float* init_normals_dev, float* normals_out_dev, float* plane_out_dev, float* support_out_dev,
+                                int32_t* inliers_out_dev, int32_t* iters_out_dev, double* moments_out_dev, float* radius_out_dev,
+                                int32_t* count_out_dev, void* stream);
 
 /* ---- feature-preserving normal smoothing over neighbour lists (smooth.hip; DESIGN.md 2 "Normal smoothing") ------------------------
  * One pass of a bilateral filter of normals (Jones et al. 2004, Sun et al. 2007, the anisotropic normal smoothing of Huang et al.

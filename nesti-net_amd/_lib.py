@@ -117,6 +117,7 @@ DEPTH_U16, DEPTH_F32 = 0, 1           # NESTI_DEPTH_*
 DEPTH_MAX_PIXELS = 1 << 26
 KNN_MAX_K = 256                       # NESTI_KNN_MAX_K
 SELECT_MAX_L = 32                     # NESTI_SELECT_MAX_L
+ROBUST_MAX_ITERS = 64                 # NESTI_ROBUST_MAX_ITERS
 HOUGH_MAX_T, HOUGH_MAX_BINS, HOUGH_MAX_ROT = 4096, 16, 8   # NESTI_HOUGH_MAX_*
 
 
@@ -202,6 +203,10 @@ SIGNATURES = {
                                      ctypes.POINTER(ctypes.c_double), _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nesti_hough_normals_nbr_at": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, ctypes.POINTER(ctypes.c_int32), _i, _i, _i, _i,
                                         ctypes.POINTER(ctypes.c_double), _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "nesti_robust_normals_nbr": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, ctypes.POINTER(ctypes.c_int32), _i, _i] + [ctypes.c_double] * 3
+                                 + [_vp] * 10),
+    "nesti_robust_normals_nbr_at": (_i, [_vp, _i, _vp, _i, _vp, _i, ctypes.POINTER(ctypes.c_int32), _i, _i] + [ctypes.c_double] * 3
+                                    + [_vp] * 10),
     "nesti_smooth_normals_nbr": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp]),
     "nesti_debug_smooth_lanes": (_i, [_i]),
     "nesti_depth_workspace_bytes": (_sz, [_i, _i]),

@@ -18,7 +18,10 @@ caller's in place of the model configuration's.  ``--estimator hough --knn K[,K.
 ``<shape>.hough_count`` (every scale) and ``<shape>.knn_radius``.  ``--smooth ITERS`` smooths the written normals of any estimator with
 the feature-preserving filter of :mod:`.smooth` before the orientation and adds ``<shape>.smooth_support``.  ``--estimator pca
 --knn_ladder K[,K...]`` is the scale-selected plane fit of :mod:`.select`: every row chooses its own neighbour count from the ladder;
-``<shape>.normals``, ``<shape>.select_k``, ``<shape>.select_eig``, ``<shape>.select_variation`` and ``<shape>.knn_radius``."""
+``<shape>.normals``, ``<shape>.select_k``, ``<shape>.select_eig``, ``<shape>.select_variation`` and ``<shape>.knn_radius``.
+``--estimator robust --knn K[,K...]`` is the robust plane fit of :mod:`.robust` (iteratively re-weighted least squares), over neighbour
+lists only: ``<shape>.normals`` (one scale), ``<shape>.robust_support``, ``<shape>.robust_inliers`` and ``<shape>.robust_count`` (every
+scale) and ``<shape>.knn_radius``."""
 import argparse
 import ctypes
 import os
@@ -30,6 +33,7 @@ from . import pca as _pca
 from . import hough as _hough
 from . import smooth as _smooth
 from . import quadric as _quadric
+from . import robust as _robust
 from . import select as _select
 from . import textio
 from . import weights as wts
@@ -111,7 +115,7 @@ def build_parser():
     p.add_argument("--orient_k", type=int, default=8, help="--orient mst: neighbours per point, 1 .. 16 [default: 8]")
     p.add_argument("--viewpoint", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"),
                    help="--orient viewpoint (required) / --orient mst (optional): the sensor position in the cloud's coordinates")
-    p.add_argument("--estimator", default="net", choices=["net", "pca", "quadric", "hough"],
+    p.add_argument("--estimator", default="net", choices=["net", "pca", "quadric", "hough", "robust"],
                    help="net (default): Nesti-Net, from the trained model in --results_path.  pca: the classical plane fit at every patch "
                         "radius of --model's configuration (DESIGN.md 2 'Plane-fit normals'); no model.nstw and no --synthetic_weights "
                         "are needed or read.  Writes <shape>.normals (the scale --pca_scale), <shape>.pca_eig (M rows of 3 S "
@@ -130,7 +134,14 @@ def build_parser():
                         "--hough_scale), <shape>.hough_conf (M rows of S confidences: the winning bin's share of the valid triplets), "
                         "<shape>.hough_votes (M rows of 2 S integers: winning votes and valid triplets per scale), <shape>.hough_count "
                         "(M rows of S neighbour counts) and <shape>.knn_radius; a row with fewer than 3 neighbours or only degenerate "
-                        "triplets is written as 0 0 0 with confidence 0")
+                        "triplets is written as 0 0 0 with confidence 0.  "
+                        "robust: the robust plane fit (DESIGN.md 2 'Robust plane fit'), under the same conditions; it too exists over "
+                        "neighbour lists only and requires --knn.  Iteratively re-weighted least squares from the plane fit's normal: "
+                        "neighbours far from the current plane lose their weight, so the fit leans to one face of a crease.  Writes "
+                        "<shape>.normals (the scale --robust_scale), <shape>.robust_support (M rows of S weight sums of the last "
+                        "iteration), <shape>.robust_inliers (M rows of S counts of neighbours within the scale of the residuals), "
+                        "<shape>.robust_count (M rows of S neighbour counts) and <shape>.knn_radius; a row with fewer than 3 "
+                        "neighbours is written as 0 0 0")
     p.add_argument("--pca_scale", type=int, default=-1,
                    help="--estimator pca: the scale whose normals go to <shape>.normals, an index into the patch radii; negative "
                         "counts from the end [default: -1, the largest]")
@@ -151,6 +162,20 @@ def build_parser():
     p.add_argument("--hough_rotations", type=int, default=_hough.DEFAULT_ROTATIONS,
                    help="--estimator hough: rotated copies of the accumulator, 1 .. 8 [default: %d]" % _hough.DEFAULT_ROTATIONS)
     p.add_argument("--hough_seed", type=int, default=0, help="--estimator hough: the seed of the triplet hash [default: 0]")
+    p.add_argument("--robust_scale", type=int, default=-1,
+                   help="--estimator robust: the scale whose normals go to <shape>.normals, an index into --knn; negative counts from "
+                        "the end [default: -1, the largest]")
+    p.add_argument("--robust_iters", type=int, default=_robust.DEFAULT_ITERS,
+                   help="--estimator robust: re-weighting iterations, 0 .. 64 [default: %d]" % _robust.DEFAULT_ITERS)
+    p.add_argument("--robust_sigma", type=float, default=_robust.DEFAULT_SIGMA,
+                   help="--estimator robust: the scale of the residuals in median absolute residuals, in (0, 1e6] [default: %g]"
+                        % _robust.DEFAULT_SIGMA)
+    p.add_argument("--robust_falloff", type=float, default=_robust.DEFAULT_FALLOFF,
+                   help="--estimator robust: the distance falloff in [0, 1]; the farthest neighbour weighs (1 - falloff)^2 [default: %g]"
+                        % _robust.DEFAULT_FALLOFF)
+    p.add_argument("--robust_floor", type=float, default=_robust.DEFAULT_FLOOR,
+                   help="--estimator robust: the smallest scale of the residuals as a fraction of the neighbourhood radius, in "
+                        "[1e-6, 1] [default: %g]" % _robust.DEFAULT_FLOOR)
     p.add_argument("--knn", default=None, metavar="K[,K...]",
                    help="--estimator pca / quadric: fit over the K nearest neighbours of every query instead of balls (DESIGN.md 2 "
                         "'k-nearest neighbourhoods'): one neighbour count per scale, at most 4, ascending, each in 1 .. 256.  The files "
@@ -295,7 +320,27 @@ FITS = {
         "files": ((".normals", textio.write_f32, "normals"), (".hough_conf", textio.write_f32, "conf"),
                   (".hough_votes", textio.write_i32_rows, "votes"), (".hough_count", textio.write_i32_rows, "n_ball")),
         "saved": "saved normals, confidences, votes and neighbour counts for "},
+    "robust": {
+        "fit": _robust.robust_cloud, "noun": "robust plane fit", "scale_flag": "robust_scale",
+        "params": (("iters", "robust_iters"), ("sigma", "robust_sigma"), ("falloff", "robust_falloff"), ("floor", "robust_floor")),
+        "missing": lambda res, scale, ks: (res["normals_all"][:, scale] == 0).all(axis=1).sum(),
+        "no_fit": (None, "without a fit (fewer than 3 neighbours, or all of them at the query: written as 0 0 0)"),
+        "subsamples": "the robust plane fit weighs the whole neighbourhood and subsamples no patch",
+        "files": ((".normals", textio.write_f32, "normals"), (".robust_support", textio.write_f32, "support"),
+                  (".robust_inliers", textio.write_i32_rows, "inliers"), (".robust_count", textio.write_i32_rows, "n_ball")),
+        "line": lambda name, res, scale, params: robust_line(name, params, res["iters_done"][:, scale], res["inliers"][:, scale],
+                                                             res["n_ball"][:, scale]),
+        "saved": "saved normals, weight sums, inlier counts and neighbour counts for "},
 }
+
+
+def robust_line(name, params, iters_done, inliers, count):
+    """The second log line of ``--estimator robust`` for shape ``name``: the parameters, the rows that stopped before the last iteration
+    and the inliers' share of the neighbours at the written scale; the three int32 columns of that scale."""
+    total = int(count.sum())
+    return ("re-weighting of %s: %d iterations (sigma %g, falloff %g, floor %g); %d rows stopped early; %.1f %% of the neighbours are inliers"
+            % (name, params["iters"], params["sigma"], params["falloff"], params["floor"], int((iters_done < params["iters"]).sum()),
+               100.0 * float(inliers.sum()) / total if total else 0.0))
 
 
 def select_line(name, rows, ladder, slack, sel):
@@ -364,6 +409,8 @@ def run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None, smooth=No
         else:
             printout(fit_line(FLAGS.estimator, name, cloud.patch_count, scale, len(ks), missing, k=ks[scale]))
             textio.write_f32(os.path.join(output_dir, name + ".knn_radius"), res["radius"])
+        if "line" in fit:
+            printout(fit["line"](name, res, scale, params))
         if smooth is not None:
             printout(smooth_line(name, cloud.patch_count, smooth, res["smooth_count"]))
             write_smooth_support(os.path.join(output_dir, name + ".smooth_support"), res["smooth_support"], res["smooth_count"])
@@ -427,6 +474,13 @@ def main(argv=None):
             _hough.check_params(FLAGS.hough_triplets, FLAGS.hough_bins, FLAGS.hough_rotations, FLAGS.hough_seed)
         except ValueError as e:
             parser.error("--estimator hough: %s" % e)
+    if FLAGS.estimator == "robust":
+        if ks is None:
+            parser.error("--estimator robust needs --knn K[,K...]: the robust plane fit exists over neighbour lists only")
+        try:
+            _robust.check_params(FLAGS.robust_iters, FLAGS.robust_sigma, FLAGS.robust_falloff, FLAGS.robust_floor)
+        except ValueError as e:
+            parser.error("--estimator robust: %s" % e)
     if fit:
         for given, flag, why in ((FLAGS.depth_images, "--depth_images 1", "depth frames belong to the network path (--estimator net)"),
                                  (FLAGS.reproducible, "--reproducible 1",

@@ -1,6 +1,7 @@
 // The walk of an untrusted neighbour list by one wave (DESIGN.md 2 "k-nearest neighbourhoods"), shared by the list kernels of knn.hip
-// (plane fit, quadric fit) and by hough.hip: the parameter block, the valid prefix of a row, the per-slot differences and what every
-// list entry refuses on the host.  One definition, so the prefix, d, d2 and r2_s of every list entry are the same values.
+// (plane fit, quadric fit), by hough.hip, select.hip and robust.hip: the parameter block, the valid prefix of a row, the per-slot
+// differences and what every list entry refuses on the host.  One definition, so the prefix, d, d2 and r2_s of every list entry are
+// the same values.
 //
 // For the including unit: include patches_dev.h first, then `#pragma clang fp contract(off)`, then pca_dev.h and this header -- every
 // product and sum below is rounded on its own.

@@ -145,25 +145,27 @@ __device__ __forceinline__ void plane_sums(const PatchParams& p, const WaveSpans
 }
 
 // covariance in units of r^2 -> Jacobi -> the normal (normalised in fp64, rounded to f32 once, signed on the f32 values so that the
-// first non-zero of (n_z, n_y, n_x) is positive, zeros +0) and the clamped eigenvalues; n < 3: all 0
+// first non-zero of (n_z, n_y, n_x) is positive, zeros +0) and the clamped eigenvalues, for sums of total mass dn: the count of the
+// plane fits (plane_solve below), the sum of the weights of the robust fit (robust.hip)
+__device__ __forceinline__ void plane_solve_mass(const double (&sum)[kSums], double dn, double r2, float (&nrm)[3], float (&ev)[3]) {
+  const double mx = sum[0] / dn, my = sum[1] / dn, mz = sum[2] / dn;
+  const double c[6] = {(sum[3] / dn - mx * mx) / r2, (sum[4] / dn - mx * my) / r2, (sum[5] / dn - mx * mz) / r2,
+                       (sum[6] / dn - my * my) / r2, (sum[7] / dn - my * mz) / r2, (sum[8] / dn - mz * mz) / r2};
+  double w[3], vec[3][3];
+  sym3_eig(c, w, vec);
+  const double len = sqrt((vec[0][0] * vec[0][0] + vec[0][1] * vec[0][1]) + vec[0][2] * vec[0][2]);
+  float fx = (float)(vec[0][0] / len), fy = (float)(vec[0][1] / len), fz = (float)(vec[0][2] / len);
+  const float lead = fz != 0.f ? fz : (fy != 0.f ? fy : fx);
+  if (lead < 0.f) { fx = -fx; fy = -fy; fz = -fz; }
+  nrm[0] = fx + 0.f; nrm[1] = fy + 0.f; nrm[2] = fz + 0.f;   // -0 + +0 = +0: no negative zero leaves
+#pragma unroll
+  for (int k = 0; k < 3; ++k) ev[k] = (float)fmax(0.0, w[k]);
+}
+// the plane fit's solve: dn = n; n < 3: all 0
 __device__ __forceinline__ void plane_solve(const double (&sum)[kSums], int n, double r2, float (&nrm)[3], float (&ev)[3]) {
   nrm[0] = 0.f; nrm[1] = 0.f; nrm[2] = 0.f;
   ev[0] = 0.f; ev[1] = 0.f; ev[2] = 0.f;
-  if (n >= 3) {
-    const double dn = (double)n;
-    const double mx = sum[0] / dn, my = sum[1] / dn, mz = sum[2] / dn;
-    const double c[6] = {(sum[3] / dn - mx * mx) / r2, (sum[4] / dn - mx * my) / r2, (sum[5] / dn - mx * mz) / r2,
-                         (sum[6] / dn - my * my) / r2, (sum[7] / dn - my * mz) / r2, (sum[8] / dn - mz * mz) / r2};
-    double w[3], vec[3][3];
-    sym3_eig(c, w, vec);
-    const double len = sqrt((vec[0][0] * vec[0][0] + vec[0][1] * vec[0][1]) + vec[0][2] * vec[0][2]);
-    float fx = (float)(vec[0][0] / len), fy = (float)(vec[0][1] / len), fz = (float)(vec[0][2] / len);
-    const float lead = fz != 0.f ? fz : (fy != 0.f ? fy : fx);
-    if (lead < 0.f) { fx = -fx; fy = -fy; fz = -fz; }
-    nrm[0] = fx + 0.f; nrm[1] = fy + 0.f; nrm[2] = fz + 0.f;   // -0 + +0 = +0: no negative zero leaves
-#pragma unroll
-    for (int k = 0; k < 3; ++k) ev[k] = (float)fmax(0.0, w[k]);
-  }
+  if (n >= 3) plane_solve_mass(sum, (double)n, r2, nrm, ev);
 }
 
 }  // namespace

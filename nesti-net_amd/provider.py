@@ -388,6 +388,23 @@ class CloudPatches:
         return self._fit_nbr("nesti_hough_normals_nbr", first, count, ks, grid, nbr, (3, ((), torch.float32), ((2,), torch.int32)),
                              stream, params=params, keyed=True)
 
+    def robust_knn(self, first, count, ks, iters, sigma, falloff, floor, init=None, nbr=None, grid=None, stream=None):
+        """Robust plane-fit normals of patch rows [first, first + count) over their nearest neighbours (``nesti_robust_normals_nbr`` /
+        ``_at``; DESIGN.md 2 "Robust plane fit"), as :meth:`pca_knn`: one search at K = max(ks), then ``iters`` re-weighted plane fits
+        per row and scale from the plane fit's normal -- or from ``init`` [count,S,3] f32 on the device, the start normals of the rows
+        (any sign; a row that is 0 0 0 or not finite comes back 0 0 0).  Device tensors ``(normals [count,S,3] f32, plane [count,S,3]
+        f32 (the bits of ``pca_knn``'s normals), support [count,S] f32, inliers [count,S] int32, iters_done [count,S] int32, moments
+        [count,S,10] f64 (the ten weighted sums of the last iteration), radius [count,S] f32, n [count,S] int32)``."""
+        from . import robust as _robust
+        iters, sigma, falloff, floor = _robust.check_params(iters, sigma, falloff, floor)
+        S = len(_knn.check_ks(ks))
+        if init is not None and (not isinstance(init, torch.Tensor) or init.dtype != torch.float32 or tuple(init.shape) != (count, S, 3)
+                                 or not init.is_contiguous() or init.device != self.device):
+            raise ValueError("init: a contiguous float32 [count, S, 3] tensor on %s" % self.device)
+        params = [iters, ctypes.c_double(sigma), ctypes.c_double(falloff), ctypes.c_double(floor), None if init is None else _lib.ptr(init)]
+        return self._fit_nbr("nesti_robust_normals_nbr", first, count, ks, grid, nbr,
+                             (3, 3, ((), torch.float32), ((), torch.int32), ((), torch.int32), ((10,), torch.float64)), stream, params=params)
+
     def smooth_knn(self, normals, first, count, k, cos_t, falloff, nbr=None, grid=None, stream=None):
         """One pass of feature-preserving normal smoothing over patch rows [first, first + count) (``nesti_smooth_normals_nbr``;
         DESIGN.md 2 "Normal smoothing"): ``normals`` [n_points,3] f32 on the device holds a normal for every cloud point; a row's

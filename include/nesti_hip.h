@@ -846,6 +846,61 @@ int nesti_smooth_normals_nbr(const float* cloud_dev, int N, const float* normals
  * forces the one-wave-per-row form.  The choice moves the time of a pass, never a byte of its result.  Any other value is refused. */
 int nesti_debug_smooth_lanes(int lanes);
 
+/* ---- outlier removal before estimation (outlier.hip; DESIGN.md 2 "Outlier removal") --------------------------------------------------
+ * The statistical and the radius outlier filter of a point cloud as three passes over the sorted lists nesti_knn returns: a score per
+ * row, the statistics of a score array, an ordered compaction.  The conventions are the library's own: fp64 throughout, every
+ * operation rounded on its own, only + - x / sqrt, comparisons and integer arithmetic, no atomics -- a restatement in plain IEEE
+ * arithmetic predicts every output bit, and the kept set is a pure function of (cloud, parameters): independent of batching, streams,
+ * the grid and the grid build.  No parity with any published code is claimed.
+ *
+ * nesti_outlier_scores_nbr: row q of M is cloud point c = query_row0 + q; nbr_dev [M, K] with row stride K (2 <= K <= NESTI_KNN_MAX_K)
+ * is untrusted, as for nesti_pca_normals_nbr; 1 <= k < K.  P = min(k + 1, valid prefix), the prefix ending at the first entry outside
+ * [0, N); d = (double)p - (double)c and d2 = (dx dx + dy dy) + dz dz per slot, as nesti_knn forms them.  Of the slots below P the first
+ * whose INDEX is c is skipped (the index, not d2 == 0: duplicates tie and sort by index); where none is, the slots below min(k, P) are
+ * used.  n_other = the number of slots used.
+ *      mean_out_dev    [M] f64    (the sum of sqrt(d2) over the used slots) / n_other;  +inf where n_other == 0
+ *      kth_d2_out_dev  [M] f64    the largest d2 used where n_other == k, else +inf
+ *      n_other_out_dev [M] int32
+ *  ORDER: slot i is added in lane i mod 64, a lane's slots in ascending order from +0.0; the lanes meet in an xor-butterfly (offsets 32,
+ *  16, ..., 1): the order of the list fits.  A used slot whose d2 is NaN makes mean and kth_d2 the quiet NaN 0x7ff8000000000000; a centre
+ *  with a non-finite coordinate has that mean and kth_d2 and n_other = 0.  Any output may be NULL.  One kernel.
+ *
+ * nesti_outlier_threshold: the statistics of ANY fp64 score array scores_dev [M] on the device.  A non-finite score (on the bits) is
+ * absent: value +0, count 0.  Blocks of 256 consecutive rows are reduced by stride halving (v[t] = v[t] + v[t + s], s = 128, 64, ..., 1);
+ * one workgroup of 256 reduces the block partials: thread t adds partials t, t + 256, ... in ascending order to +0.0, then the same
+ * stride halving.  Pass 1: S and n, mean = S / n.  Pass 2: Q = the sum of (s - mean)(s - mean) by the same tree.
+ *      stats_out_dev [4] f64:  n,  mean,  std = sqrt(Q / (n - 1)) for n >= 2 else 0,  thr = mean + std_ratio std
+ *  n == 0: mean = std = 0 and thr = +inf.  ws_dev: nesti_outlier_workspace_bytes(M) bytes.  Four kernels.
+ *
+ * nesti_outlier_compact: row i of the N is KEPT iff scores_dev[i] is finite and <= the threshold -- *thr_dev (device; a threshold of
+ * nesti_outlier_threshold, say &stats[3]) or, where thr_dev is NULL, the host value thr.  A tie is kept; NaN and the infinities leave.
+ * Per-block counts, one single-workgroup scan, a scatter in row order (the scheme of nesti_depth_to_cloud).  Outputs (device; any but
+ * n_kept_out_dev may be NULL; the caller sizes them for N rows):
+ *      xyz_out_dev        [n_kept,3] f32    the kept rows of cloud_dev, copied bit for bit (cloud_dev may be NULL without it)
+ *      kept_idx_out_dev   [n_kept]   int32  their indices, ascending
+ *      new_of_old_out_dev [N]        int32  the new index of every row, -1 for a removed one
+ *      keep_out_dev       [N]        uint8  1 / 0
+ *      n_kept_out_dev     [1]        int32
+ *  ws_dev: nesti_outlier_workspace_bytes(N) bytes.  Three kernels.  The radius filter is this entry over kth_d2 with
+ *  thr = radius * radius and k = min_neighbours: it keeps the rows with at least that many other points within the radius.
+ *
+ * Argument errors -- a null pointer; N <= 0; K outside 1 .. NESTI_KNN_MAX_K or k outside 1 .. K - 1; M < 0; query_row0 < 0 or rows
+ * beyond the cloud; a short workspace; a std_ratio or a host thr that is not finite or negative -- are reported before any device call.
+ * M = 0 is a no-op for the scores and the statistics.  No entry synchronises or reads anything back; each can be captured into a
+ * graph.  Under nesti_profile_enable the launches are booked in the patches category. */
+size_t nesti_outlier_workspace_bytes(int n);
+int nesti_outlier_scores_nbr(const float* cloud_dev, int N, int query_row0, int M, const int32_t* nbr_dev, int K, int k,
+                             double* mean_out_dev, double* kth_d2_out_dev, int32_t* n_other_out_dev, void* stream);
+int nesti_outlier_threshold(const double* scores_dev, int M, double std_ratio, double* stats_out_dev, void* ws_dev, size_t ws_bytes,
+                            void* stream);
+int nesti_outlier_compact(const float* cloud_dev, int N, const double* scores_dev, const double* thr_dev, double thr, float* xyz_out_dev,
+                          int32_t* kept_idx_out_dev, int32_t* new_of_old_out_dev, uint8_t* keep_out_dev, int32_t* n_kept_out_dev,
+                          void* ws_dev, size_t ws_bytes, void* stream);
+/* Measurement and tests only: the lane group that serves a row of nesti_outlier_scores_nbr in this process.  0 (the default): the
+ * smallest of 16, 32 and 64 lanes that holds k + 1; 16, 32 or 64: at least that many.  The choice moves the time of a pass, never a byte
+ * of its result.  Any other value is refused. */
+int nesti_debug_outlier_lanes(int lanes);
+
 /* ---- depth images in, normal images out (depth.hip; DESIGN.md 2 "Depth images") --------------------------------------------------
  * The two ends of the reference's Kinect route: MATLAB/ScanNet_depth2xyz.m (depth + intrinsics + pose -> cloud) before
  * test_n_est_w_experts.py, and MATLAB/ScanNet_world2cam_normals.m / MATLAB/export_visualizations_nyu.m:146-153 (per-point results

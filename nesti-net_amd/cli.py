@@ -21,7 +21,9 @@ the feature-preserving filter of :mod:`.smooth` before the orientation and adds 
 ``<shape>.normals``, ``<shape>.select_k``, ``<shape>.select_eig``, ``<shape>.select_variation`` and ``<shape>.knn_radius``.
 ``--estimator robust --knn K[,K...]`` is the robust plane fit of :mod:`.robust` (iteratively re-weighted least squares), over neighbour
 lists only: ``<shape>.normals`` (one scale), ``<shape>.robust_support``, ``<shape>.robust_inliers`` and ``<shape>.robust_count`` (every
-scale) and ``<shape>.knn_radius``."""
+scale) and ``<shape>.knn_radius``.  ``--outliers statistical | radius`` removes outliers with the filter of :mod:`.outliers` before any
+estimator runs: every file keeps the rows of ``<shape>.xyz`` (a removed row is written as 0, its expert as -1) and
+``<shape>.inliers`` and ``<shape>.outlier_score`` are added."""
 import argparse
 import ctypes
 import os
@@ -31,6 +33,7 @@ import torch
 
 from . import pca as _pca
 from . import hough as _hough
+from . import outliers as _outliers
 from . import smooth as _smooth
 from . import quadric as _quadric
 from . import robust as _robust
@@ -208,6 +211,23 @@ def build_parser():
     p.add_argument("--smooth_falloff", type=float, default=_smooth.DEFAULT_FALLOFF,
                    help="--smooth: the distance falloff in [0, 1]; the farthest neighbour weighs (1 - falloff)^2 [default: %g]"
                         % _smooth.DEFAULT_FALLOFF)
+    p.add_argument("--outliers", choices=["0", "statistical", "radius"], default="0",
+                   help="remove outliers before estimating (DESIGN.md 2 'Outlier removal'), for every --estimator and for --depth_images "
+                        "1 at --depth_stride 1.  statistical: a point leaves when the mean distance to its --outlier_k nearest other "
+                        "points exceeds the cloud's mean of that figure by --outlier_std standard deviations; radius: when fewer than "
+                        "--outlier_k other points lie within --outlier_radius.  The estimator, --smooth and --orient then see the kept "
+                        "points alone; every file keeps the rows of <shape>.xyz (a removed row is written as 0, its expert as -1) and "
+                        "<shape>.inliers (0 / 1) and <shape>.outlier_score are added.  Goes with --reproducible 1; refused with "
+                        "--sparse_patches 1 and --subsample reference* [default: 0 = off]")
+    p.add_argument("--outlier_k", type=int, default=_outliers.DEFAULT_K,
+                   help="--outliers: the nearest other points per row, 1 .. 255 [default: %d]" % _outliers.DEFAULT_K)
+    p.add_argument("--outlier_std", type=float, default=_outliers.DEFAULT_STD_RATIO,
+                   help="--outliers statistical: the threshold in standard deviations above the mean, >= 0 [default: %g]"
+                        % _outliers.DEFAULT_STD_RATIO)
+    p.add_argument("--outlier_radius", type=float, default=None, metavar="R",
+                   help="--outliers radius: the radius, in the cloud's units (required)")
+    p.add_argument("--outlier_passes", type=int, default=_outliers.DEFAULT_PASSES,
+                   help="--outliers: filter passes, 1 .. 8; each searches the kept points again [default: %d]" % _outliers.DEFAULT_PASSES)
     p.add_argument("--synthetic_weights", action="store_true", help="use seeded synthetic weights if model.nstw is absent")
     return p
 
@@ -224,6 +244,38 @@ def write_smooth_support(path, support, count):
     with open(path, "w") as f:
         for s, c in zip(support.tolist(), count.tolist()):
             f.write("%.9g %d\n" % (s, c))
+
+
+def outlier_line(name, params, rows, passes):
+    """The log line of ``--outliers`` for shape ``name``: the rows removed and the threshold of every pass (``outliers.remove_outliers``)."""
+    removed = sum(p["removed"] for p in passes)
+    what = ("mean distance to %d nearest other points, %g standard deviations" % (params.k, params.std_ratio) if params.mode == "statistical"
+            else "at least %d other points within %g" % (params.min_neighbours, params.radius))
+    return ("outlier filter of %s (%s: %s): %d of %d rows removed in %d pass%s; threshold %s"
+            % (name, params.mode, what, removed, rows, len(passes), "" if len(passes) == 1 else "es",
+               ", ".join("%.9g" % p["threshold"] for p in passes)))
+
+
+def write_outlier_files(output_dir, name, inlier, score):
+    """``<shape>.inliers`` (0 / 1) and ``<shape>.outlier_score``: one row per row of the cloud."""
+    import numpy as np
+    textio.write_i32(os.path.join(output_dir, name + ".inliers"), np.ascontiguousarray(inlier, dtype=np.int32))
+    with open(os.path.join(output_dir, name + ".outlier_score"), "w") as f:
+        for v in np.asarray(score, np.float64).tolist():
+            f.write("%.17g\n" % v)
+
+
+def filter_shape(cloud, params, name, output_dir, printout):
+    """``--outliers`` for one shape: filter the cloud's points, write the two files and the log line, and prepare the kept points the
+    way ``cloud`` was (configuration, seed, query positions).  Returns (the kept cloud, the result of ``outliers.remove_outliers``)."""
+    from .provider import CloudPatches
+    f = _outliers.remove_outliers(cloud.host_pts, *params, device=cloud.device)
+    printout(outlier_line(name, params, cloud.n_points, f["passes"]))
+    write_outlier_files(output_dir, name, f["inlier"], f["score"])
+    if not len(f["kept"]):
+        raise SystemExit("--outliers: the filter kept none of the %d points of %s" % (cloud.n_points, name))
+    kept = CloudPatches(f["points"], cloud.cfg, cloud.device, cloud.seed, queries=None if cloud.queries is None else cloud.queries.cpu().numpy())
+    return kept, f
 
 
 def fit_batch(cfg, dtype, batch, device, lanes=2, reserve=2 << 30):
@@ -271,13 +323,17 @@ class DepthFrames:
         return _depth.read_depth(self.path(name, ".depth.npy")), cam
 
 
-def run_depth_frame(est, frames, name, FLAGS, output_dir, printout, on_cloud, write_experts=True):
+def run_depth_frame(est, frames, name, FLAGS, output_dir, printout, on_cloud, write_experts=True, outliers=None):
     """One frame of ``--depth_images 1``: estimate, then the row files, ``.pix`` and the two images."""
     import numpy as np
     depth, cam = frames.load(name)
     res = est.estimate_depth(depth, cam, stride=FLAGS.depth_stride, orient=None if FLAGS.orient == "0" else FLAGS.orient,
-                             orient_k=FLAGS.orient_k, on_cloud=on_cloud)
+                             orient_k=FLAGS.orient_k, on_cloud=on_cloud, outliers=outliers)
     H, W = depth.shape
+    if outliers is not None and len(res["pix"]):
+        lo = est.last_outliers
+        printout(outlier_line(name, outliers, len(res["pix"]), lo["passes"]))
+        write_outlier_files(output_dir, name, lo["inlier"], lo["score"])
     printout("depth frame %s: %d x %d, %d normals estimated (stride %d), oriented: %s"
              % (name, H, W, len(res["pix"]), FLAGS.depth_stride, FLAGS.orient))
     textio.write_f32(os.path.join(output_dir, name + ".normals"), res["normals"])
@@ -352,18 +408,24 @@ def select_line(name, rows, ladder, slack, sel):
             % (name, rows, slack, ", ".join("%d: %d" % (k, n) for k, n in zip(ladder, hist[1:].tolist())), int(hist[0])))
 
 
-def run_select(FLAGS, cfg, ladder, slack, pc_path, output_dir, printout, smooth=None):
+def run_select(FLAGS, cfg, ladder, slack, pc_path, output_dir, printout, smooth=None, outliers=None):
     """``--estimator pca --knn_ladder``: per shape the selected fit, the optional smoothing and orientation of its normals, and its
     files.  No model is loaded."""
     dataset = PointcloudPatchDataset(pc_path, FLAGS.testset, cfg, seed=3627473, sparse_patches=FLAGS.sparse_patches,
                                      device="cuda:%d" % FLAGS.gpu, query_positions=bool(FLAGS.query_positions))
     for ind, name in enumerate(dataset.shape_names):
         cloud = dataset.get_shape(ind)
+        filt = None
+        if outliers is not None:
+            full, (cloud, filt) = cloud.n_points, filter_shape(cloud, outliers, name, output_dir, printout)
         res = _select.select_cloud(cloud, ladder, slack, orient=None if FLAGS.orient == "0" else FLAGS.orient, viewpoint=FLAGS.viewpoint,
                                    orient_k=FLAGS.orient_k, smooth=smooth)
         printout(select_line(name, cloud.patch_count, ladder, slack, res["sel"]))
         if smooth is not None:
             printout(smooth_line(name, cloud.patch_count, smooth, res["smooth_count"]))
+        if filt is not None and cloud.queries is None:        # the log lines above count the kept rows; the files hold every row
+            res = _outliers.scatter_result(res, filt["kept"], full)
+        if smooth is not None:
             write_smooth_support(os.path.join(output_dir, name + ".smooth_support"), res["smooth_support"], res["smooth_count"])
         if res["orient"] is not None:
             printout(orient_line(name, FLAGS.orient, res["orient"], cloud.patch_count))
@@ -392,7 +454,7 @@ def fit_line(estimator, name, rows, scale, n_scales, missing, radius=None, k=Non
                fit["no_fit"][k is not None]))
 
 
-def run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None, smooth=None):
+def run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None, smooth=None, outliers=None):
     """``--estimator pca / quadric`` (``FITS``): per shape the fit at every scale, the optional orientation of the rows of scale ``scale``
     (>= 0; the quadric fit flips their curvatures with them), and the estimator's files.  No model is loaded."""
     fit = FITS[FLAGS.estimator]
@@ -400,6 +462,9 @@ def run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None, smooth=No
                                      device="cuda:%d" % FLAGS.gpu, query_positions=bool(FLAGS.query_positions))
     for ind, name in enumerate(dataset.shape_names):
         cloud = dataset.get_shape(ind)
+        filt = None
+        if outliers is not None:
+            full, (cloud, filt) = cloud.n_points, filter_shape(cloud, outliers, name, output_dir, printout)
         params = {kw: getattr(FLAGS, flag) for kw, flag in fit.get("params", ())}
         res = fit["fit"](cloud, scale=scale, orient=None if FLAGS.orient == "0" else FLAGS.orient, viewpoint=FLAGS.viewpoint,
                          orient_k=FLAGS.orient_k, knn=ks, smooth=smooth, **params)
@@ -408,11 +473,15 @@ def run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None, smooth=No
             printout(fit_line(FLAGS.estimator, name, cloud.patch_count, scale, cfg.n_scales, missing, radius=cloud.r_abs[scale]))
         else:
             printout(fit_line(FLAGS.estimator, name, cloud.patch_count, scale, len(ks), missing, k=ks[scale]))
-            textio.write_f32(os.path.join(output_dir, name + ".knn_radius"), res["radius"])
         if "line" in fit:
             printout(fit["line"](name, res, scale, params))
         if smooth is not None:
             printout(smooth_line(name, cloud.patch_count, smooth, res["smooth_count"]))
+        if filt is not None and cloud.queries is None:        # the log lines above count the kept rows; the files hold every row
+            res = _outliers.scatter_result(res, filt["kept"], full)
+        if ks is not None:
+            textio.write_f32(os.path.join(output_dir, name + ".knn_radius"), res["radius"])
+        if smooth is not None:
             write_smooth_support(os.path.join(output_dir, name + ".smooth_support"), res["smooth_support"], res["smooth_count"])
         if res["orient"] is not None:
             printout(orient_line(name, FLAGS.orient, res["orient"], cloud.patch_count))
@@ -504,6 +573,31 @@ def main(argv=None):
         for flag in ("smooth_k", "smooth_angle", "smooth_falloff"):
             if getattr(FLAGS, flag) != parser.get_default(flag):
                 parser.error("--%s belongs to --smooth ITERS" % flag)
+    outliers = None
+    if FLAGS.outliers != "0":
+        for given, flag, why in ((FLAGS.sparse_patches, "--sparse_patches 1",
+                                  "the filter renumbers the cloud and a .pidx entry could name a removed point (left for later)"),
+                                 (FLAGS.subsample != "hash", "--subsample %s" % FLAGS.subsample,
+                                  "the reference's subsample order is that of the unfiltered cloud"),
+                                 (FLAGS.depth_images and FLAGS.depth_stride != 1, "--depth_stride %d" % FLAGS.depth_stride,
+                                  "a strided frame estimates at a subset of the cloud; use --depth_stride 1")):
+            if given:
+                parser.error("--outliers does not go with %s: %s" % (flag, why))
+        if FLAGS.outliers == "radius" and FLAGS.outlier_radius is None:
+            parser.error("--outliers radius needs --outlier_radius R")
+        if FLAGS.outliers == "statistical" and FLAGS.outlier_radius is not None:
+            parser.error("--outlier_radius belongs to --outliers radius")
+        if FLAGS.outliers == "radius" and FLAGS.outlier_std != parser.get_default("outlier_std"):
+            parser.error("--outlier_std belongs to --outliers statistical")
+        try:
+            outliers = _outliers.check_params(FLAGS.outliers, FLAGS.outlier_k, FLAGS.outlier_std, FLAGS.outlier_radius, None,
+                                              FLAGS.outlier_passes)
+        except ValueError as e:
+            parser.error("--outliers: %s" % e)
+    else:
+        for flag in ("outlier_k", "outlier_std", "outlier_radius", "outlier_passes"):
+            if getattr(FLAGS, flag) != parser.get_default(flag):
+                parser.error("--%s belongs to --outliers statistical / radius" % flag)
     if FLAGS.query_positions and FLAGS.sparse_patches:
         parser.error("--query_positions 1 and --sparse_patches 1 are mutually exclusive: the queries are positions or cloud points")
     if FLAGS.query_positions and FLAGS.subsample != "hash":
@@ -546,7 +640,7 @@ def main(argv=None):
     if fit:
         cfg = NestiConfig.for_model(FLAGS.model)
         if ladder is not None:
-            rc = run_select(FLAGS, cfg, ladder, slack, pc_path, output_dir, printout, smooth)
+            rc = run_select(FLAGS, cfg, ladder, slack, pc_path, output_dir, printout, smooth, outliers)
             flog.close()
             return rc
         if FLAGS.patch_radius is not None:
@@ -555,7 +649,7 @@ def main(argv=None):
             scale = _pca.check_scale(getattr(FLAGS, fit["scale_flag"]), cfg.n_scales if ks is None else len(ks))
         except ValueError as e:
             raise SystemExit("--%s with --model %s: %s" % (fit["scale_flag"], FLAGS.model, e))
-        rc = run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks, smooth)
+        rc = run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks, smooth, outliers)
         flog.close()
         return rc
 
@@ -632,12 +726,16 @@ def main(argv=None):
     if FLAGS.depth_images:
         for name in frames.names:
             run_depth_frame(est, frames, name, FLAGS, output_dir, printout, lambda cloud: calibrate(name, cloud),
-                            write_experts=arch != ARCH_SWITCH)
+                            write_experts=arch != ARCH_SWITCH, outliers=outliers)
         flog.close()
         return 0
 
     for ind, name in enumerate(dataset.shape_names):
         cloud = dataset.get_shape(ind)
+        filt = None
+        if outliers is not None:
+            # before anything looks at the cloud: the calibration, the network, --smooth and --orient see the kept points alone
+            full, (cloud, filt) = cloud.n_points, filter_shape(cloud, outliers, name, output_dir, printout)
         calibrate(name, cloud)
         if repro:
             normals, expert, probs = est.run_verified(cloud)
@@ -665,6 +763,14 @@ def main(argv=None):
             alone = (expert == -1) if expert is not None else (normals == 0).all(dim=1)
             printout("query positions of %s: %d, of which %d had no neighbourhood (no cloud point inside any ball: written as 0 0 0 / -1 / 0)"
                      % (name, cloud.patch_count, int(alone.sum().item())))
+        if filt is not None and cloud.queries is None:
+            # back to the rows of <shape>.xyz: a removed row is 0 0 0 / -1 / 0 (nesti_image_scatter over an image one row high)
+            kept = torch.from_numpy(filt["kept"].astype("int32")).to(normals.device)
+            normals = _outliers.scatter_rows(normals.contiguous(), kept, full, 0.0)
+            if expert is not None:
+                expert, probs = _outliers.scatter_rows(expert.contiguous(), kept, full, -1), _outliers.scatter_rows(probs.contiguous(), kept, full, 0.0)
+            if support is not None:
+                support, count = _outliers.scatter_rows(support.contiguous(), kept, full, 0.0), _outliers.scatter_rows(count.contiguous(), kept, full, 0)
         # byte-identical to the reference's np.savetxt calls (test_n_est_w_experts.py:182-188), ~6x faster
         textio.write_f32(os.path.join(output_dir, name + ".normals"), normals.cpu().numpy())
         if support is not None:

@@ -77,7 +77,8 @@ def hough_cloud(cloud, knn=DEFAULT_KNN, scale=-1, triplets=DEFAULT_TRIPLETS, bin
 
 
 def hough_normals(pts, knn=DEFAULT_KNN, pidx=None, queries=None, scale=-1, triplets=DEFAULT_TRIPLETS, bins=DEFAULT_BINS,
-                  rotations=DEFAULT_ROTATIONS, seed=0, orient=None, viewpoint=None, orient_k=8, device="cuda:0", cfg=None, smooth=None):
+                  rotations=DEFAULT_ROTATIONS, seed=0, orient=None, viewpoint=None, orient_k=8, device="cuda:0", cfg=None, smooth=None,
+                  outliers=None):
     """Hough-transform normals of a cloud: numpy in, a dict of numpy arrays out (synchronises).  Queries are all points, the points
     ``pidx`` or the positions ``queries`` [M,3] (mutually exclusive), as for ``pca.pca_normals``.  ``knn`` -- an int or an ascending
     sequence of at most 4 ints in 1 .. 256 -- names the neighbourhoods: scale s is the ``knn[s]`` nearest cloud points of the query
@@ -103,7 +104,18 @@ def hough_normals(pts, knn=DEFAULT_KNN, pidx=None, queries=None, scale=-1, tripl
 
     Raises ``ValueError`` for ``knn=None`` (there is no ball variant), for a ``cfg`` (the scales are neighbour counts: a
     configuration's radii would mean nothing), for parameters outside their ranges, for a ``scale`` outside [-S, S), for ``pidx``
-    together with ``queries``, for a bad ``smooth`` and for ``smooth`` with ``pidx`` or ``queries``."""
+    together with ``queries``, for a bad ``smooth`` and for ``smooth`` with ``pidx`` or ``queries``.
+
+    ``outliers`` -- None, ``'statistical'`` or a dict of ``mode``, ``k``, ``std_ratio``, ``radius``, ``min_neighbours``, ``passes``
+    (``outliers.remove_outliers``; DESIGN.md 2 "Outlier removal") -- filters the cloud first: the estimator, its smoothing and its
+    orientation run on the kept points, every per-row array comes back with the rows of ``pts`` (0 in the removed ones), and the dict
+    gains ``inlier`` [N] bool, ``outlier_score`` [N] and ``outlier_passes``.  With ``queries`` the rows are positions and nothing is
+    scattered; ``pidx`` with ``outliers`` is refused."""
+    if outliers is not None:
+        from . import outliers as _outliers
+        return _outliers.run_filtered(hough_normals, pts, outliers, pidx, queries, device, knn=knn, scale=scale, triplets=triplets,
+                                      bins=bins, rotations=rotations, seed=seed, orient=orient, viewpoint=viewpoint, orient_k=orient_k,
+                                      cfg=cfg, smooth=smooth)
     _need_knn(knn)
     check_params(triplets, bins, rotations, seed)
     cloud, scale, orient, viewpoint, orient_k, ks = prepare_cloud(pts, cfg, pidx, queries, scale, orient, viewpoint, orient_k, device, knn,

@@ -509,16 +509,37 @@ class NormalEstimator:
         return _orient.orient_device(cloud.centre_positions(), normals, float(cloud.r_abs[-1]), k, viewpoint, mode,
                                      torch.cuda.current_stream(self.device))
 
-    def estimate(self, pts, pidx=None, queries=None, orient=None, viewpoint=None, orient_k=8, smooth=None):
+    def estimate(self, pts, pidx=None, queries=None, orient=None, viewpoint=None, orient_k=8, smooth=None, outliers=None):
         """Convenience: numpy cloud in, numpy results out (synchronises).  ``queries`` [M,3]: positions instead of cloud points;
         a position without a neighbourhood comes back as normal (0, 0, 0), expert -1, probabilities 0.  ``orient`` = ``'mst'`` /
         ``'viewpoint'`` (default None: signs as the experts produced them): :meth:`orient` runs over the estimated rows, only signs
         change, and ``self.last_orient`` holds the stats dict.  ``smooth`` -- None, a number of passes or a dict of ``k``, ``iters``,
         ``angle``, ``falloff`` (``smooth.smooth_normals``) -- smooths the normals over all points before the orientation; it needs
         all points (``ValueError`` with ``pidx`` or ``queries``: the rows' neighbours would have no normal), leaves experts and
-        probabilities alone, and ``self.last_smooth`` holds ``smooth_support`` and ``smooth_count`` of the last pass."""
+        probabilities alone, and ``self.last_smooth`` holds ``smooth_support`` and ``smooth_count`` of the last pass.  ``outliers`` --
+        None, ``'statistical'`` or a dict (``outliers.remove_outliers``; DESIGN.md 2 "Outlier removal") -- filters the cloud first:
+        the network, the smoothing and the orientation see the kept points alone, the three arrays come back with the rows of ``pts``
+        (normal 0 0 0, expert -1, probabilities 0 in the removed ones; with ``queries`` the rows are positions and nothing is
+        scattered) and ``self.last_outliers`` holds ``inlier``, ``kept``, ``score`` and ``passes``; ``pidx`` with it is refused."""
         if orient not in (None, "mst", "viewpoint"):
             raise ValueError("orient must be None, 'mst' or 'viewpoint'")
+        if outliers is not None:
+            from . import outliers as _outliers
+            params = _outliers.as_params(outliers)
+            _outliers.refuse_pidx(pidx)
+            pts = _outliers.check_cloud(pts)
+            f = _outliers.remove_outliers(pts, *params, device=self.device)
+            if not len(f["kept"]):
+                raise ValueError("outliers: the filter kept none of the %d points" % len(pts))
+            normals, expert, probs = self.estimate(f["points"], None, queries, orient, viewpoint, orient_k, smooth)
+            self.last_outliers = {key: f[key] for key in ("inlier", "kept", "score", "passes")}
+            if queries is not None:
+                return normals, expert, probs
+            if smooth is not None:
+                self.last_smooth = _outliers.scatter_result(self.last_smooth, f["kept"], len(pts))
+            back = [None if a is None else _outliers.scatter_host(a, f["kept"], len(pts), fill) for a, fill in
+                    ((normals, 0), (expert, -1), (probs, 0))]
+            return tuple(back)
         from . import smooth as _smooth
         sm = _smooth.as_params(smooth)
         if sm is not None:
@@ -538,7 +559,7 @@ class NormalEstimator:
             return normals.cpu().numpy(), None, None
         return normals.cpu().numpy(), expert.cpu().numpy(), probs.cpu().numpy()
 
-    def estimate_depth(self, depth, camera, stride=1, orient="viewpoint", orient_k=8, on_cloud=None):
+    def estimate_depth(self, depth, camera, stride=1, orient="viewpoint", orient_k=8, on_cloud=None, outliers=None):
         """Depth frame in, normal image out (``depth.py``; DESIGN.md 2 "Depth images"): back-project ``depth`` [H,W] (uint16 or
         float32) through ``camera`` (``depth.Camera``), prepare the cloud of valid pixels, estimate -- :meth:`run`, or
         :meth:`run_verified` when the estimator is reproducible -- at every valid pixel, or with ``stride`` > 1 at the valid pixels
@@ -551,10 +572,22 @@ class NormalEstimator:
         and ``probs_map`` [H,W,E] f32 (fill 0) -- both omitted for the single-tower models -- and per estimated pixel, in pixel
         order, ``xyz``, ``pix`` (pixel index ``v W + u``), ``normals``, ``expert``, ``probs`` (None for the single-tower models).  A
         frame without a valid pixel gives all-fill maps and empty rows without touching the network.  The cloud passes through the
-        host once (``CloudPatches`` takes a host array and computes the bounding-box diagonal there)."""
+        host once (``CloudPatches`` takes a host array and computes the bounding-box diagonal there).
+
+        ``outliers`` -- None, ``'statistical'`` or a dict (``outliers.remove_outliers``; DESIGN.md 2 "Outlier removal") -- filters the
+        back-projected cloud of valid pixels first, which is where a depth discontinuity leaves its flying pixels: the network and the
+        orientation see the kept points alone; the rows stay those of the valid pixels, a removed one holding the maps' fill (0 0 0,
+        -1, 0) in the rows and in the maps, and the dict gains ``inlier`` [rows] bool (``self.last_outliers`` holds the scores and the
+        passes' statistics too).  It needs ``stride == 1`` (``ValueError``
+        otherwise: a strided frame estimates at a subset of the cloud, which is ``pidx``)."""
         from . import depth as _depth
         if orient not in (None, "mst", "viewpoint"):
             raise ValueError("orient must be None, 'mst' or 'viewpoint'")
+        from . import outliers as _outliers
+        filt = _outliers.as_params(outliers)
+        if filt is not None and int(stride) != 1:
+            raise ValueError("outliers needs stride == 1: a strided frame estimates at a subset of the cloud (pidx), which the filter "
+                             "does not serve yet")
         single_tower = self.cfg.arch in (ARCH_SINGLE, ARCH_MULTI)
         E = max(1, self.cfg.n_gate_out)
         dc = _depth.depth_to_cloud(depth, camera, stride=stride, device=self.device)
@@ -568,13 +601,27 @@ class NormalEstimator:
                 xyz, pix = dc.xyz[:0], dc.pix[:0]
             else:
                 sparse = dc.stride > 1
-                cloud = self.prepare(dc.xyz.cpu().numpy(), pidx=dc.qidx.cpu().numpy() if sparse else None)
+                host_xyz = dc.xyz.cpu().numpy()
+                kept = None
+                if filt is not None:
+                    f = _outliers.remove_outliers(host_xyz, *filt, device=self.device)
+                    if not len(f["kept"]):
+                        raise ValueError("outliers: the filter kept none of the %d valid pixels" % rows)
+                    host_xyz = f["points"]
+                    kept = torch.from_numpy(f["kept"].astype(np.int32)).to(self.device)
+                    inlier = torch.from_numpy(f["inlier"]).to(self.device)
+                    self.last_outliers = {key: f[key] for key in ("inlier", "kept", "score", "passes")}
+                cloud = self.prepare(host_xyz, pidx=dc.qidx.cpu().numpy() if sparse else None)
                 if on_cloud is not None:
                     on_cloud(cloud)
                 normals, expert, probs = self.run_verified(cloud) if self.reproducible else self.run(cloud)
                 if orient is not None:
                     from .orient import stats_dict
                     self.last_orient = stats_dict(self.orient(cloud, normals, orient, dc.viewpoint, orient_k))
+                if kept is not None:                       # back to the rows of the valid pixels; a removed one holds the maps' fill
+                    normals = _outliers.scatter_rows(normals.contiguous(), kept, rows, 0.0)
+                    expert = None if expert is None else _outliers.scatter_rows(expert.contiguous(), kept, rows, -1)
+                    probs = None if probs is None else _outliers.scatter_rows(probs.contiguous(), kept, rows, 0.0)
                 sel = dc.qidx.long() if sparse else None
                 xyz = dc.xyz[sel] if sparse else dc.xyz
                 pix = dc.pix[sel].contiguous() if sparse else dc.pix
@@ -583,5 +630,7 @@ class NormalEstimator:
                 out["expert_map"] = _depth.scatter_to_image(expert, pix, H, W, -1)
                 out["probs_map"] = _depth.scatter_to_image(probs, pix, H, W, 0.0)
             out.update(xyz=xyz, pix=pix, normals=normals, expert=expert, probs=probs)
+            if filt is not None:
+                out["inlier"] = inlier if rows else torch.zeros(0, dtype=torch.bool, device=self.device)
             torch.cuda.synchronize(self.device)
         return {k: None if v is None else v.cpu().numpy() for k, v in out.items()}

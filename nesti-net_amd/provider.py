@@ -86,7 +86,8 @@ class CloudPatches:
     the sentinel outputs.
 
     ``radius_grid=False`` skips the radius grid: only :meth:`knn`, :meth:`pca_knn`, :meth:`quadric_knn`, :meth:`hough_knn`,
-    :meth:`pca_select` and :meth:`smooth_knn` may then be called."""
+    :meth:`pca_select`, :meth:`smooth_knn` and the outlier filter's :meth:`outlier_scores`, :meth:`outlier_threshold` and
+    :meth:`outlier_compact` may then be called."""
 
     def __init__(self, pts, cfg: NestiConfig, device="cuda:0", seed=3627473, pidx=None, queries=None, radius_grid=True):
         if pidx is not None and queries is not None:
@@ -434,6 +435,92 @@ class CloudPatches:
                 _lib.check(self.lib.nesti_smooth_normals_nbr(
                     _lib.ptr(self.cloud), self.n_points, _lib.ptr(normals), _lib.ptr(q), count, first, _lib.ptr(nbr), int(nbr.shape[1]), k,
                     cos_t, falloff, *[_lib.ptr(t) for t in out], ctypes.c_void_p(st.cuda_stream)), "nesti_smooth_normals_nbr")
+        return out
+
+    # ---- outlier removal (csrc/outlier.hip; DESIGN.md 2 "Outlier removal"; outliers.py) -----------------------------------------------
+    def _outlier_ws(self, rows):
+        """The workspace of ``nesti_outlier_threshold`` / ``nesti_outlier_compact`` for ``rows`` rows: a fresh tensor per call, so calls
+        on several streams never share one."""
+        return torch.empty(max(1, self.lib.nesti_outlier_workspace_bytes(max(1, int(rows)))), dtype=torch.uint8, device=self.device)
+
+    def outlier_scores(self, first, count, k, nbr=None, grid=None, stream=None):
+        """The outlier scores of cloud rows [first, first + count) (``nesti_outlier_scores_nbr``) over their ``k`` (1 .. 255) nearest
+        OTHER points: device tensors ``(mean [count] f64 -- the mean distance to them, +inf where there are none --, kth_d2 [count] f64
+        -- the squared distance to the k-th, +inf where fewer exist --, n_other [count] int32)``.  One search at K = k + 1 (a row is its
+        own first neighbour; the slot that holds its own INDEX is the one skipped) unless ``nbr`` [count, K > k] int32 is given: the
+        caller's own sorted lists (untrusted, as for :meth:`pca_knn`).  A row's bits are a pure function of (cloud, row, k).  All points
+        only: a cloud built with ``pidx=`` or ``queries=`` raises ``ValueError``.  Asynchronous on ``stream``."""
+        from . import outliers as _outliers
+        if self.pidx is not None or self.queries is not None:
+            raise ValueError("outlier_scores: the rows are the cloud's own points; a cloud built with pidx or queries is not served")
+        k = _outliers.check_k(k)
+        self._rows(first, count)
+        st = self._stream(stream)
+        if nbr is None:
+            nbr = self.knn(first, count, k + 1, grid=grid, stream=st)[0]
+        if (not isinstance(nbr, torch.Tensor) or nbr.dtype != torch.int32 or nbr.dim() != 2 or nbr.shape[0] != count or nbr.shape[1] <= k
+                or not nbr.is_contiguous() or nbr.device != self.device):
+            raise ValueError("nbr: a contiguous int32 [count, K > k] tensor on %s" % self.device)
+        out = check_out(None, (((count,), torch.float64), ((count,), torch.float64), ((count,), torch.int32)), self.device)
+        if count:                         # 0 rows: a no-op; an empty list has no address to pass
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.nesti_outlier_scores_nbr(_lib.ptr(self.cloud), self.n_points, first, count, _lib.ptr(nbr),
+                                                             int(nbr.shape[1]), k, *[_lib.ptr(t) for t in out],
+                                                             ctypes.c_void_p(st.cuda_stream)), "nesti_outlier_scores_nbr")
+        return out
+
+    def outlier_threshold(self, scores, std_ratio, stream=None):
+        """The statistics of a score array on the device (``nesti_outlier_threshold``): ``scores`` [M] f64 -> ``stats`` [4] f64 = (n,
+        mean, std, thr = mean + std_ratio std) over the finite scores, in a fixed order of additions; n = 0 gives (0, 0, 0, +inf).
+        Nothing is read back.  Asynchronous on ``stream``."""
+        from . import outliers as _outliers
+        std_ratio = _outliers.check_std_ratio(std_ratio)
+        if (not isinstance(scores, torch.Tensor) or scores.dtype != torch.float64 or scores.dim() != 1 or not scores.is_contiguous()
+                or scores.device != self.device):
+            raise ValueError("scores: a contiguous float64 [M] tensor on %s" % self.device)
+        st = self._stream(stream)
+        M = int(scores.shape[0])
+        with torch.cuda.device(self.device), torch.cuda.stream(st):
+            stats = torch.empty(4, dtype=torch.float64, device=self.device)
+            if not M:                     # the entry is a no-op for 0 rows: the statistics of no score at all
+                stats.copy_(torch.tensor([0.0, 0.0, 0.0, float("inf")], dtype=torch.float64))
+            else:
+                ws = self._outlier_ws(M)
+                _lib.check(self.lib.nesti_outlier_threshold(_lib.ptr(scores), M, std_ratio, _lib.ptr(stats), _lib.ptr(ws), ws.numel(),
+                                                            ctypes.c_void_p(st.cuda_stream)), "nesti_outlier_threshold")
+                ws.record_stream(st)
+        return stats
+
+    def outlier_compact(self, scores, thr, stream=None):
+        """Keep the rows of the cloud whose score is finite and <= ``thr`` (``nesti_outlier_compact``): ``scores`` [n_points] f64 on the
+        device; ``thr`` a host number (finite, >= 0) or a device tensor whose FIRST element is the threshold (``stats[3:]`` of
+        :meth:`outlier_threshold`).  Device tensors ``(xyz [n_points,3] f32 -- its first n_kept rows are the kept points, bit for bit, in
+        the cloud's order --, kept_idx [n_points] int32 -- its first n_kept entries, ascending --, new_of_old [n_points] int32 (-1: removed),
+        keep [n_points] uint8, n_kept [1] int32)``.  Nothing is read back: the caller reads ``n_kept`` and slices.  Asynchronous."""
+        N = self.n_points
+        if (not isinstance(scores, torch.Tensor) or scores.dtype != torch.float64 or tuple(scores.shape) != (N,) or not scores.is_contiguous()
+                or scores.device != self.device):
+            raise ValueError("scores: a contiguous float64 [n_points] tensor on %s" % self.device)
+        thr_dev, thr_host = None, 0.0
+        if isinstance(thr, torch.Tensor):
+            if thr.dtype != torch.float64 or thr.numel() < 1 or not thr.is_contiguous() or thr.device != self.device:
+                raise ValueError("thr: a number, or a contiguous float64 tensor on %s whose first element is the threshold" % self.device)
+            thr_dev = thr
+        else:
+            from . import outliers as _outliers
+            thr_host = _outliers.check_threshold(thr)
+        st = self._stream(stream)
+        out = check_out(None, (((N, 3), torch.float32), ((N,), torch.int32), ((N,), torch.int32), ((N,), torch.uint8), ((1,), torch.int32)),
+                        self.device)
+        if N == 0:
+            out[4].zero_()
+            return out
+        with torch.cuda.device(self.device):
+            ws = self._outlier_ws(N)
+            _lib.check(self.lib.nesti_outlier_compact(_lib.ptr(self.cloud), N, _lib.ptr(scores), _lib.ptr(thr_dev), thr_host,
+                                                      *[_lib.ptr(t) for t in out], _lib.ptr(ws), ws.numel(),
+                                                      ctypes.c_void_p(st.cuda_stream)), "nesti_outlier_compact")
+            ws.record_stream(st)
         return out
 
     def build_reference_order(self, first, count, picks, pick_offsets, want_idx=False, out=None, stream=None):

@@ -33,7 +33,7 @@ def quadric_cloud(cloud, scale=-1, orient=None, viewpoint=None, orient_k=8, knn=
 
 
 def quadric_fit(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, viewpoint=None, orient_k=8, device="cuda:0", knn=None,
-                smooth=None):
+                smooth=None, outliers=None):
     """Quadric-fit normals and principal curvatures of a cloud: numpy in, a dict of numpy arrays out (synchronises).  Queries are all
     points, the points ``pidx`` or the positions ``queries`` [M,3] (mutually exclusive), as for ``pca.pca_normals``; the radii are
     ``cfg.patch_radius`` times the cloud's bounding-box diagonal.
@@ -62,5 +62,15 @@ def quadric_fit(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, v
     it (the curvatures are the fit's) and still flips with the orientation; the dict gains ``smooth_support`` and ``smooth_count``.
 
     Raises ``ValueError`` for a ``scale`` outside [-S, S), for ``pidx`` together with ``queries``, for a bad ``knn``, for ``knn``
-    together with ``cfg`` (whose radii would mean nothing), for a bad ``smooth`` and for ``smooth`` with ``pidx`` or ``queries``."""
+    together with ``cfg`` (whose radii would mean nothing), for a bad ``smooth`` and for ``smooth`` with ``pidx`` or ``queries``.
+
+    ``outliers`` -- None, ``'statistical'`` or a dict of ``mode``, ``k``, ``std_ratio``, ``radius``, ``min_neighbours``, ``passes``
+    (``outliers.remove_outliers``; DESIGN.md 2 "Outlier removal") -- filters the cloud first: the estimator, its smoothing and its
+    orientation run on the kept points, every per-row array comes back with the rows of ``pts`` (0 in the removed ones), and the dict
+    gains ``inlier`` [N] bool, ``outlier_score`` [N] and ``outlier_passes``.  With ``queries`` the rows are positions and nothing is
+    scattered; ``pidx`` with ``outliers`` is refused."""
+    if outliers is not None:
+        from . import outliers as _outliers
+        return _outliers.run_filtered(quadric_fit, pts, outliers, pidx, queries, device, cfg=cfg, scale=scale, orient=orient,
+                                      viewpoint=viewpoint, orient_k=orient_k, knn=knn, smooth=smooth)
     return quadric_cloud(*prepare_cloud(pts, cfg, pidx, queries, scale, orient, viewpoint, orient_k, device, knn, smooth), smooth=smooth)

@@ -85,7 +85,7 @@ def robust_cloud(cloud, knn=DEFAULT_KNN, scale=-1, iters=DEFAULT_ITERS, sigma=DE
 
 def robust_normals(pts, knn=DEFAULT_KNN, pidx=None, queries=None, scale=-1, iters=DEFAULT_ITERS, sigma=DEFAULT_SIGMA,
                    falloff=DEFAULT_FALLOFF, floor=DEFAULT_FLOOR, init=None, orient=None, viewpoint=None, orient_k=8, smooth=None,
-                   device="cuda:0"):
+                   device="cuda:0", outliers=None):
     """Robust plane-fit normals of a cloud: numpy in, a dict of numpy arrays out (synchronises).  Queries are all points, the points
     ``pidx`` or the positions ``queries`` [M,3] (mutually exclusive), as for ``pca.pca_normals``.  ``knn`` -- an int or an ascending
     sequence of at most 4 ints in 1 .. 256 -- names the neighbourhoods: scale s is the ``knn[s]`` nearest cloud points of the query
@@ -112,7 +112,18 @@ def robust_normals(pts, knn=DEFAULT_KNN, pidx=None, queries=None, scale=-1, iter
 
     Raises ``ValueError`` -- before any GPU work -- for ``knn=None`` (there is no ball variant), for parameters outside their ranges,
     for an ``init`` of another shape, for a ``scale`` outside [-S, S), for ``pidx`` together with ``queries``, for a bad ``orient`` or
-    ``smooth`` and for ``smooth`` with ``pidx`` or ``queries``."""
+    ``smooth`` and for ``smooth`` with ``pidx`` or ``queries``.
+
+    ``outliers`` -- None, ``'statistical'`` or a dict of ``mode``, ``k``, ``std_ratio``, ``radius``, ``min_neighbours``, ``passes``
+    (``outliers.remove_outliers``; DESIGN.md 2 "Outlier removal") -- filters the cloud first: the estimator, its smoothing and its
+    orientation run on the kept points, every per-row array comes back with the rows of ``pts`` (0 in the removed ones), and the dict
+    gains ``inlier`` [N] bool, ``outlier_score`` [N] and ``outlier_passes``.  With ``queries`` the rows are positions and nothing is
+    scattered; ``pidx`` with ``outliers`` is refused."""
+    if outliers is not None:
+        from . import outliers as _outliers
+        return _outliers.run_filtered(robust_normals, pts, outliers, pidx, queries, device, per_row={"init": init}, knn=knn, scale=scale,
+                                      iters=iters, sigma=sigma, falloff=falloff, floor=floor, orient=orient, viewpoint=viewpoint,
+                                      orient_k=orient_k, smooth=smooth)
     from .knn import check_ks
     _need_knn(knn)
     check_params(iters, sigma, falloff, floor)

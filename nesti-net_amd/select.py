@@ -88,7 +88,7 @@ def select_cloud(cloud, ladder=DEFAULT_LADDER, slack=0.0, orient=None, viewpoint
 
 
 def select_normals(pts, ladder=DEFAULT_LADDER, slack=0.0, pidx=None, queries=None, orient=None, viewpoint=None, orient_k=8, smooth=None,
-                   device="cuda:0"):
+                   device="cuda:0", outliers=None):
     """Scale-selected plane-fit normals of a cloud: numpy in, a dict of numpy arrays out (synchronises).  Queries are all points, the
     points ``pidx`` or the positions ``queries`` [M,3] (mutually exclusive), as for ``pca.pca_normals``.  ``ladder`` -- an int or a
     strictly ascending sequence of at most 32 ints in 1 .. 256 -- names the candidates: candidate c is the plane fit over the
@@ -115,7 +115,17 @@ def select_normals(pts, ladder=DEFAULT_LADDER, slack=0.0, pidx=None, queries=Non
     ``ladder[-1]`` reaches its ``k`` and needs all points; ``'mst'`` uses the default configuration's largest patch radius.
 
     Raises ``ValueError`` -- before any GPU work -- for a bad ``ladder`` or ``slack``, for ``pidx`` together with ``queries``, for a bad
-    ``orient`` or ``smooth`` and for ``smooth`` with ``pidx`` or ``queries``."""
+    ``orient`` or ``smooth`` and for ``smooth`` with ``pidx`` or ``queries``.
+
+    ``outliers`` -- None, ``'statistical'`` or a dict of ``mode``, ``k``, ``std_ratio``, ``radius``, ``min_neighbours``, ``passes``
+    (``outliers.remove_outliers``; DESIGN.md 2 "Outlier removal") -- filters the cloud first: the estimator, its smoothing and its
+    orientation run on the kept points, every per-row array comes back with the rows of ``pts`` (0 in the removed ones), and the dict
+    gains ``inlier`` [N] bool, ``outlier_score`` [N] and ``outlier_passes``.  With ``queries`` the rows are positions and nothing is
+    scattered; ``pidx`` with ``outliers`` is refused."""
+    if outliers is not None:
+        from . import outliers as _outliers
+        return _outliers.run_filtered(select_normals, pts, outliers, pidx, queries, device, ladder=ladder, slack=slack, orient=orient,
+                                      viewpoint=viewpoint, orient_k=orient_k, smooth=smooth)
     from . import smooth as _smooth
     from .config import NestiConfig
     ladder, slack = check_ladder(ladder), check_slack(slack)

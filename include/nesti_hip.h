@@ -901,6 +901,61 @@ int nesti_outlier_compact(const float* cloud_dev, int N, const double* scores_de
  * of its result.  Any other value is refused. */
 int nesti_debug_outlier_lanes(int lanes);
 
+/* ---- voxel-grid downsampling before estimation (voxel.hip; DESIGN.md 2 "Voxel downsampling") ---------------------------------------
+ * One point per occupied cell of a regular grid, as three entries: a key per row, a stable device-wide radix sort of (key, row index)
+ * pairs, a reduction of the sorted runs.  The conventions are the library's own: fp64 where there is arithmetic, every operation
+ * rounded on its own, only + - x /, floor, comparisons and integer arithmetic, no floating-point atomics and no global-memory atomics,
+ * no workgroup waits on another -- a restatement in plain IEEE arithmetic predicts every output bit, and every output is a pure
+ * function of its inputs: independent of streams and of timing.  No parity with any published code is claimed.
+ *
+ * nesti_voxel_workspace_bytes: the one size that serves nesti_sort_pairs and nesti_voxel_reduce over n rows; a multiple of 256; 0 for
+ * n <= 0.  nesti_sort_tile_items: the keys one workgroup handles per pass of the sort, a constant (tests place their sizes around it).
+ *
+ * nesti_voxel_keys: origin [3] and voxel [3] are HOST doubles, dims [3] HOST int64; keys_out_dev [N] uint64.  Per axis a:
+ *      d_a = (double)p_a - origin_a,  t_a = d_a / voxel_a,  i_a = (int64)floor(t_a);   key = (i_z dims_y + i_y) dims_x + i_x
+ *  A row with a non-finite coordinate (tested on the bits) or with an i_a outside [0, dims_a) is LOST: its key is dims_x dims_y dims_z,
+ *  one past the largest real key, so lost rows sort last.  One kernel.
+ *
+ * nesti_sort_pairs: keys_out_dev [N] uint64 and idx_out_dev [N] int32 = the keys of keys_in_dev [N] in ascending order of their low
+ * key_bits (1 .. 64) bits and the row each came from; rows of equal low bits keep their order (STABLE): the result is
+ * argsort(keys & mask, stable).  Keys are carried whole; bits at and above key_bits take no part in the order.  Least-significant-digit
+ * radix sort, 8-bit digits, ceil(key_bits / 8) passes that ping-pong between the outputs and the workspace; a pass is a per-workgroup
+ * digit histogram of a tile (one 256-bin LDS histogram per wave), a two-level scan of the digit-major table [256, blocks] (chunks of
+ * 4096 entries by a workgroup each, their totals by ONE workgroup) and a scatter in which a workgroup recomputes the stable rank of
+ * each of its keys among the keys of the same digit in its tile with 64-bit ballots: four kernels per pass.  keys_out_dev must not be keys_in_dev (keys_in_dev is left as it is).  ws_dev: nesti_voxel_workspace_bytes(N) bytes.
+ *
+ * nesti_voxel_reduce: sorted_keys_dev / sorted_idx_dev [N] as nesti_sort_pairs returns them for the keys of nesti_voxel_keys (row
+ * indices outside [0, N) are skipped, never followed); lost_key = dims_x dims_y dims_z; origin as for the keys.  Sorted position i
+ * starts a voxel when key[i] != key[i - 1] and key[i] != lost_key; ordered compaction by per-block counts, one single-workgroup scan
+ * and a scatter (the scheme of nesti_outlier_compact).  Voxels come in ascending key order (z-major).  Outputs (device; any but
+ * n_voxels_out_dev may be NULL; the per-voxel ones are sized for N rows by the caller, the first V are written):
+ *      centroid_out_dev [V,3] f32    c_a = origin_a + S_a / (double)count, rounded to f32 once
+ *      rep_out_dev      [V]   int32  the row nearest the fp64 centroid: the smallest (d2, index), e_a = d_a - S_a / count,
+ *                                    d2 = (e_x e_x + e_y e_y) + e_z e_z
+ *      count_out_dev    [V]   int32
+ *      key_out_dev      [V]   uint64
+ *      voxel_of_out_dev [N]   int32  the voxel of every row, -1 for a lost one
+ *      n_voxels_out_dev [1]   int32  V
+ *  ORDER of S_a: a voxel's rows come in ascending index (the sort is stable); row number s of the voxel adds d_a = (double)p_a - origin_a
+ *  in lane s mod 64, a lane's slots in ascending order from +0.0; the lanes meet in an xor-butterfly (offsets 32, 16, ..., 1): the order
+ *  of the list fits.  An idle lane holds +0.0 and changes no bit, so a voxel of up to 256 rows is served by 16 lanes with four
+ *  accumulators each, met as (a0 + a2) + (a1 + a3), and a larger one by a whole wave: the same bytes.  ws_dev:
+ *  nesti_voxel_workspace_bytes(N) bytes.  Four kernels (three where centroid, rep and count are all NULL).
+ *
+ * Argument errors -- a null pointer; N <= 0; a voxel size that is not finite or not > 0; a non-finite origin; a dims entry < 1 or a
+ * product of the dims >= 2^62; key_bits outside 1 .. 64; keys_out_dev == keys_in_dev; a short workspace -- are reported before any
+ * device call.  No entry synchronises or reads anything back; each can be captured into a graph.  Under nesti_profile_enable the
+ * launches are booked in the patches category. */
+size_t nesti_voxel_workspace_bytes(int n);
+int nesti_sort_tile_items(void);
+int nesti_voxel_keys(const float* cloud_dev, int N, const double* origin, const double* voxel, const int64_t* dims, uint64_t* keys_out_dev,
+                     void* stream);
+int nesti_sort_pairs(const uint64_t* keys_in_dev, int N, int key_bits, uint64_t* keys_out_dev, int32_t* idx_out_dev, void* ws_dev,
+                     size_t ws_bytes, void* stream);
+int nesti_voxel_reduce(const float* cloud_dev, int N, const uint64_t* sorted_keys_dev, const int32_t* sorted_idx_dev, uint64_t lost_key,
+                       const double* origin, float* centroid_out_dev, int32_t* rep_out_dev, int32_t* count_out_dev, uint64_t* key_out_dev,
+                       int32_t* voxel_of_out_dev, int32_t* n_voxels_out_dev, void* ws_dev, size_t ws_bytes, void* stream);
+
 /* ---- depth images in, normal images out (depth.hip; DESIGN.md 2 "Depth images") --------------------------------------------------
  * The two ends of the reference's Kinect route: MATLAB/ScanNet_depth2xyz.m (depth + intrinsics + pose -> cloud) before
  * test_n_est_w_experts.py, and MATLAB/ScanNet_world2cam_normals.m / MATLAB/export_visualizations_nyu.m:146-153 (per-point results

@@ -214,6 +214,12 @@ SIGNATURES = {
     "nesti_outlier_threshold": (_i, [_vp, _i, ctypes.c_double, _vp, _vp, _sz, _vp]),
     "nesti_outlier_compact": (_i, [_vp, _i, _vp, _vp, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "nesti_debug_outlier_lanes": (_i, [_i]),
+    "nesti_voxel_workspace_bytes": (_sz, [_i]),
+    "nesti_sort_tile_items": (_i, []),
+    "nesti_voxel_keys": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64),
+                              _vp, _vp]),
+    "nesti_sort_pairs": (_i, [_vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "nesti_voxel_reduce": (_i, [_vp, _i, _vp, _vp, _u64, ctypes.POINTER(ctypes.c_double), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "nesti_depth_workspace_bytes": (_sz, [_i, _i]),
     "nesti_depth_to_cloud": (_i, [_vp, _i, _i, _i, ctypes.POINTER(CCamera), _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "nesti_image_scatter": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),

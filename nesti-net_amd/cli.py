@@ -23,7 +23,9 @@ the feature-preserving filter of :mod:`.smooth` before the orientation and adds 
 lists only: ``<shape>.normals`` (one scale), ``<shape>.robust_support``, ``<shape>.robust_inliers`` and ``<shape>.robust_count`` (every
 scale) and ``<shape>.knn_radius``.  ``--outliers statistical | radius`` removes outliers with the filter of :mod:`.outliers` before any
 estimator runs: every file keeps the rows of ``<shape>.xyz`` (a removed row is written as 0, its expert as -1) and
-``<shape>.inliers`` and ``<shape>.outlier_score`` are added."""
+``<shape>.inliers`` and ``<shape>.outlier_score`` are added.  ``--voxel_size V`` downsamples the cloud on a voxel grid
+(:mod:`.downsample`) before all of that, for the model-free estimators: every file still has the rows of the ``.xyz``, a row holding the
+result of its voxel, and ``<shape>.voxel_xyz``, ``<shape>.voxel_of`` and ``<shape>.voxel_count`` are added."""
 import argparse
 import ctypes
 import os
@@ -33,6 +35,7 @@ import torch
 
 from . import pca as _pca
 from . import hough as _hough
+from . import downsample as _downsample
 from . import outliers as _outliers
 from . import smooth as _smooth
 from . import quadric as _quadric
@@ -228,6 +231,15 @@ def build_parser():
                    help="--outliers radius: the radius, in the cloud's units (required)")
     p.add_argument("--outlier_passes", type=int, default=_outliers.DEFAULT_PASSES,
                    help="--outliers: filter passes, 1 .. 8; each searches the kept points again [default: %d]" % _outliers.DEFAULT_PASSES)
+    p.add_argument("--voxel_size", type=float, default=0.0, metavar="V",
+                   help="downsample the cloud on a voxel grid of this cell size, in the cloud's units, before anything else (DESIGN.md 2 "
+                        "'Voxel downsampling'), for --estimator pca | quadric | hough | robust and for --knn_ladder; 0: off [default].  "
+                        "--outliers, the estimator, --smooth and --orient then see one point per occupied cell; every file keeps one row "
+                        "per row of the .xyz (a row holds the result of its voxel), and <shape>.voxel_xyz, <shape>.voxel_of and "
+                        "<shape>.voxel_count are added.  Refused with --estimator net, --depth_images 1, --sparse_patches 1, "
+                        "--query_positions 1 and --subsample reference*")
+    p.add_argument("--voxel_mode", choices=list(_downsample.MODES), default=None,
+                   help="--voxel_size: a cell's point is the centroid of its points, or the nearest of them to it [default: centroid]")
     p.add_argument("--synthetic_weights", action="store_true", help="use seeded synthetic weights if model.nstw is absent")
     return p
 
@@ -265,13 +277,41 @@ def write_outlier_files(output_dir, name, inlier, score):
             f.write("%.17g\n" % v)
 
 
-def filter_shape(cloud, params, name, output_dir, printout):
+def voxel_line(name, params, rows, count):
+    """The log line of ``--voxel_size`` for shape ``name``: voxels, rows, largest count; ``count``: the int32 counts of the voxels."""
+    return ("voxel grid of %s (cell %s, %s): %d voxels from %d rows; largest count %d"
+            % (name, " ".join("%g" % v for v in params.voxel), params.mode, len(count), rows, int(count.max()) if len(count) else 0))
+
+
+def voxel_shape(cloud, params, name, output_dir, printout):
+    """``--voxel_size`` for one shape: downsample the cloud's points, write the three files -- one row per row of the cloud: the point
+    and the count of its voxel -- and the log line, and prepare the voxels' points the way ``cloud`` was (configuration, seed).
+    Returns (the downsampled cloud, the result of ``downsample.voxel_downsample``)."""
+    import numpy as np
+    from .provider import CloudPatches
+    try:
+        vd = _downsample.voxel_downsample(cloud.host_pts, *params, device=cloud.device)
+    except ValueError as e:
+        raise SystemExit("--voxel_size: %s: %s" % (name, e))
+    printout(voxel_line(name, params, cloud.n_points, vd["count"]))
+    textio.write_f32(os.path.join(output_dir, name + ".voxel_xyz"), _downsample.gather_host(vd["points"], vd["voxel_of"]))
+    textio.write_i32(os.path.join(output_dir, name + ".voxel_of"), np.ascontiguousarray(vd["voxel_of"], dtype=np.int32))
+    textio.write_i32(os.path.join(output_dir, name + ".voxel_count"), _downsample.gather_host(vd["count"], vd["voxel_of"]))
+    return CloudPatches(vd["points"], cloud.cfg, cloud.device, cloud.seed), vd
+
+
+def filter_shape(cloud, params, name, output_dir, printout, voxel_of=None):
     """``--outliers`` for one shape: filter the cloud's points, write the two files and the log line, and prepare the kept points the
-    way ``cloud`` was (configuration, seed, query positions).  Returns (the kept cloud, the result of ``outliers.remove_outliers``)."""
+    way ``cloud`` was (configuration, seed, query positions).  ``voxel_of``: the cloud is a downsampled one (``voxel_shape``) and the
+    two files are written with the rows of the input, a row holding what its voxel holds.  Returns (the kept cloud, the result of
+    ``outliers.remove_outliers``)."""
     from .provider import CloudPatches
     f = _outliers.remove_outliers(cloud.host_pts, *params, device=cloud.device)
     printout(outlier_line(name, params, cloud.n_points, f["passes"]))
-    write_outlier_files(output_dir, name, f["inlier"], f["score"])
+    if voxel_of is None:
+        write_outlier_files(output_dir, name, f["inlier"], f["score"])
+    else:
+        write_outlier_files(output_dir, name, _downsample.gather_host(f["inlier"], voxel_of), _downsample.gather_host(f["score"], voxel_of))
     if not len(f["kept"]):
         raise SystemExit("--outliers: the filter kept none of the %d points of %s" % (cloud.n_points, name))
     kept = CloudPatches(f["points"], cloud.cfg, cloud.device, cloud.seed, queries=None if cloud.queries is None else cloud.queries.cpu().numpy())
@@ -408,16 +448,19 @@ def select_line(name, rows, ladder, slack, sel):
             % (name, rows, slack, ", ".join("%d: %d" % (k, n) for k, n in zip(ladder, hist[1:].tolist())), int(hist[0])))
 
 
-def run_select(FLAGS, cfg, ladder, slack, pc_path, output_dir, printout, smooth=None, outliers=None):
+def run_select(FLAGS, cfg, ladder, slack, pc_path, output_dir, printout, smooth=None, outliers=None, voxel=None):
     """``--estimator pca --knn_ladder``: per shape the selected fit, the optional smoothing and orientation of its normals, and its
     files.  No model is loaded."""
     dataset = PointcloudPatchDataset(pc_path, FLAGS.testset, cfg, seed=3627473, sparse_patches=FLAGS.sparse_patches,
                                      device="cuda:%d" % FLAGS.gpu, query_positions=bool(FLAGS.query_positions))
     for ind, name in enumerate(dataset.shape_names):
         cloud = dataset.get_shape(ind)
-        filt = None
+        filt = vox = None
+        if voxel is not None:                                  # first: the filter below is a density test, the grid evens the density
+            cloud, vox = voxel_shape(cloud, voxel, name, output_dir, printout)
         if outliers is not None:
-            full, (cloud, filt) = cloud.n_points, filter_shape(cloud, outliers, name, output_dir, printout)
+            full, (cloud, filt) = cloud.n_points, filter_shape(cloud, outliers, name, output_dir, printout,
+                                                               None if vox is None else vox["voxel_of"])
         res = _select.select_cloud(cloud, ladder, slack, orient=None if FLAGS.orient == "0" else FLAGS.orient, viewpoint=FLAGS.viewpoint,
                                    orient_k=FLAGS.orient_k, smooth=smooth)
         printout(select_line(name, cloud.patch_count, ladder, slack, res["sel"]))
@@ -425,6 +468,8 @@ def run_select(FLAGS, cfg, ladder, slack, pc_path, output_dir, printout, smooth=
             printout(smooth_line(name, cloud.patch_count, smooth, res["smooth_count"]))
         if filt is not None and cloud.queries is None:        # the log lines above count the kept rows; the files hold every row
             res = _outliers.scatter_result(res, filt["kept"], full)
+        if vox is not None:                                    # ... and a row of the input holds the result of its voxel
+            res = _downsample.gather_result(res, vox["voxel_of"], len(vox["rep"]))
         if smooth is not None:
             write_smooth_support(os.path.join(output_dir, name + ".smooth_support"), res["smooth_support"], res["smooth_count"])
         if res["orient"] is not None:
@@ -454,7 +499,7 @@ def fit_line(estimator, name, rows, scale, n_scales, missing, radius=None, k=Non
                fit["no_fit"][k is not None]))
 
 
-def run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None, smooth=None, outliers=None):
+def run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None, smooth=None, outliers=None, voxel=None):
     """``--estimator pca / quadric`` (``FITS``): per shape the fit at every scale, the optional orientation of the rows of scale ``scale``
     (>= 0; the quadric fit flips their curvatures with them), and the estimator's files.  No model is loaded."""
     fit = FITS[FLAGS.estimator]
@@ -462,9 +507,12 @@ def run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None, smooth=No
                                      device="cuda:%d" % FLAGS.gpu, query_positions=bool(FLAGS.query_positions))
     for ind, name in enumerate(dataset.shape_names):
         cloud = dataset.get_shape(ind)
-        filt = None
+        filt = vox = None
+        if voxel is not None:                                  # first: the filter below is a density test, the grid evens the density
+            cloud, vox = voxel_shape(cloud, voxel, name, output_dir, printout)
         if outliers is not None:
-            full, (cloud, filt) = cloud.n_points, filter_shape(cloud, outliers, name, output_dir, printout)
+            full, (cloud, filt) = cloud.n_points, filter_shape(cloud, outliers, name, output_dir, printout,
+                                                               None if vox is None else vox["voxel_of"])
         params = {kw: getattr(FLAGS, flag) for kw, flag in fit.get("params", ())}
         res = fit["fit"](cloud, scale=scale, orient=None if FLAGS.orient == "0" else FLAGS.orient, viewpoint=FLAGS.viewpoint,
                          orient_k=FLAGS.orient_k, knn=ks, smooth=smooth, **params)
@@ -479,6 +527,8 @@ def run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None, smooth=No
             printout(smooth_line(name, cloud.patch_count, smooth, res["smooth_count"]))
         if filt is not None and cloud.queries is None:        # the log lines above count the kept rows; the files hold every row
             res = _outliers.scatter_result(res, filt["kept"], full)
+        if vox is not None:                                    # ... and a row of the input holds the result of its voxel
+            res = _downsample.gather_result(res, vox["voxel_of"], len(vox["rep"]))
         if ks is not None:
             textio.write_f32(os.path.join(output_dir, name + ".knn_radius"), res["radius"])
         if smooth is not None:
@@ -550,6 +600,25 @@ def main(argv=None):
             _robust.check_params(FLAGS.robust_iters, FLAGS.robust_sigma, FLAGS.robust_falloff, FLAGS.robust_floor)
         except ValueError as e:
             parser.error("--estimator robust: %s" % e)
+    voxel = None
+    if FLAGS.voxel_size != 0.0:
+        later = "left for later: the network route and depth frames are a pull request of their own"
+        for given, flag, why in ((FLAGS.depth_images, "--depth_images 1", later),
+                                 (FLAGS.sparse_patches, "--sparse_patches 1",
+                                  "left for later: the grid renumbers the cloud and a .pidx entry names a row that no longer exists"),
+                                 (FLAGS.query_positions, "--query_positions 1",
+                                  "left for later: the rows of the files would be positions, not the rows of the .xyz"),
+                                 (FLAGS.subsample != "hash", "--subsample %s" % FLAGS.subsample,
+                                  "left for later: the reference's subsample order is that of the full cloud"),
+                                 (not fit, "--estimator net", later)):
+            if given:
+                parser.error("--voxel_size does not go with %s: %s" % (flag, why))
+        try:
+            voxel = _downsample.check_params(FLAGS.voxel_size, FLAGS.voxel_mode or "centroid")
+        except ValueError as e:
+            parser.error("--voxel_size: %s" % e)
+    elif FLAGS.voxel_mode is not None:
+        parser.error("--voxel_mode belongs to --voxel_size V")
     if fit:
         for given, flag, why in ((FLAGS.depth_images, "--depth_images 1", "depth frames belong to the network path (--estimator net)"),
                                  (FLAGS.reproducible, "--reproducible 1",
@@ -640,7 +709,7 @@ def main(argv=None):
     if fit:
         cfg = NestiConfig.for_model(FLAGS.model)
         if ladder is not None:
-            rc = run_select(FLAGS, cfg, ladder, slack, pc_path, output_dir, printout, smooth, outliers)
+            rc = run_select(FLAGS, cfg, ladder, slack, pc_path, output_dir, printout, smooth, outliers, voxel)
             flog.close()
             return rc
         if FLAGS.patch_radius is not None:
@@ -649,7 +718,7 @@ def main(argv=None):
             scale = _pca.check_scale(getattr(FLAGS, fit["scale_flag"]), cfg.n_scales if ks is None else len(ks))
         except ValueError as e:
             raise SystemExit("--%s with --model %s: %s" % (fit["scale_flag"], FLAGS.model, e))
-        rc = run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks, smooth, outliers)
+        rc = run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks, smooth, outliers, voxel)
         flog.close()
         return rc
 

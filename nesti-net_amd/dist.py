@@ -136,7 +136,8 @@ def _verified(estimator, run_once, group):
 
 def estimate_sharded(estimator, cloud, group=None):
     """Run this rank's block of ``cloud``'s patch rows and gather everyone's results.  It does not filter outliers: filter first
-    (``outliers.remove_outliers``) and shard the kept cloud, so that every rank sees the same bounding box and the same rows."""
+    (``outliers.remove_outliers``) and shard the kept cloud, so that every rank sees the same bounding box and the same rows.  Nor does it
+    downsample: a voxel grid (``downsample.voxel_downsample``) before a sharded run is left for later, with the network route."""
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     lo, hi = shard_range(cloud.patch_count, rank, world)

@@ -133,7 +133,7 @@ def prepare_cloud(pts, cfg, pidx, queries, scale, orient, viewpoint, orient_k, d
 
 
 def pca_normals(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, viewpoint=None, orient_k=8, device="cuda:0", knn=None,
-                smooth=None, outliers=None):
+                smooth=None, outliers=None, downsample=None):
     """Plane-fit normals of a cloud: numpy in, a dict of numpy arrays out (synchronises).  Queries are all points, the points
     ``pidx`` or the positions ``queries`` [M,3] (mutually exclusive), as for ``NormalEstimator.estimate``; the radii are
     ``cfg.patch_radius`` times the cloud's bounding-box diagonal.
@@ -168,7 +168,17 @@ def pca_normals(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, v
     (``outliers.remove_outliers``; DESIGN.md 2 "Outlier removal") -- filters the cloud first: the estimator, its smoothing and its
     orientation run on the kept points, every per-row array comes back with the rows of ``pts`` (0 in the removed ones), and the dict
     gains ``inlier`` [N] bool, ``outlier_score`` [N] and ``outlier_passes``.  With ``queries`` the rows are positions and nothing is
-    scattered; ``pidx`` with ``outliers`` is refused."""
+    scattered; ``pidx`` with ``outliers`` is refused.
+
+    ``downsample`` -- None, a voxel size (a number or three, in the cloud's units) or a dict of ``voxel``, ``mode``, ``origin``
+    (``downsample.voxel_downsample``; DESIGN.md 2 "Voxel downsampling") -- downsamples the cloud on a voxel grid first: the estimator,
+    ``outliers`` (which comes second), the smoothing and the orientation run on the voxels' points, every per-row array comes back
+    with the rows of ``pts`` -- row i holds the result of its voxel --, and the dict gains ``voxel_of`` [N], ``voxel_points`` [V,3] and
+    ``voxel_count`` [V].  With ``queries`` nothing is gathered; ``pidx`` with ``downsample`` is refused."""
+    if downsample is not None:
+        from . import downsample as _downsample
+        return _downsample.run_downsampled(pca_normals, pts, downsample, outliers, pidx, queries, device, cfg=cfg, scale=scale, orient=orient,
+                                      viewpoint=viewpoint, orient_k=orient_k, knn=knn, smooth=smooth)
     if outliers is not None:
         from . import outliers as _outliers
         return _outliers.run_filtered(pca_normals, pts, outliers, pidx, queries, device, cfg=cfg, scale=scale, orient=orient,

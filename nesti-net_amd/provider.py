@@ -86,8 +86,8 @@ class CloudPatches:
     the sentinel outputs.
 
     ``radius_grid=False`` skips the radius grid: only :meth:`knn`, :meth:`pca_knn`, :meth:`quadric_knn`, :meth:`hough_knn`,
-    :meth:`pca_select`, :meth:`smooth_knn` and the outlier filter's :meth:`outlier_scores`, :meth:`outlier_threshold` and
-    :meth:`outlier_compact` may then be called."""
+    :meth:`pca_select`, :meth:`smooth_knn`, the outlier filter's :meth:`outlier_scores`, :meth:`outlier_threshold` and
+    :meth:`outlier_compact` and the voxel grid's :meth:`voxel_keys`, :meth:`sort_pairs` and :meth:`voxel_reduce` may then be called."""
 
     def __init__(self, pts, cfg: NestiConfig, device="cuda:0", seed=3627473, pidx=None, queries=None, radius_grid=True):
         if pidx is not None and queries is not None:
@@ -522,6 +522,90 @@ class CloudPatches:
                                                       ctypes.c_void_p(st.cuda_stream)), "nesti_outlier_compact")
             ws.record_stream(st)
         return out
+
+    # ---- voxel-grid downsampling (csrc/voxel.hip; DESIGN.md 2 "Voxel downsampling"; downsample.py) ---------------------------------------
+    # Keys cross as int64 tensors that hold the uint64 bits (torch has no arithmetic on uint64; a voxel key is below 2^62 anyway).
+    VOXEL_OUTPUTS = ("centroid", "rep", "count", "key", "voxel_of")
+
+    def _voxel_ws(self, rows):
+        """The workspace of ``nesti_sort_pairs`` / ``nesti_voxel_reduce`` for ``rows`` rows: a fresh tensor per call, so calls on
+        several streams never share one."""
+        return torch.empty(max(1, self.lib.nesti_voxel_workspace_bytes(max(1, int(rows)))), dtype=torch.uint8, device=self.device)
+
+    def _check_keys(self, keys, what):
+        if (not isinstance(keys, torch.Tensor) or keys.dtype != torch.int64 or keys.dim() != 1 or not keys.is_contiguous()
+                or keys.device != self.device):
+            raise ValueError("%s: a contiguous int64 [n] tensor (the uint64 bits) on %s" % (what, self.device))
+
+    def voxel_keys(self, origin, voxel, dims, stream=None):
+        """The voxel key of every cloud row (``nesti_voxel_keys``): ``origin`` and ``voxel`` three host floats, ``dims`` three host
+        ints (``downsample.grid_of``).  A device tensor [n_points] int64 holding the uint64 keys ``(i_z dims_y + i_y) dims_x + i_x``;
+        a row outside the grid has the lost key ``dims_x dims_y dims_z``.  Asynchronous on ``stream``."""
+        from . import downsample as _downsample
+        origin, voxel, dims = _downsample.check_grid(origin, voxel, dims)
+        st = self._stream(stream)
+        N = self.n_points
+        with torch.cuda.device(self.device), torch.cuda.stream(st):
+            keys = torch.empty(N, dtype=torch.int64, device=self.device)
+            if N:
+                _lib.check(self.lib.nesti_voxel_keys(_lib.ptr(self.cloud), N, (ctypes.c_double * 3)(*origin), (ctypes.c_double * 3)(*voxel),
+                                                     (ctypes.c_int64 * 3)(*dims), _lib.ptr(keys), ctypes.c_void_p(st.cuda_stream)),
+                           "nesti_voxel_keys")
+        return keys
+
+    def sort_pairs(self, keys, key_bits, stream=None):
+        """A stable sort of ``keys`` [n] int64 (the uint64 bits; any n, not only the cloud's) by their low ``key_bits`` (1 .. 64) bits
+        (``nesti_sort_pairs``): device tensors ``(sorted_keys [n] int64, idx [n] int32)`` with ``sorted_keys = keys[idx]`` and ``idx`` the
+        stable argsort of ``keys & mask``.  ``keys`` is left as it is.  Asynchronous on ``stream``."""
+        from . import downsample as _downsample
+        key_bits = _downsample.check_key_bits(key_bits)
+        self._check_keys(keys, "keys")
+        st = self._stream(stream)
+        n = int(keys.shape[0])
+        with torch.cuda.device(self.device), torch.cuda.stream(st):
+            out = check_out(None, (((n,), torch.int64), ((n,), torch.int32)), self.device)
+            if n:
+                ws = self._voxel_ws(n)
+                _lib.check(self.lib.nesti_sort_pairs(_lib.ptr(keys), n, key_bits, _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(ws), ws.numel(),
+                                                     ctypes.c_void_p(st.cuda_stream)), "nesti_sort_pairs")
+                ws.record_stream(st)
+        return out
+
+    def voxel_reduce(self, sorted_keys, sorted_idx, lost_key, origin, outputs=VOXEL_OUTPUTS, stream=None):
+        """The voxels of the cloud from its sorted keys (``nesti_voxel_reduce``): ``sorted_keys`` / ``sorted_idx`` [n_points] as
+        :meth:`sort_pairs` returns them for :meth:`voxel_keys`, ``lost_key`` = ``dims_x dims_y dims_z``, ``origin`` as for the keys.
+        Device tensors ``(centroid [n_points,3] f32, rep [n_points] int32, count [n_points] int32, key [n_points] int64, voxel_of
+        [n_points] int32 (-1: a lost row), n_voxels [1] int32)``: the first V = n_voxels rows of the first four are written, voxels in
+        ascending key order.  An output not named in ``outputs`` is not computed and comes back as None.  Nothing is read back: the
+        caller reads ``n_voxels`` and slices.  Asynchronous on ``stream``."""
+        from . import downsample as _downsample
+        N = self.n_points
+        self._check_keys(sorted_keys, "sorted_keys")
+        if (tuple(sorted_keys.shape) != (N,) or not isinstance(sorted_idx, torch.Tensor) or sorted_idx.dtype != torch.int32
+                or tuple(sorted_idx.shape) != (N,) or not sorted_idx.is_contiguous() or sorted_idx.device != self.device):
+            raise ValueError("sorted_keys int64 [n_points] and sorted_idx int32 [n_points], contiguous on %s" % self.device)
+        extra = sorted(set(outputs) - set(self.VOXEL_OUTPUTS))
+        if extra:
+            raise ValueError("outputs: unknown name %r (%s)" % (extra[0], ", ".join(self.VOXEL_OUTPUTS)))
+        lost_key = int(lost_key)
+        if not 0 < lost_key < 1 << 62:
+            raise ValueError("lost_key must be the number of cells, in 1 .. 2^62 - 1: got %r" % (lost_key,))
+        origin = _downsample.check_origin(origin)
+        st = self._stream(stream)
+        specs = {"centroid": ((N, 3), torch.float32), "rep": ((N,), torch.int32), "count": ((N,), torch.int32), "key": ((N,), torch.int64),
+                 "voxel_of": ((N,), torch.int32)}
+        with torch.cuda.device(self.device), torch.cuda.stream(st):
+            out = [torch.empty(specs[name][0], dtype=specs[name][1], device=self.device) if name in outputs else None
+                   for name in self.VOXEL_OUTPUTS]
+            n_voxels = torch.zeros(1, dtype=torch.int32, device=self.device)
+            if N:
+                ws = self._voxel_ws(N)
+                _lib.check(self.lib.nesti_voxel_reduce(_lib.ptr(self.cloud), N, _lib.ptr(sorted_keys), _lib.ptr(sorted_idx),
+                                                       ctypes.c_uint64(lost_key), (ctypes.c_double * 3)(*origin),
+                                                       *[_lib.ptr(t) for t in out], _lib.ptr(n_voxels), _lib.ptr(ws), ws.numel(),
+                                                       ctypes.c_void_p(st.cuda_stream)), "nesti_voxel_reduce")
+                ws.record_stream(st)
+        return tuple(out) + (n_voxels,)
 
     def build_reference_order(self, first, count, picks, pick_offsets, want_idx=False, out=None, stream=None):
         """Patch tensors of rows [first, first + count) exactly as the reference's ``PointcloudPatchDataset.__getitem__`` builds

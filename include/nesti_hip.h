@@ -846,6 +846,57 @@ int nesti_smooth_normals_nbr(const float* cloud_dev, int N, const float* normals
  * forces the one-wave-per-row form.  The choice moves the time of a pass, never a byte of its result.  Any other value is refused. */
 int nesti_debug_smooth_lanes(int lanes);
 
+/* ---- point denoising over neighbour lists (denoise.hip; DESIGN.md 2 "Point denoising") -----------------------------------------------
+ * One pass of the bilateral point filter (Fleishman, Drori and Cohen-Or 2003; Digne and de Franchis 2017; the projection step of Huang
+ * et al. 2013): a row's point moves along its own normal by the weighted mean of its neighbours' heights over its tangent plane.  The
+ * weight is smoothing's cone weight on the normals times a distance falloff times a Geman-McClure weight on the height, so a face is
+ * flattened and a crease is not rounded off.  It runs between outlier removal and estimation; normals are read, never written.  The
+ * conventions are the library's own: fp64 throughout, every operation rounded on its own, only + - x / sqrt, comparisons and integer
+ * arithmetic -- a restatement in plain IEEE arithmetic predicts every output bit.
+ *
+ * Centres (query_idx_dev / query_row0, M rows), nbr_dev [M, K] with row stride K (1 <= K <= NESTI_KNN_MAX_K) and the valid prefix are
+ * exactly as for nesti_smooth_normals_nbr.  normals_in_dev [N, 3] f32 holds a normal for every cloud point and is indexed like the
+ * cloud.  k in 1 .. K: the number of leading entries used.  cos_t in [0, 0.999999], falloff in [0, 1], sigma in (0, 1e6] (the height
+ * scale in neighbourhood radii; at 1e6 the height weight is 1 to rounding) and step in (0, 1]: fp64 on the host.  There is no _at
+ * entry: a position that is not a cloud point has nothing to move.
+ *  1 ELIGIBILITY.  As for nesti_smooth_normals_nbr, on the bits.  c = the centre's cloud index, p_c = cloud[c], n_c = normals_in[c],
+ *    q_c = (x x + y y) + z z of n_c in fp64.  A row whose n_c is not eligible, whose prefix is empty or whose centre is not finite
+ *    moves nothing: the three floats of p_c are copied bit for bit, delta, support and count are 0.
+ *  2 PREFIX.  n = min(k, valid prefix); d = (double)p - (double)c and d2 = (dx dx + dy dy) + dz dz per slot; r2 = the largest d2 of
+ *    the prefix; rad = sqrt(r2).
+ *  3 CENTRE NORMAL.  v = (double)n_c / sqrt(q_c), component by component.
+ *  4 SLOT i < n with neighbour j, n_j = normals_in[j] eligible (an ineligible neighbour adds nothing), q_j like q_c:
+ *      t as in step 3 of nesti_smooth_normals_nbr: dd = (n_c.x n_j.x + n_c.y n_j.y) + n_c.z n_j.z;   ca = |dd| / sqrt(q_c q_j);
+ *      t = (ca - cos_t) / (1 - cos_t);   if not t > 0 the slot adds nothing (this also catches NaN);   t = min(t, 1);
+ *      u = 1 - (falloff d2) / r2 if r2 > 0, else u = 1;
+ *      h = (v.x dx + v.y dy) + v.z dz;   x = h / (sigma rad) if r2 > 0, else x = 0;   g = 1 / (1 + x x);
+ *      a = (u t) g;   W = a a;   H += W h;   Wsum += W;   cnt += 1, an integer.
+ *  5 ORDER.  That of nesti_smooth_normals_nbr: lane l of a 64-lane wave adds its slots l, l + 64, ... in ascending order into partial
+ *    sums that start at +0.0; the lanes meet in an xor-butterfly (offsets 32, 16, ..., 1).
+ *  6 RESULT.  If Wsum > 0 and delta = step (H / Wsum) is finite, the output is (float)((double)p_c + delta v) per component, the
+ *    product and the sum rounded separately; otherwise the input row is copied bit for bit and delta is 0 (support and count are
+ *    still those of step 4).
+ *  7 OUTPUTS (device; any may be NULL):
+ *      points_out_dev  [M,3] f32
+ *      delta_out_dev   [M]   f32    (float)delta, the signed displacement along the centre's normal
+ *      support_out_dev [M]   f32    (float)Wsum
+ *      count_out_dev   [M]   int32  cnt
+ * DETERMINISM: no atomics.  A row's bits are a pure function of (cloud, centre, list prefix, the normals it reads, k, cos_t, falloff,
+ * sigma, step).  The output position does not depend on the sign of any input normal; delta takes the sign of the centre's.
+ * Argument errors -- those of nesti_smooth_normals_nbr; sigma not finite or outside (0, 1e6]; step not finite or outside (0, 1];
+ * points_out_dev [M,3] overlapping the cloud [N,3], equal base pointers included (the pass is a Jacobi step: rows read their
+ * neighbours' input positions) -- are reported before any device call; M = 0 is a no-op.  Each call enqueues one kernel on `stream`,
+ * neither synchronises nor reads anything back, and can be captured into a graph.  Under nesti_profile_enable the launch is booked in
+ * the patches category, like the other list fits. */
+int nesti_denoise_points_nbr(const float* cloud_dev, int N, const float* normals_in_dev, const int32_t* query_idx_dev, int M,
+                             int query_row0, const int32_t* nbr_dev, int K, int k, double cos_t, double falloff, double sigma,
+                             double step, float* points_out_dev, float* delta_out_dev, float* support_out_dev, int32_t* count_out_dev,
+                             void* stream);
+/* Measurement and tests only: the lane group that serves a row of nesti_denoise_points_nbr in this process, as
+ * nesti_debug_smooth_lanes: 0 (the default) the smallest of 16, 32 and 64 lanes that holds k; 16, 32 or 64: at least that many.  The
+ * choice moves the time of a pass, never a byte of its result.  Any other value is refused. */
+int nesti_debug_denoise_lanes(int lanes);
+
 /* ---- outlier removal before estimation (outlier.hip; DESIGN.md 2 "Outlier removal") --------------------------------------------------
  * The statistical and the radius outlier filter of a point cloud as three passes over the sorted lists nesti_knn returns: a score per
  * row, the statistics of a score array, an ordered compaction.  The conventions are the library's own: fp64 throughout, every

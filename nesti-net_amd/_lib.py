@@ -209,6 +209,8 @@ SIGNATURES = {
                                     + [_vp] * 10),
     "nesti_smooth_normals_nbr": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp]),
     "nesti_debug_smooth_lanes": (_i, [_i]),
+    "nesti_denoise_points_nbr": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _i, _i] + [ctypes.c_double] * 4 + [_vp] * 5),
+    "nesti_debug_denoise_lanes": (_i, [_i]),
     "nesti_outlier_workspace_bytes": (_sz, [_i]),
     "nesti_outlier_scores_nbr": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "nesti_outlier_threshold": (_i, [_vp, _i, ctypes.c_double, _vp, _vp, _sz, _vp]),

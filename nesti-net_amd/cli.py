@@ -25,7 +25,9 @@ scale) and ``<shape>.knn_radius``.  ``--outliers statistical | radius`` removes 
 estimator runs: every file keeps the rows of ``<shape>.xyz`` (a removed row is written as 0, its expert as -1) and
 ``<shape>.inliers`` and ``<shape>.outlier_score`` are added.  ``--voxel_size V`` downsamples the cloud on a voxel grid
 (:mod:`.downsample`) before all of that, for the model-free estimators: every file still has the rows of the ``.xyz``, a row holding the
-result of its voxel, and ``<shape>.voxel_xyz``, ``<shape>.voxel_of`` and ``<shape>.voxel_count`` are added."""
+result of its voxel, and ``<shape>.voxel_xyz``, ``<shape>.voxel_of`` and ``<shape>.voxel_count`` are added.  ``--denoise ITERS`` moves the
+positions with the bilateral point filter of :mod:`.denoise` after those two and before a model-free estimator, and adds
+``<shape>.denoised.xyz`` and ``<shape>.denoise_delta``."""
 import argparse
 import ctypes
 import os
@@ -35,6 +37,7 @@ import torch
 
 from . import pca as _pca
 from . import hough as _hough
+from . import denoise as _denoise
 from . import downsample as _downsample
 from . import outliers as _outliers
 from . import smooth as _smooth
@@ -240,8 +243,56 @@ def build_parser():
                         "--query_positions 1 and --subsample reference*")
     p.add_argument("--voxel_mode", choices=list(_downsample.MODES), default=None,
                    help="--voxel_size: a cell's point is the centroid of its points, or the nearest of them to it [default: centroid]")
+    p.add_argument("--denoise", type=int, default=0, metavar="ITERS",
+                   help="denoise the positions with ITERS passes (1 .. 64) of the bilateral point filter of DESIGN.md 2 'Point denoising', "
+                        "for --estimator pca | quadric | hough | robust and for --knn_ladder, after --voxel_size and --outliers and before "
+                        "the estimator: a point moves along its plane-fit normal by the weighted mean of its neighbours' heights.  The "
+                        "estimator, --smooth and --orient then see the denoised positions; <shape>.denoised.xyz and "
+                        "<shape>.denoise_delta (one row per row of the .xyz) are added.  0: off [default].  Refused with --estimator net, "
+                        "--depth_images 1, --sparse_patches 1, --query_positions 1, --subsample reference* and --reproducible 1")
+    p.add_argument("--denoise_k", type=int, default=_denoise.DEFAULT_K,
+                   help="--denoise: nearest neighbours per row, 1 .. 256; the normals are fitted over twice as many [default: %d]"
+                        % _denoise.DEFAULT_K)
+    p.add_argument("--denoise_angle", type=float, default=_denoise.DEFAULT_ANGLE,
+                   help="--denoise: the angle in degrees, in (0, 90], at which a neighbour's weight reaches 0 [default: %g]"
+                        % _denoise.DEFAULT_ANGLE)
+    p.add_argument("--denoise_falloff", type=float, default=_denoise.DEFAULT_FALLOFF,
+                   help="--denoise: the distance falloff in [0, 1] [default: %g]" % _denoise.DEFAULT_FALLOFF)
+    p.add_argument("--denoise_sigma", type=float, default=_denoise.DEFAULT_SIGMA,
+                   help="--denoise: the height scale in neighbourhood radii, in (0, 1e6]; 1e6 switches the height weight off [default: %g]"
+                        % _denoise.DEFAULT_SIGMA)
+    p.add_argument("--denoise_step", type=float, default=_denoise.DEFAULT_STEP,
+                   help="--denoise: the share of the weighted mean height a pass moves a point by, in (0, 1] [default: %g]"
+                        % _denoise.DEFAULT_STEP)
     p.add_argument("--synthetic_weights", action="store_true", help="use seeded synthetic weights if model.nstw is absent")
     return p
+
+
+def denoise_line(name, rows, params, moved, delta):
+    """The log line of ``--denoise`` for shape ``name``: the rows, the passes, the rows that moved and the largest displacement."""
+    return ("denoising of %s: %d rows, %d pass%s over %d nearest neighbours (%g degrees, falloff %g, sigma %g, step %g); %d rows moved, "
+            "largest displacement %.6g"
+            % (name, rows, params.iters, "" if params.iters == 1 else "es", params.k, params.angle, params.falloff, params.sigma, params.step,
+               moved, float(delta.max()) if len(delta) else 0.0))
+
+
+def denoise_shape(cloud, params, name, output_dir, printout, kept=None, full=None, voxel_of=None):
+    """``--denoise`` for one shape: denoise the cloud's points, write ``<shape>.denoised.xyz`` and ``<shape>.denoise_delta`` and the log
+    line, and prepare the denoised points the way ``cloud`` was (configuration, seed).  ``kept`` / ``full``: the cloud is a filtered one
+    (``filter_shape``); ``voxel_of``: a downsampled one (``voxel_shape``) -- the two files are written with the rows of the input, a
+    removed row holding 0 and a row of a voxel what its voxel holds.  Returns the denoised cloud."""
+    from .provider import CloudPatches
+    p = params
+    d = _denoise.denoise_points(cloud.host_pts, p.k, p.iters, p.angle, p.falloff, p.sigma, p.step, None, p.normal_k, device=cloud.device)
+    printout(denoise_line(name, cloud.n_points, p, d["moved"], d["delta"]))
+    points, delta = d["points"], d["delta"]
+    if kept is not None:
+        points, delta = _outliers.scatter_host(points, kept, full, 0), _outliers.scatter_host(delta, kept, full, 0)
+    if voxel_of is not None:
+        points, delta = _downsample.gather_host(points, voxel_of), _downsample.gather_host(delta, voxel_of)
+    textio.write_f32(os.path.join(output_dir, name + ".denoised.xyz"), points)
+    textio.write_f32(os.path.join(output_dir, name + ".denoise_delta"), delta)
+    return CloudPatches(d["points"], cloud.cfg, cloud.device, cloud.seed)
 
 
 def smooth_line(name, rows, params, count):
@@ -448,7 +499,7 @@ def select_line(name, rows, ladder, slack, sel):
             % (name, rows, slack, ", ".join("%d: %d" % (k, n) for k, n in zip(ladder, hist[1:].tolist())), int(hist[0])))
 
 
-def run_select(FLAGS, cfg, ladder, slack, pc_path, output_dir, printout, smooth=None, outliers=None, voxel=None):
+def run_select(FLAGS, cfg, ladder, slack, pc_path, output_dir, printout, smooth=None, outliers=None, voxel=None, denoise=None):
     """``--estimator pca --knn_ladder``: per shape the selected fit, the optional smoothing and orientation of its normals, and its
     files.  No model is loaded."""
     dataset = PointcloudPatchDataset(pc_path, FLAGS.testset, cfg, seed=3627473, sparse_patches=FLAGS.sparse_patches,
@@ -461,6 +512,9 @@ def run_select(FLAGS, cfg, ladder, slack, pc_path, output_dir, printout, smooth=
         if outliers is not None:
             full, (cloud, filt) = cloud.n_points, filter_shape(cloud, outliers, name, output_dir, printout,
                                                                None if vox is None else vox["voxel_of"])
+        if denoise is not None:                                # last before the estimator: rows stay one-to-one
+            cloud = denoise_shape(cloud, denoise, name, output_dir, printout, None if filt is None else filt["kept"],
+                                  None if filt is None else full, None if vox is None else vox["voxel_of"])
         res = _select.select_cloud(cloud, ladder, slack, orient=None if FLAGS.orient == "0" else FLAGS.orient, viewpoint=FLAGS.viewpoint,
                                    orient_k=FLAGS.orient_k, smooth=smooth)
         printout(select_line(name, cloud.patch_count, ladder, slack, res["sel"]))
@@ -499,7 +553,7 @@ def fit_line(estimator, name, rows, scale, n_scales, missing, radius=None, k=Non
                fit["no_fit"][k is not None]))
 
 
-def run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None, smooth=None, outliers=None, voxel=None):
+def run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None, smooth=None, outliers=None, voxel=None, denoise=None):
     """``--estimator pca / quadric`` (``FITS``): per shape the fit at every scale, the optional orientation of the rows of scale ``scale``
     (>= 0; the quadric fit flips their curvatures with them), and the estimator's files.  No model is loaded."""
     fit = FITS[FLAGS.estimator]
@@ -513,6 +567,9 @@ def run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None, smooth=No
         if outliers is not None:
             full, (cloud, filt) = cloud.n_points, filter_shape(cloud, outliers, name, output_dir, printout,
                                                                None if vox is None else vox["voxel_of"])
+        if denoise is not None:                                # last before the estimator: rows stay one-to-one
+            cloud = denoise_shape(cloud, denoise, name, output_dir, printout, None if filt is None else filt["kept"],
+                                  None if filt is None else full, None if vox is None else vox["voxel_of"])
         params = {kw: getattr(FLAGS, flag) for kw, flag in fit.get("params", ())}
         res = fit["fit"](cloud, scale=scale, orient=None if FLAGS.orient == "0" else FLAGS.orient, viewpoint=FLAGS.viewpoint,
                          orient_k=FLAGS.orient_k, knn=ks, smooth=smooth, **params)
@@ -619,6 +676,29 @@ def main(argv=None):
             parser.error("--voxel_size: %s" % e)
     elif FLAGS.voxel_mode is not None:
         parser.error("--voxel_mode belongs to --voxel_size V")
+    denoise = None
+    if FLAGS.denoise:
+        later = "left for later: the network route and depth frames are a pull request of their own"
+        for given, flag, why in ((FLAGS.depth_images, "--depth_images 1", later),
+                                 (FLAGS.sparse_patches, "--sparse_patches 1",
+                                  "the filter moves all points and the rows of a .pidx would not be the rows of the denoised cloud"),
+                                 (FLAGS.query_positions, "--query_positions 1",
+                                  "left for later: the rows of the files would be positions, not the rows of the .xyz"),
+                                 (FLAGS.subsample != "hash", "--subsample %s" % FLAGS.subsample,
+                                  "the reference's subsample order is that of the cloud as given"),
+                                 (FLAGS.reproducible, "--reproducible 1", "it belongs to the network route"),
+                                 (not fit, "--estimator net", later)):
+            if given:
+                parser.error("--denoise does not go with %s: %s" % (flag, why))
+        try:
+            denoise = _denoise.check_params(FLAGS.denoise_k, FLAGS.denoise, FLAGS.denoise_angle, FLAGS.denoise_falloff, FLAGS.denoise_sigma,
+                                            FLAGS.denoise_step)
+        except ValueError as e:
+            parser.error("--denoise: %s" % e)
+    else:
+        for flag in ("denoise_k", "denoise_angle", "denoise_falloff", "denoise_sigma", "denoise_step"):
+            if getattr(FLAGS, flag) != parser.get_default(flag):
+                parser.error("--%s belongs to --denoise ITERS" % flag)
     if fit:
         for given, flag, why in ((FLAGS.depth_images, "--depth_images 1", "depth frames belong to the network path (--estimator net)"),
                                  (FLAGS.reproducible, "--reproducible 1",
@@ -709,7 +789,7 @@ def main(argv=None):
     if fit:
         cfg = NestiConfig.for_model(FLAGS.model)
         if ladder is not None:
-            rc = run_select(FLAGS, cfg, ladder, slack, pc_path, output_dir, printout, smooth, outliers, voxel)
+            rc = run_select(FLAGS, cfg, ladder, slack, pc_path, output_dir, printout, smooth, outliers, voxel, denoise)
             flog.close()
             return rc
         if FLAGS.patch_radius is not None:
@@ -718,7 +798,7 @@ def main(argv=None):
             scale = _pca.check_scale(getattr(FLAGS, fit["scale_flag"]), cfg.n_scales if ks is None else len(ks))
         except ValueError as e:
             raise SystemExit("--%s with --model %s: %s" % (fit["scale_flag"], FLAGS.model, e))
-        rc = run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks, smooth, outliers, voxel)
+        rc = run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks, smooth, outliers, voxel, denoise)
         flog.close()
         return rc
 

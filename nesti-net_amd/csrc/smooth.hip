@@ -52,6 +52,7 @@
 
 #include "pca_dev.h"
 #include "nbr_dev.h"
+#include "group_dev.h"
 
 namespace nesti {
 namespace {
@@ -65,37 +66,7 @@ struct SmoothParams {
   int32_t* count_out;                 // [M] or NULL
 };
 
-__device__ __forceinline__ bool nonzero_bits(float v) { return (__float_as_uint(v) & 0x7fffffffu) != 0u; }
-// all three components finite and at least one non-zero, on the bits: orient.hip's rule
-__device__ __forceinline__ bool eligible_normal(float x, float y, float z) {
-  return finite_bits(x) && finite_bits(y) && finite_bits(z) && (nonzero_bits(x) || nonzero_bits(y) || nonzero_bits(z));
-}
-
-// the reductions of a group of G lanes (G = 64: wave_sum / wave_min / wave_max of pca_dev.h, offset for offset)
-template <int G>
-__device__ __forceinline__ double group_sum(double v) {
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) v = v + __shfl_xor(v, off, kWave);
-  return v;
-}
-template <int G>
-__device__ __forceinline__ int group_sum(int v) {
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-template <int G>
-__device__ __forceinline__ int group_min(int v) {
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, kWave));
-  return v;
-}
-template <int G>
-__device__ __forceinline__ double group_max(double v) {
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, kWave));
-  return v;
-}
+// eligible_normal and the reductions of a group of G lanes (group_sum / group_min / group_max): group_dev.h
 
 // G = 64: one row per wave.  G = 16, 32 (k <= G): 64 / G rows per wave, one per group of G lanes; a lane holds at most one slot, its
 // partial sums are 0 + the slot's terms, and the butterfly of the group is the tail (offsets G / 2, ..., 1) of the wave's, whose head

@@ -78,7 +78,7 @@ def hough_cloud(cloud, knn=DEFAULT_KNN, scale=-1, triplets=DEFAULT_TRIPLETS, bin
 
 def hough_normals(pts, knn=DEFAULT_KNN, pidx=None, queries=None, scale=-1, triplets=DEFAULT_TRIPLETS, bins=DEFAULT_BINS,
                   rotations=DEFAULT_ROTATIONS, seed=0, orient=None, viewpoint=None, orient_k=8, device="cuda:0", cfg=None, smooth=None,
-                  outliers=None, downsample=None):
+                  outliers=None, downsample=None, denoise=None):
     """Hough-transform normals of a cloud: numpy in, a dict of numpy arrays out (synchronises).  Queries are all points, the points
     ``pidx`` or the positions ``queries`` [M,3] (mutually exclusive), as for ``pca.pca_normals``.  ``knn`` -- an int or an ascending
     sequence of at most 4 ints in 1 .. 256 -- names the neighbourhoods: scale s is the ``knn[s]`` nearest cloud points of the query
@@ -116,15 +116,28 @@ def hough_normals(pts, knn=DEFAULT_KNN, pidx=None, queries=None, scale=-1, tripl
     (``downsample.voxel_downsample``; DESIGN.md 2 "Voxel downsampling") -- downsamples the cloud on a voxel grid first: the estimator,
     ``outliers`` (which comes second), the smoothing and the orientation run on the voxels' points, every per-row array comes back
     with the rows of ``pts`` -- row i holds the result of its voxel --, and the dict gains ``voxel_of`` [N], ``voxel_points`` [V,3] and
-    ``voxel_count`` [V].  With ``queries`` nothing is gathered; ``pidx`` with ``downsample`` is refused."""
+    ``voxel_count`` [V].  With ``queries`` nothing is gathered; ``pidx`` with ``downsample`` is refused.
+
+    ``denoise`` -- None, True (the defaults) or a dict of ``k``, ``iters``, ``angle``, ``falloff``, ``sigma``, ``step``, ``normal_k``
+    (``denoise.denoise_points``; DESIGN.md 2 "Point denoising") -- denoises the positions after ``downsample`` and ``outliers`` and
+    before the estimator, whose smoothing and orientation then run over the denoised positions.  Rows stay one-to-one: every per-row
+    array keeps its rows and the dict gains ``points`` [N,3] f32 and ``denoise_delta`` [N] f32 (0 in rows that ``outliers`` removed).
+    With ``queries`` the cloud is denoised and the queries are left alone; ``pidx`` with ``denoise`` is refused."""
+    if denoise is not None:
+        from . import denoise as _denoise
+        denoise = _denoise.check_arg(denoise, pidx)
     if downsample is not None:
         from . import downsample as _downsample
         return _downsample.run_downsampled(hough_normals, pts, downsample, outliers, pidx, queries, device, knn=knn, scale=scale, triplets=triplets,
                                       bins=bins, rotations=rotations, seed=seed, orient=orient, viewpoint=viewpoint, orient_k=orient_k,
-                                      cfg=cfg, smooth=smooth)
+                                      cfg=cfg, smooth=smooth, denoise=denoise)
     if outliers is not None:
         from . import outliers as _outliers
         return _outliers.run_filtered(hough_normals, pts, outliers, pidx, queries, device, knn=knn, scale=scale, triplets=triplets,
+                                      bins=bins, rotations=rotations, seed=seed, orient=orient, viewpoint=viewpoint, orient_k=orient_k,
+                                      cfg=cfg, smooth=smooth, denoise=denoise)
+    if denoise is not None:
+        return _denoise.run_denoised(hough_normals, pts, denoise, pidx, queries, device, knn=knn, scale=scale, triplets=triplets,
                                       bins=bins, rotations=rotations, seed=seed, orient=orient, viewpoint=viewpoint, orient_k=orient_k,
                                       cfg=cfg, smooth=smooth)
     _need_knn(knn)

@@ -86,7 +86,7 @@ class CloudPatches:
     the sentinel outputs.
 
     ``radius_grid=False`` skips the radius grid: only :meth:`knn`, :meth:`pca_knn`, :meth:`quadric_knn`, :meth:`hough_knn`,
-    :meth:`pca_select`, :meth:`smooth_knn`, the outlier filter's :meth:`outlier_scores`, :meth:`outlier_threshold` and
+    :meth:`pca_select`, :meth:`smooth_knn`, :meth:`denoise_knn`, the outlier filter's :meth:`outlier_scores`, :meth:`outlier_threshold` and
     :meth:`outlier_compact` and the voxel grid's :meth:`voxel_keys`, :meth:`sort_pairs` and :meth:`voxel_reduce` may then be called."""
 
     def __init__(self, pts, cfg: NestiConfig, device="cuda:0", seed=3627473, pidx=None, queries=None, radius_grid=True):
@@ -435,6 +435,41 @@ class CloudPatches:
                 _lib.check(self.lib.nesti_smooth_normals_nbr(
                     _lib.ptr(self.cloud), self.n_points, _lib.ptr(normals), _lib.ptr(q), count, first, _lib.ptr(nbr), int(nbr.shape[1]), k,
                     cos_t, falloff, *[_lib.ptr(t) for t in out], ctypes.c_void_p(st.cuda_stream)), "nesti_smooth_normals_nbr")
+        return out
+
+    def denoise_knn(self, normals, first, count, k, cos_t, falloff, sigma, step, nbr=None, grid=None, stream=None):
+        """One pass of point denoising over patch rows [first, first + count) (``nesti_denoise_points_nbr``; DESIGN.md 2 "Point
+        denoising"): ``normals`` [n_points,3] f32 on the device holds a normal for every cloud point; a row's point moves along its
+        own normal by ``step`` times the weighted mean of the heights of its ``k`` nearest cloud points over its tangent plane, the
+        weight 0 where the (unoriented) angle between the normals reaches acos(``cos_t``), falling with the distance by ``falloff``
+        and with the height over ``sigma`` neighbourhood radii.  Device tensors ``(points [count,3] f32, delta [count] f32 (the signed
+        displacement along the row's normal), support [count] f32 (the sum of the weights), count [count] int32 (the neighbours that
+        had one))``.  ``nbr`` [count,K >= k] int32: the caller's own lists instead of a search at K = k (untrusted, as for
+        :meth:`pca_knn`).  The pass is a Jacobi step: the returned points are a fresh tensor, never the cloud.  Serves all points and
+        ``pidx``; a cloud built with ``queries=`` raises ``ValueError`` (a position that is not a cloud point has nothing to move).
+        Asynchronous on ``stream``."""
+        from . import denoise as _denoise
+        if self.queries is not None:
+            raise ValueError("denoise_knn: a cloud with position queries cannot be denoised: a position that is not a cloud point has "
+                             "nothing to move")
+        k, cos_t, falloff, sigma, step = _denoise.check_pass(k, cos_t, falloff, sigma, step)
+        if (not isinstance(normals, torch.Tensor) or normals.dtype != torch.float32 or tuple(normals.shape) != (self.n_points, 3)
+                or not normals.is_contiguous() or normals.device != self.device):
+            raise ValueError("normals: a contiguous float32 [n_points, 3] tensor on %s" % self.device)
+        st = self._stream(stream)
+        if nbr is None:
+            nbr = self.knn(first, count, k, grid=grid, stream=st)[0]
+        at, q = self._rows(first, count)
+        if (nbr.dtype != torch.int32 or nbr.dim() != 2 or nbr.shape[0] != count or nbr.shape[1] < k or not nbr.is_contiguous()
+                or nbr.device != self.device):
+            raise ValueError("nbr: a contiguous int32 [count, K >= k] tensor on %s" % self.device)
+        out = check_out(None, (((count, 3), torch.float32), ((count,), torch.float32), ((count,), torch.float32), ((count,), torch.int32)),
+                        self.device)
+        if count:                         # 0 rows: a no-op; an empty list has no address to pass
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.nesti_denoise_points_nbr(
+                    _lib.ptr(self.cloud), self.n_points, _lib.ptr(normals), _lib.ptr(q), count, first, _lib.ptr(nbr), int(nbr.shape[1]), k,
+                    cos_t, falloff, sigma, step, *[_lib.ptr(t) for t in out], ctypes.c_void_p(st.cuda_stream)), "nesti_denoise_points_nbr")
         return out
 
     # ---- outlier removal (csrc/outlier.hip; DESIGN.md 2 "Outlier removal"; outliers.py) -----------------------------------------------

@@ -1067,6 +1067,49 @@ int nesti_project_to_image(const float* xyz_dev, const void* values_dev, int M, 
                            const nesti_camera_t* camera, const void* fill, void* image_dev, int32_t* index_image_dev,
                            void* ws_dev, size_t ws_bytes, void* stream);
 
+/* ---- image-window neighbour lists (window.hip; DESIGN.md 2 "Image-window neighbourhoods") ------------------------------------------
+ * A depth frame is an organized cloud: the neighbours of a pixel's point are, almost always, points of nearby pixels, and rank_dev of
+ * nesti_depth_to_cloud is the search structure.  nesti_depth_window_knn returns, per row, the K nearest among the points of a
+ * (2 R + 1) x (2 R + 1) pixel window -- lists every nesti_*_nbr entry takes -- and PROVES where that list is the exact list of nesti_knn.
+ * Everything is fp64, every operation rounded on its own, only + - * / sqrt, fabs and comparisons: a restatement in plain IEEE
+ * arithmetic predicts every bit.
+ * CENTRE.  Cloud row i = query_idx_dev[q] (clamped into the cloud, as for nesti_knn), or query_row0 + q where query_idx_dev is NULL.
+ * Its pixel is p = pix_dev[i], v0 = p / W, u0 = p % W.  A p outside [0, H W), or a centre with a non-finite coordinate (tested on the
+ * bits), gives count 0 and proven 0.
+ * CANDIDATES.  One per pixel of [u0 - R, u0 + R] x [v0 - R, v0 + R], clipped to the image, whose rank_dev entry j lies in [0, N).
+ * rank_dev [H W] and pix_dev [N] are untrusted: no entry causes an out-of-bounds read.
+ * LIST.  d2_j as nesti_knn computes it from the f32 rows (d = (double)p_j - (double)c, d2 = (dx dx + dy dy) + dz dz; a NaN d2 is never
+ * a neighbour).  The result is the K smallest pairs (d2_j, j), ascending:
+ *     nbr_out_dev    [M, K] int32   j
+ *     d2_out_dev     [M, K] fp64    d2_j                                  (may be NULL)
+ *     count_out_dev  [M]    int32   min(K, candidates)                    (may be NULL)
+ *     proven_out_dev [M]    int32   1: the list is nesti_knn's, bit for bit (may be NULL)
+ * Slots beyond the count hold -1 and +inf.  1 <= K <= NESTI_KNN_MAX_K, 1 <= R <= NESTI_WINDOW_MAX_R.
+ * PROOF.  A valid pixel outside the window lies, in the camera frame, beyond one of the four planes through the camera centre and
+ * the window's edges; the distance from the centre to the nearest of them is a lower bound on the distance to every point outside.
+ * A side has image beyond it when u0 - R > 0 (left), u0 + R < W - 1 (right), likewise top and bottom in v.  For such a side:
+ *     e    = (u0 - R) - 0.5, resp. (u0 + R) + 0.5 (likewise in v): the edge coordinate
+ *     a    = (e - cx) / fx                       (cy, fy for top and bottom)
+ *     m_r  = T[r][axis] - a * T[r][2],  rel_r = c_r - T[r][3]   (axis 0 for left / right, 1 for top / bottom; T the pose, the
+ *                                                                identity without one)
+ *     s    = (m_0 rel_0 + m_1 rel_1) + m_2 rel_2,   dist = fabs(s) / sqrt(1 + a a)
+ * bound is the smallest dist over those sides.  With no such side the window covers the image and proven = 1.  Otherwise
+ *     b = max(0, bound (1 - 2^-21) - 2^-21 ((|c_0| + |c_1|) + |c_2|)),   proven = (count == K) && d2[K - 1] < b b   (strictly).
+ * The margin covers the one f32 rounding of every stored point (8 x the bound derived in csrc/window.hip); the half pixel between the
+ * edge and the first pixel centre outside covers the fp64 noise of nesti_depth_to_cloud.  The proof presumes that xyz_dev, pix_dev,
+ * rank_dev and camera come from ONE nesti_depth_to_cloud call, that the points have not moved since, and that the pose is rigid.
+ * Otherwise the lists are still as defined and proven means nothing.  depth_scale, z_near and z_far are not read.
+ * One wave per row; the window's pairs go to an LDS buffer by ballot compaction and are sorted once: no atomics, no dependence on
+ * which workgroup runs first.  Argument errors (null cloud / pix / rank / camera / nbr_out_dev, N <= 0, H or W <= 0, H W > 2^26, fx or
+ * fy zero or not finite, cx / cy / pose not finite, R or K out of range, M < 0, rows beyond the cloud) are reported before any device
+ * call; M = 0 is a no-op.  The call enqueues one kernel on `stream`, neither synchronises nor reads anything back, and is booked in
+ * the patches category under nesti_profile_enable. */
+#define NESTI_WINDOW_MAX_R 15   /* (2 R + 1)^2 = 961 candidates at most: one fill of the search's pair buffer */
+int nesti_depth_window_knn(const float* xyz_dev, int N, const int32_t* pix_dev /*[N]*/, const int32_t* rank_dev /*[H W]*/,
+                           int H, int W, const nesti_camera_t* camera, const int32_t* query_idx_dev, int M, int query_row0,
+                           int R, int K, int32_t* nbr_out_dev, double* d2_out_dev, int32_t* count_out_dev,
+                           int32_t* proven_out_dev, void* stream);
+
 /* Several shapes in flight (BASELINE config 4; also every rank of a multi-GPU job, which holds a block of rows of
  * every shape): the queries of all items are processed as ONE stream of `batch`-sized batches, so small shapes / small
  * shards share the gate and expert launches instead of each paying for its own partially filled rounds.  Item i

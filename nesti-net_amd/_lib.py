@@ -116,6 +116,7 @@ ORIENT_MST, ORIENT_VIEWPOINT = 0, 1   # NESTI_ORIENT_*
 DEPTH_U16, DEPTH_F32 = 0, 1           # NESTI_DEPTH_*
 DEPTH_MAX_PIXELS = 1 << 26
 KNN_MAX_K = 256                       # NESTI_KNN_MAX_K
+WINDOW_MAX_R = 15                     # NESTI_WINDOW_MAX_R
 SELECT_MAX_L = 32                     # NESTI_SELECT_MAX_L
 ROBUST_MAX_ITERS = 64                 # NESTI_ROBUST_MAX_ITERS
 HOUGH_MAX_T, HOUGH_MAX_BINS, HOUGH_MAX_ROT = 4096, 16, 8   # NESTI_HOUGH_MAX_*
@@ -226,6 +227,7 @@ SIGNATURES = {
     "nesti_depth_to_cloud": (_i, [_vp, _i, _i, _i, ctypes.POINTER(CCamera), _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "nesti_image_scatter": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "nesti_project_to_image": (_i, [_vp, _vp, _i, _i, _i, _i, ctypes.POINTER(CCamera), _vp, _vp, _vp, _vp, _sz, _vp]),
+    "nesti_depth_window_knn": (_i, [_vp, _i, _vp, _vp, _i, _i, ctypes.POINTER(CCamera), _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "nesti_estimate_normals_multi_at": (_i, [_vp, ctypes.POINTER(CShapePositions), _i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
     "nesti_crc32c": (ctypes.c_uint32, [_vp, _sz, ctypes.c_uint32]),
     "nesti_f32_to_e2m3": (_i, [ctypes.c_float, ctypes.c_float]),

@@ -27,7 +27,10 @@ estimator runs: every file keeps the rows of ``<shape>.xyz`` (a removed row is w
 (:mod:`.downsample`) before all of that, for the model-free estimators: every file still has the rows of the ``.xyz``, a row holding the
 result of its voxel, and ``<shape>.voxel_xyz``, ``<shape>.voxel_of`` and ``<shape>.voxel_count`` are added.  ``--denoise ITERS`` moves the
 positions with the bilateral point filter of :mod:`.denoise` after those two and before a model-free estimator, and adds
-``<shape>.denoised.xyz`` and ``<shape>.denoise_delta``."""
+``<shape>.denoised.xyz`` and ``<shape>.denoise_delta``.  ``--depth_images 1 --depth_window auto | R`` with ``--estimator pca | quadric |
+hough | robust`` and ``--knn`` (or ``--knn_ladder``) runs those estimators on depth frames over image-window neighbour lists
+(``depth.depth_normals``; DESIGN.md 2 "Image-window neighbourhoods"): the estimator's row files, ``<name>.pix``,
+``<name>.normal_map.npy``, ``<name>.knn_radius`` and ``<name>.window_proven``."""
 import argparse
 import ctypes
 import os
@@ -114,6 +117,18 @@ def build_parser():
     p.add_argument("--depth_stride", type=int, default=1,
                    help="--depth_images 1: estimate at the valid pixels whose row and column are multiples of S only (neighbourhoods "
                         "still come from every valid pixel) [default: 1]")
+    p.add_argument("--depth_window", default="0", metavar="{0,auto,R}",
+                   help="--depth_images 1 with --estimator pca / quadric / hough / robust and --knn K[,K...] (or --knn_ladder): the "
+                        "model-free estimators on depth frames (DESIGN.md 2 'Image-window neighbourhoods').  The neighbour lists come "
+                        "from a (2 R + 1) x (2 R + 1) pixel window round every pixel instead of a grid search; auto picks R from the "
+                        "largest neighbour count, R is 1 .. 15.  Writes <name>.normals, <name>.pix, <name>.normal_map.npy, the "
+                        "estimator's own row files, <name>.knn_radius and <name>.window_proven (1 where the window's list is proven "
+                        "to be the exact k-NN list).  --smooth is served at --depth_stride 1; --outliers, --denoise, --voxel_size and "
+                        "--estimator net are left for later [default: 0 = off]")
+    p.add_argument("--depth_window_exact", type=int, default=1, choices=[0, 1],
+                   help="--depth_window: 1 (default) re-searches the rows the window cannot prove on the search grid, so every list is "
+                        "the exact k-NN list and the files equal those of the same estimator on the back-projected cloud; 0 keeps "
+                        "the window's lists as they are")
     p.add_argument("--orient", default=None, choices=["0", "mst", "viewpoint"],
                    help="orient the written normals consistently (only signs in <shape>.normals change; .experts and .experts_probs "
                         "do not).  0 (default): signs as the experts produced them.  mst: propagate signs along the minimum spanning "
@@ -439,6 +454,93 @@ def run_depth_frame(est, frames, name, FLAGS, output_dir, printout, on_cloud, wr
     printout("saved experts for " + name)
 
 
+def depth_window_args(FLAGS, parser, fit, ks, ladder):
+    """``--depth_window`` / ``--depth_window_exact`` resolved: None (off), or (window, exact) -- ``'auto'`` or R, and a bool -- after the
+    refusals of what the window route does not serve."""
+    if FLAGS.depth_window == "0":
+        if FLAGS.depth_window_exact != 1:
+            parser.error("--depth_window_exact belongs to --depth_window auto / R")
+        return None
+    from . import depth as _depth
+    word = FLAGS.depth_window.strip()
+    try:
+        window = "auto" if word == "auto" else int(word)
+        _depth.check_window(window, 1)
+    except ValueError:
+        parser.error("--depth_window takes 0, auto or R in 1 .. 15: got %r" % FLAGS.depth_window)
+    if not FLAGS.depth_images:
+        parser.error("--depth_window belongs to --depth_images 1: the window is a window of pixels")
+    if not fit:
+        parser.error("--depth_window does not go with --estimator net: the network on window lists is left for later; it serves "
+                     "--estimator pca / quadric / hough / robust")
+    if ks is None and ladder is None:
+        parser.error("--depth_window needs --knn K[,K...] or --knn_ladder: the window's lists are neighbour lists, not balls")
+    for given, flag, why in ((FLAGS.outliers != "0", "--outliers %s" % FLAGS.outliers,
+                              "left for later: the filter renumbers the cloud and the frame's rank image no longer names its rows"),
+                             (bool(FLAGS.denoise), "--denoise",
+                              "left for later: the filter moves points off their pixels' rays and the window's proof is void"),
+                             (FLAGS.voxel_size != 0.0, "--voxel_size", "left for later: a voxel grid's points have no pixels")):
+        if given:
+            parser.error("%s does not go with --depth_window: %s" % (flag, why))
+    return window, bool(FLAGS.depth_window_exact)
+
+
+def window_line(name, res, exact):
+    """The log line of ``--depth_window`` for frame ``name``: the window, the share of rows it proved and the rows re-searched."""
+    rows = len(res["window_proven"])
+    return ("image window of %s: R = %d (%d x %d pixels), %d rows, %.1f %% proven exact by the window, %d rows re-searched on the grid%s"
+            % (name, res["window"], 2 * res["window"] + 1, 2 * res["window"] + 1, rows,
+               100.0 * float(res["window_proven"].mean()) if rows else 100.0, res["window_exact_rows"],
+               "" if exact else " (--depth_window_exact 0: the window's lists as they are)"))
+
+
+def run_window_frame(frames, name, FLAGS, window, ks, ladder, slack, scale, smooth, output_dir, printout):
+    """One frame of ``--depth_images 1 --depth_window``: ``depth.depth_normals`` with the estimator of the command line, then
+    ``.normals``, ``.pix``, ``.normal_map.npy``, the estimator's row files, ``.knn_radius`` and ``.window_proven``."""
+    import numpy as np
+    from . import depth as _depth
+    depth, cam = frames.load(name)
+    orient = None if FLAGS.orient == "0" else FLAGS.orient
+    common = dict(window=window[0], exact=window[1], stride=FLAGS.depth_stride, orient=orient, orient_k=FLAGS.orient_k, smooth=smooth,
+                  device="cuda:%d" % FLAGS.gpu)
+    if ladder is not None:
+        res = _depth.depth_normals(depth, cam, estimator="select", ladder=ladder, slack=slack, **common)
+        files = ((".normals", textio.write_f32, "normals"), (".select_k", textio.write_i32, "k"), (".select_eig", textio.write_f32, "eig"),
+                 (".select_variation", textio.write_f32, "variation_all"))
+    else:
+        fit = FITS[FLAGS.estimator]
+        params = {kw: getattr(FLAGS, flag) for kw, flag in fit.get("params", ())}
+        res = _depth.depth_normals(depth, cam, estimator=FLAGS.estimator, knn=ks, scale=scale, **common, **params)
+        files = fit["files"]
+    H, W = depth.shape
+    rows = len(res["pix"])
+    printout("depth frame %s: %d x %d, %d normals estimated (stride %d), oriented: %s" % (name, H, W, rows, FLAGS.depth_stride, FLAGS.orient))
+    printout(window_line(name, res, window[1]))
+    if rows:
+        if ladder is not None:
+            printout(select_line(name, rows, ladder, slack, res["sel"]))
+        else:
+            printout(fit_line(FLAGS.estimator, name, rows, scale, len(ks), int(FITS[FLAGS.estimator]["missing"](res, scale, ks)), k=ks[scale]))
+            if "line" in FITS[FLAGS.estimator]:
+                printout(FITS[FLAGS.estimator]["line"](name, res, scale, params))
+        if smooth is not None:
+            printout(smooth_line(name, rows, smooth, res["smooth_count"]))
+            write_smooth_support(os.path.join(output_dir, name + ".smooth_support"), res["smooth_support"], res["smooth_count"])
+        if res.get("orient") is not None:
+            printout(orient_line(name, FLAGS.orient, res["orient"], rows))
+        for ext, write, key in files:
+            write(os.path.join(output_dir, name + ext), res[key].reshape(len(res[key]), -1) if write is not textio.write_i32 else res[key])
+        textio.write_f32(os.path.join(output_dir, name + ".knn_radius"), res["radius"])
+    else:
+        textio.write_f32(os.path.join(output_dir, name + ".normals"), res["normals"])
+    textio.write_i32(os.path.join(output_dir, name + ".pix"), res["pix"])
+    textio.write_i32(os.path.join(output_dir, name + ".window_proven"), res["window_proven"].astype(np.int32))
+    np.save(os.path.join(output_dir, name + ".normal_map.npy"), res["normal_map"])
+    if "curv_map" in res:
+        np.save(os.path.join(output_dir, name + ".curv_map.npy"), res["curv_map"])
+    printout("saved normals, the normal image and the window's proof flags for " + name)
+
+
 # --estimator pca / quadric: what differs between the two model-free fits.  ``missing(res, scale, ks)`` counts the rows without a fit at
 # the written scale, ``no_fit`` says what they are for balls and for neighbour counts; ``files`` = (extension, writer, key of the result)
 FITS = {
@@ -657,6 +759,7 @@ def main(argv=None):
             _robust.check_params(FLAGS.robust_iters, FLAGS.robust_sigma, FLAGS.robust_falloff, FLAGS.robust_floor)
         except ValueError as e:
             parser.error("--estimator robust: %s" % e)
+    window = depth_window_args(FLAGS, parser, fit, ks, ladder)
     voxel = None
     if FLAGS.voxel_size != 0.0:
         later = "left for later: the network route and depth frames are a pull request of their own"
@@ -700,7 +803,8 @@ def main(argv=None):
             if getattr(FLAGS, flag) != parser.get_default(flag):
                 parser.error("--%s belongs to --denoise ITERS" % flag)
     if fit:
-        for given, flag, why in ((FLAGS.depth_images, "--depth_images 1", "depth frames belong to the network path (--estimator net)"),
+        for given, flag, why in ((FLAGS.depth_images and window is None, "--depth_images 1",
+                                  "depth frames belong to the network path (--estimator net), or to --depth_window auto with --knn"),
                                  (FLAGS.reproducible, "--reproducible 1",
                                   "it freezes the network's thresholds (--estimator net); the %s has none" % fit["noun"]),
                                  (FLAGS.subsample != "hash", "--subsample %s" % FLAGS.subsample,
@@ -711,7 +815,10 @@ def main(argv=None):
     if FLAGS.smooth:
         for given, flag, why in ((FLAGS.sparse_patches, "--sparse_patches 1", "not all rows have normals"),
                                  (FLAGS.query_positions, "--query_positions 1", "not all rows have normals"),
-                                 (FLAGS.depth_images, "--depth_images 1", "smoothing of depth frames is left for later")):
+                                 (FLAGS.depth_images and window is None, "--depth_images 1",
+                                  "smoothing of depth frames is left for later on the network path (--depth_window serves it)"),
+                                 (window is not None and FLAGS.depth_stride != 1, "--depth_stride %d" % FLAGS.depth_stride,
+                                  "not all rows have normals; use --depth_stride 1")):
             if given:
                 parser.error("--smooth does not go with %s: %s" % (flag, why))
         try:
@@ -786,6 +893,16 @@ def main(argv=None):
         flog.write(data + "\n")
         sys.stdout.flush()
 
+    if window is not None:
+        try:
+            scale = 0 if ladder is not None else _pca.check_scale(getattr(FLAGS, fit["scale_flag"]), len(ks))
+        except ValueError as e:
+            raise SystemExit("--%s: %s" % (fit["scale_flag"], e))
+        frames = DepthFrames(pc_path, FLAGS.testset, FLAGS.depth_stride)
+        for name in frames.names:
+            run_window_frame(frames, name, FLAGS, window, ks, ladder, slack, scale, smooth, output_dir, printout)
+        flog.close()
+        return 0
     if fit:
         cfg = NestiConfig.for_model(FLAGS.model)
         if ladder is not None:

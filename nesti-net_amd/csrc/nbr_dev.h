@@ -29,6 +29,39 @@ __device__ __forceinline__ void wave_lds_fence() {
 
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// ---- the cut of a wave's candidate pairs, shared by the grid search (knn.hip) and the image-window search (window.hip) ---------------
+constexpr int kKnnCap = 1024;                               // pairs per wave
+static_assert(NESTI_KNN_MAX_K + kWave <= kKnnCap, "a cut leaves room for the next trip");
+
+// Sorts the wave's pairs [0, cnt) ascending by (d2, j) -- bitonic, over the next power of two >= 64, padded with (+inf, INT_MAX) -- and
+// returns min(cnt, K), the number kept.  cnt <= kKnnCap, the same in every lane.
+__device__ __forceinline__ int knn_cut(double* bd, int* bj, int cnt, int K, int lane) {
+  int n2 = kWave;
+  while (n2 < cnt) n2 <<= 1;
+  for (int i = cnt + lane; i < n2; i += kWave) {
+    bd[i] = INFINITY;
+    bj[i] = 0x7fffffff;
+  }
+  wave_lds_fence();
+  for (int k = 2; k <= n2; k <<= 1) {
+    for (int s = k >> 1; s > 0; s >>= 1) {
+      for (int t = lane; t < (n2 >> 1); t += kWave) {
+        const int a = ((t & ~(s - 1)) << 1) | (t & (s - 1)), b = a | s;
+        const bool up = (a & k) == 0;
+        const double da = bd[a], db = bd[b];
+        const int ja = bj[a], jb = bj[b];
+        const bool a_after_b = da > db || (da == db && ja > jb);
+        if (a_after_b == up) {
+          bd[a] = db; bd[b] = da;
+          bj[a] = jb; bj[b] = ja;
+        }
+      }
+      wave_lds_fence();
+    }
+  }
+  return min(cnt, K);
+}
+
 struct NbrParams {
   PatchParams p;                      // cloud, query_idx / query_xyz, M, N, row0 (no grid)
   const int32_t* nbr;                 // [M, K]

@@ -74,7 +74,7 @@ class Camera:
 class DepthCloud:
     """What :func:`depth_to_cloud` returns.  Device tensors, rows in row-major pixel order: ``xyz`` [n_valid,3] f32, ``pix`` [n_valid]
     int32 (pixel index ``v W + u``), ``rank`` [H W] int32 (cloud row of a pixel or -1), ``qidx`` [n_queries] int32 (cloud rows of the
-    valid pixels on the stride); ``viewpoint``: the camera centre, three floats on the host."""
+    valid pixels on the stride); ``viewpoint``: the camera centre, three floats on the host; ``camera``: the :class:`Camera` itself."""
     xyz: object
     pix: object
     rank: object
@@ -85,6 +85,7 @@ class DepthCloud:
     W: int
     stride: int
     viewpoint: object
+    camera: object = None             # the Camera of the back-projection: what :func:`window_knn` proves its lists with
 
 
 def _upload_depth(depth, dev):
@@ -142,7 +143,7 @@ def depth_to_cloud(depth, camera, stride=1, device="cuda:0", stream=None):
                                             _lib.ptr(qidx), _lib.ptr(counts), _lib.ptr(ws), ws.numel(),
                                             ctypes.c_void_p(st.cuda_stream)), "nesti_depth_to_cloud")
         n_valid, n_queries = (int(v) for v in counts.cpu().tolist())          # the one readback
-    return DepthCloud(xyz[:n_valid], pix[:n_valid], rank, qidx[:n_queries], n_valid, n_queries, H, W, s, camera.centre)
+    return DepthCloud(xyz[:n_valid], pix[:n_valid], rank, qidx[:n_queries], n_valid, n_queries, H, W, s, camera.centre, camera)
 
 
 def _fill_words(fill, C, torch_dtype):
@@ -223,6 +224,179 @@ def project_to_image(xyz, values, camera, H, W, fill=0, stream=None):
                                               _lib.ptr(f), _lib.ptr(image), _lib.ptr(index), _lib.ptr(ws), ws.numel(),
                                               ctypes.c_void_p(st.cuda_stream)), "nesti_project_to_image")
     return image, index
+
+
+# ---- image-window neighbour lists and model-free normals (csrc/window.hip; DESIGN.md 2 "Image-window neighbourhoods") ---------------
+WINDOW_FACTOR = 1.5
+ESTIMATORS = ("pca", "quadric", "hough", "robust", "select")
+
+
+def default_window(k):
+    """The half-width R of the pixel window for ``k`` neighbours: ``ceil(WINDOW_FACTOR * sqrt(k / pi))``, within 1 ..
+    ``_lib.WINDOW_MAX_R``.  On a surface seen face-on the ``k`` nearest points fill a disc of ``sqrt(k / pi)`` pixels radius; the factor
+    1.5 leaves the room the proof needs on tilted surfaces.  Measured on the 96 x 128 test scene (the restatement of
+    tests/_window_fixture.py predicts the flags bit for bit; profiles/window_check.json has the 480 x 640 frame): with the factor 1.5 the
+    window proves 98.5 / 97.4 / 95.4 / 94.2 / 92.6 / 90.6 % of the rows at k = 8 / 16 / 32 / 64 / 128 / 256; with a window as wide as
+    the disc itself (factor 1) 94.6 / 93.4 / 86.8 / 61.1 / 40.8 / 28.5 %; with the factor 2, 99.4 / 99.0 / 98.6 / 98.5 / 97.9 / 94.0 %
+    at 1.8 x the candidates.  The rows left over sit at depth discontinuities and on steep surfaces.  The choice moves the share of
+    rows the exact mode re-searches, never a result."""
+    from .knn import check_k
+    return max(1, min(_lib.WINDOW_MAX_R, int(math.ceil(WINDOW_FACTOR * math.sqrt(check_k(k) / math.pi)))))
+
+
+def check_window(window, k):
+    """``window`` -- ``'auto'`` (:func:`default_window`) or an int in 1 .. ``_lib.WINDOW_MAX_R`` -- as the half-width R; ``ValueError``
+    otherwise."""
+    if isinstance(window, str) and window == "auto":
+        return default_window(k)
+    if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or not 1 <= int(window) <= _lib.WINDOW_MAX_R:
+        raise ValueError("window must be 'auto' or an integer in 1 .. %d: got %r" % (_lib.WINDOW_MAX_R, window))
+    return int(window)
+
+
+def window_knn(dc, k, window="auto", exact=True, rows=None, stream=None, cloud=None):
+    """The ``k`` nearest cloud points of the rows of a :class:`DepthCloud` among the points of a (2 R + 1)^2 pixel window round each
+    row's pixel (``nesti_depth_window_knn``): all rows, or the cloud rows ``rows`` (int32 [M] on the device: ``dc.qidx`` for a strided
+    frame).  Device tensors ``(idx [M,k] int32, d2 [M,k] float64, n [M] int32, proven [M] int32)``; ``proven`` is 1 where the window's
+    list is PROVEN to be the exact k-NN list over the whole cloud, bit for bit ``knn.knn``'s row.  ``window``: ``'auto'``
+    (:func:`default_window`) or R in 1 .. 15.
+
+    ``exact=True``: the unproven rows are compacted (one readback: their number), searched by ``CloudPatches.knn_rows`` over a
+    search-only grid -- built only when there is such a row; ``cloud``: a prepared ``CloudPatches`` of ``dc.xyz`` to search with instead
+    of one made here, which passes the cloud through the host -- and written back.  The result then equals ``knn.knn`` on every row;
+    ``proven`` is returned as it came from the window.  ``exact=False``: the window's lists as they are, nothing read back.
+
+    The proof presumes an untouched cloud: ``dc`` as :func:`depth_to_cloud` returned it, under a rigid pose."""
+    import torch
+    from .knn import check_k
+    k = check_k(k)
+    R = check_window(window, k)
+    if dc.camera is None:
+        raise ValueError("window_knn: the DepthCloud carries no camera (depth_to_cloud sets it)")
+    lib = _lib.load()
+    dev = dc.xyz.device
+    N = int(dc.n_valid)
+    if rows is not None and (not hasattr(rows, "data_ptr") or rows.dtype != torch.int32 or rows.dim() != 1 or rows.device != dev):
+        raise ValueError("rows: an int32 [M] tensor on %s" % dev)
+    M = N if rows is None else int(rows.shape[0])
+    cam = dc.camera.to_c()
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev), torch.cuda.stream(st):
+        idx = torch.empty((M, k), dtype=torch.int32, device=dev)
+        d2 = torch.empty((M, k), dtype=torch.float64, device=dev)
+        n = torch.empty((M,), dtype=torch.int32, device=dev)
+        proven = torch.empty((M,), dtype=torch.int32, device=dev)
+        if M == 0 or N == 0:
+            return idx, d2, n, proven
+        xyz, pix, rank = dc.xyz.contiguous(), dc.pix.contiguous(), dc.rank.contiguous()
+        q = None if rows is None else rows.contiguous()
+        _lib.check(lib.nesti_depth_window_knn(_lib.ptr(xyz), N, _lib.ptr(pix), _lib.ptr(rank), dc.H, dc.W, ctypes.byref(cam), _lib.ptr(q), M, 0,
+                                              R, k, _lib.ptr(idx), _lib.ptr(d2), _lib.ptr(n), _lib.ptr(proven),
+                                              ctypes.c_void_p(st.cuda_stream)), "nesti_depth_window_knn")
+        if exact:
+            open_rows = torch.nonzero(proven == 0).reshape(-1)              # the one readback: their number
+            if open_rows.numel():
+                if cloud is None:
+                    from .config import NestiConfig
+                    from .provider import CloudPatches
+                    cloud = CloudPatches(xyz.cpu().numpy(), NestiConfig(), device=dev, radius_grid=False)
+                which = open_rows.to(torch.int32) if q is None else q[open_rows].contiguous()
+                e_idx, e_d2, e_n = cloud.knn_rows(which, k, stream=st)
+                idx.index_copy_(0, open_rows, e_idx)
+                d2.index_copy_(0, open_rows, e_d2)
+                n.index_copy_(0, open_rows, e_n)
+    return idx, d2, n, proven
+
+
+def _fit_by_name(estimator):
+    from . import hough, pca, quadric, robust, select
+    return {"pca": pca.pca_cloud, "quadric": quadric.quadric_cloud, "hough": hough.hough_cloud, "robust": robust.robust_cloud,
+            "select": select.select_cloud}[estimator]
+
+
+def check_normals_args(estimator, knn, ladder, scale, stride, orient, smooth):
+    """The argument checks of :func:`depth_normals` that need no GPU -> (neighbour counts, the largest count to search at, the smoothing
+    parameters or None); ``ValueError`` otherwise."""
+    from . import smooth as _smooth
+    from .knn import check_ks
+    from .pca import ORIENT_MODES, check_scale
+    if estimator not in ESTIMATORS:
+        raise ValueError("estimator must be one of %s: got %r" % (", ".join(ESTIMATORS), estimator))
+    if int(stride) < 1:
+        raise ValueError("stride must be >= 1")
+    if orient not in ORIENT_MODES:
+        raise ValueError("orient must be None, 'mst' or 'viewpoint'")
+    if estimator == "select":
+        from .select import DEFAULT_LADDER, check_ladder
+        ks = check_ladder(DEFAULT_LADDER if ladder is None else ladder)
+    else:
+        if ladder is not None:
+            raise ValueError("ladder belongs to estimator='select'")
+        ks = check_ks(knn)
+        check_scale(scale, len(ks))
+    sm = _smooth.as_params(smooth)
+    if sm is not None and int(stride) != 1:
+        raise ValueError("smooth needs stride == 1: on a strided frame the rows' neighbours would have no normal")
+    return ks, max(ks[-1], sm.k if sm is not None else 0), sm
+
+
+def depth_normals(depth, camera, estimator="pca", knn=(32,), scale=-1, window="auto", exact=True, stride=1, orient="viewpoint",
+                  orient_k=8, smooth=None, device="cuda:0", **params):
+    """Depth frame in, MODEL-FREE normal image out: back-project ``depth`` [H,W] (uint16 or float32) through ``camera``
+    (:func:`depth_to_cloud`), search ONCE over the pixel windows (:func:`window_knn`) at the largest neighbour count -- ``max(knn)``, or
+    the smoothing's ``k`` where that is larger --, run ``estimator`` and the optional smoothing over those lists, orient, scatter.
+
+    ``estimator``: ``'pca'`` (plane fit), ``'quadric'``, ``'hough'``, ``'robust'`` -- over the neighbour counts ``knn`` (an int or up to
+    four ascending ints), ``scale`` indexing them -- or ``'select'`` (the scale-selected plane fit; ``ladder=`` instead of ``knn=``);
+    ``params`` are the estimator's own keywords (``triplets``, ``iters``, ``slack``, ...).  ``stride`` > 1 estimates at the valid pixels
+    on the stride only; the neighbourhoods still come from every valid pixel.  ``orient``: ``'viewpoint'`` (the camera centre),
+    ``'mst'`` or None.  ``smooth`` (``smooth.as_params``) needs ``stride == 1``.  ``exact=True``: every row's list is the exact k-NN list
+    (the rows the window cannot prove are searched on the grid), so the result equals the estimator's own ``*_normals(xyz, knn=...)``
+    bit for bit; ``exact=False``: the window's lists as they are -- at a depth discontinuity a row may then miss a nearer point of a
+    far-away pixel.
+
+    Returns a dict of numpy arrays (synchronises): the estimator's usual arrays per estimated pixel (``normals`` [M,3] among them),
+    ``xyz`` [M,3], ``pix`` [M], ``normal_map`` [H,W,3] f32 (fill 0 0 0), for the quadric fit ``curv_map`` [H,W,2] (fill 0 0), ``window``
+    (R), ``window_proven`` [M] bool and ``window_exact_rows`` (the rows re-searched; 0 with ``exact=False``).  A frame without a valid
+    pixel gives all-fill maps and empty rows.  Raises ``ValueError`` for a bad ``estimator``, ``knn``, ``window``, ``scale`` or
+    ``orient`` and for ``smooth`` with ``stride > 1``."""
+    import torch
+    from .config import NestiConfig
+    from .provider import CloudPatches
+    ladder = params.pop("ladder", None)
+    ks, kmax, sm = check_normals_args(estimator, knn, ladder, scale, stride, orient, smooth)
+    R = check_window(window, kmax)
+    dc = depth_to_cloud(depth, camera, stride=stride, device=device)
+    H, W, dev = dc.H, dc.W, dc.xyz.device
+    sparse = dc.stride > 1
+    rows = dc.n_queries if sparse else dc.n_valid
+    with torch.cuda.device(dev):
+        if rows == 0:
+            res = {"normals": np.zeros((0, 3), np.float32)}
+            xyz, pix = dc.xyz[:0], dc.pix[:0]
+            proven = np.zeros(0, bool)
+            n_exact = 0
+            if estimator == "quadric":
+                res["curv"] = np.zeros((0, 2), np.float32)
+        else:
+            cloud = CloudPatches(dc.xyz.cpu().numpy(), NestiConfig(), device=dev, pidx=dc.qidx.cpu().numpy() if sparse else None,
+                                 radius_grid=False)
+            lists, _, _, proven = window_knn(dc, kmax, R, exact, rows=dc.qidx if sparse else None, cloud=cloud)
+            proven = proven.cpu().numpy().astype(bool)
+            n_exact = int((~proven).sum()) if exact else 0
+            common = dict(orient=orient, viewpoint=dc.viewpoint, orient_k=orient_k, smooth=sm, lists=lists)
+            if estimator == "select":
+                res = _fit_by_name(estimator)(cloud, ks, **common, **params)
+            else:
+                res = _fit_by_name(estimator)(cloud, knn=ks, scale=scale, **common, **params)
+            sel = dc.qidx.long() if sparse else None
+            xyz = dc.xyz[sel] if sparse else dc.xyz
+            pix = dc.pix[sel].contiguous() if sparse else dc.pix
+        res["normal_map"] = scatter_to_image(torch.from_numpy(res["normals"]).to(dev), pix, H, W, 0.0).cpu().numpy()
+        if estimator == "quadric":
+            res["curv_map"] = scatter_to_image(torch.from_numpy(res["curv"]).to(dev), pix, H, W, 0.0).cpu().numpy()
+        res.update(xyz=xyz.cpu().numpy(), pix=pix.cpu().numpy(), window=R, window_proven=proven, window_exact_rows=n_exact)
+    return res
 
 
 # ---- the command line's per-frame files ---------------------------------------------------------------------------------------------

@@ -64,8 +64,8 @@ def _need_knn(knn):
 
 
 def hough_cloud(cloud, knn=DEFAULT_KNN, scale=-1, triplets=DEFAULT_TRIPLETS, bins=DEFAULT_BINS, rotations=DEFAULT_ROTATIONS, seed=0,
-                orient=None, viewpoint=None, orient_k=8, smooth=None):
-    """``hough_normals`` for a prepared ``provider.CloudPatches`` (all of its patch rows); synchronises.  ``smooth``: see
+                orient=None, viewpoint=None, orient_k=8, smooth=None, lists=None):
+    """``hough_normals`` for a prepared ``provider.CloudPatches`` (all of its patch rows); synchronises.  ``smooth``, ``lists``: see
     ``pca.fit_cloud``."""
     _need_knn(knn)
     T, B, R, seed = check_params(triplets, bins, rotations, seed)
@@ -73,7 +73,8 @@ def hough_cloud(cloud, knn=DEFAULT_KNN, scale=-1, triplets=DEFAULT_TRIPLETS, bin
     def nbr(first, count, ks, nbr=None):
         return cloud.hough_knn(first, count, ks, T, B, R, seed, nbr=nbr)
 
-    return fit_cloud(cloud, None, nbr, ("normals_all", "conf", "votes", "n_ball"), scale, orient, viewpoint, orient_k, knn, smooth=smooth)
+    return fit_cloud(cloud, None, nbr, ("normals_all", "conf", "votes", "n_ball"), scale, orient, viewpoint, orient_k, knn, smooth=smooth,
+                     lists=lists)
 
 
 def hough_normals(pts, knn=DEFAULT_KNN, pidx=None, queries=None, scale=-1, triplets=DEFAULT_TRIPLETS, bins=DEFAULT_BINS,

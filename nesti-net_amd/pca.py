@@ -36,7 +36,7 @@ def orient_rows(cloud, normals, scale, mode, viewpoint=None, k=8, radius=None):
     return _orient.orient_device(cloud.centre_positions(), normals, r, k, viewpoint, mode, torch.cuda.current_stream(cloud.device))
 
 
-def fit_cloud(cloud, ball, nbr, names, scale, orient, viewpoint, orient_k, knn, after=None, smooth=None):
+def fit_cloud(cloud, ball, nbr, names, scale, orient, viewpoint, orient_k, knn, after=None, smooth=None, lists=None):
     """What ``pca_cloud`` and ``quadric.quadric_cloud`` share: fit all patch rows of a prepared cloud with the method ``ball`` -- over
     the neighbour counts ``knn`` with the method ``nbr`` --, take the normals of ``scale``, orient them, synchronise.  ``names``: the
     dict keys of the ball method's outputs, normals first and counts last (a k-NN method returns ``radius`` before the counts).
@@ -46,11 +46,15 @@ def fit_cloud(cloud, ball, nbr, names, scale, orient, viewpoint, orient_k, knn, 
     a number of passes or a dict) smooths the scale's normals over all points between those two steps -- ``normals_all`` stays as
     fitted -- and adds ``smooth_support`` and ``smooth_count``; a k-NN fit whose lists hold at least ``k`` entries is given the lists
     of ONE search (``nbr`` then takes them as its ``nbr=`` keyword) which the passes reuse, a prefix of a sorted list being the k-NN
-    list; otherwise the passes search once for themselves.  Returns the dict as numpy arrays, with ``orient``."""
+    list; otherwise the passes search once for themselves.  ``lists`` -- a contiguous int32 [patch_count, K >= max(knn)] device tensor of
+    sorted neighbour lists (``depth.window_knn``) -- is used instead of the fit's own search, and by the passes where K reaches their
+    ``k``; it needs ``knn``.  Returns the dict as numpy arrays, with ``orient``."""
     import torch
     from . import orient as _orient
     if ball is None and knn is None:
         raise ValueError("this estimator exists over neighbour lists only: knn must be given")
+    if lists is not None and knn is None:
+        raise ValueError("lists are neighbour lists: knn must be given")
     ks = None
     if knn is not None:
         from .knn import check_ks
@@ -64,9 +68,14 @@ def fit_cloud(cloud, ball, nbr, names, scale, orient, viewpoint, orient_k, knn, 
     if sm is not None:
         _smooth.refuse_subset(cloud.pidx, cloud.queries)
     with torch.cuda.device(cloud.device):
-        lists = None
         if ks is None:
             out = dict(zip(names, ball(0, cloud.patch_count)))
+        elif lists is not None:
+            if lists.dim() != 2 or lists.shape[1] < ks[-1]:
+                raise ValueError("lists: an int32 [patch_count, K >= %d] tensor" % ks[-1])
+            out = dict(zip(names, nbr(0, cloud.patch_count, ks, nbr=lists)))
+            if sm is not None and lists.shape[1] < sm.k:
+                lists = None                                   # too short for the passes: they search for themselves
         elif sm is not None and ks[-1] >= sm.k:
             lists = cloud.knn(0, cloud.patch_count, ks[-1])[0]
             out = dict(zip(names, nbr(0, cloud.patch_count, ks, nbr=lists)))
@@ -88,11 +97,11 @@ def fit_cloud(cloud, ball, nbr, names, scale, orient, viewpoint, orient_k, knn, 
     return res
 
 
-def pca_cloud(cloud, scale=-1, orient=None, viewpoint=None, orient_k=8, knn=None, smooth=None):
+def pca_cloud(cloud, scale=-1, orient=None, viewpoint=None, orient_k=8, knn=None, smooth=None, lists=None):
     """``pca_normals`` for a prepared ``provider.CloudPatches`` (all of its patch rows); synchronises.  ``knn``: neighbour counts
-    instead of the cloud's radii (``scale`` then indexes them, and the dict gains ``radius``).  ``smooth``: see ``fit_cloud``."""
+    instead of the cloud's radii (``scale`` then indexes them, and the dict gains ``radius``).  ``smooth``, ``lists``: see ``fit_cloud``."""
     res = fit_cloud(cloud, cloud.pca, cloud.pca_knn, ("normals_all", "eig", "n_ball"), scale, orient, viewpoint, orient_k, knn,
-                    smooth=smooth)
+                    smooth=smooth, lists=lists)
     res["variation"] = variation(res["eig"])
     return res
 

@@ -85,7 +85,7 @@ class CloudPatches:
     this cloud and ``r_abs`` from ITS bounding box.  Patch row i is ``queries[i]``; a position whose balls are all empty gets
     the sentinel outputs.
 
-    ``radius_grid=False`` skips the radius grid: only :meth:`knn`, :meth:`pca_knn`, :meth:`quadric_knn`, :meth:`hough_knn`,
+    ``radius_grid=False`` skips the radius grid: only :meth:`knn`, :meth:`knn_rows`, :meth:`pca_knn`, :meth:`quadric_knn`, :meth:`hough_knn`,
     :meth:`pca_select`, :meth:`smooth_knn`, :meth:`denoise_knn`, the outlier filter's :meth:`outlier_scores`, :meth:`outlier_threshold` and
     :meth:`outlier_compact` and the voxel grid's :meth:`voxel_keys`, :meth:`sort_pairs` and :meth:`voxel_reduce` may then be called."""
 
@@ -308,6 +308,22 @@ class CloudPatches:
         out = check_out(None, (((count, k), torch.int32), ((count, k), torch.float64), ((count,), torch.int32)), self.device)
         if count:                         # 0 rows: a no-op; an empty tensor has no address to pass
             self._call("nesti_knn", at, q, count, first, [k] + [_lib.ptr(t) for t in out] + [_lib.ptr(ws), ws.numel()], st, ball=False)
+        return out
+
+    def knn_rows(self, rows, k, grid=None, stream=None):
+        """:meth:`knn` for the cloud points ``rows`` (a contiguous int32 [count] tensor on the cloud's device, whatever ``pidx`` or
+        ``queries`` the cloud was prepared with): what ``depth.window_knn`` hands its unproven rows to.  An index is clamped into the
+        cloud, as by ``nesti_knn``."""
+        k = _knn.check_k(k)
+        if (not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() != 1 or not rows.is_contiguous()
+                or rows.device != self.device):
+            raise ValueError("rows: a contiguous int32 [count] tensor on %s" % self.device)
+        count = int(rows.shape[0])
+        st = self._stream(stream)
+        out = check_out(None, (((count, k), torch.int32), ((count, k), torch.float64), ((count,), torch.int32)), self.device)
+        if count:                         # 0 rows: no grid is built
+            ws = self.knn_grid(grid, k, st)
+            self._call("nesti_knn", False, rows, count, 0, [k] + [_lib.ptr(t) for t in out] + [_lib.ptr(ws), ws.numel()], st, ball=False)
         return out
 
     def _fit_nbr(self, name, first, count, ks, grid, nbr, widths, stream, params=(), keyed=False):

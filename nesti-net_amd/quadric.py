@@ -15,9 +15,9 @@ def mean_gauss(curv):
     return (curv[..., 0] + curv[..., 1]) * np.float32(0.5), curv[..., 0] * curv[..., 1]
 
 
-def quadric_cloud(cloud, scale=-1, orient=None, viewpoint=None, orient_k=8, knn=None, smooth=None):
+def quadric_cloud(cloud, scale=-1, orient=None, viewpoint=None, orient_k=8, knn=None, smooth=None, lists=None):
     """``quadric_fit`` for a prepared ``provider.CloudPatches`` (all of its patch rows); synchronises.  ``knn``: neighbour counts
-    instead of the cloud's radii (``scale`` then indexes them, and the dict gains ``radius``).  ``smooth``: see ``pca.fit_cloud``; the
+    instead of the cloud's radii (``scale`` then indexes them, and the dict gains ``radius``).  ``smooth``, ``lists``: see ``pca.fit_cloud``; the
     curvatures are untouched by the smoothing and still flip with the orientation."""
     import torch
 
@@ -29,7 +29,7 @@ def quadric_cloud(cloud, scale=-1, orient=None, viewpoint=None, orient_k=8, knn=
             out["curv"] = torch.where(flipped, -out["curv"].flip(1), out["curv"])
 
     return fit_cloud(cloud, cloud.quadric, cloud.quadric_knn, ("normals_all", "curv_all", "plane_all", "n_ball"), scale, orient, viewpoint,
-                     orient_k, knn, after=curvatures, smooth=smooth)
+                     orient_k, knn, after=curvatures, smooth=smooth, lists=lists)
 
 
 def quadric_fit(pts, cfg=None, pidx=None, queries=None, scale=-1, orient=None, viewpoint=None, orient_k=8, device="cuda:0", knn=None,

@@ -62,8 +62,8 @@ def _need_knn(knn):
 
 
 def robust_cloud(cloud, knn=DEFAULT_KNN, scale=-1, iters=DEFAULT_ITERS, sigma=DEFAULT_SIGMA, falloff=DEFAULT_FALLOFF, floor=DEFAULT_FLOOR,
-                 init=None, orient=None, viewpoint=None, orient_k=8, smooth=None):
-    """``robust_normals`` for a prepared ``provider.CloudPatches`` (all of its patch rows); synchronises.  ``smooth``: see
+                 init=None, orient=None, viewpoint=None, orient_k=8, smooth=None, lists=None):
+    """``robust_normals`` for a prepared ``provider.CloudPatches`` (all of its patch rows); synchronises.  ``smooth``, ``lists``: see
     ``pca.fit_cloud``."""
     import torch
     from .knn import check_ks
@@ -78,7 +78,7 @@ def robust_cloud(cloud, knn=DEFAULT_KNN, scale=-1, iters=DEFAULT_ITERS, sigma=DE
                                 nbr=nbr)
 
     res = fit_cloud(cloud, None, nbr, ("normals_all", "plane_all", "support", "inliers", "iters_done", "moments", "n_ball"), scale, orient,
-                    viewpoint, orient_k, knn, smooth=smooth)
+                    viewpoint, orient_k, knn, smooth=smooth, lists=lists)
     del res["moments"]
     return res
 

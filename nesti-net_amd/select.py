@@ -54,10 +54,11 @@ def selected_variation(variation_all, sel):
     return out
 
 
-def select_cloud(cloud, ladder=DEFAULT_LADDER, slack=0.0, orient=None, viewpoint=None, orient_k=8, smooth=None):
+def select_cloud(cloud, ladder=DEFAULT_LADDER, slack=0.0, orient=None, viewpoint=None, orient_k=8, smooth=None, lists=None):
     """``select_normals`` for a prepared ``provider.CloudPatches`` (all of its patch rows; ``radius_grid=False`` will do): one search at
     ``ladder[-1]``, one selected fit over its lists, the optional smoothing over the same lists where they reach its ``k``, the optional
-    orientation; synchronises."""
+    orientation; synchronises.  ``lists`` -- a contiguous int32 [patch_count, K >= ladder[-1]] device tensor of sorted neighbour lists
+    (``depth.window_knn``) -- is used instead of the search."""
     import torch
     from . import orient as _orient
     from . import smooth as _smooth
@@ -69,12 +70,13 @@ def select_cloud(cloud, ladder=DEFAULT_LADDER, slack=0.0, orient=None, viewpoint
         _smooth.refuse_subset(cloud.pidx, cloud.queries)
     names = ("normals", "eig", "sel", "k", "radius", "variation_all", "normals_all", "eig_all", "radius_all", "n_ball")
     with torch.cuda.device(cloud.device):
-        lists = cloud.knn(0, cloud.patch_count, ladder[-1])[0]
+        if lists is None:
+            lists = cloud.knn(0, cloud.patch_count, ladder[-1])[0]
         out = dict(zip(names, cloud.pca_select(0, cloud.patch_count, ladder, slack, nbr=lists)))
         normals = out["normals"]
         if sm is not None:
             normals, out["smooth_support"], out["smooth_count"] = _smooth.smooth_cloud(cloud, normals, sm,
-                                                                                       nbr=lists if ladder[-1] >= sm.k else None)
+                                                                                       nbr=lists if lists.shape[1] >= sm.k else None)
             out["normals"] = normals
         stats = None
         if orient is not None and cloud.patch_count:

@@ -44,6 +44,7 @@ from . import denoise as _denoise
 from . import downsample as _downsample
 from . import outliers as _outliers
 from . import smooth as _smooth
+from . import stages
 from . import quadric as _quadric
 from . import robust as _robust
 from . import select as _select
@@ -291,25 +292,6 @@ def denoise_line(name, rows, params, moved, delta):
                moved, float(delta.max()) if len(delta) else 0.0))
 
 
-def denoise_shape(cloud, params, name, output_dir, printout, kept=None, full=None, voxel_of=None):
-    """``--denoise`` for one shape: denoise the cloud's points, write ``<shape>.denoised.xyz`` and ``<shape>.denoise_delta`` and the log
-    line, and prepare the denoised points the way ``cloud`` was (configuration, seed).  ``kept`` / ``full``: the cloud is a filtered one
-    (``filter_shape``); ``voxel_of``: a downsampled one (``voxel_shape``) -- the two files are written with the rows of the input, a
-    removed row holding 0 and a row of a voxel what its voxel holds.  Returns the denoised cloud."""
-    from .provider import CloudPatches
-    p = params
-    d = _denoise.denoise_points(cloud.host_pts, p.k, p.iters, p.angle, p.falloff, p.sigma, p.step, None, p.normal_k, device=cloud.device)
-    printout(denoise_line(name, cloud.n_points, p, d["moved"], d["delta"]))
-    points, delta = d["points"], d["delta"]
-    if kept is not None:
-        points, delta = _outliers.scatter_host(points, kept, full, 0), _outliers.scatter_host(delta, kept, full, 0)
-    if voxel_of is not None:
-        points, delta = _downsample.gather_host(points, voxel_of), _downsample.gather_host(delta, voxel_of)
-    textio.write_f32(os.path.join(output_dir, name + ".denoised.xyz"), points)
-    textio.write_f32(os.path.join(output_dir, name + ".denoise_delta"), delta)
-    return CloudPatches(d["points"], cloud.cfg, cloud.device, cloud.seed)
-
-
 def smooth_line(name, rows, params, count):
     """The log line of ``--smooth`` for shape ``name``: the rows, the passes and the rows whose count is 1 (nothing but the row's own
     normal had a weight in the last pass); ``count``: the int32 counts of the last pass."""
@@ -349,39 +331,44 @@ def voxel_line(name, params, rows, count):
             % (name, " ".join("%g" % v for v in params.voxel), params.mode, len(count), rows, int(count.max()) if len(count) else 0))
 
 
-def voxel_shape(cloud, params, name, output_dir, printout):
-    """``--voxel_size`` for one shape: downsample the cloud's points, write the three files -- one row per row of the cloud: the point
-    and the count of its voxel -- and the log line, and prepare the voxels' points the way ``cloud`` was (configuration, seed).
-    Returns (the downsampled cloud, the result of ``downsample.voxel_downsample``)."""
+def stage_shape(cloud, voxel, outliers, denoise, name, output_dir, printout):
+    """``--voxel_size``, ``--outliers`` and ``--denoise`` for one shape: run the preprocessing chain (``stages.run``) on the cloud's
+    points, write each stage's log line and its files -- with the rows of the input: a removed row holds 0, a row of a voxel what its
+    voxel holds -- and prepare the resulting points the way ``cloud`` was (configuration, seed, query positions).  Returns (the
+    cloud to estimate on -- ``cloud`` itself where no stage is given --, the ``stages.Chain``)."""
     import numpy as np
     from .provider import CloudPatches
+    path = os.path.join(output_dir, name)
+    seen = []
+
+    def report(stage, out, chain):
+        seen.append(stage)
+        if stage == "downsample":
+            printout(voxel_line(name, voxel, chain.n, out["count"]))
+            textio.write_f32(path + ".voxel_xyz", stages.take_rows(out["points"], out["voxel_of"]))
+            textio.write_i32(path + ".voxel_of", np.ascontiguousarray(out["voxel_of"], dtype=np.int32))
+            textio.write_i32(path + ".voxel_count", stages.take_rows(out["count"], out["voxel_of"]))
+        elif stage == "outliers":
+            printout(outlier_line(name, outliers, len(out["inlier"]), out["passes"]))
+            write_outlier_files(output_dir, name, chain.to_input(out["inlier"]), chain.to_input(out["score"]))
+            if not len(out["kept"]):
+                raise SystemExit("--outliers: the filter kept none of the %d points of %s" % (len(out["inlier"]), name))
+        else:
+            printout(denoise_line(name, len(out["points"]), denoise, out["moved"], out["delta"]))
+            textio.write_f32(path + ".denoised.xyz", chain.to_input(out["points"]))
+            textio.write_f32(path + ".denoise_delta", chain.to_input(out["delta"]))
+
+    params = None if voxel is outliers is denoise is None else stages.Stages(voxel, outliers, denoise)
+    queries = None if cloud.queries is None else cloud.queries.cpu().numpy()
     try:
-        vd = _downsample.voxel_downsample(cloud.host_pts, *params, device=cloud.device)
+        chain = stages.run(cloud.host_pts, params, queries, cloud.device, report)
     except ValueError as e:
+        if voxel is None or seen:
+            raise
         raise SystemExit("--voxel_size: %s: %s" % (name, e))
-    printout(voxel_line(name, params, cloud.n_points, vd["count"]))
-    textio.write_f32(os.path.join(output_dir, name + ".voxel_xyz"), _downsample.gather_host(vd["points"], vd["voxel_of"]))
-    textio.write_i32(os.path.join(output_dir, name + ".voxel_of"), np.ascontiguousarray(vd["voxel_of"], dtype=np.int32))
-    textio.write_i32(os.path.join(output_dir, name + ".voxel_count"), _downsample.gather_host(vd["count"], vd["voxel_of"]))
-    return CloudPatches(vd["points"], cloud.cfg, cloud.device, cloud.seed), vd
-
-
-def filter_shape(cloud, params, name, output_dir, printout, voxel_of=None):
-    """``--outliers`` for one shape: filter the cloud's points, write the two files and the log line, and prepare the kept points the
-    way ``cloud`` was (configuration, seed, query positions).  ``voxel_of``: the cloud is a downsampled one (``voxel_shape``) and the
-    two files are written with the rows of the input, a row holding what its voxel holds.  Returns (the kept cloud, the result of
-    ``outliers.remove_outliers``)."""
-    from .provider import CloudPatches
-    f = _outliers.remove_outliers(cloud.host_pts, *params, device=cloud.device)
-    printout(outlier_line(name, params, cloud.n_points, f["passes"]))
-    if voxel_of is None:
-        write_outlier_files(output_dir, name, f["inlier"], f["score"])
-    else:
-        write_outlier_files(output_dir, name, _downsample.gather_host(f["inlier"], voxel_of), _downsample.gather_host(f["score"], voxel_of))
-    if not len(f["kept"]):
-        raise SystemExit("--outliers: the filter kept none of the %d points of %s" % (cloud.n_points, name))
-    kept = CloudPatches(f["points"], cloud.cfg, cloud.device, cloud.seed, queries=None if cloud.queries is None else cloud.queries.cpu().numpy())
-    return kept, f
+    if params is not None:
+        cloud = CloudPatches(chain.points, cloud.cfg, cloud.device, cloud.seed, queries=queries)
+    return cloud, chain
 
 
 def fit_batch(cfg, dtype, batch, device, lanes=2, reserve=2 << 30):
@@ -608,24 +595,13 @@ def run_select(FLAGS, cfg, ladder, slack, pc_path, output_dir, printout, smooth=
                                      device="cuda:%d" % FLAGS.gpu, query_positions=bool(FLAGS.query_positions))
     for ind, name in enumerate(dataset.shape_names):
         cloud = dataset.get_shape(ind)
-        filt = vox = None
-        if voxel is not None:                                  # first: the filter below is a density test, the grid evens the density
-            cloud, vox = voxel_shape(cloud, voxel, name, output_dir, printout)
-        if outliers is not None:
-            full, (cloud, filt) = cloud.n_points, filter_shape(cloud, outliers, name, output_dir, printout,
-                                                               None if vox is None else vox["voxel_of"])
-        if denoise is not None:                                # last before the estimator: rows stay one-to-one
-            cloud = denoise_shape(cloud, denoise, name, output_dir, printout, None if filt is None else filt["kept"],
-                                  None if filt is None else full, None if vox is None else vox["voxel_of"])
+        cloud, chain = stage_shape(cloud, voxel, outliers, denoise, name, output_dir, printout)
         res = _select.select_cloud(cloud, ladder, slack, orient=None if FLAGS.orient == "0" else FLAGS.orient, viewpoint=FLAGS.viewpoint,
                                    orient_k=FLAGS.orient_k, smooth=smooth)
         printout(select_line(name, cloud.patch_count, ladder, slack, res["sel"]))
         if smooth is not None:
             printout(smooth_line(name, cloud.patch_count, smooth, res["smooth_count"]))
-        if filt is not None and cloud.queries is None:        # the log lines above count the kept rows; the files hold every row
-            res = _outliers.scatter_result(res, filt["kept"], full)
-        if vox is not None:                                    # ... and a row of the input holds the result of its voxel
-            res = _downsample.gather_result(res, vox["voxel_of"], len(vox["rep"]))
+        res = chain.back(res)                                  # the log lines above count the estimated rows; the files hold every row
         if smooth is not None:
             write_smooth_support(os.path.join(output_dir, name + ".smooth_support"), res["smooth_support"], res["smooth_count"])
         if res["orient"] is not None:
@@ -663,15 +639,7 @@ def run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None, smooth=No
                                      device="cuda:%d" % FLAGS.gpu, query_positions=bool(FLAGS.query_positions))
     for ind, name in enumerate(dataset.shape_names):
         cloud = dataset.get_shape(ind)
-        filt = vox = None
-        if voxel is not None:                                  # first: the filter below is a density test, the grid evens the density
-            cloud, vox = voxel_shape(cloud, voxel, name, output_dir, printout)
-        if outliers is not None:
-            full, (cloud, filt) = cloud.n_points, filter_shape(cloud, outliers, name, output_dir, printout,
-                                                               None if vox is None else vox["voxel_of"])
-        if denoise is not None:                                # last before the estimator: rows stay one-to-one
-            cloud = denoise_shape(cloud, denoise, name, output_dir, printout, None if filt is None else filt["kept"],
-                                  None if filt is None else full, None if vox is None else vox["voxel_of"])
+        cloud, chain = stage_shape(cloud, voxel, outliers, denoise, name, output_dir, printout)
         params = {kw: getattr(FLAGS, flag) for kw, flag in fit.get("params", ())}
         res = fit["fit"](cloud, scale=scale, orient=None if FLAGS.orient == "0" else FLAGS.orient, viewpoint=FLAGS.viewpoint,
                          orient_k=FLAGS.orient_k, knn=ks, smooth=smooth, **params)
@@ -684,10 +652,7 @@ def run_fit(FLAGS, cfg, scale, pc_path, output_dir, printout, ks=None, smooth=No
             printout(fit["line"](name, res, scale, params))
         if smooth is not None:
             printout(smooth_line(name, cloud.patch_count, smooth, res["smooth_count"]))
-        if filt is not None and cloud.queries is None:        # the log lines above count the kept rows; the files hold every row
-            res = _outliers.scatter_result(res, filt["kept"], full)
-        if vox is not None:                                    # ... and a row of the input holds the result of its voxel
-            res = _downsample.gather_result(res, vox["voxel_of"], len(vox["rep"]))
+        res = chain.back(res)                                  # the log lines above count the estimated rows; the files hold every row
         if ks is not None:
             textio.write_f32(os.path.join(output_dir, name + ".knn_radius"), res["radius"])
         if smooth is not None:
@@ -998,10 +963,8 @@ def main(argv=None):
 
     for ind, name in enumerate(dataset.shape_names):
         cloud = dataset.get_shape(ind)
-        filt = None
-        if outliers is not None:
-            # before anything looks at the cloud: the calibration, the network, --smooth and --orient see the kept points alone
-            full, (cloud, filt) = cloud.n_points, filter_shape(cloud, outliers, name, output_dir, printout)
+        # before anything looks at the cloud: the calibration, the network, --smooth and --orient see the kept points alone
+        cloud, chain = stage_shape(cloud, None, outliers, None, name, output_dir, printout)
         calibrate(name, cloud)
         if repro:
             normals, expert, probs = est.run_verified(cloud)
@@ -1029,14 +992,14 @@ def main(argv=None):
             alone = (expert == -1) if expert is not None else (normals == 0).all(dim=1)
             printout("query positions of %s: %d, of which %d had no neighbourhood (no cloud point inside any ball: written as 0 0 0 / -1 / 0)"
                      % (name, cloud.patch_count, int(alone.sum().item())))
-        if filt is not None and cloud.queries is None:
+        if chain.kept is not None and cloud.queries is None:
             # back to the rows of <shape>.xyz: a removed row is 0 0 0 / -1 / 0 (nesti_image_scatter over an image one row high)
-            kept = torch.from_numpy(filt["kept"].astype("int32")).to(normals.device)
-            normals = _outliers.scatter_rows(normals.contiguous(), kept, full, 0.0)
+            kept = torch.from_numpy(chain.kept.astype("int32")).to(normals.device)
+            normals = _outliers.scatter_rows(normals.contiguous(), kept, chain.n, 0.0)
             if expert is not None:
-                expert, probs = _outliers.scatter_rows(expert.contiguous(), kept, full, -1), _outliers.scatter_rows(probs.contiguous(), kept, full, 0.0)
+                expert, probs = _outliers.scatter_rows(expert.contiguous(), kept, chain.n, -1), _outliers.scatter_rows(probs.contiguous(), kept, chain.n, 0.0)
             if support is not None:
-                support, count = _outliers.scatter_rows(support.contiguous(), kept, full, 0.0), _outliers.scatter_rows(count.contiguous(), kept, full, 0)
+                support, count = _outliers.scatter_rows(support.contiguous(), kept, chain.n, 0.0), _outliers.scatter_rows(count.contiguous(), kept, chain.n, 0)
         # byte-identical to the reference's np.savetxt calls (test_n_est_w_experts.py:182-188), ~6x faster
         textio.write_f32(os.path.join(output_dir, name + ".normals"), normals.cpu().numpy())
         if support is not None:

@@ -76,14 +76,6 @@ def refuse_pidx(pidx):
                          "have the rows of pidx; denoise first (denoise.denoise_points) and index the denoised cloud")
 
 
-def check_arg(denoise, pidx):
-    """What every estimator does with its ``denoise=`` before any work: ``as_params``, and ``refuse_pidx`` where the filter is on."""
-    params = as_params(denoise)
-    if params is not None:
-        refuse_pidx(pidx)
-    return params
-
-
 def denoise_cloud(cloud, normals_dev, params, stream=None):
     """``params.iters`` Jacobi passes over ALL points of a prepared ``provider.CloudPatches`` (no ``pidx``, no ``queries``;
     ``radius_grid=False`` serves).  Every pass works on the CURRENT positions: it searches lists of ``max(k, normal_k)`` on them,
@@ -172,15 +164,3 @@ def denoise_points(pts, k=DEFAULT_K, iters=DEFAULT_ITERS, angle=DEFAULT_ANGLE, f
     out = {key: res[key].cpu().numpy() for key in ("points", "delta", "support", "count")}
     out["moved"] = int(res["moved"])
     return out
-
-
-def run_denoised(fit, pts, denoise, pidx, queries, device, **kw):
-    """What ``denoise=`` of the numpy-in estimators does: denoise ``pts`` (``denoise_points``) and run ``fit(points, queries=...,
-    device=..., **kw)`` on the denoised positions -- bounding box, neighbourhoods, smoothing and orientation are then theirs.  Rows
-    stay one-to-one, so nothing is scattered; with ``queries`` the cloud is denoised and the queries are left alone.  The result gains
-    ``points`` [N,3] f32 and ``denoise_delta`` [N] f32.  ``ValueError`` for ``pidx`` and for bad parameters."""
-    params = check_arg(denoise, pidx)
-    d = denoise_points(pts, *params[:3], params.falloff, params.sigma, params.step, None, params.normal_k, device=device)
-    res = fit(d["points"], queries=queries, device=device, **kw)
-    res.update(points=d["points"], denoise_delta=d["delta"])
-    return res

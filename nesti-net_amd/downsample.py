@@ -13,6 +13,8 @@ import collections
 import numpy as np
 
 from . import outliers as _outliers
+from ._args import int_in as _int_in
+from .stages import take_result, take_rows
 
 MODES = ("centroid", "nearest")
 KEYS = ("voxel", "mode", "origin")
@@ -44,7 +46,7 @@ def check_origin(origin):
 
 def check_key_bits(key_bits):
     """The low bits a sort looks at, 1 .. 64, as an int; ``ValueError`` otherwise."""
-    return _outliers._int_in("key_bits", key_bits, 1, 64)
+    return _int_in("key_bits", key_bits, 1, 64)
 
 
 def check_grid(origin, voxel, dims):
@@ -206,50 +208,10 @@ def voxel_downsample(pts, voxel, mode="centroid", origin=None, device="cuda:0"):
 # ---- the voxels' rows back to the rows of the input ----------------------------------------------------------------------------------------
 def gather_host(rows, voxel_of, fill=0):
     """Host: numpy ``rows`` [V, ...] of the voxels -> [N, ...] with ``rows[voxel_of[i]]`` at row i and ``fill`` where ``voxel_of`` is -1."""
-    rows = np.asarray(rows)
-    voxel_of = np.asarray(voxel_of, np.int64)
-    out = np.full((len(voxel_of),) + rows.shape[1:], fill, dtype=rows.dtype)
-    live = voxel_of >= 0
-    out[live] = rows[voxel_of[live]]
-    return out
+    return take_rows(rows, voxel_of, fill)
 
 
 def gather_result(res, voxel_of, rows):
     """A result dict of numpy arrays over the ``rows`` voxels -> over the rows of the input: every array whose first dimension is
     ``rows`` is gathered through ``voxel_of``, with 0 -- ``expert``: -1 -- in the lost rows; everything else passes through."""
-    out = {}
-    for key, v in res.items():
-        if isinstance(v, np.ndarray) and v.ndim >= 1 and v.shape[0] == rows:
-            out[key] = gather_host(v, voxel_of, _outliers.FILLS.get(key, 0))
-        else:
-            out[key] = v
-    return out
-
-
-def run_downsampled(fit, pts, downsample, outliers, pidx, queries, device, per_row=None, **kw):
-    """What ``downsample=`` of the numpy-in estimators does: downsample ``pts`` (``voxel_downsample``), run ``fit(points, queries=...,
-    outliers=..., device=..., **kw)`` on the voxels' points -- the outlier filter, bounding box, neighbourhoods, smoothing and
-    orientation are then the downsampled cloud's; downsampling comes FIRST, the statistical filter being a density test and the grid
-    what makes density uniform -- and bring its per-row arrays back to the rows of ``pts``: row i holds the result of its voxel
-    (``gather_result``; where the filter ran, its own scatter is composed with the gather, a removed voxel's rows hold the fill).  With
-    ``queries`` the rows are positions and nothing is gathered.  ``per_row``: keyword arguments of ``fit`` that hold one entry per
-    point (``init=`` of the robust fit) and are taken at ``rep``.  The result gains ``voxel_of`` [N] int64, ``voxel_points`` [V,3] f32
-    and ``voxel_count`` [V] int32.  ``ValueError`` for ``pidx`` (left for later), for bad parameters and for an empty cloud."""
-    params = as_params(downsample)
-    refuse_pidx(pidx)
-    if outliers is not None:
-        _outliers.as_params(outliers)                                        # a bad filter is refused before any work
-    pts = _outliers.check_cloud(pts)
-    if not len(pts):
-        raise ValueError("downsample: an empty cloud")
-    vd = voxel_downsample(pts, *params, device=device)
-    V = len(vd["rep"])
-    if not V:
-        raise ValueError("downsample: none of the %d points lies in the grid of origin %s" % (len(pts), list(vd["origin"])))
-    for key, v in (per_row or {}).items():
-        kw[key] = v if v is None or queries is not None else np.asarray(v)[vd["rep"]]
-    res = fit(vd["points"], queries=queries, outliers=outliers, device=device, **kw)
-    if queries is None:
-        res = gather_result(res, vd["voxel_of"], V)
-    res.update(voxel_of=vd["voxel_of"], voxel_points=vd["points"], voxel_count=vd["count"])
-    return res
+    return take_result(res, voxel_of, rows)

@@ -7,6 +7,7 @@ fit average across a crease, the vote picks one of its faces.  It needs no model
 import numpy as np
 
 from . import _lib
+from ._args import int_in as _int_in
 from .pca import fit_cloud, prepare_cloud
 
 # The rotation table of the accumulator: 8 orthonormal 3 x 3 matrices, row 0 the identity, generated once (QR of seeded normal draws)
@@ -39,12 +40,6 @@ ROTATIONS = (
 )
 
 DEFAULT_KNN, DEFAULT_TRIPLETS, DEFAULT_BINS, DEFAULT_ROTATIONS = 100, 1000, 16, 5
-
-
-def _int_in(name, v, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
-        raise ValueError("%s must be an integer in %d .. %d: got %r" % (name, lo, hi, v))
-    return int(v)
 
 
 def check_params(triplets, bins, rotations, seed):
@@ -107,42 +102,13 @@ def hough_normals(pts, knn=DEFAULT_KNN, pidx=None, queries=None, scale=-1, tripl
     configuration's radii would mean nothing), for parameters outside their ranges, for a ``scale`` outside [-S, S), for ``pidx``
     together with ``queries``, for a bad ``smooth`` and for ``smooth`` with ``pidx`` or ``queries``.
 
-    ``outliers`` -- None, ``'statistical'`` or a dict of ``mode``, ``k``, ``std_ratio``, ``radius``, ``min_neighbours``, ``passes``
-    (``outliers.remove_outliers``; DESIGN.md 2 "Outlier removal") -- filters the cloud first: the estimator, its smoothing and its
-    orientation run on the kept points, every per-row array comes back with the rows of ``pts`` (0 in the removed ones), and the dict
-    gains ``inlier`` [N] bool, ``outlier_score`` [N] and ``outlier_passes``.  With ``queries`` the rows are positions and nothing is
-    scattered; ``pidx`` with ``outliers`` is refused.
-
-    ``downsample`` -- None, a voxel size (a number or three, in the cloud's units) or a dict of ``voxel``, ``mode``, ``origin``
-    (``downsample.voxel_downsample``; DESIGN.md 2 "Voxel downsampling") -- downsamples the cloud on a voxel grid first: the estimator,
-    ``outliers`` (which comes second), the smoothing and the orientation run on the voxels' points, every per-row array comes back
-    with the rows of ``pts`` -- row i holds the result of its voxel --, and the dict gains ``voxel_of`` [N], ``voxel_points`` [V,3] and
-    ``voxel_count`` [V].  With ``queries`` nothing is gathered; ``pidx`` with ``downsample`` is refused.
-
-    ``denoise`` -- None, True (the defaults) or a dict of ``k``, ``iters``, ``angle``, ``falloff``, ``sigma``, ``step``, ``normal_k``
-    (``denoise.denoise_points``; DESIGN.md 2 "Point denoising") -- denoises the positions after ``downsample`` and ``outliers`` and
-    before the estimator, whose smoothing and orientation then run over the denoised positions.  Rows stay one-to-one: every per-row
-    array keeps its rows and the dict gains ``points`` [N,3] f32 and ``denoise_delta`` [N] f32 (0 in rows that ``outliers`` removed).
-    With ``queries`` the cloud is denoised and the queries are left alone; ``pidx`` with ``denoise`` is refused."""
-    if denoise is not None:
-        from . import denoise as _denoise
-        denoise = _denoise.check_arg(denoise, pidx)
-    if downsample is not None:
-        from . import downsample as _downsample
-        return _downsample.run_downsampled(hough_normals, pts, downsample, outliers, pidx, queries, device, knn=knn, scale=scale, triplets=triplets,
-                                      bins=bins, rotations=rotations, seed=seed, orient=orient, viewpoint=viewpoint, orient_k=orient_k,
-                                      cfg=cfg, smooth=smooth, denoise=denoise)
-    if outliers is not None:
-        from . import outliers as _outliers
-        return _outliers.run_filtered(hough_normals, pts, outliers, pidx, queries, device, knn=knn, scale=scale, triplets=triplets,
-                                      bins=bins, rotations=rotations, seed=seed, orient=orient, viewpoint=viewpoint, orient_k=orient_k,
-                                      cfg=cfg, smooth=smooth, denoise=denoise)
-    if denoise is not None:
-        return _denoise.run_denoised(hough_normals, pts, denoise, pidx, queries, device, knn=knn, scale=scale, triplets=triplets,
-                                      bins=bins, rotations=rotations, seed=seed, orient=orient, viewpoint=viewpoint, orient_k=orient_k,
-                                      cfg=cfg, smooth=smooth)
+    ``downsample``, ``outliers``, ``denoise`` -- the preprocessing chain (``stages``: the arguments, their order, the keys they add,
+    the way back to the rows of ``pts`` and what ``queries`` changes) -- run in front of the estimator; ``pidx`` with any is refused."""
+    from . import stages
+    params = stages.check(downsample, outliers, denoise, pidx)
     _need_knn(knn)
     check_params(triplets, bins, rotations, seed)
-    cloud, scale, orient, viewpoint, orient_k, ks = prepare_cloud(pts, cfg, pidx, queries, scale, orient, viewpoint, orient_k, device, knn,
-                                                                  smooth)
-    return hough_cloud(cloud, ks, scale, triplets, bins, rotations, seed, orient, viewpoint, orient_k, smooth=smooth)
+    chain = stages.run(pts, params, queries, device)
+    cloud, scale, orient, viewpoint, orient_k, ks = prepare_cloud(chain.points, cfg, pidx, queries, scale, orient, viewpoint, orient_k, device,
+                                                                  knn, smooth)
+    return chain.back(hough_cloud(cloud, ks, scale, triplets, bins, rotations, seed, orient, viewpoint, orient_k, smooth=smooth))

@@ -12,6 +12,8 @@ import math
 import numpy as np
 
 from . import _lib
+from ._args import int_in as _int_in, number as _number
+from .stages import FILLS, inverse, take_result, take_rows
 
 MODES = ("statistical", "radius")
 DEFAULT_K, DEFAULT_STD_RATIO, DEFAULT_PASSES = 16, 1.0, 1
@@ -22,22 +24,6 @@ KEYS = ("mode", "k", "std_ratio", "radius", "min_neighbours", "passes")
 # mode; k (statistical: the neighbours of the mean; radius: what min_neighbours defaults to); std_ratio (statistical); radius and
 # min_neighbours (radius mode, else None); passes
 Params = collections.namedtuple("Params", KEYS)
-
-
-def _int_in(name, v, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
-        raise ValueError("%s must be an integer in %d .. %d: got %r" % (name, lo, hi, v))
-    return int(v)
-
-
-def _number(name, v):
-    try:
-        f = float(v)
-    except (TypeError, ValueError):
-        f = float("nan")
-    if isinstance(v, bool) or not math.isfinite(f):
-        raise ValueError("%s must be a finite number: got %r" % (name, v))
-    return f
 
 
 def check_k(k):
@@ -235,46 +221,11 @@ def scatter_rows(rows, kept_idx, n, fill=0, stream=None):
 def scatter_host(rows, kept, n, fill=0):
     """Host: numpy ``rows`` [M, ...] of the kept points -> [n, ...] with ``rows[i]`` at row ``kept[i]`` and ``fill`` elsewhere, for the
     results an estimator has already brought to the host."""
-    rows = np.asarray(rows)
-    out = np.full((int(n),) + rows.shape[1:], fill, dtype=rows.dtype)
-    out[np.asarray(kept, np.int64)] = rows
-    return out
-
-
-FILLS = {"expert": -1}                 # every other per-row array is filled with 0
+    return take_rows(rows, inverse(kept, n), fill)
 
 
 def scatter_result(res, kept, n, rows=None):
     """A result dict of numpy arrays over the kept points -> over the ``n`` rows of the input: every array whose first dimension is the
-    kept count (``rows``: that count, default ``len(kept)``) is scattered, with 0 -- ``expert``: -1 -- in the removed rows; everything
-    else (``orient`` statistics, scalars) passes through."""
-    rows = len(kept) if rows is None else rows
-    out = {}
-    for key, v in res.items():
-        if isinstance(v, np.ndarray) and v.ndim >= 1 and v.shape[0] == rows:
-            out[key] = scatter_host(v, kept, n, FILLS.get(key, 0))
-        else:
-            out[key] = v
-    return out
-
-
-def run_filtered(fit, pts, outliers, pidx, queries, device, per_row=None, **kw):
-    """What ``outliers=`` of the numpy-in estimators does: filter ``pts`` (``remove_outliers``), run ``fit(points, queries=..., device=...,
-    **kw)`` on the kept points -- bounding box, grid, neighbourhoods, smoothing and orientation are then the kept cloud's -- and bring its
-    per-row arrays back to the rows of ``pts`` (``scatter_result``).  With ``queries`` the rows are positions and nothing is scattered.
-    ``per_row``: keyword arguments of ``fit`` that hold one entry per point (``init=`` of the robust fit) and are cut to the kept points.
-    The result gains ``inlier`` [N] bool, ``outlier_score`` [N] f64 and ``outlier_passes``.  ``ValueError`` for ``pidx`` (left for later),
-    for bad parameters and where the filter keeps no point."""
-    params = as_params(outliers)
-    refuse_pidx(pidx)
-    pts = check_cloud(pts)
-    f = remove_outliers(pts, *params, device=device)
-    if not len(f["kept"]):
-        raise ValueError("outliers: the filter kept none of the %d points" % len(pts))
-    for key, v in (per_row or {}).items():
-        kw[key] = v if v is None or queries is not None else np.asarray(v)[f["kept"]]
-    res = fit(f["points"], queries=queries, device=device, **kw)
-    if queries is None:
-        res = scatter_result(res, f["kept"], len(pts))
-    res.update(inlier=f["inlier"], outlier_score=f["score"], outlier_passes=f["passes"])
-    return res
+    kept count (``rows``: that count, default ``len(kept)``) is scattered, with 0 -- ``expert``: -1 (``FILLS``) -- in the removed rows;
+    everything else (``orient`` statistics, scalars) passes through."""
+    return take_result(res, inverse(kept, n), len(kept) if rows is None else rows)

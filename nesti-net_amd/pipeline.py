@@ -517,34 +517,18 @@ class NormalEstimator:
         ``angle``, ``falloff`` (``smooth.smooth_normals``) -- smooths the normals over all points before the orientation; it needs
         all points (``ValueError`` with ``pidx`` or ``queries``: the rows' neighbours would have no normal), leaves experts and
         probabilities alone, and ``self.last_smooth`` holds ``smooth_support`` and ``smooth_count`` of the last pass.  ``outliers`` --
-        None, ``'statistical'`` or a dict (``outliers.remove_outliers``; DESIGN.md 2 "Outlier removal") -- filters the cloud first:
-        the network, the smoothing and the orientation see the kept points alone, the three arrays come back with the rows of ``pts``
-        (normal 0 0 0, expert -1, probabilities 0 in the removed ones; with ``queries`` the rows are positions and nothing is
-        scattered) and ``self.last_outliers`` holds ``inlier``, ``kept``, ``score`` and ``passes``; ``pidx`` with it is refused."""
+        None, ``'statistical'`` or a dict: the filter of the preprocessing chain (``stages``), alone -- filters the cloud first: the three arrays come back with the rows of
+        ``pts`` (normal 0 0 0, expert -1, probabilities 0 in the removed ones; nothing is mapped with ``queries``) and
+        ``self.last_outliers`` holds ``inlier``, ``kept``, ``score`` and ``passes``; ``pidx`` with it is refused."""
         if orient not in (None, "mst", "viewpoint"):
             raise ValueError("orient must be None, 'mst' or 'viewpoint'")
-        if outliers is not None:
-            from . import outliers as _outliers
-            params = _outliers.as_params(outliers)
-            _outliers.refuse_pidx(pidx)
-            pts = _outliers.check_cloud(pts)
-            f = _outliers.remove_outliers(pts, *params, device=self.device)
-            if not len(f["kept"]):
-                raise ValueError("outliers: the filter kept none of the %d points" % len(pts))
-            normals, expert, probs = self.estimate(f["points"], None, queries, orient, viewpoint, orient_k, smooth)
-            self.last_outliers = {key: f[key] for key in ("inlier", "kept", "score", "passes")}
-            if queries is not None:
-                return normals, expert, probs
-            if smooth is not None:
-                self.last_smooth = _outliers.scatter_result(self.last_smooth, f["kept"], len(pts))
-            back = [None if a is None else _outliers.scatter_host(a, f["kept"], len(pts), fill) for a, fill in
-                    ((normals, 0), (expert, -1), (probs, 0))]
-            return tuple(back)
-        from . import smooth as _smooth
+        from . import smooth as _smooth, stages
+        params = stages.check(None, outliers, None, pidx)
         sm = _smooth.as_params(smooth)
         if sm is not None:
             _smooth.refuse_subset(pidx, queries)
-        cloud = self.prepare(np.asarray(pts, dtype=np.float32), pidx, queries)
+        chain = stages.run(pts, params, queries, self.device)
+        cloud = self.prepare(np.asarray(chain.points, dtype=np.float32), pidx, queries)
         normals, expert, probs = self.run(cloud)
         if sm is not None:
             with torch.cuda.device(self.device):
@@ -554,10 +538,11 @@ class NormalEstimator:
             self.last_orient = stats_dict(self.orient(cloud, normals, orient, viewpoint, orient_k))
         torch.cuda.synchronize(self.device)
         if sm is not None:
-            self.last_smooth = {"smooth_support": support.cpu().numpy(), "smooth_count": count.cpu().numpy()}
-        if expert is None:
-            return normals.cpu().numpy(), None, None
-        return normals.cpu().numpy(), expert.cpu().numpy(), probs.cpu().numpy()
+            self.last_smooth = {"smooth_support": chain.to_input(support.cpu().numpy()), "smooth_count": chain.to_input(count.cpu().numpy())}
+        if chain.kept is not None:
+            self.last_outliers = {"inlier": chain.keys["inlier"], "kept": chain.kept, "score": chain.keys["outlier_score"],
+                                  "passes": chain.keys["outlier_passes"]}
+        return tuple(None if a is None else chain.to_input(a.cpu().numpy(), fill) for a, fill in ((normals, 0), (expert, -1), (probs, 0)))
 
     def estimate_depth(self, depth, camera, stride=1, orient="viewpoint", orient_k=8, on_cloud=None, outliers=None):
         """Depth frame in, normal image out (``depth.py``; DESIGN.md 2 "Depth images"): back-project ``depth`` [H,W] (uint16 or

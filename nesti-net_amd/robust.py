@@ -5,25 +5,14 @@ of a crease, so the fit leans to one face where the plane fit and the quadric fi
 and no triplets, so it loses little on noisy smooth surfaces where the Hough transform pays for its bins.  With ``init=`` the same call
 refines any other estimator's normals against the points.  It needs no model and no weights.  The conventions are the library's own (no
 parity with any published code is claimed).  There is no ball variant and no CPU fallback."""
-import math
-
 import numpy as np
 
 from . import _lib
+from ._args import number as _number
 from .pca import fit_cloud, prepare_cloud
 
 DEFAULT_KNN, DEFAULT_ITERS, DEFAULT_SIGMA, DEFAULT_FALLOFF, DEFAULT_FLOOR = 100, 8, 2.0, 0.5, 0.01
 SIGMA_MAX, FLOOR_MIN = 1e6, 1e-6
-
-
-def _number(name, v):
-    try:
-        f = float(v)
-    except (TypeError, ValueError):
-        f = float("nan")
-    if isinstance(v, bool) or not math.isfinite(f):
-        raise ValueError("%s must be a finite number: got %r" % (name, v))
-    return f
 
 
 def check_params(iters=DEFAULT_ITERS, sigma=DEFAULT_SIGMA, falloff=DEFAULT_FALLOFF, floor=DEFAULT_FLOOR):
@@ -114,47 +103,18 @@ def robust_normals(pts, knn=DEFAULT_KNN, pidx=None, queries=None, scale=-1, iter
     for an ``init`` of another shape, for a ``scale`` outside [-S, S), for ``pidx`` together with ``queries``, for a bad ``orient`` or
     ``smooth`` and for ``smooth`` with ``pidx`` or ``queries``.
 
-    ``outliers`` -- None, ``'statistical'`` or a dict of ``mode``, ``k``, ``std_ratio``, ``radius``, ``min_neighbours``, ``passes``
-    (``outliers.remove_outliers``; DESIGN.md 2 "Outlier removal") -- filters the cloud first: the estimator, its smoothing and its
-    orientation run on the kept points, every per-row array comes back with the rows of ``pts`` (0 in the removed ones), and the dict
-    gains ``inlier`` [N] bool, ``outlier_score`` [N] and ``outlier_passes``.  With ``queries`` the rows are positions and nothing is
-    scattered; ``pidx`` with ``outliers`` is refused.
-
-    ``downsample`` -- None, a voxel size (a number or three, in the cloud's units) or a dict of ``voxel``, ``mode``, ``origin``
-    (``downsample.voxel_downsample``; DESIGN.md 2 "Voxel downsampling") -- downsamples the cloud on a voxel grid first: the estimator,
-    ``outliers`` (which comes second), the smoothing and the orientation run on the voxels' points, every per-row array comes back
-    with the rows of ``pts`` -- row i holds the result of its voxel --, and the dict gains ``voxel_of`` [N], ``voxel_points`` [V,3] and
-    ``voxel_count`` [V].  With ``queries`` nothing is gathered; ``pidx`` with ``downsample`` is refused.
-
-    ``denoise`` -- None, True (the defaults) or a dict of ``k``, ``iters``, ``angle``, ``falloff``, ``sigma``, ``step``, ``normal_k``
-    (``denoise.denoise_points``; DESIGN.md 2 "Point denoising") -- denoises the positions after ``downsample`` and ``outliers`` and
-    before the estimator, whose smoothing and orientation then run over the denoised positions.  Rows stay one-to-one: every per-row
-    array keeps its rows and the dict gains ``points`` [N,3] f32 and ``denoise_delta`` [N] f32 (0 in rows that ``outliers`` removed).
-    With ``queries`` the cloud is denoised and the queries are left alone; ``pidx`` with ``denoise`` is refused."""
-    if denoise is not None:
-        from . import denoise as _denoise
-        denoise = _denoise.check_arg(denoise, pidx)
-    if downsample is not None:
-        from . import downsample as _downsample
-        return _downsample.run_downsampled(robust_normals, pts, downsample, outliers, pidx, queries, device, per_row={"init": init}, knn=knn, scale=scale,
-                                      iters=iters, sigma=sigma, falloff=falloff, floor=floor, orient=orient, viewpoint=viewpoint,
-                                      orient_k=orient_k, smooth=smooth, denoise=denoise)
-    if outliers is not None:
-        from . import outliers as _outliers
-        return _outliers.run_filtered(robust_normals, pts, outliers, pidx, queries, device, per_row={"init": init}, knn=knn, scale=scale,
-                                      iters=iters, sigma=sigma, falloff=falloff, floor=floor, orient=orient, viewpoint=viewpoint,
-                                      orient_k=orient_k, smooth=smooth, denoise=denoise)
-    if denoise is not None:
-        return _denoise.run_denoised(robust_normals, pts, denoise, pidx, queries, device, init=init, knn=knn, scale=scale,
-                                      iters=iters, sigma=sigma, falloff=falloff, floor=floor, orient=orient, viewpoint=viewpoint,
-                                      orient_k=orient_k, smooth=smooth)
+    ``downsample``, ``outliers``, ``denoise`` -- the preprocessing chain (``stages``: the arguments, their order, the keys they add,
+    the way back to the rows of ``pts`` and what ``queries`` changes) -- run in front of the estimator; ``pidx`` with any is refused."""
+    from . import stages
     from .knn import check_ks
+    params = stages.check(downsample, outliers, denoise, pidx)
     _need_knn(knn)
     check_params(iters, sigma, falloff, floor)
     if pidx is not None and queries is not None:
         raise ValueError("pidx and queries are mutually exclusive: a query is a cloud point (pidx) or a position (queries)")
     rows = len(pidx) if pidx is not None else len(queries) if queries is not None else len(pts)
     init = check_init(init, rows, len(check_ks(knn)))
-    cloud, scale, orient, viewpoint, orient_k, ks = prepare_cloud(pts, None, pidx, queries, scale, orient, viewpoint, orient_k, device, knn,
-                                                                  smooth)
-    return robust_cloud(cloud, ks, scale, iters, sigma, falloff, floor, init, orient, viewpoint, orient_k, smooth=smooth)
+    chain = stages.run(pts, params, queries, device)
+    cloud, scale, orient, viewpoint, orient_k, ks = prepare_cloud(chain.points, None, pidx, queries, scale, orient, viewpoint, orient_k, device,
+                                                                  knn, smooth)
+    return chain.back(robust_cloud(cloud, ks, scale, iters, sigma, falloff, floor, chain.take(init), orient, viewpoint, orient_k, smooth=smooth))

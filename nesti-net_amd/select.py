@@ -119,39 +119,11 @@ def select_normals(pts, ladder=DEFAULT_LADDER, slack=0.0, pidx=None, queries=Non
     Raises ``ValueError`` -- before any GPU work -- for a bad ``ladder`` or ``slack``, for ``pidx`` together with ``queries``, for a bad
     ``orient`` or ``smooth`` and for ``smooth`` with ``pidx`` or ``queries``.
 
-    ``outliers`` -- None, ``'statistical'`` or a dict of ``mode``, ``k``, ``std_ratio``, ``radius``, ``min_neighbours``, ``passes``
-    (``outliers.remove_outliers``; DESIGN.md 2 "Outlier removal") -- filters the cloud first: the estimator, its smoothing and its
-    orientation run on the kept points, every per-row array comes back with the rows of ``pts`` (0 in the removed ones), and the dict
-    gains ``inlier`` [N] bool, ``outlier_score`` [N] and ``outlier_passes``.  With ``queries`` the rows are positions and nothing is
-    scattered; ``pidx`` with ``outliers`` is refused.
-
-    ``downsample`` -- None, a voxel size (a number or three, in the cloud's units) or a dict of ``voxel``, ``mode``, ``origin``
-    (``downsample.voxel_downsample``; DESIGN.md 2 "Voxel downsampling") -- downsamples the cloud on a voxel grid first: the estimator,
-    ``outliers`` (which comes second), the smoothing and the orientation run on the voxels' points, every per-row array comes back
-    with the rows of ``pts`` -- row i holds the result of its voxel --, and the dict gains ``voxel_of`` [N], ``voxel_points`` [V,3] and
-    ``voxel_count`` [V].  With ``queries`` nothing is gathered; ``pidx`` with ``downsample`` is refused.
-
-    ``denoise`` -- None, True (the defaults) or a dict of ``k``, ``iters``, ``angle``, ``falloff``, ``sigma``, ``step``, ``normal_k``
-    (``denoise.denoise_points``; DESIGN.md 2 "Point denoising") -- denoises the positions after ``downsample`` and ``outliers`` and
-    before the estimator, whose smoothing and orientation then run over the denoised positions.  Rows stay one-to-one: every per-row
-    array keeps its rows and the dict gains ``points`` [N,3] f32 and ``denoise_delta`` [N] f32 (0 in rows that ``outliers`` removed).
-    With ``queries`` the cloud is denoised and the queries are left alone; ``pidx`` with ``denoise`` is refused."""
-    if denoise is not None:
-        from . import denoise as _denoise
-        denoise = _denoise.check_arg(denoise, pidx)
-    if downsample is not None:
-        from . import downsample as _downsample
-        return _downsample.run_downsampled(select_normals, pts, downsample, outliers, pidx, queries, device, ladder=ladder, slack=slack, orient=orient,
-                                      viewpoint=viewpoint, orient_k=orient_k, smooth=smooth, denoise=denoise)
-    if outliers is not None:
-        from . import outliers as _outliers
-        return _outliers.run_filtered(select_normals, pts, outliers, pidx, queries, device, ladder=ladder, slack=slack, orient=orient,
-                                      viewpoint=viewpoint, orient_k=orient_k, smooth=smooth, denoise=denoise)
-    if denoise is not None:
-        return _denoise.run_denoised(select_normals, pts, denoise, pidx, queries, device, ladder=ladder, slack=slack, orient=orient,
-                                      viewpoint=viewpoint, orient_k=orient_k, smooth=smooth)
-    from . import smooth as _smooth
+    ``downsample``, ``outliers``, ``denoise`` -- the preprocessing chain (``stages``: the arguments, their order, the keys they add,
+    the way back to the rows of ``pts`` and what ``queries`` changes) -- run in front of the estimator; ``pidx`` with any is refused."""
+    from . import smooth as _smooth, stages
     from .config import NestiConfig
+    params = stages.check(downsample, outliers, denoise, pidx)
     ladder, slack = check_ladder(ladder), check_slack(slack)
     if smooth is not None:
         _smooth.as_params(smooth)
@@ -164,5 +136,6 @@ def select_normals(pts, ladder=DEFAULT_LADDER, slack=0.0, pidx=None, queries=Non
         from .orient import _check_args
         _check_args(1.0, orient_k, viewpoint, orient)
     from .provider import CloudPatches
-    cloud = CloudPatches(np.asarray(pts, dtype=np.float32), NestiConfig(), device=device, pidx=pidx, queries=queries, radius_grid=False)
-    return select_cloud(cloud, ladder, slack, orient, viewpoint, orient_k, smooth)
+    chain = stages.run(pts, params, queries, device)
+    cloud = CloudPatches(np.asarray(chain.points, dtype=np.float32), NestiConfig(), device=device, pidx=pidx, queries=queries, radius_grid=False)
+    return chain.back(select_cloud(cloud, ladder, slack, orient, viewpoint, orient_k, smooth))

@@ -11,6 +11,7 @@ import math
 import numpy as np
 
 from . import _lib
+from ._args import int_in as _int_in
 
 DEFAULT_K, DEFAULT_ITERS, DEFAULT_ANGLE, DEFAULT_FALLOFF = 16, 2, 45.0, 0.75
 MAX_ITERS = 64
@@ -18,12 +19,6 @@ MAX_COS = 0.999999                     # nesti_smooth_normals_nbr: cos_t in [0, 
 
 # k, iters, angle (degrees), falloff, and cos_t = cos(angle), computed once on the host
 Params = collections.namedtuple("Params", "k iters angle falloff cos_t")
-
-
-def _int_in(name, v, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
-        raise ValueError("%s must be an integer in %d .. %d: got %r" % (name, lo, hi, v))
-    return int(v)
 
 
 def _float_in(name, v, lo, hi, what):

@@ -293,9 +293,10 @@ def test_restatement_ties_duplicates_and_lost_rows():
 
 
 def test_downsample_none_leaves_an_estimator_untouched(monkeypatch):
-    """With ``downsample=None`` the helper is not entered and the estimator's arguments reach its preparation as they were given."""
+    """With no stage given no primitive of the preprocessing chain is entered and the estimator's arguments reach its preparation as
+    they were given."""
     import nesti_net_amd  # noqa: F401
-    from nesti_net_amd import downsample as ds, pca
+    from nesti_net_amd import denoise, downsample as ds, outliers, pca
     seen = {}
 
     def prepare(*args):
@@ -303,10 +304,12 @@ def test_downsample_none_leaves_an_estimator_untouched(monkeypatch):
         raise RuntimeError("stop here")
 
     def never(*a, **kw):
-        raise AssertionError("run_downsampled entered")
+        raise AssertionError("a stage was entered")
 
     monkeypatch.setattr(pca, "prepare_cloud", prepare)
-    monkeypatch.setattr(ds, "run_downsampled", never)
+    monkeypatch.setattr(ds, "voxel_downsample", never)
+    monkeypatch.setattr(outliers, "remove_outliers", never)
+    monkeypatch.setattr(denoise, "denoise_points", never)
     pts = np.zeros((10, 3), np.float32)
     with pytest.raises(RuntimeError, match="stop here"):
         pca.pca_normals(pts, knn=8, scale=0, orient_k=4)

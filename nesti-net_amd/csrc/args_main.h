@@ -79,6 +79,24 @@ static void ball_fit_refusals(Idx&& idx, At&& at) {
   refused(at(&cfg, cloud, N, NULL, M, r, 0, p, gws), "null query_xyz_dev", "positions: null positions");
 }
 
+// The lane switch of a list pass (nesti_debug_smooth_lanes, _denoise_lanes, _outlier_lanes): a value that is no lane group is
+// refused under the entry's name, 16, 32 and 64 are accepted, and 0 -- the default, set last -- too.
+static void lane_switch_refusals(int (*entry)(int), const char* name) {
+  char what[96];
+  const int bad_lanes[] = {-1, 1, 8, 48, 128};
+  for (int lanes : bad_lanes) {
+    snprintf(what, sizeof(what), "%s(%d): a lane group that is none", name, lanes);
+    refused(entry(lanes), "lanes must be", what);
+    refused(1, name, what);
+  }
+  const int good_lanes[] = {16, 32, 64, 0};
+  for (int lanes : good_lanes)
+    if (entry(lanes) != 0) {
+      printf("FAIL %s(%d): '%s'\n", name, lanes, nesti_last_error());
+      ++failures;
+    }
+}
+
 // prints "<name>: ok" or the number of failures; the value main() returns
 static int finish(const char* name) {
   if (failures) printf("%s: %d failure(s)\n", name, failures);

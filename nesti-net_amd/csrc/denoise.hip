@@ -21,8 +21,8 @@
 //    r2 = the largest d2 of the prefix; rad = sqrt(r2).
 //  3 CENTRE NORMAL.  v = (double)n_c / sqrt(q_c), component by component.
 //  4 SLOT i < n with neighbour j = nbr[i], n_j = normals_in[j] eligible (an ineligible one adds nothing), q_j like q_c:
-//      t: smoothing's step 3 -- dd = (n_c.x n_j.x + n_c.y n_j.y) + n_c.z n_j.z;  ca = |dd| / sqrt(q_c q_j);
-//      t = (ca - cos_t) / (1 - cos_t);  if not t > 0 the slot adds nothing (NaN included);  t = min(t, 1);
+//      t: smoothing's step 3, the one cone_weight of group_dev.h -- dd = (n_c.x n_j.x + n_c.y n_j.y) + n_c.z n_j.z;
+//      ca = |dd| / sqrt(q_c q_j);  t = (ca - cos_t) / (1 - cos_t);  if not t > 0 the slot adds nothing (NaN included);  t = min(t, 1);
 //      u = 1 - (falloff d2) / r2 if r2 > 0, else u = 1;
 //      h = (v.x dx + v.y dy) + v.z dz;  x = h / (sigma rad) if r2 > 0, else x = 0;  g = 1 / (1 + x x);
 //      a = (u t) g;  W = a a;  H += W h;  Wsum += W;  cnt += 1 (integer).
@@ -41,7 +41,8 @@
 // THE KERNEL.  The form of smooth_nbr_kernel: a dependent gather, list entry -> position (walk_list, which gives r2 before any weight
 // is formed) -> normal.  A slot's d2 and h stay in registers between the two walks (v needs the centre's normal alone), so the list
 // and the positions are read once.  A row is served by a GROUP of G lanes, the smallest of 16, 32 and 64 that holds k: 64 / G rows
-// per wave, four waves per workgroup; groups never meet and whole groups leave for q >= M.  No LDS, no scratch.
+// per wave, four waves per workgroup; groups never meet and whole groups leave for q >= M -- group_row, group_centre_lost and
+// group_nbr_row of nbr_dev.h, the very definitions smooth_nbr_kernel runs.  No LDS, no scratch.
 #include <string.h>
 
 #include <algorithm>
@@ -78,36 +79,19 @@ struct DenoiseParams {
 // would add the +0.0 of lanes without a slot: the bytes of the 64-lane statement.
 template <int G>
 __global__ __launch_bounds__(kThreads) void denoise_nbr_kernel(const DenoiseParams dp) {
-  static_assert(G == 16 || G == 32 || G == kWave, "a lane group");
   constexpr int kTrips = G == kWave ? kNbrTrips : 1;          // slots per lane
   const NbrParams& np = dp.np;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int sl = lane & (G - 1);                              // the lane within its group
-  const int q = G == kWave ? wave_row() : (int)(blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6)) * (kWave / G) + lane / G;
+  const GroupRow row = group_row<G>();
+  const int q = row.q, sl = row.sl;                           // sl: the lane within its group
   if (q >= np.p.M) return;                                    // whole groups leave: the shuffles below stay inside a group
   const float* centre = query_centre(np.p, q);                // a cloud point: there is no positions form
   const float cf0 = centre[0], cf1 = centre[1], cf2 = centre[2];
   const double cx = cf0, cy = cf1, cz = cf2;
   const float* nc = dp.normals_in + (centre - np.p.cloud);    // the normal of the same (clamped) cloud index
   const float ncf0 = nc[0], ncf1 = nc[1], ncf2 = nc[2];
-  // centre_lost (patches_dev.h) ties its argument to a scalar register: right for the wave's one row, not for a group's
-  const bool lost = G == kWave ? centre_lost(cf0, cf1, cf2) : !(finite_bits(cf0) && finite_bits(cf1) && finite_bits(cf2));
-  int j[kNbrTrips], ns[1];
-  if constexpr (G == kWave) {
-    nbr_row<1>(np, q, lane, lost, j, ns);
-  } else {                                                    // nbr_row for a group: k <= G, one trip
-    const int k = np.ks[0];
-    int bad = lost ? 0 : k;
-#pragma unroll
-    for (int t = 0; t < kNbrTrips; ++t) j[t] = 0;
-    if (sl < k) {
-      const int v = np.nbr[(size_t)q * np.K + sl];
-      if ((unsigned)v >= (unsigned)np.p.N) bad = sl;
-      else j[0] = v;
-    }
-    ns[0] = min(min(k, G), group_min<G>(bad));
-  }
-  const int n = eligible_normal(ncf0, ncf1, ncf2) ? ns[0] : 0;   // an ineligible centre normal walks nothing
+  int j[kNbrTrips];
+  const int prefix = group_nbr_row<G>(np, q, sl, group_centre_lost<G>(cf0, cf1, cf2), j);
+  const int n = eligible_normal(ncf0, ncf1, ncf2) ? prefix : 0;   // an ineligible centre normal walks nothing
   // ---- step 3: the centre's unit normal (n = 0: never used) ---------------------------------------------------------------------------
   const double ncx = ncf0, ncy = ncf1, ncz = ncf2;
   const double qc = knn_d2(ncx, ncy, ncz);
@@ -135,25 +119,17 @@ __global__ __launch_bounds__(kThreads) void denoise_nbr_kernel(const DenoisePara
     const int i = sl + t * kWave;
     if (i < n) {                                              // j[t] lies in [0, N): checked above
       const float* nj = dp.normals_in + (size_t)j[t] * 3;
-      const float f0 = nj[0], f1 = nj[1], f2 = nj[2];
-      if (eligible_normal(f0, f1, f2)) {
-        const double nx = f0, ny = f1, nz = f2;
-        const double qj = knn_d2(nx, ny, nz);
-        const double dd = (ncx * nx + ncy * ny) + ncz * nz;
-        const double ca = fabs(dd) / sqrt(qc * qj);
-        double tt = (ca - dp.cos_t) / span;
-        if (tt > 0.0) {                                       // false for NaN
-          tt = tt < 1.0 ? tt : 1.0;
-          const double u = r2 > 0.0 ? 1.0 - (dp.falloff * d2s[t]) / r2 : 1.0;
-          const double h = hs[t];
-          const double x = r2 > 0.0 ? h / hscale : 0.0;
-          const double g = 1.0 / (1.0 + x * x);
-          const double a = (u * tt) * g;
-          const double W = a * a;
-          H = H + W * h;
-          Wsum = Wsum + W;
-          ++cnt;
-        }
+      const ConeWeight c = cone_weight(ncx, ncy, ncz, qc, nj[0], nj[1], nj[2], dp.cos_t, span);
+      if (c.counts) {
+        const double u = cone_falloff(dp.falloff, d2s[t], r2);
+        const double h = hs[t];
+        const double x = r2 > 0.0 ? h / hscale : 0.0;
+        const double g = 1.0 / (1.0 + x * x);
+        const double a = (u * c.tt) * g;
+        const double W = a * a;
+        H = H + W * h;
+        Wsum = Wsum + W;
+        ++cnt;
       }
     }
   }
@@ -221,19 +197,12 @@ int nesti_denoise_points_nbr(const float* cloud_dev, int N, const float* normals
   dp.delta_out = delta_out_dev;
   dp.support_out = support_out_dev;
   dp.count_out = count_out_dev;
-  // the lane group: the smallest of 16, 32, 64 that holds k, or a wider one asked for (nesti_debug_denoise_lanes); the launch is one
-  // of waves, each serving 64 / G rows
-  const int asked = g_denoise_lanes.load(std::memory_order_relaxed);
-  const int G = std::max(asked, k <= 16 ? 16 : k <= 32 ? 32 : kWave);
-  if (G == 16) return launch_wave_rows(denoise_nbr_kernel<16>, dp, (M + 3) / 4, stream);
-  if (G == 32) return launch_wave_rows(denoise_nbr_kernel<32>, dp, (M + 1) / 2, stream);
-  return launch_wave_rows(denoise_nbr_kernel<kWave>, dp, M, stream);
+  // the lane group: the smallest of 16, 32, 64 that holds k, or a wider one asked for (nesti_debug_denoise_lanes)
+  return with_lane_group(k, g_denoise_lanes.load(std::memory_order_relaxed), [&](auto g) {
+    return launch_group_rows<decltype(g)::value>(denoise_nbr_kernel<decltype(g)::value>, dp, M, stream);
+  });
 }
 
-int nesti_debug_denoise_lanes(int lanes) {
-  if (lanes != 0 && lanes != 16 && lanes != 32 && lanes != kWave) NESTI_FAIL(std::string("nesti_debug_denoise_lanes: lanes must be 0, 16, 32 or 64"));
-  g_denoise_lanes.store(lanes, std::memory_order_relaxed);
-  return 0;
-}
+int nesti_debug_denoise_lanes(int lanes) { return set_lane_group("nesti_debug_denoise_lanes", g_denoise_lanes, lanes); }
 
 }  // extern "C"

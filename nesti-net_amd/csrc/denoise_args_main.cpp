@@ -64,14 +64,6 @@ int main() {
   }
   REFUSED("sigma", "M = 0 with a NaN sigma", p, N, p, NULL, 0, 0, p, K, 16, 0.7, 0.75, (double)NAN, 1.0, o);
   REFUSED("must not lie inside the cloud", "M = 0 with the output the cloud", p, N, p, NULL, 0, 0, p, K, 16, 0.7, 0.75, 0.5, 1.0, p);
-  // the lane switch
-  const int bad_lanes[] = {-1, 1, 8, 48, 128};
-  for (int lanes : bad_lanes) refused(nesti_debug_denoise_lanes(lanes), "nesti_debug_denoise_lanes", "a lane group that is none");
-  const int good_lanes[] = {16, 32, 64, 0};
-  for (int lanes : good_lanes)
-    if (nesti_debug_denoise_lanes(lanes) != 0) {
-      printf("FAIL nesti_debug_denoise_lanes(%d): '%s'\n", lanes, nesti_last_error());
-      ++failures;
-    }
+  lane_switch_refusals(nesti_debug_denoise_lanes, "nesti_debug_denoise_lanes");
   return finish("denoise_args");
 }

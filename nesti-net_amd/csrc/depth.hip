@@ -24,19 +24,17 @@
 // every product, quotient and sum below is rounded on its own: the CPU restatement (tests/_depth_fixture.py) predicts each bit
 #pragma clang fp contract(off)
 
+#include "compact_dev.h"   // kThreads, blocks_of (wave_dev.h); block_rank, compact_scan_kernel
+
 namespace nesti {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
-constexpr int kWaves = kThreads / kWave;
 constexpr long long kMaxPixels = 1ll << 26;
 constexpr unsigned long long kNoKey = ~0ull;
 
 struct DepthLayout {
   size_t cnt_valid, cnt_query, rank, keys, total;
 };
-inline size_t blocks_of(size_t n) { return (n + kThreads - 1) / kThreads; }
 inline DepthLayout depth_layout(size_t n) {
   DepthLayout L;
   size_t o = 0;
@@ -128,26 +126,7 @@ struct StridePixels {
   }
 };
 
-// ---- ordered compaction: count per block, one scan, scatter ------------------------------------------------------------------------
-// Position of a thread's element among the block's true predicates, and the block's total.  Every thread of the block calls it.
-__device__ __forceinline__ int block_rank(bool pred, int* total) {
-  __shared__ int wave_count[kWaves];
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  const unsigned long long b = __ballot(pred);
-  const int before = __popcll(b & ((1ull << lane) - 1ull));
-  if (lane == 0) wave_count[wave] = __popcll(b);
-  __syncthreads();
-  int off = 0, sum = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    const int c = wave_count[w];
-    if (w < wave) off += c;
-    sum += c;
-  }
-  *total = sum;
-  return off + before;
-}
-
+// ---- ordered compaction: count per block, one scan (compact_scan_kernel), scatter; block_rank and the scan: compact_dev.h -------------
 template <class P>
 __global__ __launch_bounds__(kThreads) void compact_count_kernel(Frame f, Cam c, int32_t* __restrict__ block_count) {
   const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
@@ -156,36 +135,6 @@ __global__ __launch_bounds__(kThreads) void compact_count_kernel(Frame f, Cam c,
   int total;
   block_rank(pred, &total);
   if (threadIdx.x == 0) block_count[blockIdx.x] = total;
-}
-
-// ONE workgroup: block_count[0 .. nb) -> exclusive prefix sums in place, the grand total to *total_out.  Loops when nb > kThreads.
-__global__ __launch_bounds__(kThreads) void compact_scan_kernel(int32_t* __restrict__ block_count, int nb, int32_t* __restrict__ total_out) {
-  __shared__ int wave_sum[kWaves];
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  int carry = 0;                                          // the same in every thread
-  for (int base = 0; base < nb; base += kThreads) {
-    const int i = base + (int)threadIdx.x;
-    const int v = i < nb ? block_count[i] : 0;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      const int o = __shfl_up(incl, d, kWave);
-      if (lane >= d) incl += o;
-    }
-    if (lane == kWave - 1) wave_sum[wave] = incl;
-    __syncthreads();
-    int off = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-      const int s = wave_sum[w];
-      if (w < wave) off += s;
-      sum += s;
-    }
-    if (i < nb) block_count[i] = carry + off + incl - v;
-    carry += sum;
-    __syncthreads();                                      // wave_sum is rewritten by the next chunk
-  }
-  if (threadIdx.x == 0) *total_out = carry;
 }
 
 template <class P>
@@ -335,8 +284,8 @@ int nesti_depth_to_cloud(const void* depth_dev, int depth_type, int H, int W, co
   const unsigned nb = grid_for(n);
   hipLaunchKernelGGL(compact_count_kernel<ValidPixels>, dim3(nb), dim3(kThreads), 0, st, f, c, cnt_valid);
   hipLaunchKernelGGL(compact_count_kernel<StridePixels>, dim3(nb), dim3(kThreads), 0, st, f, c, cnt_query);
-  hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(kThreads), 0, st, cnt_valid, (int)nb, counts_dev);
-  hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(kThreads), 0, st, cnt_query, (int)nb, counts_dev + 1);
+  hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(kThreads), 0, st, cnt_valid, (long long)nb, counts_dev);
+  hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(kThreads), 0, st, cnt_query, (long long)nb, counts_dev + 1);
   CloudOut co;
   co.xyz = xyz_dev; co.pix = pix_dev; co.rank = rank;
   hipLaunchKernelGGL(compact_scatter_kernel<ValidPixels>, dim3(nb), dim3(kThreads), 0, st, f, c, (const int32_t*)cnt_valid, co);

@@ -1,7 +1,8 @@
 // The walk of an untrusted neighbour list by one wave (DESIGN.md 2 "k-nearest neighbourhoods"), shared by the list kernels of knn.hip
 // (plane fit, quadric fit), by hough.hip, select.hip and robust.hip: the parameter block, the valid prefix of a row, the per-slot
-// differences and what every list entry refuses on the host.  One definition, so the prefix, d, d2 and r2_s of every list entry are
-// the same values.
+// differences and what every list entry refuses on the host -- and the same row served by a group of 16 or 32 lanes, for the list
+// passes of smooth.hip, denoise.hip and outlier.hip.  One definition, so the prefix, d, d2 and r2_s of every list entry are the same
+// values.
 //
 // For the including unit: include patches_dev.h first, then `#pragma clang fp contract(off)`, then pca_dev.h and this header -- every
 // product and sum below is rounded on its own.
@@ -106,6 +107,46 @@ __device__ __forceinline__ int nbr_row_upto(const NbrParams& np, int q, int lane
     }
   }
   return wave_min(bad);
+}
+
+// ---- a row by a GROUP of G lanes, G = 16, 32 or 64 (smooth.hip, denoise.hip, outlier.hip): 64 / G rows per wave, one per group -------
+// The row of this lane's group and the lane within it.  G = 64 is wave_row(): the row stays in a scalar register.  The caller lets
+// whole groups leave for q >= M, so every shuffle of the others stays inside a full group.
+struct GroupRow {
+  int q, sl;
+};
+template <int G>
+__device__ __forceinline__ GroupRow group_row() {
+  static_assert(G == 16 || G == 32 || G == kWave, "a lane group");
+  const int lane = threadIdx.x & (kWave - 1);
+  const int q = G == kWave ? wave_row() : (int)(blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6)) * (kWave / G) + lane / G;
+  return {q, lane & (G - 1)};
+}
+// centre_lost (patches_dev.h) ties its argument to a scalar register: right for the wave's one row, not for a group's
+template <int G>
+__device__ __forceinline__ bool group_centre_lost(float x, float y, float z) {
+  return G == kWave ? centre_lost(x, y, z) : !(finite_bits(x) && finite_bits(y) && finite_bits(z));
+}
+// nbr_row for a group: the slots of row q into j[] and min(ks[0], valid prefix), the same in every lane of the group.  G = 64 is
+// nbr_row<1> as it stands; a smaller group holds the whole list in one trip -- the host picks G >= ks[0] (with_lane_group, group_dev.h)
+template <int G>
+__device__ __forceinline__ int group_nbr_row(const NbrParams& np, int q, int sl, bool lost, int (&j)[kNbrTrips]) {
+  if constexpr (G == kWave) {
+    int ns[1];
+    nbr_row<1>(np, q, sl, lost, j, ns);
+    return ns[0];
+  } else {
+    const int k = np.ks[0];
+    int bad = lost ? 0 : k;
+#pragma unroll
+    for (int t = 0; t < kNbrTrips; ++t) j[t] = 0;
+    if (sl < k) {
+      const int v = np.nbr[(size_t)q * np.K + sl];
+      if ((unsigned)v >= (unsigned)np.p.N) bad = sl;
+      else j[0] = v;
+    }
+    return min(min(k, G), group_min<G>(bad));                 // k <= G; said so, the walk's trips beyond the first fall away
+  }
 }
 
 // body(slot, dx, dy, dz, d2) for the slots lane, lane + 64, ... below n of the list: the walk of the list kernels

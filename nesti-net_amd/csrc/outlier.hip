@@ -14,7 +14,7 @@
 //   kth_d2 = the largest d2 used where n_other == k, else +inf
 // The sum has the list fits' order: slot i is added in lane i mod 64, a lane's slots ascending from +0.0, the lanes meet in the xor
 // butterfly 32 .. 1.  Every term is >= +0, so a skipped slot and an idle lane change no bit -- which is why a row may be served by a
-// GROUP of 16, 32 or 64 lanes, the smallest that holds k + 1 (smooth.hip's scheme), with the bytes of the 64-lane statement.  A used
+// GROUP of 16, 32 or 64 lanes, the smallest that holds k + 1 (group_row of nbr_dev.h), with the bytes of the 64-lane statement.  A used
 // slot whose d2 is NaN (a cloud point with a NaN coordinate, in a list of the caller's) makes mean and kth_d2 the canonical quiet NaN
 // (0x7ff8000000000000); so does a centre with a non-finite coordinate, whose n_other is 0.
 //
@@ -26,7 +26,7 @@
 //
 // COMPACTION (nesti_outlier_compact).  A row is kept iff its score is finite and <= the threshold (a tie stays; NaN and +-inf leave).
 // Per-block counts (ballot / popcount in a wave, LDS across waves), one single-workgroup scan of the block counts, a scatter in row
-// order: the scheme of depth.hip, in a copy of this unit's own.  No atomics, no workgroup waits on another: kept_idx is ascending.
+// order: compact_dev.h, shared with depth.hip and voxel.hip.  No atomics, no workgroup waits on another: kept_idx is ascending.
 #include <string.h>
 
 #include <algorithm>
@@ -42,11 +42,12 @@
 
 #include "pca_dev.h"
 #include "nbr_dev.h"
+#include "group_dev.h"
+#include "compact_dev.h"
 
 namespace nesti {
 namespace {
 
-constexpr int kWaves = kThreads / kWave;
 constexpr unsigned long long kQuietNaN = 0x7ff8000000000000ull;
 
 __device__ __forceinline__ bool finite_bits64(double v) {
@@ -62,58 +63,23 @@ struct ScoreParams {
   int32_t* n_other_out;               // [M] or NULL
 };
 
-// the reductions of a group of G lanes (G = 64: wave_sum / wave_min / wave_max of pca_dev.h, offset for offset)
-template <int G>
-__device__ __forceinline__ double group_sum(double v) {
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) v = v + __shfl_xor(v, off, kWave);
-  return v;
-}
-template <int G>
-__device__ __forceinline__ int group_min(int v) {
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, kWave));
-  return v;
-}
-template <int G>
-__device__ __forceinline__ double group_max(double v) {
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, kWave));
-  return v;
-}
-
 // G = 64: one row per wave.  G = 16, 32 (k + 1 <= G): 64 / G rows per wave, one per group of G lanes; a lane holds at most one slot and
 // the butterfly of the group is the tail (offsets G / 2, .., 1) of the wave's, whose head would add the +0.0 of lanes without a slot.
+// The group's row and list: group_row, group_centre_lost, group_nbr_row (nbr_dev.h), shared with smooth.hip and denoise.hip.
 template <int G>
 __global__ __launch_bounds__(kThreads) void outlier_scores_kernel(const ScoreParams sp) {
-  static_assert(G == 16 || G == 32 || G == kWave, "a lane group");
   const NbrParams& np = sp.np;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int sl = lane & (G - 1);                              // the lane within its group
-  const int q = G == kWave ? wave_row() : (int)(blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6)) * (kWave / G) + lane / G;
+  const GroupRow row = group_row<G>();
+  const int q = row.q, sl = row.sl;                           // sl: the lane within its group
   if (q >= np.p.M) return;                                    // whole groups leave: the shuffles below stay inside a group
   const int own = np.p.row0 + q;                              // in [0, N): refused on the host otherwise
   const float* centre = np.p.cloud + (size_t)own * 3;
   const float cf0 = centre[0], cf1 = centre[1], cf2 = centre[2];
   const double cx = cf0, cy = cf1, cz = cf2;
-  // centre_lost (patches_dev.h) ties its argument to a scalar register: right for the wave's one row, not for a group's
-  const bool lost = G == kWave ? centre_lost(cf0, cf1, cf2) : !(finite_bits(cf0) && finite_bits(cf1) && finite_bits(cf2));
+  const bool lost = group_centre_lost<G>(cf0, cf1, cf2);
   const int k = sp.k;
-  int j[kNbrTrips], ns[1];
-  if constexpr (G == kWave) {
-    nbr_row<1>(np, q, lane, lost, j, ns);
-  } else {                                                    // nbr_row for a group: k + 1 <= G, one trip
-    int bad = lost ? 0 : k + 1;
-#pragma unroll
-    for (int t = 0; t < kNbrTrips; ++t) j[t] = 0;
-    if (sl < k + 1) {
-      const int v = np.nbr[(size_t)q * np.K + sl];
-      if ((unsigned)v >= (unsigned)np.p.N) bad = sl;
-      else j[0] = v;
-    }
-    ns[0] = min(k + 1, group_min<G>(bad));
-  }
-  const int P = ns[0];
+  int j[kNbrTrips];
+  const int P = group_nbr_row<G>(np, q, sl, lost, j);         // min(k + 1, valid prefix): np.ks[0] = k + 1
   // the first slot below P that holds the row's own index (kNone: absent)
   constexpr int kNone = NESTI_KNN_MAX_K;
   int self = kNone;
@@ -156,7 +122,6 @@ std::atomic<int> g_outlier_lanes{0};
 struct OutlierLayout {
   size_t part_sum, part_cnt, block_cnt, total;
 };
-inline size_t blocks_of(size_t n) { return (n + kThreads - 1) / kThreads; }
 inline OutlierLayout outlier_layout(size_t n) {
   OutlierLayout L;
   size_t o = 0;
@@ -239,7 +204,7 @@ __global__ __launch_bounds__(kThreads) void outlier_final_kernel(const double* _
   }
 }
 
-// ---- ordered compaction: count per block, one scan, scatter (depth.hip's scheme) -----------------------------------------------------------
+// ---- ordered compaction: count per block, one scan, scatter (block_rank and compact_scan_kernel: compact_dev.h) ----------------------
 struct CompactParams {
   const float* cloud;                 // [N, 3]; NULL with xyz_out NULL
   const double* scores;               // [N]
@@ -259,60 +224,11 @@ __device__ __forceinline__ bool row_kept(const CompactParams& p, long long i) {
   return finite_bits64(s) && s <= thr;
 }
 
-// Position of a thread's element among the block's true predicates, and the block's total.  Every thread of the block calls it.
-__device__ __forceinline__ int block_rank(bool pred, int* total) {
-  __shared__ int wave_count[kWaves];
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  const unsigned long long b = __ballot(pred);
-  const int before = __popcll(b & ((1ull << lane) - 1ull));
-  if (lane == 0) wave_count[wave] = __popcll(b);
-  __syncthreads();
-  int off = 0, sum = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    const int c = wave_count[w];
-    if (w < wave) off += c;
-    sum += c;
-  }
-  *total = sum;
-  return off + before;
-}
-
 __global__ __launch_bounds__(kThreads) void outlier_count_kernel(const CompactParams p, int32_t* __restrict__ block_count) {
   const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
   int total;
   block_rank(row_kept(p, i), &total);
   if (threadIdx.x == 0) block_count[blockIdx.x] = total;
-}
-
-// ONE workgroup: block_count[0 .. nb) -> exclusive prefix sums in place, the grand total to *total_out.  Loops when nb > kThreads.
-__global__ __launch_bounds__(kThreads) void outlier_scan_kernel(int32_t* __restrict__ block_count, int nb, int32_t* __restrict__ total_out) {
-  __shared__ int wave_total[kWaves];
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  int carry = 0;                                            // the same in every thread
-  for (int base = 0; base < nb; base += kThreads) {
-    const int i = base + (int)threadIdx.x;
-    const int v = i < nb ? block_count[i] : 0;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      const int o = __shfl_up(incl, d, kWave);
-      if (lane >= d) incl += o;
-    }
-    if (lane == kWave - 1) wave_total[wave] = incl;
-    __syncthreads();
-    int off = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-      const int s = wave_total[w];
-      if (w < wave) off += s;
-      sum += s;
-    }
-    if (i < nb) block_count[i] = carry + off + incl - v;
-    carry += sum;
-    __syncthreads();                                        // wave_total is rewritten by the next chunk
-  }
-  if (threadIdx.x == 0) *total_out = carry;
 }
 
 __global__ __launch_bounds__(kThreads) void outlier_scatter_kernel(const CompactParams p, const int32_t* __restrict__ block_start) {
@@ -357,20 +273,13 @@ int nesti_outlier_scores_nbr(const float* cloud_dev, int N, int query_row0, int 
   sp.mean_out = mean_out_dev;
   sp.kth_out = kth_d2_out_dev;
   sp.n_other_out = n_other_out_dev;
-  // the lane group: the smallest of 16, 32, 64 that holds k + 1, or a wider one asked for (nesti_debug_outlier_lanes); the launch is
-  // one of waves, each serving 64 / G rows
-  const int asked = g_outlier_lanes.load(std::memory_order_relaxed);
-  const int G = std::max(asked, k + 1 <= 16 ? 16 : k + 1 <= 32 ? 32 : kWave);
-  if (G == 16) return launch_wave_rows(outlier_scores_kernel<16>, sp, (M + 3) / 4, stream);
-  if (G == 32) return launch_wave_rows(outlier_scores_kernel<32>, sp, (M + 1) / 2, stream);
-  return launch_wave_rows(outlier_scores_kernel<kWave>, sp, M, stream);
+  // the lane group: the smallest of 16, 32, 64 that holds k + 1, or a wider one asked for (nesti_debug_outlier_lanes)
+  return with_lane_group(k + 1, g_outlier_lanes.load(std::memory_order_relaxed), [&](auto g) {
+    return launch_group_rows<decltype(g)::value>(outlier_scores_kernel<decltype(g)::value>, sp, M, stream);
+  });
 }
 
-int nesti_debug_outlier_lanes(int lanes) {
-  if (lanes != 0 && lanes != 16 && lanes != 32 && lanes != kWave) NESTI_FAIL(std::string("nesti_debug_outlier_lanes: lanes must be 0, 16, 32 or 64"));
-  g_outlier_lanes.store(lanes, std::memory_order_relaxed);
-  return 0;
-}
+int nesti_debug_outlier_lanes(int lanes) { return set_lane_group("nesti_debug_outlier_lanes", g_outlier_lanes, lanes); }
 
 int nesti_outlier_threshold(const double* scores_dev, int M, double std_ratio, double* stats_out_dev, void* ws_dev, size_t ws_bytes,
                             void* stream) {
@@ -417,7 +326,7 @@ int nesti_outlier_compact(const float* cloud_dev, int N, const double* scores_de
   const int nb = (int)blocks_of((size_t)N);
   const int tok = prof_begin(NESTI_PROF_PATCHES, st);
   hipLaunchKernelGGL(outlier_count_kernel, dim3(nb), dim3(kThreads), 0, st, p, block_cnt);
-  hipLaunchKernelGGL(outlier_scan_kernel, dim3(1), dim3(kThreads), 0, st, block_cnt, nb, n_kept_out_dev);
+  hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(kThreads), 0, st, block_cnt, (long long)nb, n_kept_out_dev);
   hipLaunchKernelGGL(outlier_scatter_kernel, dim3(nb), dim3(kThreads), 0, st, p, (const int32_t*)block_cnt);
   prof_end(NESTI_PROF_PATCHES, tok, st);
   NESTI_CHECK_HIP(hipGetLastError());

@@ -83,17 +83,6 @@ int main() {
   REFUSED(COMPACT, "workspace too small", "compact: device thr, NaN host thr, short workspace", p, N, p, p, (double)NAN, p, p, p, ws - 1);
 
   // ---- nesti_debug_outlier_lanes -----------------------------------------------------------------------------------------------------------
-  name = "nesti_debug_outlier_lanes";
-  const int bad_lanes[] = {-1, 1, 8, 48, 128};
-  for (int lanes : bad_lanes) {
-    REFUSED(nesti_debug_outlier_lanes, "lanes must be", "lanes: another value", lanes);
-  }
-  const int good_lanes[] = {16, 32, 64, 0};
-  for (int lanes : good_lanes) {
-    if (nesti_debug_outlier_lanes(lanes) != 0) {
-      printf("FAIL lanes: %d is accepted\n", lanes);
-      ++failures;
-    }
-  }
+  lane_switch_refusals(nesti_debug_outlier_lanes, "nesti_debug_outlier_lanes");
   return finish("outlier_args");
 }

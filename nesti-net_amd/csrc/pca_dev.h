@@ -8,35 +8,12 @@
 #pragma once
 #include "patches_dev.h"
 #include "pca_eig.h"
+#include "wave_dev.h"      // kThreads, kWave, kRowsPerBlock; wave_sum / wave_min / wave_max: the 64-lane case of group_sum / _min / _max
 
 namespace nesti {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
-constexpr int kRowsPerBlock = kThreads / kWave;
 constexpr int kSums = 9;              // sum d (3), sum d d^T (6: xx xy xz yy yz zz)
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v = v + __shfl_xor(v, off, kWave);
-  return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, kWave));
-  return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, kWave));
-  return v;
-}
 
 // the row of this wave (the same in every lane: said so, and the centre and its tests live in scalar registers); a wave beyond the
 // last row gets M or more and leaves whole, so the shuffles of the others see full waves

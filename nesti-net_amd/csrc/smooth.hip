@@ -36,7 +36,7 @@
 // k = 16 .. 32 one wave per row would leave most lanes without a slot, so a row is served by a GROUP of G lanes, the smallest of 16, 32
 // and 64 that holds k: 64 / G rows per wave, four waves per workgroup; groups never meet (every shuffle stays inside one) and whole
 // groups leave for q >= M.  G = 64 is the one-wave-per-row form of pca_nbr_kernel, over nbr_row and walk_list as they stand; a smaller
-// group forms the prefix of its one trip itself and walks it with the same walk_list.  No LDS, no scratch.
+// group forms the prefix of its one trip itself (group_nbr_row, nbr_dev.h) and walks it with the same walk_list.  No LDS, no scratch.
 #include <string.h>
 
 #include <algorithm>
@@ -66,43 +66,26 @@ struct SmoothParams {
   int32_t* count_out;                 // [M] or NULL
 };
 
-// eligible_normal and the reductions of a group of G lanes (group_sum / group_min / group_max): group_dev.h
+// eligible_normal, cone_weight and the host side of a lane group: group_dev.h; its row and list: nbr_dev.h; its reductions: wave_dev.h
 
 // G = 64: one row per wave.  G = 16, 32 (k <= G): 64 / G rows per wave, one per group of G lanes; a lane holds at most one slot, its
 // partial sums are 0 + the slot's terms, and the butterfly of the group is the tail (offsets G / 2, ..., 1) of the wave's, whose head
 // would add the +0.0 of lanes without a slot: the bytes of the 64-lane statement.
 template <int G>
 __global__ __launch_bounds__(kThreads) void smooth_nbr_kernel(const SmoothParams sp) {
-  static_assert(G == 16 || G == 32 || G == kWave, "a lane group");
   constexpr int kTrips = G == kWave ? kNbrTrips : 1;          // slots per lane
   const NbrParams& np = sp.np;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int sl = lane & (G - 1);                              // the lane within its group
-  const int q = G == kWave ? wave_row() : (int)(blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6)) * (kWave / G) + lane / G;
+  const GroupRow row = group_row<G>();
+  const int q = row.q, sl = row.sl;                           // sl: the lane within its group
   if (q >= np.p.M) return;                                    // whole groups leave: the shuffles below stay inside a group
   const float* centre = query_centre(np.p, q);                // a cloud point: there is no positions form
   const float cf0 = centre[0], cf1 = centre[1], cf2 = centre[2];
   const double cx = cf0, cy = cf1, cz = cf2;
   const float* nc = sp.normals_in + (centre - np.p.cloud);    // the normal of the same (clamped) cloud index
   const float ncf0 = nc[0], ncf1 = nc[1], ncf2 = nc[2];
-  // centre_lost (patches_dev.h) ties its argument to a scalar register: right for the wave's one row, not for a group's
-  const bool lost = G == kWave ? centre_lost(cf0, cf1, cf2) : !(finite_bits(cf0) && finite_bits(cf1) && finite_bits(cf2));
-  int j[kNbrTrips], ns[1];
-  if constexpr (G == kWave) {
-    nbr_row<1>(np, q, lane, lost, j, ns);
-  } else {                                                    // nbr_row for a group: k <= G, one trip
-    const int k = np.ks[0];
-    int bad = lost ? 0 : k;
-#pragma unroll
-    for (int t = 0; t < kNbrTrips; ++t) j[t] = 0;
-    if (sl < k) {
-      const int v = np.nbr[(size_t)q * np.K + sl];
-      if ((unsigned)v >= (unsigned)np.p.N) bad = sl;
-      else j[0] = v;
-    }
-    ns[0] = min(min(k, G), group_min<G>(bad));
-  }
-  const int n = eligible_normal(ncf0, ncf1, ncf2) ? ns[0] : 0;   // an ineligible centre normal walks nothing
+  int j[kNbrTrips];
+  const int prefix = group_nbr_row<G>(np, q, sl, group_centre_lost<G>(cf0, cf1, cf2), j);
+  const int n = eligible_normal(ncf0, ncf1, ncf2) ? prefix : 0;   // an ineligible centre normal walks nothing
   // ---- step 2: d2 of every slot, kept for step 3, and r2 -----------------------------------------------------------------------------
   double d2s[kTrips], r2 = 0.0;
 #pragma unroll
@@ -125,23 +108,15 @@ __global__ __launch_bounds__(kThreads) void smooth_nbr_kernel(const SmoothParams
     const int i = sl + t * kWave;
     if (i < n) {                                              // j[t] lies in [0, N): checked above
       const float* nj = sp.normals_in + (size_t)j[t] * 3;
-      const float f0 = nj[0], f1 = nj[1], f2 = nj[2];
-      if (eligible_normal(f0, f1, f2)) {
-        const double nx = f0, ny = f1, nz = f2;
-        const double qj = knn_d2(nx, ny, nz);
-        const double d = (ncx * nx + ncy * ny) + ncz * nz;
-        const double ca = fabs(d) / sqrt(qc * qj);
-        double tt = (ca - sp.cos_t) / span;
-        if (tt > 0.0) {                                       // false for NaN
-          tt = tt < 1.0 ? tt : 1.0;
-          const double u = r2 > 0.0 ? 1.0 - (sp.falloff * d2s[t]) / r2 : 1.0;
-          const double W = (u * u) * (tt * tt);
-          double g = W / sqrt(qj);
-          if (d < 0.0) g = -g;
-          X = X + g * nx; Y = Y + g * ny; Z = Z + g * nz;
-          Wsum = Wsum + W;
-          ++cnt;
-        }
+      const ConeWeight c = cone_weight(ncx, ncy, ncz, qc, nj[0], nj[1], nj[2], sp.cos_t, span);
+      if (c.counts) {
+        const double u = cone_falloff(sp.falloff, d2s[t], r2);
+        const double W = (u * u) * (c.tt * c.tt);
+        double g = W / sqrt(c.qj);
+        if (c.dd < 0.0) g = -g;
+        X = X + g * c.nx; Y = Y + g * c.ny; Z = Z + g * c.nz;
+        Wsum = Wsum + W;
+        ++cnt;
       }
     }
   }
@@ -193,19 +168,12 @@ int nesti_smooth_normals_nbr(const float* cloud_dev, int N, const float* normals
   sp.normals_out = normals_out_dev;
   sp.support_out = support_out_dev;
   sp.count_out = count_out_dev;
-  // the lane group: the smallest of 16, 32, 64 that holds k, or a wider one asked for (nesti_debug_smooth_lanes); the launch is one
-  // of waves, each serving 64 / G rows
-  const int asked = g_smooth_lanes.load(std::memory_order_relaxed);
-  const int G = std::max(asked, k <= 16 ? 16 : k <= 32 ? 32 : kWave);
-  if (G == 16) return launch_wave_rows(smooth_nbr_kernel<16>, sp, (M + 3) / 4, stream);
-  if (G == 32) return launch_wave_rows(smooth_nbr_kernel<32>, sp, (M + 1) / 2, stream);
-  return launch_wave_rows(smooth_nbr_kernel<kWave>, sp, M, stream);
+  // the lane group: the smallest of 16, 32, 64 that holds k, or a wider one asked for (nesti_debug_smooth_lanes)
+  return with_lane_group(k, g_smooth_lanes.load(std::memory_order_relaxed), [&](auto g) {
+    return launch_group_rows<decltype(g)::value>(smooth_nbr_kernel<decltype(g)::value>, sp, M, stream);
+  });
 }
 
-int nesti_debug_smooth_lanes(int lanes) {
-  if (lanes != 0 && lanes != 16 && lanes != 32 && lanes != kWave) NESTI_FAIL(std::string("nesti_debug_smooth_lanes: lanes must be 0, 16, 32 or 64"));
-  g_smooth_lanes.store(lanes, std::memory_order_relaxed);
-  return 0;
-}
+int nesti_debug_smooth_lanes(int lanes) { return set_lane_group("nesti_debug_smooth_lanes", g_smooth_lanes, lanes); }
 
 }  // extern "C"

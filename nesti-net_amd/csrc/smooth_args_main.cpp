@@ -1,6 +1,6 @@
 // Stand-alone driver of the normal-smoothing entry's host side (smooth.hip): every argument refusal of nesti_smooth_normals_nbr --
 // those of the list fits, the null input normals, the ranges of k, cos_t and falloff, and the output that is the input -- all of which
-// return before any device call.  Built and run by `make asan-smooth` against the AddressSanitizer build of the library.
+// return before any device call, and the lane switch.  Built and run by `make asan-smooth` against the AddressSanitizer build of the library.
 #include "args_main.h"
 
 int main() {
@@ -48,5 +48,6 @@ int main() {
   }
   REFUSED("cos_t", "M = 0 with a NaN cos_t", p, N, p, NULL, 0, 0, p, K, 16, (double)NAN, 0.75, o);
   REFUSED("must not be normals_in_dev", "M = 0 with the output the input", p, N, p, NULL, 0, 0, p, K, 16, 0.7, 0.75, p);
+  lane_switch_refusals(nesti_debug_smooth_lanes, "nesti_debug_smooth_lanes");
   return finish("smooth_args");
 }

@@ -26,7 +26,7 @@
 // np.argsort(keys & mask, kind="stable").
 //
 // REDUCE.  Heads: sorted position i starts a voxel when key[i] != key[i - 1] and key[i] != lost_key; ordered compaction by count / one
-// single-workgroup scan / scatter (the scheme of outlier.hip and depth.hip, in a copy of this unit's own) gives V, every voxel's first
+// single-workgroup scan / scatter (compact_dev.h, shared with outlier.hip and depth.hip) gives V, every voxel's first
 // position, count and key, and voxel_of[idx[i]].  Centroid: the voxel's rows come in ascending index (stability); row number s adds
 // d_a = (double)p_a - origin_a in lane s mod 64, a lane's slots ascending from +0.0, the lanes meet in the xor butterfly 32 .. 1 (the
 // list fits' statement); c_a = origin_a + S_a / (double)count, rounded to f32 once.  An idle lane holds +0.0 and changes no bit, so a
@@ -44,21 +44,16 @@
 // every product, quotient and sum below is rounded on its own: the CPU restatement (tests/_voxel_fixture.py) predicts every bit
 #pragma clang fp contract(off)
 
+#include "compact_dev.h"   // kThreads, kWave, kWaves, blocks_of, group_sum (wave_dev.h); block_rank, block_scan, compact_scan_kernel
+
 namespace nesti {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
-constexpr int kWaves = kThreads / kWave;
 constexpr int kDigits = 256;
 constexpr int kSortItems = 4;                       // keys per thread and pass
 constexpr int kSortTile = kThreads * kSortItems;    // keys per workgroup and pass
-constexpr int kScanPer = 16;                        // entries per thread and trip of a scan
-constexpr int kScanChunk = kThreads * kScanPer;     // table entries a workgroup scans at the first level of the sort's scan
 constexpr int kGroup = 16;                          // lanes that serve a voxel of at most kGroupMax rows
 constexpr int kGroupMax = 256;
-
-inline size_t blocks_of(size_t n, size_t per) { return (n + per - 1) / per; }
 
 struct VoxelLayout {
   size_t keys, idx, hist, chunk, block_cnt, first, total;
@@ -70,7 +65,7 @@ inline VoxelLayout voxel_layout(size_t n) {
   L.idx = o; o += align_up(n * 4, 256);
   L.hist = o; o += align_up(blocks_of(n, kSortTile) * kDigits * 4, 256);            // [256, blocks] digit-major
   L.chunk = o; o += align_up(blocks_of(blocks_of(n, kSortTile) * kDigits, kScanChunk) * 4, 256);   // the table's chunk totals
-  L.block_cnt = o; o += align_up(blocks_of(n, kThreads) * 4, 256);                  // the reduce: heads per block
+  L.block_cnt = o; o += align_up(blocks_of(n) * 4, 256);                  // the reduce: heads per block
   L.first = o; o += align_up((n + 1) * 4, 256);                                     // the reduce: first sorted position of voxel v; [V] = the live rows
   L.total = o;
   return L;
@@ -149,60 +144,8 @@ __global__ __launch_bounds__(kThreads) void sort_hist_kernel(const SortPass p) {
   p.hist[(size_t)threadIdx.x * p.nb + blockIdx.x] = sum;
 }
 
-// The exclusive prefix sums of the kThreads * kScanPer values a workgroup holds, kScanPer consecutive ones per thread, in place; returns
-// their total, the same in every thread.  Every thread of the block calls it; a second call needs a barrier first.
-__device__ __forceinline__ int block_scan(int (&e)[kScanPer]) {
-  __shared__ int wave_total[kWaves];
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  int sum = 0;
-#pragma unroll
-  for (int j = 0; j < kScanPer; ++j) sum += e[j];
-  int incl = sum;
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const int o = __shfl_up(incl, d, kWave);
-    if (lane >= d) incl += o;
-  }
-  if (lane == kWave - 1) wave_total[wave] = incl;
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    const int s = wave_total[w];
-    if (w < wave) off += s;
-    tot += s;
-  }
-  int run = off + incl - sum;
-#pragma unroll
-  for (int j = 0; j < kScanPer; ++j) {
-    const int x = e[j];
-    e[j] = run;
-    run += x;
-  }
-  return tot;
-}
-
-// ONE workgroup: v[0 .. n) -> exclusive prefix sums in place, the grand total to *total_out (or nowhere).  kScanPer consecutive
-// entries per thread and trip; the sums stay below 2^31 (they count rows).
-__global__ __launch_bounds__(kThreads) void voxel_scan_kernel(int32_t* __restrict__ v, long long n, int32_t* __restrict__ total_out) {
-  int carry = 0;                                            // the same in every thread
-  for (long long base = 0; base < n; base += kScanChunk) {
-    const long long i0 = base + (long long)threadIdx.x * kScanPer;
-    int e[kScanPer];
-#pragma unroll
-    for (int j = 0; j < kScanPer; ++j) e[j] = i0 + j < n ? v[i0 + j] : 0;
-    const int tot = block_scan(e);
-#pragma unroll
-    for (int j = 0; j < kScanPer; ++j)
-      if (i0 + j < n) v[i0 + j] = carry + e[j];
-    carry += tot;
-    __syncthreads();                                        // block_scan's LDS is rewritten by the next trip
-  }
-  if (total_out && threadIdx.x == 0) *total_out = carry;
-}
-
-// The first level of the sort's scan: workgroup b scans entries [b kScanChunk, (b + 1) kScanChunk) of v[0 .. n) in place and leaves
-// their total in chunk_total[b]
+// The first level of the sort's scan, over block_scan (compact_dev.h): workgroup b scans entries [b kScanChunk, (b + 1) kScanChunk)
+// of v[0 .. n) in place and leaves their total in chunk_total[b]
 __global__ __launch_bounds__(kThreads) void sort_scan_chunks_kernel(int32_t* __restrict__ v, long long n, int32_t* __restrict__ chunk_total) {
   const long long i0 = (long long)blockIdx.x * kScanChunk + (long long)threadIdx.x * kScanPer;
   int e[kScanPer];
@@ -298,25 +241,6 @@ __device__ __forceinline__ bool is_head(const ReduceParams& p, long long i) {
   return k != p.lost && (i == 0 || k != p.keys[i - 1]);
 }
 
-// Position of a thread's element among the block's true predicates, and the block's total.  Every thread of the block calls it.
-__device__ __forceinline__ int block_rank(bool pred, int* total) {
-  __shared__ int wave_count[kWaves];
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-  const unsigned long long b = __ballot(pred);
-  const int before = __popcll(b & ((1ull << lane) - 1ull));
-  if (lane == 0) wave_count[wave] = __popcll(b);
-  __syncthreads();
-  int off = 0, sum = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    const int c = wave_count[w];
-    if (w < wave) off += c;
-    sum += c;
-  }
-  *total = sum;
-  return off + before;
-}
-
 __global__ __launch_bounds__(kThreads) void voxel_count_kernel(const ReduceParams p, int32_t* __restrict__ block_count) {
   const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
   int total;
@@ -343,14 +267,6 @@ __global__ __launch_bounds__(kThreads) void voxel_heads_kernel(const ReduceParam
     const int32_t row = p.idx[i];
     if ((unsigned)row < (unsigned)p.N) p.voxel_of_out[row] = lost ? -1 : before + (head ? 1 : 0) - 1;
   }
-}
-
-// the tail of the wave's xor butterfly inside a group of G lanes
-template <int G>
-__device__ __forceinline__ double group_sum(double v) {
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) v = v + __shfl_xor(v, off, kWave);
-  return v;
 }
 
 // One voxel by a group of G lanes (sl: the lane within it): G = 64 is the statement; G = 16 holds the four lanes sl, sl + 16, sl + 32,
@@ -488,7 +404,7 @@ int nesti_voxel_keys(const float* cloud_dev, int N, const double* origin, const 
   }
   hipStream_t st = (hipStream_t)stream;
   const int tok = prof_begin(NESTI_PROF_PATCHES, st);
-  hipLaunchKernelGGL(voxel_keys_kernel, dim3((unsigned)blocks_of((size_t)N, kThreads)), dim3(kThreads), 0, st, p);
+  hipLaunchKernelGGL(voxel_keys_kernel, dim3((unsigned)blocks_of((size_t)N)), dim3(kThreads), 0, st, p);
   prof_end(NESTI_PROF_PATCHES, tok, st);
   NESTI_CHECK_HIP(hipGetLastError());
   return 0;
@@ -528,7 +444,7 @@ int nesti_sort_pairs(const uint64_t* keys_in_dev, int N, int key_bits, uint64_t*
     p.mask = (1u << bits) - 1u;
     hipLaunchKernelGGL(sort_hist_kernel, dim3(nb), dim3(kThreads), 0, st, p);
     hipLaunchKernelGGL(sort_scan_chunks_kernel, dim3(n_chunks), dim3(kThreads), 0, st, p.hist, entries, chunk);
-    hipLaunchKernelGGL(voxel_scan_kernel, dim3(1), dim3(kThreads), 0, st, chunk, (long long)n_chunks, (int32_t*)nullptr);
+    hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(kThreads), 0, st, chunk, (long long)n_chunks, (int32_t*)nullptr);
     hipLaunchKernelGGL(sort_scatter_kernel, dim3(nb), dim3(kThreads), 0, st, p);
     p.keys_in = p.keys_out;
     p.idx_in = p.idx_out;
@@ -557,10 +473,10 @@ int nesti_voxel_reduce(const float* cloud_dev, int N, const uint64_t* sorted_key
   p.centroid_out = centroid_out_dev; p.rep_out = rep_out_dev; p.count_out = count_out_dev;
   p.key_out = (unsigned long long*)key_out_dev; p.voxel_of_out = voxel_of_out_dev;
   p.n_voxels = n_voxels_out_dev; p.first = (int32_t*)(ws + L.first);
-  const int nb = (int)blocks_of((size_t)N, kThreads);
+  const int nb = (int)blocks_of((size_t)N);
   const int tok = prof_begin(NESTI_PROF_PATCHES, st);
   hipLaunchKernelGGL(voxel_count_kernel, dim3(nb), dim3(kThreads), 0, st, p, block_cnt);
-  hipLaunchKernelGGL(voxel_scan_kernel, dim3(1), dim3(kThreads), 0, st, block_cnt, (long long)nb, n_voxels_out_dev);
+  hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(kThreads), 0, st, block_cnt, (long long)nb, n_voxels_out_dev);
   hipLaunchKernelGGL(voxel_heads_kernel, dim3(nb), dim3(kThreads), 0, st, p, (const int32_t*)block_cnt);
   if (centroid_out_dev || rep_out_dev || count_out_dev) {
     // a voxel per group of 16 lanes, over the N voxels there may be; the groups beyond V leave at once

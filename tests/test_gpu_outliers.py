@@ -14,6 +14,8 @@ pytestmark = pytest.mark.gpu
 
 K = 256
 SIZES = (1, 2, 255, 256, 257, 65535, 65536, 65537, 65536 + 257)
+# the compaction's: a trip of the kept scan covers 256 x 16 block counts of 256 rows -- the smallest sizes that take one full trip and two
+COMPACT_SIZES = SIZES + (1048576, 1048577)
 _state = {}
 
 
@@ -239,7 +241,7 @@ def _compact(cloud_t, sc_t, thr, on_device):
             "untouched": (xyz[n:] == 7.0).all() and (kept_idx[n:] == -7).all()}
 
 
-@pytest.mark.parametrize("M", SIZES)
+@pytest.mark.parametrize("M", COMPACT_SIZES)
 def test_compaction_equals_the_restatement(M, gpu_device):
     """4.  Patterns all / none / alternating / only the first / only the last / random; a tie on the threshold is kept, NaN and +inf are
     removed; the threshold on the device and on the host; every output, a -0.0 coordinate among them; nothing beyond n_kept is written."""

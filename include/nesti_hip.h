@@ -269,9 +269,52 @@ typedef struct {
   uint64_t pairs;
   uint64_t widened, widen_events;
   float tau_eff;
+  /* recheck stage 2 (NESTI_F16X8C, below); all zero for NESTI_F16X3C */
+  int stage2;                       /* 1: forward calls run it (format 6, not switched off) */
+  uint64_t stage2_rows, stage2_decided, stage2_residual;
+  float max_margin_err2, tau2, tau2_eff;
+  double sum_sq_pair_err2;
+  uint64_t pairs2;
+  uint64_t stage2_widened, stage2_dropped;
 } nesti_cascade_stats_t;
 int nesti_model_set_gate_margin(nesti_model_t* m, float tau);
 int nesti_model_cascade_stats(const nesti_model_t* m, nesti_cascade_stats_t* out, int reset, void* stream);
+/* ---- NESTI_F16X8C: recheck stage 2 ------------------------------------------------------------------------------------
+ * The rows the filter flags (`rechecked` above) are first decided by the gating net with its six k^3 tap layers at 8^3 in the
+ * block-scaled FP6 cross-term form the experts' tap layers run (NESTI_DEBUG_FORM_X6; the planes come from the blocks' 1x1x1
+ * launches) -- every other layer keeps the f16x3 form.  A row whose stage-2 top-2 logit margin is at least
+ *     tau2_eff = max(tau2, NESTI_GATE_WIDEN x max_margin_err2 measured since the last reset)
+ * is final; the others, and every row with a stage-2 logit that is not finite, are the RESIDUAL and go through the f16x3 gate
+ * (stage 3) as before.  The residual rows are decided by both stages and measure the stage-2 error on a logit difference
+ * against the stage-2 arg-max -- max_margin_err2, sum_sq_pair_err2 / pairs2 like their filter twins -- and after its rounds a
+ * call passes the rows stage 2 decided inside [tau2_eff, NESTI_GATE_WIDEN x the error known by then) on to stage 3 as well
+ * (stage2_widened; stage2_dropped: rows that round could not hold, 0 unless tau2 is absurd).  Every row's arg-max is therefore
+ * decided by a pass whose measured error leaves a NESTI_GATE_WIDEN margin; the probabilities of a row stage 2 decides carry
+ * that pass's error.  The filter's own error is measured on every rechecked row against the pass that decides it.
+ * stage2_rows = stage2_decided + stage2_residual.  The reproducible mode freezes tau2 like tau, enqueues no widening round and
+ * counts a residual row whose error would have widened the margin in gate_violations.
+ * The stage runs once a second margin has been set (nesti_model_set_gate_margin2: calibrate.calibrate_gate_margin does it together
+ * with tau; there is no default tau2 -- until one is set every flagged row is decided by the f16x3 gate, as without the stage) and
+ * while the model's cross-term format is 6 (nesti_model_set_x8_format); nesti_model_set_gate_stage2(m, 0) switches it off -- forward
+ * calls are then those of a model without it, launch by launch.  tau2 = +inf sends every flagged row
+ * through both stages (what the calibration does to measure the error), tau2 = 0 lets stage 2 decide every row with finite logits.
+ * The stage takes no workspace of its own: its rounds run inside the tower arena of the forward workspace, which the filter pass
+ * over the whole batch (batches above 4096) or the f16x3 gate of a round sizes.  A round holds as many flagged rows as fit there
+ * together with the block of FP6 planes, the residual list, its logits and the margins (nesti_debug_gate_stage2_plan): the
+ * recheck's own round above 4096 rows, about 7/8 of the batch below; a batch too small for any round runs without the stage.
+ * nesti_model_gate_error2_export / _import are the multi-GPU twins of the _gate_error_ pair below for max_margin_err2. */
+typedef struct {
+  int cap, rounds;        /* flagged rows per stage-2 round and rounds for a full flag list; cap 0: the stage does not run at this batch */
+  int64_t tower_bytes;    /* the stage-2 gating net at `cap` rows (nesti_debug_tower_ops, tower -1, x8_mask 0x3F), at offset 0 of the arena */
+  int64_t residual, logits2, margin2, end;   /* arena offsets of the residual list, its logits, the margins; end of the block */
+  int64_t arena_offset, arena_bytes;          /* the tower arena inside the forward workspace */
+} nesti_debug_stage2_t;
+/* Where recheck stage 2 lives for a forward call of capacity `batch`; needs no device.  dtype without the stage: cap 0. */
+int nesti_debug_gate_stage2_plan(const nesti_config_t* cfg, int dtype, int batch, nesti_debug_stage2_t* out);
+int nesti_model_set_gate_margin2(nesti_model_t* m, float tau2);
+int nesti_model_set_gate_stage2(nesti_model_t* m, int on);
+int nesti_model_gate_error2_export(const nesti_model_t* m, float* dst_dev, void* stream);
+int nesti_model_gate_error2_import(nesti_model_t* m, const float* src_dev, int n, void* stream);
 /* Multi-GPU (no reference counterpart): every rank should filter with the largest error ANY rank has
  * measured.  _export writes this model's max_margin_err to dst_dev[0]; _import raises it to the largest finite value of
  * src_dev[0..n).  Both are one tiny kernel on `stream`, no host synchronisation: the value rides in a spare row of the
@@ -1192,7 +1235,8 @@ enum { NESTI_DEBUG_FORM_PLAIN = 0, /* one product of f32 / f16 / bf16 elements  
        NESTI_DEBUG_FORM_X6 = 4 };  /* ... as block-scaled e2m3 products (format 6)                                          */
 typedef struct {
   int fast;     /* 1: the two-stage gate's plain-f16 filter pass (gating net of NESTI_F16X3C / NESTI_F16X8C models)          */
-  int x8_mask;  /* expert towers of NESTI_F16X8 / NESTI_F16X8C models: the tap layers that take the narrow cross terms
+  int x8_mask;  /* (tower -1 of NESTI_F16X8C models: six bits, the gating net's 8^3 tap layers -- the form of recheck stage 2, format 6)
+                   expert towers of NESTI_F16X8 / NESTI_F16X8C models: the tap layers that take the narrow cross terms
                  * (nesti_model_set_x8_layers; 0 = f16x3 proper)                                                           */
   int x8_fmt;   /* 8 or 6 (nesti_model_set_x8_format); 0 = 6.  nesti_debug_tower_step refuses a format the model does not run */
 } nesti_debug_pass_t;

@@ -39,7 +39,17 @@ class CCascadeStats(ctypes.Structure):
     _fields_ = [("queries", ctypes.c_uint64), ("rechecked", ctypes.c_uint64), ("changed", ctypes.c_uint64),
                 ("max_margin_err", ctypes.c_float), ("tau", ctypes.c_float),
                 ("sum_sq_pair_err", ctypes.c_double), ("pairs", ctypes.c_uint64),
-                ("widened", ctypes.c_uint64), ("widen_events", ctypes.c_uint64), ("tau_eff", ctypes.c_float)]
+                ("widened", ctypes.c_uint64), ("widen_events", ctypes.c_uint64), ("tau_eff", ctypes.c_float),
+                ("stage2", ctypes.c_int), ("stage2_rows", ctypes.c_uint64), ("stage2_decided", ctypes.c_uint64),
+                ("stage2_residual", ctypes.c_uint64), ("max_margin_err2", ctypes.c_float), ("tau2", ctypes.c_float),
+                ("tau2_eff", ctypes.c_float), ("sum_sq_pair_err2", ctypes.c_double), ("pairs2", ctypes.c_uint64),
+                ("stage2_widened", ctypes.c_uint64), ("stage2_dropped", ctypes.c_uint64)]
+
+
+class CDebugStage2(ctypes.Structure):
+    """Mirror of ``nesti_debug_stage2_t``."""
+    _fields_ = [("cap", ctypes.c_int), ("rounds", ctypes.c_int)] + [(n, ctypes.c_int64) for n in (
+        "tower_bytes", "residual", "logits2", "margin2", "end", "arena_offset", "arena_bytes")]
 
 
 class CX8GuardStats(ctypes.Structure):
@@ -153,6 +163,11 @@ SIGNATURES = {
     "nesti_model_destroy": (None, [_vp]),
     "nesti_model_set_gate_margin": (_i, [_vp, ctypes.c_float]),
     "nesti_model_cascade_stats": (_i, [_vp, ctypes.POINTER(CCascadeStats), _i, _vp]),
+    "nesti_debug_gate_stage2_plan": (_i, [_vp, _i, _i, ctypes.POINTER(CDebugStage2)]),
+    "nesti_model_set_gate_margin2": (_i, [_vp, ctypes.c_float]),
+    "nesti_model_set_gate_stage2": (_i, [_vp, _i]),
+    "nesti_model_gate_error2_export": (_i, [_vp, _vp, _vp]),
+    "nesti_model_gate_error2_import": (_i, [_vp, _vp, _i, _vp]),
     "nesti_model_gate_error_export": (_i, [_vp, _vp, _vp]),
     "nesti_model_gate_error_import": (_i, [_vp, _vp, _i, _vp]),
     "nesti_model_set_reproducible": (_i, [_vp, _i]),

@@ -49,6 +49,9 @@ GATE_MARGIN_OVER_MAX = 1.5   # ... and at least this x the largest such error se
                              # widening factor (NESTI_GATE_WIDEN), so that a freshly calibrated margin starts un-widened
 
 
+GATE_MARGIN2_FLOOR = 1e-4    # the smallest tau2 (dtype 'f16x8c', recheck stage 2): the stage's errors are ~30x below the filter's, its floor 10x
+
+
 GATE_MARGIN_MIN_QUERIES = 256   # fewer calibration queries than this: no filtering (every query is decided by the f16x3 gate)
 
 
@@ -88,14 +91,31 @@ def calibrate_gate_margin(net, points, n_eff, sigmas=GATE_MARGIN_SIGMAS, over_ma
     infinity, which makes the mode plain f16x3 (always safe, no filter gain).
     ``reproducible=True``: tau = :func:`reproducible_gate_margin` of the sample's largest error, its pair count and
     ``shape_queries`` (the number of queries the margin has to hold for; default: the sample's) -- the same bits on every run."""
+    stage2 = getattr(net, "stage2", False)
     if int(points.shape[0]) < GATE_MARGIN_MIN_QUERIES:
         net.cascade_stats(reset=True)         # the counters start from zero for this shape here too (ADVICE r04)
         net.set_gate_margin(1e30)
+        if stage2:
+            net.set_gate_margin2(1e30)
         return float("inf")
     net.cascade_stats(reset=True)
     net.set_gate_margin(1e30)
+    if stage2:
+        # dtype 'f16x8c': with BOTH margins at infinity every query also goes through recheck stage 2 (the gating net with its 8^3 tap
+        # layers in the FP6 form) before the f16x3 gate, which measures that stage's error on the logit differences the same way; the
+        # filter's error is measured against the f16x3 gate exactly as without the stage.  tau2 follows the same two rules
+        net.set_gate_margin2(1e30)
     net.gate(net.mups(points, n_eff))
     st = net.cascade_stats(reset=True)
+    if stage2:
+        if reproducible:
+            E = net.cfg.n_gate_out
+            tau2 = reproducible_gate_margin(st["max_margin_err2"], st["stage2_residual"] * (E - 1),
+                                            st["rechecked"] if shape_queries is None else shape_queries, E, floor=GATE_MARGIN2_FLOOR,
+                                            widen=over_max)
+        else:
+            tau2 = max(float(sigmas) * st["sigma2"], float(over_max) * st["max_margin_err2"], GATE_MARGIN2_FLOOR)
+        net.set_gate_margin2(tau2 if st["stage2"] else 1e30)
     if reproducible:
         E = net.cfg.n_gate_out
         tau = reproducible_gate_margin(st["max_margin_err"], st["rechecked"] * (E - 1),

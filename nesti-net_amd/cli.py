@@ -1015,6 +1015,10 @@ def main(argv=None):
             printout("two-stage gate on %s: %d of %d queries decided by the f16x3 gate, f16 gate error on a logit difference "
                      "<= %.4g (tau %.4g, threshold now %.4g)" % (name, st["rechecked"], st["queries"], st["max_margin_err"],
                                                                 st["tau"], st["tau_eff"]))
+            if st.get("stage2"):
+                printout("  of those, %d were decided by the gating net with FP6 cross terms at 8^3 (its error on a logit difference "
+                         "<= %.4g, margin %.4g) and %d went on to the f16x3 gate" % (st["stage2_decided"], st["max_margin_err2"],
+                                                                                    st["tau2_eff"], st["stage2_residual"]))
             if st["widen_events"]:
                 printout("  the measured error came within a factor 1.5 of the margin: the library widened it and re-decided "
                          "%d more queries with the f16x3 gate before these files were written" % st["widened"])

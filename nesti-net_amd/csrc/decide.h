@@ -26,6 +26,22 @@ int launch_gate_widen(const float* keep, int B, int E, float widen, int32_t* fco
 int launch_gate_recheck(const float* logits, int lstride, const int32_t* flag_list, const int32_t* count_ptr, int cap, int E,
                         const float* keep, float* probs, int32_t* expert, unsigned long long* cstat, const int32_t* fcounts,
                         float widen, unsigned long long* rstat, hipStream_t stream);
+// NESTI_F16X8C, recheck stage 2 (decide.hip): cstat2 = the model's second counter block (host.h: C2Stat); residual [cap], logits2
+// [cap, NESTI_MAX_EXPERTS] and margin2 (one float per flag-list position; a round passes its slice) are the call's workspace.
+// _begin snapshots tau2_eff; _decide finishes the rows of a round whose stage-2 margin reaches it and lists the others; _gate3_recheck
+// finishes the listed rows from the f16x3 logits (logits2 null: the widening round, nothing measured); _widen lists the rows the
+// call's later measurements no longer cover
+int launch_gate2_begin(int32_t* fcounts, const unsigned long long* cstat2, float tau2, float widen, const unsigned long long* rstat,
+                       hipStream_t stream);
+int launch_gate2_decide(const float* logits, int lstride, const int32_t* flag_list, const int32_t* count_ptr, int cap, int E,
+                        const float* keep, float* probs, int32_t* expert, unsigned long long* cstat, unsigned long long* cstat2,
+                        int32_t* fcounts, float widen, unsigned long long* rstat, int32_t* residual, float* logits2, float* margin2,
+                        hipStream_t stream);
+int launch_gate3_recheck(const float* logits, int lstride, const int32_t* residual, int cap, int E, const float* keep,
+                         const float* logits2, float* probs, int32_t* expert, unsigned long long* cstat, unsigned long long* cstat2,
+                         const int32_t* fcounts, float widen, unsigned long long* rstat, hipStream_t stream);
+int launch_gate2_widen(int B, int32_t* fcounts, const int32_t* flag_list, const float* margin2, int32_t* residual, int cap,
+                       unsigned long long* cstat2, float widen, hipStream_t stream);
 // a float maximum kept as bits in one counter word (cstat[kCMaxErrBits], gstat[kGMaxDnBits]) <-> a device float (multi-GPU: every
 // rank works with the largest value any rank has measured, nesti_model_gate_error_export / _import and the _guard_ twins)
 int launch_stat_max_export(const unsigned long long* word, float* dst, hipStream_t stream);

@@ -77,8 +77,8 @@ __device__ __forceinline__ float top2_margin(const float* l, int E, bool* nonfin
   return mx - second;
 }
 
-// Stage 1 (on the plain-f16 gate's logits): softmax + first-index arg-max like gate_finish_kernel; the logits are kept for
-// stage 2's error measurement and every row whose top-2 logit margin is below tau_eff -- or that holds a logit that is not finite:
+// The filter (on the plain-f16 gate's logits): softmax + first-index arg-max like gate_finish_kernel; the logits are kept for
+// the recheck's error measurement and every row whose top-2 logit margin is below tau_eff -- or that holds a logit that is not finite:
 // fmaxf and the > comparisons above skip NaNs, so a NaN row could otherwise keep a large finite margin; a +inf logit gives the
 // margin inf (never below tau_eff) and NaN probabilities, a -inf one hides an expert -- is appended to flag_list.
 __global__ void gate_flag_kernel(const float* __restrict__ logits, int lstride, int B, int E,
@@ -165,18 +165,11 @@ __global__ void round_counts_kernel(const int32_t* __restrict__ counts, int n_li
   if (t < n_lists * n_rounds) out[t] = max(0, min(cap, counts[t / n_rounds] - (t % n_rounds) * cap));
 }
 
-// Stage 2 (on the f16x3 gate's logits of one round, compact rows j <-> query flag_list[j]): the final probabilities and
-// arg-max of those queries, and the f16 gate's error on the logit differences against its own arg-max.
-__global__ void gate_recheck_kernel(const float* __restrict__ logits, int lstride, const int32_t* __restrict__ flag_list,
-                                    const int32_t* __restrict__ count_ptr, int cap, int E, const float* __restrict__ keep,
-                                    float* __restrict__ probs, int32_t* __restrict__ expert,
-                                    unsigned long long* __restrict__ cstat, const int32_t* __restrict__ fcounts, float widen,
-                                    unsigned long long* __restrict__ rstat) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= min(cap, *count_ptr)) return;
-  const int b = flag_list[j];
-  float l[NESTI_MAX_EXPERTS], mx = -INFINITY;
-  for (int e = 0; e < E; ++e) { l[e] = logits[(size_t)j * lstride + e]; mx = fmaxf(mx, l[e]); }
+// What deciding row b from the logits l of a more exact pass takes (l is replaced by exp(l - mx)): the final probabilities and
+// arg-max, and the f16 gate's error on the logit differences against its own arg-max (gate_recheck_kernel; stage 2 below)
+__device__ __forceinline__ void recheck_row(float* l, float mx, int b, int E, const float* __restrict__ keep, float* __restrict__ probs,
+                                            int32_t* __restrict__ expert, unsigned long long* __restrict__ cstat,
+                                            const int32_t* __restrict__ fcounts, float widen, unsigned long long* __restrict__ rstat) {
   const int a = expert[b];                       // the f16 gate's arg-max
   float err = 0.f, sq = 0.f;
   int pairs = 0;
@@ -196,6 +189,129 @@ __global__ void gate_recheck_kernel(const float* __restrict__ logits, int lstrid
   atomicAdd(&cstat[kCPairs], (unsigned long long)pairs);
   // reproducible mode: the error that would have widened the call's margin is counted, not acted on
   if (rstat && widen * err > reinterpret_cast<const float*>(fcounts)[kTauEffOff]) atomicAdd(&rstat[kRGateViolations], 1ull);
+}
+
+// The recheck (on the f16x3 gate's logits of one round, compact rows j <-> query flag_list[j]): the final probabilities and
+// arg-max of those queries, and the f16 gate's error on the logit differences against its own arg-max.
+__global__ void gate_recheck_kernel(const float* __restrict__ logits, int lstride, const int32_t* __restrict__ flag_list,
+                                    const int32_t* __restrict__ count_ptr, int cap, int E, const float* __restrict__ keep,
+                                    float* __restrict__ probs, int32_t* __restrict__ expert,
+                                    unsigned long long* __restrict__ cstat, const int32_t* __restrict__ fcounts, float widen,
+                                    unsigned long long* __restrict__ rstat) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= min(cap, *count_ptr)) return;
+  float l[NESTI_MAX_EXPERTS], mx = -INFINITY;
+  for (int e = 0; e < E; ++e) { l[e] = logits[(size_t)j * lstride + e]; mx = fmaxf(mx, l[e]); }
+  recheck_row(l, mx, flag_list[j], E, keep, probs, expert, cstat, fcounts, widen, rstat);
+}
+
+// ---- NESTI_F16X8C: recheck stage 2 (model.hip: gate_cascade) ----------------------------------------------------------------------
+// The flagged rows first go through the gating net with its six 8^3 tap layers in the FP6 cross-term form (conv8n.hip X6), whose
+// error on a logit difference is far below the filter's.  A row whose stage-2 top-2 margin is at least
+//   tau2_eff = max(tau2, NESTI_GATE_WIDEN * largest stage-2 error measured so far)       (snapshotted per call, like tau_eff)
+// is final: gate2_decide_kernel does for it what gate_recheck_kernel does, with the stage-2 logits.  The others -- and every row
+// with a logit that is not finite -- form the round's residual list, with their stage-2 logits kept; stage 3 is today's f16x3 gate
+// over that list, and gate3_recheck_kernel measures BOTH errors on it: the filter's (exactly as gate_recheck_kernel) and stage 2's,
+// |(l_a - l_k)_stage2 - (l_a - l_k)_f16x3| over all k with a = the stage-2 arg-max.  Every rechecked row therefore measures the filter
+// once, against the pass that decides it.  After the rounds one widening round (gate2_widen_kernel) passes the rows stage 2 decided
+// with a margin in [tau2_eff, NESTI_GATE_WIDEN * the largest stage-2 error now known) on to stage 3 as well (normally none: the
+// tower's launches find a zero count).  Reproducible mode (rstat): tau2_eff = tau2, no widening round, and a residual row whose
+// stage-2 error would have widened the margin is counted in rstat[kRGateViolations].
+//   margin2[i]: the stage-2 margin of flag-list position i (+inf for a row passed on), what the widening round reads
+__global__ void gate2_begin_kernel(int32_t* __restrict__ fcounts, const unsigned long long* __restrict__ cstat2, float tau2, float widen,
+                                   const unsigned long long* __restrict__ rstat) {
+  if (threadIdx.x != 0) return;
+  reinterpret_cast<float*>(fcounts)[kTau2EffOff] = rstat ? tau2 : gate_tau_eff(tau2, widen, counter_float(cstat2[kC2MaxErrBits]));
+}
+
+__global__ void gate2_decide_kernel(const float* __restrict__ logits, int lstride, const int32_t* __restrict__ flag_list,
+                                    const int32_t* __restrict__ count_ptr, int cap, int E, const float* __restrict__ keep,
+                                    float* __restrict__ probs, int32_t* __restrict__ expert, unsigned long long* __restrict__ cstat,
+                                    unsigned long long* __restrict__ cstat2, int32_t* __restrict__ fcounts, float widen,
+                                    unsigned long long* __restrict__ rstat, int32_t* __restrict__ residual,
+                                    float* __restrict__ logits2, float* __restrict__ margin2) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= min(cap, *count_ptr)) return;
+  const int b = flag_list[j];
+  float l[NESTI_MAX_EXPERTS], mx = -INFINITY;
+  for (int e = 0; e < E; ++e) { l[e] = logits[(size_t)j * lstride + e]; mx = fmaxf(mx, l[e]); }
+  bool nonfinite;
+  const float margin = top2_margin(l, E, &nonfinite);
+  const bool pass_on = nonfinite || !(margin >= reinterpret_cast<const float*>(fcounts)[kTau2EffOff]);
+  margin2[j] = pass_on ? INFINITY : margin;
+  if (pass_on) {
+    const int pos = atomicAdd(&fcounts[kResCountOff], 1);      // at most the round's rows: pos < cap
+    residual[pos] = b;
+    for (int e = 0; e < E; ++e) logits2[(size_t)pos * NESTI_MAX_EXPERTS + e] = l[e];
+  } else {
+    recheck_row(l, mx, b, E, keep, probs, expert, cstat, fcounts, widen, rstat);
+  }
+  const unsigned long long pm = __ballot(pass_on), am = __ballot(true);
+  if ((threadIdx.x & 63) == (unsigned)__ffsll((long long)am) - 1u) {
+    atomicAdd(&cstat2[kC2Rows], (unsigned long long)__popcll(am));
+    if (am & ~pm) atomicAdd(&cstat2[kC2Decided], (unsigned long long)__popcll(am & ~pm));
+    if (pm) atomicAdd(&cstat2[kC2Residual], (unsigned long long)__popcll(pm));
+  }
+}
+
+// Stage 3 over the residual list (compact rows j <-> query residual[j], fcounts[kResCountOff] of them): final probabilities and
+// arg-max from the f16x3 logits.  logits2 != null (a round's residual): both error measurements; null (the widening round, whose
+// rows stage 2 had already decided and measured the filter with): none
+__global__ void gate3_recheck_kernel(const float* __restrict__ logits, int lstride, const int32_t* __restrict__ residual, int cap, int E,
+                                     const float* __restrict__ keep, const float* __restrict__ logits2, float* __restrict__ probs,
+                                     int32_t* __restrict__ expert, unsigned long long* __restrict__ cstat,
+                                     unsigned long long* __restrict__ cstat2, const int32_t* __restrict__ fcounts, float widen,
+                                     unsigned long long* __restrict__ rstat) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= min(cap, fcounts[kResCountOff])) return;
+  const int b = residual[j];
+  float l[NESTI_MAX_EXPERTS], mx = -INFINITY;
+  for (int e = 0; e < E; ++e) { l[e] = logits[(size_t)j * lstride + e]; mx = fmaxf(mx, l[e]); }
+  if (!logits2) {
+    expert[b] = softmax_argmax(l, E, mx, probs ? probs + (size_t)b * E : nullptr);
+    return;
+  }
+  float l3[NESTI_MAX_EXPERTS];
+  for (int e = 0; e < E; ++e) l3[e] = l[e];
+  recheck_row(l, mx, b, E, keep, probs, expert, cstat, fcounts, widen, rstat);     // replaces l by exp(l - mx)
+  const float* l2 = logits2 + (size_t)j * NESTI_MAX_EXPERTS;
+  int a = 0;
+  for (int e = 1; e < E; ++e) if (l2[e] > l2[a]) a = e;                            // the stage-2 arg-max (first index on ties)
+  float err = 0.f, sq = 0.f;
+  int pairs = 0;
+  for (int e = 0; e < E; ++e) {
+    const float pe = fabsf((l2[a] - l2[e]) - (l3[a] - l3[e]));
+    if (!(pe < INFINITY)) continue;
+    err = fmaxf(err, pe);
+    sq += pe * pe;
+    pairs += e != a;
+  }
+  atomicMax(&cstat2[kC2MaxErrBits], (unsigned long long)__float_as_uint(err));
+  atomicAdd(reinterpret_cast<double*>(&cstat2[kC2SumSq]), (double)sq);
+  atomicAdd(&cstat2[kC2Pairs], (unsigned long long)pairs);
+  if (rstat && widen * err > reinterpret_cast<const float*>(fcounts)[kTau2EffOff]) atomicAdd(&rstat[kRGateViolations], 1ull);
+}
+
+// The stage's widening round: the rows of the call's flag list (n_flagged = fcounts[0] positions) that stage 2 decided with a margin
+// inside [tau2_eff, widen x the largest stage-2 error known now) become the residual list once more (at most cap of them; the rest
+// are counted in cstat2[kC2Dropped])
+__global__ void gate2_widen_begin_kernel(int32_t* __restrict__ fcounts, const unsigned long long* __restrict__ cstat2, float widen) {
+  if (threadIdx.x != 0) return;
+  fcounts[kResCountOff] = 0;
+  reinterpret_cast<float*>(fcounts)[kTau2UpperOff] = widen * counter_float(cstat2[kC2MaxErrBits]);
+}
+__global__ void gate2_widen_kernel(int B, int32_t* __restrict__ fcounts, const int32_t* __restrict__ flag_list,
+                                   const float* __restrict__ margin2, int32_t* __restrict__ residual, int cap,
+                                   unsigned long long* __restrict__ cstat2) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= min(B, fcounts[0])) return;
+  const float lower = reinterpret_cast<const float*>(fcounts)[kTau2EffOff];
+  const float upper = reinterpret_cast<const float*>(fcounts)[kTau2UpperOff];
+  const float m = margin2[i];
+  if (!(m >= lower && m < upper)) return;
+  const int pos = atomicAdd(&fcounts[kResCountOff], 1);
+  if (pos < cap) { residual[pos] = flag_list[i]; atomicAdd(&cstat2[kC2Widened], 1ull); }
+  else atomicAdd(&cstat2[kC2Dropped], 1ull);
 }
 
 // tf.where(noise_est < 0.015, n_est_small, n_est_large) as a routing decision (models/ms_sw_n_est.py:80-82)
@@ -379,6 +495,44 @@ int launch_gate_recheck(const float* logits, int lstride, const int32_t* flag_li
   if (cap <= 0) return 0;
   hipLaunchKernelGGL(gate_recheck_kernel, dim3((cap + 255) / 256), dim3(256), 0, stream, logits, lstride, flag_list,
                      count_ptr, cap, E, keep, probs, expert, cstat, fcounts, widen, rstat);
+  NESTI_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_gate2_begin(int32_t* fcounts, const unsigned long long* cstat2, float tau2, float widen, const unsigned long long* rstat,
+                       hipStream_t stream) {
+  hipLaunchKernelGGL(gate2_begin_kernel, dim3(1), dim3(64), 0, stream, fcounts, cstat2, tau2, widen, rstat);
+  NESTI_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_gate2_decide(const float* logits, int lstride, const int32_t* flag_list, const int32_t* count_ptr, int cap, int E,
+                        const float* keep, float* probs, int32_t* expert, unsigned long long* cstat, unsigned long long* cstat2,
+                        int32_t* fcounts, float widen, unsigned long long* rstat, int32_t* residual, float* logits2, float* margin2,
+                        hipStream_t stream) {
+  if (cap <= 0) return 0;
+  hipLaunchKernelGGL(zero_counts_kernel, dim3(1), dim3(64), 0, stream, fcounts + kResCountOff, 1);
+  hipLaunchKernelGGL(gate2_decide_kernel, dim3((cap + 255) / 256), dim3(256), 0, stream, logits, lstride, flag_list, count_ptr, cap, E,
+                     keep, probs, expert, cstat, cstat2, fcounts, widen, rstat, residual, logits2, margin2);
+  NESTI_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_gate3_recheck(const float* logits, int lstride, const int32_t* residual, int cap, int E, const float* keep,
+                         const float* logits2, float* probs, int32_t* expert, unsigned long long* cstat, unsigned long long* cstat2,
+                         const int32_t* fcounts, float widen, unsigned long long* rstat, hipStream_t stream) {
+  if (cap <= 0) return 0;
+  hipLaunchKernelGGL(gate3_recheck_kernel, dim3((cap + 255) / 256), dim3(256), 0, stream, logits, lstride, residual, cap, E, keep,
+                     logits2, probs, expert, cstat, cstat2, fcounts, widen, rstat);
+  NESTI_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_gate2_widen(int B, int32_t* fcounts, const int32_t* flag_list, const float* margin2, int32_t* residual, int cap,
+                       unsigned long long* cstat2, float widen, hipStream_t stream) {
+  if (B <= 0) return 0;
+  hipLaunchKernelGGL(gate2_widen_begin_kernel, dim3(1), dim3(64), 0, stream, fcounts, cstat2, widen);
+  hipLaunchKernelGGL(gate2_widen_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, B, fcounts, flag_list, margin2, residual, cap, cstat2);
   NESTI_CHECK_HIP(hipGetLastError());
   return 0;
 }

@@ -164,6 +164,34 @@ struct Builder {
     T.n_out = g.cfg.n_experts;
   }
 
+  // The stage-2 form of the gating net on the 8^3 grid (graph.h: Graph::gate2): a copy of `gate` whose 8^3 blocks' conv1 | conv4
+  // launches are producers and whose 8^3 tap layers read the planes, like build_expert's first two blocks
+  void build_gate2() {
+    Tower& T = g.gate2;
+    T = g.gate;
+    T.side_tail = true;
+    int block = 0, ab = -1, producer = -1;
+    for (size_t k = 0; k < T.ops.size(); ++k) {
+      Op& op = T.ops[k];
+      if (op.kind != Op::CONV || op.log2S != 3) continue;
+      const LayerDesc& d = g.layers[op.layer];
+      if (!d.scope2.empty()) {   // conv1 | conv4 of an 8^3 block
+        BufSpec ax{3, d.Cout_p / 2, false};
+        ax.aux8 = true;
+        T.bufs.push_back(ax);
+        ab = (int)T.bufs.size() - 1;
+        op.aux_out_buf = ab;
+        op.x8_bits = 3 << (2 * block);
+        producer = op.layer;
+      } else if (ab >= 0 && (d.k == 3 || d.k == 5)) {
+        op.aux_in_buf = ab;
+        op.aux_layer = producer;
+        op.x8_bit = 2 * block + (d.scope.back() == '3' ? 1 : 0);
+        if (d.scope.back() == '3') { ++block; ab = -1; }
+      }
+    }
+  }
+
   // The "ss" tower shared by the ablation models: inception x3 @8^3 [3,5] -> maxpool -> inception x2 @4^3
   // [3,k1_small] -> maxpool -> flatten 2^3 x 1536 voxel-major (tf.reshape) -> fc 1024/256/128/n_out.  Used by
   // ss_norm_est.get_model (models/ss_norm_est.py:35-92), ms_norm_est.get_model (models/ms_norm_est.py:45-140) and
@@ -262,6 +290,7 @@ int build_graph(const nesti_config_t* cfg, Graph* g, bool x8) {
   g->layers.clear();
   Builder b(*g);
   g->gate = Tower();
+  g->gate2 = Tower();
   if (cfg->arch == NESTI_ARCH_SINGLE || cfg->arch == NESTI_ARCH_MULTI) {
     g->cfg.n_experts = 1;
     g->experts.assign(1, Tower());
@@ -277,6 +306,7 @@ int build_graph(const nesti_config_t* cfg, Graph* g, bool x8) {
     return 0;
   }
   b.build_gate();
+  if (g->x8) b.build_gate2();
   g->experts.assign(cfg->n_experts, Tower());
   for (int i = 0; i < cfg->n_experts; ++i) b.build_expert(i);
   return 0;

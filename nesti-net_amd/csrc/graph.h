@@ -44,6 +44,7 @@ struct Tower {
   std::vector<Op> ops;
   int out_buf = -1;            // f32 [NB, 64]
   int n_out = 0;               // real outputs (E or 3)
+  bool side_tail = false;      // the aux8 buffers share ONE block behind everything else (place_tower): the gating net's stage-2 form
 };
 
 struct ChanMap { std::vector<int> pos; int C = 0; };   // real channel -> padded position, padded width
@@ -55,8 +56,14 @@ struct Graph {
   bool x8 = false;           // NESTI_F16X8 / NESTI_F16X8C: the expert towers carry side buffers for the FP8 cross terms
   std::vector<LayerDesc> layers;
   Tower gate;
+  // NESTI_F16X8C (x8 and a gating net on the 8^3 grid): the gating net once more, same layers and launches, with the side buffers of
+  // its three 8^3 blocks (bits 0 .. 5 of Pass::x8_mask = inception1 conv2 / conv3, inception2 ..., inception3 ...) -- the form the
+  // recheck's stage 2 runs (model.hip: gate_cascade).  `gate` itself stays free of them: the filter pass and stage 3 never pay for them
+  Tower gate2;
+  bool has_gate2() const { return !gate2.ops.empty(); }
   std::vector<Tower> experts;
-  const Tower& tower(int t) const { return t < 0 ? gate : experts[t]; }   // -1: the gating net, else an expert
+  // -1: the gating net (x8_mask != 0: its stage-2 form), else an expert
+  const Tower& tower(int t, int x8_mask = 0) const { return t < 0 ? (x8_mask && has_gate2() ? gate2 : gate) : experts[t]; }
 };
 
 // x8: an NESTI_F16X8 / NESTI_F16X8C model (only experts_n_est on the 8^3 grid gets the side buffers)

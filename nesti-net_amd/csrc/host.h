@@ -50,6 +50,11 @@ constexpr int kMaxTaps = 125;     // 5^3
 // included); changed; the bits of max_margin_err; a double, the sum of the squared pair errors; the number of pairs in that sum; rows
 // rechecked by a widening round; forward calls whose widening round was not empty
 enum CStat { kCQueries, kCRechecked, kCChanged, kCMaxErrBits, kCSumSq, kCPairs, kCWidened, kCWidenEvents };
+// cstat2, recheck stage 2 of NESTI_F16X8C (the gating net with its 8^3 tap layers in the FP6 form; decide.hip): rows that went through
+// it; rows it decided; rows it passed on to stage 3, the f16x3 gate (the residual); the bits of its largest error on a logit
+// difference, measured on the rows both stages decided; the sum of those errors squared and their number; rows the call's widening
+// round passed on to stage 3 afterwards; rows that round could not hold
+enum C2Stat { kC2Rows, kC2Decided, kC2Residual, kC2MaxErrBits, kC2SumSq, kC2Pairs, kC2Widened, kC2Dropped };
 // gstat, the conditioning guard: queries; rows re-evaluated; the bits of the largest |dn|; rows dropped because a list was full
 enum GStat { kGQueries, kGRechecked, kGMaxDnBits, kGDropped };
 // rstat, the reproducible mode: rows whose error would have widened the gate's margin / the guard's band
@@ -71,9 +76,15 @@ inline float x8_guard_scale() { return NESTI_X8_GUARD_WIDEN / sqrtf(2.f * NESTI_
 //   [kTauEffOff] the call's threshold tau_eff as a float (raised to the upper end of every band a widening pass has covered),
 //   [kWidenUpperOff] the upper end of the current widening pass's band (float, snapshotted when the pass starts),
 //   [kWidenCountOff] rows flagged by the current widening pass, [kWidenRoundsOff + r] of them in its tower round r
+//   recheck stage 2: [kResCountOff] rows of the current residual list, [kTau2EffOff] the call's second threshold tau2_eff (float),
+//   [kTau2UpperOff] the upper end of the band of the stage's widening round (float), [kRound2Off + r] the flagged rows in the stage's
+//   round r (plan.h: Stage2Plan::cap rows per round)
 constexpr int kFcountsBytes = 512;
 constexpr int kMaxCascadeRounds = 24;
 constexpr int kRoundCountsOff = 8, kTauEffOff = 40, kWidenUpperOff = 41, kWidenCountOff = 48, kWidenRoundsOff = 56;
+constexpr int kResCountOff = 80, kTau2EffOff = 81, kTau2UpperOff = 82, kRound2Off = 88;
+static_assert(kWidenRoundsOff + kMaxCascadeRounds <= kResCountOff && kTau2UpperOff < kRound2Off &&
+              (kRound2Off + kMaxCascadeRounds) * 4 <= kFcountsBytes, "fcounts layout: stage 2");
 static_assert(kRoundCountsOff + kMaxCascadeRounds <= kTauEffOff && (kWidenRoundsOff + kMaxCascadeRounds) * 4 <= kFcountsBytes, "fcounts layout");
 // ecounts, the next block, as int32 words: [e * rounds + r] rows of expert e's round r from word 0 (plan.h: they end before the
 // guard's words), [kGuardCountOff + e] the length of the guard's list for expert e, [kGuardSlotOff], [+ 1] the |n| band (floats)

@@ -139,6 +139,16 @@ struct nesti_model {
   int gate_mix = 0;          // EXPERIMENT (nesti_model_set_gate_mix): the f16x3 gating passes run their tap layers single-product
   float tau = 0.25f;
   nesti::StatBlock cstat;
+  // NESTI_F16X8C: recheck stage 2 (gate_cascade) -- the flagged rows first go through the gating net with its 8^3 tap layers in the FP6
+  // form (graph.h: Graph::gate2); only those whose stage-2 margin is below tau2_eff reach the f16x3 gate.  cstat2 = its counters
+  // (host.h: C2Stat).  On while the model's cross-term format is 6, nesti_model_set_gate_stage2 has not switched it off and a second
+  // margin has been SET (nesti_model_set_gate_margin2; the calibration does): the stage's error is two orders below the filter's, and
+  // no constant is a safe margin for weights nobody has measured -- until then every flagged row is the f16x3 gate's, as without the stage
+  float tau2 = 0.f;
+  bool tau2_set = false;
+  bool stage2 = true;
+  nesti::StatBlock cstat2;
+  bool stage2_on() const { return cascade && cstat2 && stage2 && tau2_set && x8_fmt == 6; }
   // nesti_model_set_reproducible: rstat = the mode's own 64-byte counter block (host.h: RStat), allocated
   // with cstat / gstat; forward calls hand it to the kernels only while the mode is on (frozen() below), and then no decision of
   // theirs reads cstat / gstat
@@ -277,9 +287,45 @@ int gate_cascade(const nesti_model* m, const void* X0, int B, const Arena& A, fl
   // threshold reached so far and NESTI_GATE_WIDEN x the largest error measured up to the start of the pass, so an error first
   // seen inside a widening pass is covered by the next one of the SAME call (normally every pass is empty: its launches find a
   // zero row count on the device and return; no host synchronisation, so the whole call stays graph-capturable)
+  // recheck stage 2 (NESTI_F16X8C, format 6): in pass 0 a round's rows go through the gating net in its FP6 form first; the rows whose
+  // stage-2 margin stays below tau2_eff -- the round's residual list, a fraction of a per cent of a batch -- then go through the f16x3
+  // gate as walking launches.  The widening passes of the filter's margin (normally empty) keep the two-pass form
+  // The stage's buffers sit inside the tower arena (plan.h: Stage2Plan), in rounds of S2.cap rows of the flag list
+  const Stage2Plan S2 = m->stage2_on() ? stage2_plan(m->mode(), A.NB) : Stage2Plan();
+  const bool s2 = S2.cap > 0;
+  const int cap2 = std::min(S2.cap, B), rounds2 = s2 ? (B + cap2 - 1) / cap2 : 0;
+  int32_t* residual = reinterpret_cast<int32_t*>(A.tower() + S2.residual);
+  float* logits2 = reinterpret_cast<float*>(A.tower() + S2.logits2);
+  float* margin2 = reinterpret_cast<float*>(A.tower() + S2.margin2);
+  // stage 3 over the current residual list: the f16x3 gate on fcounts[kResCountOff] rows
+  auto stage3 = [&](const float* l2) {
+    const RunCtx exact = pass_ctx(m, -1, false, 0, S2.cap, fcounts + kResCountOff, residual, stream, NESTI_GATE_WIDEN_WALK_GRID);
+    if (run_tower(exact, m->graph.gate, X0, A.tower(), S2.tower_bytes, &logits)) return 1;
+    return launch_gate3_recheck(logits, lstride, residual, S2.cap, E, keep, l2, probs, expert, m->cstat.dev, m->cstat2.dev, fcounts,
+                                NESTI_GATE_WIDEN, rstat, stream);
+  };
+  if (s2 && (launch_gate2_begin(fcounts, m->cstat2.dev, m->tau2, NESTI_GATE_WIDEN, rstat, stream) ||
+             launch_round_counts(fcounts, 1, cap2, rounds2, fcounts + kRound2Off, stream)))
+    return 1;
   for (int pass = 0; pass <= (rstat ? 0 : NESTI_GATE_WIDEN_PASSES); ++pass) {
     if (pass >= 1 && launch_gate_widen(keep, B, E, NESTI_GATE_WIDEN, fcounts, flag_list, cap, rounds, m->cstat.dev, stream)) return 1;
     const int32_t* round_counts = fcounts + (pass == 0 ? kRoundCountsOff : kWidenRoundsOff);
+    for (int r = 0; s2 && pass == 0 && r < rounds2; ++r) {
+      const int32_t* list = flag_list + (size_t)r * cap2;
+      const int32_t* count = fcounts + kRound2Off + r;
+      const RunCtx fp6 = pass_ctx(m, -1, false, 0x3F, S2.cap, count, list, stream, r >= 1 ? 1 : 0);
+      if (run_tower(fp6, m->graph.gate2, X0, A.tower(), S2.tower_bytes, &logits)) return 1;
+      if (launch_gate2_decide(logits, lstride, list, count, cap2, E, keep, probs, expert, m->cstat.dev, m->cstat2.dev, fcounts,
+                              NESTI_GATE_WIDEN, rstat, residual, logits2, margin2 + (size_t)r * cap2, stream))
+        return 1;
+      if (stage3(logits2)) return 1;
+    }
+    if (s2 && pass == 0) {
+      // the stage's widening round: what this call has measured since its tau2_eff was taken (normally nothing: an empty list)
+      if (!rstat && (launch_gate2_widen(B, fcounts, flag_list, margin2, residual, S2.cap, m->cstat2.dev, NESTI_GATE_WIDEN, stream) || stage3(nullptr)))
+        return 1;
+      continue;
+    }
     for (int r = 0; r < rounds; ++r) {
       // round 0 of pass 0 holds the flagged rows; everything after it is normally empty
       const RunCtx exact = pass_ctx(m, -1, false, 0, cap, round_counts + r, flag_list + (size_t)r * cap, stream,
@@ -496,12 +542,13 @@ int nesti_model_create(const nesti_config_t* cfg, const nesti_tensor_t* tensors,
   for (int t = -1; t < (int)m->graph.experts.size(); ++t) {
     std::vector<Pass> passes(1);
     if (m->cascade && t < 0) { passes.push_back(Pass()); passes.back().fast = true; }
+    if (m->cascade && t < 0 && m->graph.has_gate2()) { passes.push_back(Pass()); passes.back().x8_mask = 0x3F; passes.back().x8_fmt = 6; }
     for (int fmt : {8, 6})
       if (x8 && t >= 0) { passes.push_back(Pass()); passes.back().x8_mask = 0xF; passes.back().x8_fmt = fmt; }
     if (m->has_mix) { passes.push_back(Pass()); passes.back().mix = t < 0 ? 1 << kGateMixBit : 0x3F; }
     for (Pass& ps : passes) {
       ps.tower = t;
-      for (const Op& op : m->graph.tower(t).ops) {
+      for (const Op& op : m->graph.tower(t, ps.x8_mask).ops) {
         if (op.kind != Op::CONV) continue;
         const LayerDesc& d = m->graph.layers[op.layer];
         const LaunchForm f = launch_form(m->graph, op, ps, dtype);
@@ -523,6 +570,7 @@ int nesti_model_create(const nesti_config_t* cfg, const nesti_tensor_t* tensors,
     }
   }
   if (m->cascade && m->cstat.alloc()) return 1;
+  if (m->cascade && m->graph.has_gate2() && m->cstat2.alloc()) return 1;
   if ((m->cstat || m->gstat) && m->rstat.alloc()) return 1;   // the reproducible mode's own counters (nesti_model_set_reproducible)
   NESTI_CHECK_HIP(hipDeviceSynchronize());
   *out = m.release();
@@ -535,6 +583,20 @@ int nesti_model_set_gate_margin(nesti_model_t* m, float tau) {
   if (!m || !m->cascade) NESTI_FAIL("nesti_model_set_gate_margin: not a NESTI_F16X3C model");
   if (!(tau >= 0.f)) NESTI_FAIL("nesti_model_set_gate_margin: tau must be >= 0");
   m->tau = tau;
+  return 0;
+}
+
+int nesti_model_set_gate_margin2(nesti_model_t* m, float tau2) {
+  if (!m || !m->cstat2) NESTI_FAIL("nesti_model_set_gate_margin2: not a NESTI_F16X8C model");
+  if (!(tau2 >= 0.f)) NESTI_FAIL("nesti_model_set_gate_margin2: tau2 must be >= 0");
+  m->tau2 = tau2;
+  m->tau2_set = true;
+  return 0;
+}
+
+int nesti_model_set_gate_stage2(nesti_model_t* m, int on) {
+  if (!m || !m->cstat2) NESTI_FAIL("nesti_model_set_gate_stage2: not a NESTI_F16X8C model");
+  m->stage2 = on != 0;
   return 0;
 }
 
@@ -612,6 +674,16 @@ int nesti_model_cascade_stats(const nesti_model_t* m, nesti_cascade_stats_t* out
   out->widened = h[kCWidened];
   out->widen_events = h[kCWidenEvents];
   out->tau_eff = m->reproducible ? m->tau : gate_tau_eff(m->tau, NESTI_GATE_WIDEN, out->max_margin_err);
+  unsigned long long h2[8];
+  if (m->cstat2.read(h2, reset)) return 1;
+  out->stage2 = m->stage2_on() ? 1 : 0;
+  out->stage2_rows = h2[kC2Rows]; out->stage2_decided = h2[kC2Decided]; out->stage2_residual = h2[kC2Residual];
+  out->max_margin_err2 = counter_float(h2[kC2MaxErrBits]);
+  out->tau2 = m->cstat2 ? m->tau2 : 0.f;
+  memcpy(&out->sum_sq_pair_err2, &h2[kC2SumSq], 8);
+  out->pairs2 = h2[kC2Pairs];
+  out->stage2_widened = h2[kC2Widened]; out->stage2_dropped = h2[kC2Dropped];
+  out->tau2_eff = !m->cstat2 ? 0.f : m->reproducible ? m->tau2 : gate_tau_eff(m->tau2, NESTI_GATE_WIDEN, out->max_margin_err2);
   return 0;
 }
 
@@ -625,7 +697,8 @@ int nesti_model_reproducible_stats(const nesti_model_t* m, nesti_reproducible_st
   if (!m || !out) NESTI_FAIL("nesti_model_reproducible_stats: null model / null argument");
   unsigned long long r[8], c[8], g[8];
   NESTI_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
-  if (m->rstat.read(r, reset) || m->cstat.read(c, reset) || m->gstat.read(g, reset)) return 1;
+  unsigned long long c2[8];
+  if (m->rstat.read(r, reset) || m->cstat.read(c, reset) || m->gstat.read(g, reset) || m->cstat2.read(c2, reset)) return 1;
   memset(out, 0, sizeof(*out));
   out->on = m->reproducible ? 1 : 0;
   out->gate_violations = r[kRGateViolations]; out->guard_violations = r[kRGuardViolations]; out->guard_dropped = g[kGDropped];
@@ -644,6 +717,16 @@ int nesti_model_gate_error_export(const nesti_model_t* m, float* dst_dev, void* 
 int nesti_model_gate_error_import(nesti_model_t* m, const float* src_dev, int n, void* stream) {
   if (!m || !m->cascade || (n > 0 && !src_dev)) NESTI_FAIL("nesti_model_gate_error_import: not a NESTI_F16X3C model / null argument");
   return launch_stat_max_import(m->cstat.dev + kCMaxErrBits, src_dev, n, (hipStream_t)stream);
+}
+
+int nesti_model_gate_error2_export(const nesti_model_t* m, float* dst_dev, void* stream) {
+  if (!m || !m->cstat2 || !dst_dev) NESTI_FAIL("nesti_model_gate_error2_export: not a NESTI_F16X8C model / null argument");
+  return launch_stat_max_export(m->cstat2.dev + kC2MaxErrBits, dst_dev, (hipStream_t)stream);
+}
+
+int nesti_model_gate_error2_import(nesti_model_t* m, const float* src_dev, int n, void* stream) {
+  if (!m || !m->cstat2 || (n > 0 && !src_dev)) NESTI_FAIL("nesti_model_gate_error2_import: not a NESTI_F16X8C model / null argument");
+  return launch_stat_max_import(m->cstat2.dev + kC2MaxErrBits, src_dev, n, (hipStream_t)stream);
 }
 
 int nesti_model_guard_error_export(const nesti_model_t* m, float* dst_dev, void* stream) {
@@ -943,7 +1026,7 @@ int nesti_debug_tower_step(const nesti_model_t* m, int tower, const nesti_debug_
   if (check_pass("nesti_debug_tower_step", m->graph, m->cascade, tower, ps)) return 1;
   if (ps.x8_fmt != 0 && ps.x8_fmt != m->x8_fmt) NESTI_FAIL("nesti_debug_tower_step: x8_fmt differs from the model's (nesti_model_set_x8_format)");
   if (walk < 0 || (walk > 1 && walk % 8)) NESTI_FAIL("nesti_debug_tower_step: walk is 0, 1 or a multiple of 8");
-  const Tower& T = m->graph.tower(tower);
+  const Tower& T = m->graph.tower(tower, ps.x8_mask);
   if (op < 0 || op >= (int)T.ops.size()) NESTI_FAIL("nesti_debug_tower_step: op index outside the tower");
   const RunCtx rc = pass_ctx(m, tower, ps.fast != 0, ps.x8_mask, batch, npoints_dev, point_index_dev, (hipStream_t)stream, walk);
   std::vector<unsigned char*> ptr;

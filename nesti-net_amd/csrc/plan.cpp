@@ -77,6 +77,7 @@ Placement place_tower(const Tower& T, int NB, int dtype) {
   Placement P;
   P.off.assign(n, 0);
   P.first = first; P.last = last;
+  if (T.side_tail) order.erase(std::remove_if(order.begin(), order.end(), [&](int i) { return T.bufs[i].aux8; }), order.end());
   for (int i : order) {
     // first fit: the lowest gap between the blocks still read that holds the buffer, else right above the highest of them
     const size_t need = buf_bytes(T.bufs[i], NB, dtype);
@@ -90,6 +91,13 @@ Placement place_tower(const Tower& T, int NB, int dtype) {
     P.total = std::max(P.total, at + need);
     placed.insert(std::find_if(placed.begin(), placed.end(), [&](const Block& b) { return b.off > at; }), {at, at + need, last[i]});
   }
+  if (T.side_tail) {
+    // the stage-2 gating net: its side buffers (one per 8^3 block, lifetimes apart) share one block behind everything else, so
+    // that the tower is its pair form's bytes plus exactly that block
+    const size_t main = P.total;
+    for (int i = 1; i < n; ++i)
+      if (T.bufs[i].aux8 && last[i] >= 0) { P.off[i] = main; P.total = std::max(P.total, main + buf_bytes(T.bufs[i], NB, dtype)); }
+  }
   return P;
 }
 
@@ -98,6 +106,26 @@ static size_t max_tower_bytes(const Mode& m, int NB) {
                        : tower_bytes(m.g.gate, NB, m.dtype);
   for (const Tower& e : m.g.experts) t = std::max(t, tower_bytes(e, expert_cap(NB), m.dtype));
   return t;
+}
+
+Stage2Plan stage2_plan(const Mode& m, int NB) {
+  Stage2Plan S;
+  if (!stage2_planned(m)) return S;
+  const size_t arena = max_tower_bytes(m, NB);
+  const int cap = cascade_cap(NB);
+  // the largest round that fits: the recheck's own where the arena has room behind the f16x3 gate of a round (large batches: the
+  // filter pass over the whole batch sets the arena), else 7/8 of it (a multiple of 4 rows, one tap-kernel tile), and so on; row
+  // by row for small batches
+  for (int c = cap; c >= 1; c = c > 64 ? ((c * 7 / 8) & ~3) : c - 1) {
+    if ((NB + c - 1) / c > kMaxCascadeRounds) break;
+    S.tower_bytes = tower_bytes(m.g.gate2, c, m.dtype);
+    S.residual = S.tower_bytes;
+    S.logits2 = S.residual + align_up((size_t)c * 4, 256);
+    S.margin2 = S.logits2 + align_up((size_t)c * NESTI_MAX_EXPERTS * 4, 256);
+    S.end = S.margin2 + align_up((size_t)NB * 4, 256);
+    if (S.end <= arena) { S.cap = c; S.rounds = (NB + c - 1) / c; return S; }
+  }
+  return Stage2Plan();
 }
 
 WsLayout ws_layout(const Mode& m, int NB) {
@@ -239,8 +267,12 @@ int check_pass(const std::string& who, const Graph& g, bool cascade, int tower, 
   if (tower < -1 || tower >= (int)g.experts.size()) NESTI_FAIL(who + ": tower must be -1 (gate) or an expert index");
   if (tower < 0 && g.cfg.arch != NESTI_ARCH_EXPERTS && g.cfg.arch != NESTI_ARCH_SWITCH) NESTI_FAIL(who + ": this model has no gating net");
   if (ps.fast && !(cascade && tower < 0)) NESTI_FAIL(who + ": the filter pass is the gating net's of NESTI_F16X3C / NESTI_F16X8C models");
-  if (ps.x8_mask < 0 || ps.x8_mask > 0xF || (ps.x8_mask && !(g.x8 && tower >= 0)))
+  if (tower < 0 && ps.x8_mask) {   // recheck stage 2: the gating net's six 8^3 tap layers in the FP6 form
+    if (ps.x8_mask < 0 || ps.x8_mask > 0x3F || ps.fast || !(cascade && g.has_gate2()) || ps.x8_fmt == 8)
+      NESTI_FAIL(who + ": the gating net takes an x8_mask of six bits, format 6, in NESTI_F16X8C models, outside the filter pass");
+  } else if (ps.x8_mask < 0 || ps.x8_mask > 0xF || (ps.x8_mask && !(g.x8 && tower >= 0))) {
     NESTI_FAIL(who + ": x8_mask has four bits and applies to the expert towers of NESTI_F16X8 / NESTI_F16X8C models");
+  }
   if (ps.x8_fmt != 0 && ps.x8_fmt != 6 && ps.x8_fmt != 8) NESTI_FAIL(who + ": x8_fmt is 0 (= 6), 6 or 8");
   return 0;
 }
@@ -325,6 +357,22 @@ size_t nesti_estimate_workspace_bytes_for_config(const nesti_config_t* cfg, int 
   return est_workspace_bytes({g, main_dtype(dtype), dtype_cascade(dtype)}, batch);
 }
 
+int nesti_debug_gate_stage2_plan(const nesti_config_t* cfg, int dtype, int batch, nesti_debug_stage2_t* out) {
+  if (!cfg || !out) NESTI_FAIL("nesti_debug_gate_stage2_plan: null argument");
+  if (batch <= 0) NESTI_FAIL("nesti_debug_gate_stage2_plan: batch must be positive");
+  Graph g;
+  if (build_graph(cfg, &g, dtype_x8(dtype))) return 1;
+  const Mode m = {g, main_dtype(dtype), dtype_cascade(dtype)};
+  const Stage2Plan S = stage2_plan(m, batch);
+  const WsLayout L = ws_layout(m, batch);
+  memset(out, 0, sizeof(*out));
+  out->cap = S.cap; out->rounds = S.rounds;
+  out->tower_bytes = (int64_t)S.tower_bytes; out->residual = (int64_t)S.residual; out->logits2 = (int64_t)S.logits2;
+  out->margin2 = (int64_t)S.margin2; out->end = (int64_t)S.end;
+  out->arena_offset = (int64_t)L.tower; out->arena_bytes = (int64_t)(L.total - L.tower);
+  return 0;
+}
+
 // ---- test hook: one tower, launch by launch (include/nesti_hip.h) -----------------------------------------------------------
 int nesti_debug_tower_ops(const nesti_config_t* cfg, int dtype, int tower, int batch, const nesti_debug_pass_t* pass,
                           nesti_debug_buf_t* bufs, int max_bufs, int* n_bufs, nesti_debug_op_t* ops, int max_ops, int* n_ops,
@@ -335,7 +383,7 @@ int nesti_debug_tower_ops(const nesti_config_t* cfg, int dtype, int tower, int b
   Graph g;
   if (build_graph(cfg, &g, dtype_x8(dtype))) return 1;
   if (check_pass("nesti_debug_tower_ops", g, dtype_cascade(dtype), tower, ps)) return 1;
-  const Tower& T = g.tower(tower);
+  const Tower& T = g.tower(tower, ps.x8_mask);
   Pass run;
   run.tower = tower; run.fast = ps.fast != 0; run.x8_mask = ps.x8_mask; run.x8_fmt = ps.x8_fmt == 8 ? 8 : 6;
   const int mdt = main_dtype(dtype), dt = pass_dtype(run.fast, mdt);

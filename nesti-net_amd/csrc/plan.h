@@ -51,6 +51,9 @@ struct Placement {
 };
 Placement place_tower(const Tower& T, int NB, int dtype);
 inline size_t tower_bytes(const Tower& T, int NB, int dtype) { return place_tower(T, NB, dtype).total; }
+// recheck stage 2 -- the gating net's 8^3 tap layers in the FP6 cross-term form (model.hip: gate_cascade) -- is planned for: the
+// two-stage gate of an NESTI_F16X8C model.  Whether a call runs it is the model's (x8 format 6, nesti_model_set_gate_stage2)
+inline bool stage2_planned(const Mode& m) { return m.cascade && m.g.has_gate2(); }
 
 // NESTI_F16X3C: the f16x3 gate re-decides the flagged rows `cap` at a time (its workspace is 3x the filter's per row, and
 // only a fraction of a batch is flagged): small batches in one round, large ones in quarters
@@ -77,6 +80,14 @@ struct WsLayout {
   size_t x0, probs, expert, counts, lists, ecounts, glist, keep, flags, fcounts, tower, total;
 };
 WsLayout ws_layout(const Mode& m, int NB);
+
+// Recheck stage 2 lives INSIDE the tower arena, whose size it does not change: [the stage-2 gating net of a round of `cap` rows
+// (Graph::gate2; the f16x3 gate over the round's residual list reuses its front) | residual list [cap] | stage-2 logits of the
+// residual rows [cap, NESTI_MAX_EXPERTS] | stage-2 margin of every flag-list position [NB]], offsets from the arena's start.  cap is
+// the recheck's own round where that fits -- batches above 4096, whose arena is set by the filter pass over the whole batch -- and
+// the largest smaller round that does otherwise; cap == 0: no round fits (a batch of one row), the call runs without the stage
+struct Stage2Plan { int cap = 0, rounds = 0; size_t tower_bytes = 0, residual = 0, logits2 = 0, margin2 = 0, end = 0; };
+Stage2Plan stage2_plan(const Mode& m, int NB);
 
 // The fused end-to-end entries put their staging in front of the forward workspace: [points (3^3 grid only) | n_eff | forward]
 // 8^3 Gaussian grid: patches_mups_kernel goes from the cloud to the MuPS tensor in one kernel (the patch tensors are never

@@ -53,6 +53,11 @@ def agree_on_gate_margin(net, tau, device, group=None):
     dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
     hi, lo = float(t[0].item()), -float(t[1].item())
     net.set_gate_margin(hi)
+    st2 = net.cascade_stats() if getattr(net, "stage2", False) else {}
+    if st2.get("stage2"):                      # dtype 'f16x8c' with recheck stage 2 running: the second margin the same way
+        t2 = torch.tensor([min(st2["tau2"], big)], dtype=torch.float64, device=device)
+        dist.all_reduce(t2, op=dist.ReduceOp.MAX, group=group)
+        net.set_gate_margin2(float(t2[0].item()))
     return hi, (hi - lo if hi < big else 0.0)
 
 
@@ -78,11 +83,16 @@ def _cascade_net(estimator):
 def _all_gather(mine, everyone, rows, net, group):
     """THE collective of the path; ``net`` (a cascade model or None): its gate error rides in the spare row."""
     world, _, cols = everyone.shape
+    stage2 = getattr(net, "stage2", False)     # dtype 'f16x8c': the error of recheck stage 2 rides in element 1 of the spare row
     if net is not None:
         net.export_gate_error(mine[rows, 0:1])
+        if stage2:
+            net.export_gate_error2(mine[rows, 1:2])
     dist.all_gather_into_tensor(everyone.view(world * (rows + 1), cols), mine, group=group)
     if net is not None:
         net.import_gate_error(everyone[:, rows, 0].contiguous())
+        if stage2:
+            net.import_gate_error2(everyone[:, rows, 1].contiguous())
 
 
 def pack_results(normals, expert, probs, out):

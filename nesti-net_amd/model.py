@@ -98,6 +98,7 @@ class NestiNet:
                                                    ctypes.byref(self._handle)), "nesti_model_create")
         self._keep = None
         self.cascade = dtype in CASCADE_DTYPES
+        self.stage2 = dtype == "f16x8c"      # the two-stage gate has the FP6-form recheck stage (set_gate_margin2, set_gate_stage2)
         self.reproducible = False
         self.mups_cstride = self.lib.nesti_model_mups_cstride(self._handle)
         self._ws = None
@@ -129,9 +130,38 @@ class NestiNet:
             _lib.check(self.lib.nesti_model_cascade_stats(self._handle, ctypes.byref(st), int(bool(reset)), self._stream(stream)),
                        "nesti_model_cascade_stats")
         sigma = (st.sum_sq_pair_err / st.pairs) ** 0.5 if st.pairs else 0.0
-        return {"queries": int(st.queries), "rechecked": int(st.rechecked), "changed": int(st.changed),
-                "max_margin_err": float(st.max_margin_err), "sigma": float(sigma), "tau": float(st.tau),
-                "widened": int(st.widened), "widen_events": int(st.widen_events), "tau_eff": float(st.tau_eff)}
+        out = {"queries": int(st.queries), "rechecked": int(st.rechecked), "changed": int(st.changed),
+               "max_margin_err": float(st.max_margin_err), "sigma": float(sigma), "tau": float(st.tau),
+               "widened": int(st.widened), "widen_events": int(st.widen_events), "tau_eff": float(st.tau_eff)}
+        if self.stage2:     # dtype 'f16x8c': recheck stage 2 (include/nesti_hip.h); stage2_rows = stage2_decided + stage2_residual
+            out.update({"stage2": bool(st.stage2), "stage2_rows": int(st.stage2_rows), "stage2_decided": int(st.stage2_decided),
+                        "stage2_residual": int(st.stage2_residual), "max_margin_err2": float(st.max_margin_err2),
+                        "sigma2": float((st.sum_sq_pair_err2 / st.pairs2) ** 0.5 if st.pairs2 else 0.0), "tau2": float(st.tau2),
+                        "tau2_eff": float(st.tau2_eff), "stage2_widened": int(st.stage2_widened),
+                        "stage2_dropped": int(st.stage2_dropped)})
+        return out
+
+    def set_gate_margin2(self, tau2):
+        """dtype 'f16x8c': flagged queries whose top-2 margin in the FP6-form gating pass (recheck stage 2) is below ``tau2`` go on
+        to the f16x3 gating net; the others are decided there (``nesti_model_set_gate_margin2``).  The stage runs only once this has been
+        called (:func:`calibrate.calibrate_gate_margin` does): there is no default ``tau2``."""
+        _lib.check(self.lib.nesti_model_set_gate_margin2(self._handle, float(tau2)), "nesti_model_set_gate_margin2")
+
+    def set_gate_stage2(self, on):
+        """dtype 'f16x8c': switch recheck stage 2 on (the default with x8 format 6) or off (``nesti_model_set_gate_stage2``)."""
+        _lib.check(self.lib.nesti_model_set_gate_stage2(self._handle, int(bool(on))), "nesti_model_set_gate_stage2")
+
+    def export_gate_error2(self, dst, stream=None):
+        """dtype 'f16x8c': the twin of :meth:`export_gate_error` for ``max_margin_err2``."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.nesti_model_gate_error2_export(self._handle, _lib.ptr(dst), self._stream(stream)),
+                       "nesti_model_gate_error2_export")
+
+    def import_gate_error2(self, src, stream=None):
+        """dtype 'f16x8c': the twin of :meth:`import_gate_error` for ``max_margin_err2``."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.nesti_model_gate_error2_import(self._handle, _lib.ptr(src), int(src.numel()), self._stream(stream)),
+                       "nesti_model_gate_error2_import")
 
     def set_x8_layers(self, mask):
         """dtype 'f16x8' / 'f16x8c': which expert tap layers at 8^3 take their cross terms through the narrow format (``nesti_model_set_x8_layers``:

@@ -256,6 +256,9 @@ class NormalEstimator:
         torch.cuda.synchronize(self.device)
         st = self.net.reproducible_stats(reset=True)
         self._verify_thr = (st["tau"], st["thr"])
+        # dtype 'f16x8c' with recheck stage 2 running (a second margin has been set): that margin is saved and restored too
+        cs = self.net.cascade_stats() if getattr(self.net, "stage2", False) else {}
+        self._verify_tau2 = cs["tau2"] if cs.get("stage2") else None
         return self._verify_thr
 
     def verify_flags(self):
@@ -278,6 +281,11 @@ class NormalEstimator:
         f = np.float32
         tau, thr = self._verify_thr
         tau = max(f(tau), f(_lib.GATE_WIDEN) * f(max_margin_err))
+        if getattr(self, "_verify_tau2", None) is not None:
+            # recheck stage 2 is running: its margin follows the largest error of the stage the same way (after a sharded pass
+            # every rank holds the largest any rank measured: dist.py's gather carries it)
+            st = self.net.cascade_stats()
+            self.net.set_gate_margin2(float(max(f(st["tau2"]), f(_lib.GATE_WIDEN) * f(st["max_margin_err2"]))))
         if self._has_guard and thr >= 0.0:
             scale = f(_lib.X8_GUARD_WIDEN) / np.sqrt(f(2.0) * f(_lib.X8_GUARD_BAR))
             thr = max(f(thr), scale * f(max_dn))
@@ -291,6 +299,8 @@ class NormalEstimator:
 
     def verify_end(self, saved):
         torch.cuda.synchronize(self.device)
+        if getattr(self, "_verify_tau2", None) is not None:
+            self.net.set_gate_margin2(self._verify_tau2)
         self._set_thresholds(*saved)
 
     def _prefetch(self, spans, make, consume):
